@@ -5,10 +5,15 @@ A "step" = one `F5TTS.sample()` call (32-point Euler = 31 updates = 62 DiT forwa
 batch of synthetic 10 s utterances (N = 937 mel frames, SURVEY.md §8(d) inputs), inputs resident in
 HBM, output = final mel on device.  value = mel frames produced per second, whole job.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision f16|bf16|bf16x3|mxfp8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision f16|bf16|bf16x3|mxfp8] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`ms_per_step` = one timed step).  `--dump-outputs DIR`
+writes what the last timed step returned (`out`, `trajectory`) as DIR/<name>.npy, float32, at most 64 MB in all.  Everything else
+-- parity against the committed golden, kernel rooflines and the measured MFMA peak, the sub-records (wave-to-wave, batch 32, bf16,
+eager, configs[4]) and the CPU baseline -- runs only with `--full` (`--no-sub` / `--no-cpu-baseline` then drop parts of it).
 
 Precision: the headline mode is "f16" (IEEE-half MFMA operands, fp32 everywhere else), the one-pass mode that meets the
-1e-3 mel-L1 parity gate; the line carries `parity_l1`, the measured distance of the TIMED configuration's output from the fp32
+1e-3 mel-L1 parity gate; a --full line carries `parity_l1`, the measured distance of the TIMED configuration's output from the fp32
 oracle's committed answer for this very workload (tests/golden/full_b1_euler32.npz).  "bf16" (BASELINE's label) is reported
 as a sub-record together with its parity figure, which is outside the gate.
 
@@ -44,6 +49,7 @@ ODE_POINTS = 32
 BF16_PEAK_TFLOPS = 2500.0  # dense bf16 / fp16 MFMA peak, MI355X_MICROARCH.md
 FP8_PEAK_TFLOPS = 5000.0   # dense fp8 (MX) MFMA peak, MI355X_MICROARCH.md
 PARITY_TOL = 1e-3
+DUMP_BYTES = 64 << 20      # --dump-outputs: budget of all files together
 GOLDEN = os.path.join(ROOT, "tests", "golden", "full_b1_euler32.npz")
 DTYPE_TEXT = {
     "f16": "f16 (IEEE-half MFMA operands, fp32 accumulate / residual stream / LayerNorm / softmax state; meets the 1e-3 gate)",
@@ -460,15 +466,35 @@ def parity_against_golden(out_utt0: torch.Tensor, args) -> dict | None:
 
 
 def timed_samples(f5, cond, text, kw, steps, warmup, barrier):
-    out = None
+    """-> (seconds of the `steps` timed calls, out and trajectory of the last call)"""
+    out = traj = None
     for _ in range(warmup):
-        out, _ = f5.sample(cond, text, **kw)
+        out, traj = f5.sample(cond, text, **kw)
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
-        out, _ = f5.sample(cond, text, **kw)
+        out, traj = f5.sample(cond, text, **kw)
     barrier()
-    return time.perf_counter() - t0, out
+    return time.perf_counter() - t0, out, traj
+
+
+def dump_outputs(dirname: str, arrays: dict) -> dict:
+    """--dump-outputs: each array as DIR/<name>.npy in float32, in order, within DUMP_BYTES together.  An array larger than the budget
+    left is written as a fixed sample of its flattened elements (indices drawn from default_rng(0), sorted) to DIR/<name>_sample.npy,
+    so that two builds run with the same arguments write comparable files.  Returns {file name: shape written}."""
+    os.makedirs(dirname, exist_ok=True)
+    left, written = DUMP_BYTES, {}
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().to(torch.float32)
+        cap = left // 4
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), cap))
+            t, name = t.reshape(-1)[torch.from_numpy(idx).to(t.device)], name + "_sample"
+        a = t.cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes
+        written[name + ".npy"] = list(a.shape)
+    return written
 
 
 def main():
@@ -494,6 +520,11 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-sub", action="store_true", help="skip the sub-records (batch 32, bf16, wave-to-wave RTF)")
     ap.add_argument("--dry-run", action="store_true", help="CPU / gloo: launch, barrier, reduce and report only (no engine)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, <= 64 MB in all; rank 0's shard)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: parity against the golden, kernel rooflines and the measured MFMA "
+                         "peak, the sub-records (unless --no-sub) and the CPU baseline (unless --no-cpu-baseline)")
     args = ap.parse_args()
     batch_explicit = args.batch is not None
     if args.config == "c5":
@@ -539,7 +570,7 @@ def main():
 
     if args.dry_run:
         # same skeleton, no GPU: a "step" is a small CPU matmul; proves the N-rank launch path and the report fields
-        a = torch.randn(256, 256)
+        a = torch.randn(256, 256, generator=torch.Generator().manual_seed(0))
         for _ in range(args.warmup):
             a = torch.tanh(a @ a.T / 256)
         barrier()
@@ -550,6 +581,8 @@ def main():
         mine = time.perf_counter() - t0
         elapsed = max_over_ranks(mine)
         fastest = -max_over_ranks(-mine)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"out": a})
         if rank == 0:
             ms = elapsed / args.steps * 1e3
             print(json.dumps({"metric": "mel_frames_per_sec", "value": world * B * N_FRAMES / (ms * 1e-3), "unit": "mel-frames/s",
@@ -602,7 +635,7 @@ def main():
     load_s = time.perf_counter() - t_w
 
     vocoder = None
-    if args.vocoder or not args.no_sub:
+    if args.vocoder or (args.full and not args.no_sub):
         from f5_tts_mlx_amd.vocos import Vocos, synthetic_vocos_weights
         vocoder = Vocos(synthetic_vocos_weights(seed=7), precision=args.precision if args.precision != "mxfp8" else "bf16", device=device)
     f5 = F5TTS(transformer=model, vocoder=vocoder.decode if args.vocoder else None)
@@ -610,7 +643,10 @@ def main():
     kw = dict(duration=N_FRAMES, steps=args.ode_points, method=args.method, cfg_strength=2.0, sway_sampling_coef=-1.0, y0=y0,
               use_graph=not args.no_graph)
 
-    elapsed, out = timed_samples(f5, cond, text, kw, args.steps, args.warmup, barrier)
+    elapsed, out, traj = timed_samples(f5, cond, text, kw, args.steps, args.warmup, barrier)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"out": out, "trajectory": traj})
+    del traj
     rank_elapsed = elapsed
     elapsed = max_over_ranks(elapsed)
     rank_ms_min = -max_over_ranks(-rank_elapsed) / args.steps * 1e3        # the fastest rank (diagnosis of a scaling run: a slow GPU / link
@@ -631,14 +667,6 @@ def main():
 
         ms_per_step = elapsed / args.steps * 1e3
         head = summarize(ms_per_step, B, world)
-        if args.precision == "mxfp8":
-            kernels, sym = [gemm_roofline_f8(device, B)], {}
-        else:
-            kernels, sym = kernel_rooflines(args.precision, device, B)
-        dominant = max(kernels, key=lambda k: k.get("share_of_block", 1.0))
-        if sym and sym.get("f5_gemm*_kernel<EPI_RESID_GATE>", 0.0) >= max(sym.values(), default=0.0):
-            # the residual-update GEMM symbol (out-proj + FF2 launches) leads the rocprof CSV: report its heavier instance
-            dominant = max((k for k in kernels if k["key"] in ("out_proj_gemm", "ff2_gemm")), key=lambda k: k["share_of_block"])
         rec = {
             "metric": "mel_frames_per_sec", "value": head["value"], "unit": "mel-frames/s", "n_gpus": world, "gpus_arg": args.gpus,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
@@ -661,37 +689,47 @@ def main():
             "rank_ms_min": rank_ms_min, "rank_ms_max": rank_ms_max,
             "ln_fold_range_events": model.engine.range_events, "fp16_saturation_events": model.engine.saturation_events,
             "range_check": model.engine.range_check,
-            "roofline": dominant, "roofline_kernels": kernels, "roofline_symbol_shares": sym,
         }
-        if dominant.get("peak_measured_tflops"):
-            # the measured MFMA micro-benchmark peak next to the data-sheet figure every `frac` divides by
-            rec["peak_tflops_datasheet"] = BF16_PEAK_TFLOPS
-            rec["peak_measured_tflops"] = dominant["peak_measured_tflops"]
-            rec["peak_measured_constant_operands_tflops"] = dominant["peak_measured_constant_operands_tflops"]
-            rec["whole_path_frac_of_measured_peak"] = head["whole_path_tflops"] / (world * dominant["peak_measured_tflops"])
-        # utterance 0 against the fp32 oracle's golden of this solver (with a vocoder in the loop `out` is a waveform: compare the mel
-        # of one extra un-vocoded call instead -- outside the timed region)
-        if real:
-            par = None
-        elif args.vocoder:
-            # the SAME batch without the vocoder (same kernels, same LN-fold decision as the timed call): utterance 0 of it
-            o_mel, _ = F5TTS(transformer=model).sample(cond, text, **kw)
-            torch.cuda.synchronize()
-            par = parity_against_golden(o_mel[0], args)
-            del o_mel
-        else:
-            par = parity_against_golden(out[0], args)
-        if par:
-            rec.update(par)
+        # --full: everything beyond the headline, measured after it
+        if args.full:
             if args.precision == "mxfp8":
-                rec["parity_note"] = ("mxfp8 is a reduced-precision mode outside the 1e-3 gate by design; parity_l1 is its measured distance from "
-                                      "the fp32 oracle (the oracle with the same MX rounding: tests/golden/make_fullsize_golden.py --emulate mxfp8)")
+                kernels, sym = [gemm_roofline_f8(device, B)], {}
+            else:
+                kernels, sym = kernel_rooflines(args.precision, device, B)
+            dominant = max(kernels, key=lambda k: k.get("share_of_block", 1.0))
+            if sym and sym.get("f5_gemm*_kernel<EPI_RESID_GATE>", 0.0) >= max(sym.values(), default=0.0):
+                # the residual-update GEMM symbol (out-proj + FF2 launches) leads the rocprof CSV: report its heavier instance
+                dominant = max((k for k in kernels if k["key"] in ("out_proj_gemm", "ff2_gemm")), key=lambda k: k["share_of_block"])
+            rec.update(roofline=dominant, roofline_kernels=kernels, roofline_symbol_shares=sym)
+            if dominant.get("peak_measured_tflops"):
+                # the measured MFMA micro-benchmark peak next to the data-sheet figure every `frac` divides by
+                rec["peak_tflops_datasheet"] = BF16_PEAK_TFLOPS
+                rec["peak_measured_tflops"] = dominant["peak_measured_tflops"]
+                rec["peak_measured_constant_operands_tflops"] = dominant["peak_measured_constant_operands_tflops"]
+                rec["whole_path_frac_of_measured_peak"] = head["whole_path_tflops"] / (world * dominant["peak_measured_tflops"])
+            # utterance 0 against the fp32 oracle's golden of this solver (with a vocoder in the loop `out` is a waveform: compare the mel
+            # of one extra un-vocoded call instead -- outside the timed region)
+            if real:
+                par = None
+            elif args.vocoder:
+                # the SAME batch without the vocoder (same kernels, same LN-fold decision as the timed call): utterance 0 of it
+                o_mel, _ = F5TTS(transformer=model).sample(cond, text, **kw)
+                torch.cuda.synchronize()
+                par = parity_against_golden(o_mel[0], args)
+                del o_mel
+            else:
+                par = parity_against_golden(out[0], args)
+            if par:
+                rec.update(par)
+                if args.precision == "mxfp8":
+                    rec["parity_note"] = ("mxfp8 is a reduced-precision mode outside the 1e-3 gate by design; parity_l1 is its measured distance from "
+                                          "the fp32 oracle (the oracle with the same MX rounding: tests/golden/make_fullsize_golden.py --emulate mxfp8)")
         if world == 1 and B == 32:
             # the line itself is the batch-32 configuration: the same top-level scalars as the sub-record of the default run
             rec.update(b32_ms_per_step=ms_per_step, b32_value=head["value"], b32_whole_path_frac=head["whole_path_frac_of_bf16_peak"],
                        b32_frac_of_measured=rec.get("whole_path_frac_of_measured_peak"), b32_parity_l1=rec.get("parity_l1"))
 
-        if world == 1 and not args.no_sub:
+        if args.full and world == 1 and not args.no_sub:
             sub = {}
             # (1) RTF as SURVEY §8(d) defines it: reference WAVE in -> mel front-end -> sample -> Vocos -> WAVE out
             f5w = F5TTS(transformer=model, vocoder=vocoder.decode)
@@ -719,7 +757,7 @@ def main():
                 kw32 = dict(kw, y0=y32)
                 n32 = 5
                 with ClockPowerSampler() as smi32:
-                    el, o32 = timed_samples(f5, c32, t32, kw32, n32, 1, barrier)
+                    el, o32, _ = timed_samples(f5, c32, t32, kw32, n32, 1, barrier)
                 s32 = summarize(el / n32 * 1e3, 32)
                 s32["timed_iterations"] = n32
                 if smi32.summary():
@@ -751,7 +789,7 @@ def main():
             if args.precision != "bf16" and B == 1:
                 mb = make_model("bf16")
                 mb.load_weights(weights)
-                el, ob = timed_samples(F5TTS(transformer=mb), cond, text, kw, 3, 1, barrier)
+                el, ob, _ = timed_samples(F5TTS(transformer=mb), cond, text, kw, 3, 1, barrier)
                 sb = summarize(el / 3 * 1e3, B)
                 pb = parity_against_golden(ob[0], args) if not real else None
                 if pb:
@@ -766,7 +804,7 @@ def main():
                 legs = {"eager": [], "graph": []}
                 for _ in range(2):
                     for name, g in (("eager", False), ("graph", True)):
-                        el, oe = timed_samples(f5, cond, text, dict(kw, use_graph=g), 3, 1, barrier)
+                        el, oe, _ = timed_samples(f5, cond, text, dict(kw, use_graph=g), 3, 1, barrier)
                         legs[name].append(el / 3 * 1e3)
                 se = summarize(min(legs["eager"]), B)
                 se["note"] = "eager launches (no hipGraph): the cost of a shape signature the first time it is seen"
@@ -783,7 +821,7 @@ def main():
                 kw8 = dict(duration=N_FRAMES, steps=16, method="midpoint", cfg_strength=2.0, sway_sampling_coef=-1.0, y0=y32, use_graph=not args.no_graph)
                 v8 = Vocos(synthetic_vocos_weights(seed=7), precision="bf16", device=device)
                 n8 = 3
-                el, o8 = timed_samples(F5TTS(transformer=m8, vocoder=v8.decode), c32, t32, kw8, n8, 1, barrier)
+                el, o8, _ = timed_samples(F5TTS(transformer=m8, vocoder=v8.decode), c32, t32, kw8, n8, 1, barrier)
                 ms8 = el / n8 * 1e3
                 nf8 = 2 * 2 * 15
                 tf8 = 32 * nf8 * fwd_exec / 1e12 / (ms8 * 1e-3)
@@ -807,7 +845,7 @@ def main():
             rec["sub"] = sub
         else:
             rec["rtf"] = None if not args.vocoder else head["rtf_mel_only"]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(weights)
         print(json.dumps(rec))
     if dist_on:

@@ -1,6 +1,7 @@
 """Golden vectors produced by the REFERENCE's own Python source.
 
     python tests/golden/make_reference_golden.py          (build container only: needs /root/reference)
+    python tests/golden/make_reference_golden.py --only-recorded     (the recorded checks only: see `recorded`)
 
 MLX is not installable here, so the reference modules (`f5_tts_mlx/{dit,cfm,rope,convnext_v2,audio,utils}.py`) are imported
 unmodified from /root/reference on top of `oracle/mlx_shim.py`, a numpy emulation of the mlx primitives they call.  What the
@@ -261,5 +262,105 @@ def main():
     print("reference goldens written:", {k: v.shape for k, v in fwd.items()}, {k: float(v) for k, v in losses.items()})
 
 
+# ------------------------------------------------------------------------------------------------
+# recorded checks: reference answers that the suite compares the oracle / the package with, so that no test needs the reference
+#     python tests/golden/make_reference_golden.py --only-recorded
+# ------------------------------------------------------------------------------------------------
+FRONT_END_TEXTS = ["Some call me nature, others call me mother nature. Hello;world", "“q” ‘x’", "x,yz a:b 'cd' \"ef\" 3.5% done; ok",
+                   "", "a", " ab  cd ", "it's 12:30pm - really?!", "One fish. Two fish! Red fish", "no terminator"]
+FRONT_END_DURATIONS = [("Some call me nature.", "Hello there; general Kenobi", 1.3), ("abc", "。，、；：？！ x", 1.0)]
+FUZZ_CASES = 6
+CKPT_DEPTH = 2          # the 335M tree cut to 2 blocks: the same per-key code as 22 at a fraction of the time
+CKPT_SEED = 9           # synthetic weights of tests/test_reference_golden.py upstream_checkpoint_dir
+
+
+def recorded():
+    """ref_text_front_end.json, ref_sample_fuzz.npz, ref_from_pretrained.json: the reference's answers to the checks of
+    tests/test_reference_golden.py that need more than one fixed configuration"""
+    import dataclasses
+    import tempfile
+    from pathlib import Path
+    import f5_tts_mlx.generate as ref_generate
+    from f5_tts_mlx_amd import utils as U
+    sys.path.insert(0, os.path.dirname(HERE))
+    from test_reference_golden import array_digest, upstream_checkpoint_dir
+
+    # ---- text front-end (utils.py convert_char_to_pinyin, generate.py split_sentences / estimated_duration); jieba's
+    # segmentation of single-byte text is the package's emulation
+    sys.modules["jieba"].cut = U._ascii_segments
+    audio = np.zeros(127987, np.float32)
+    front = dict(texts=FRONT_END_TEXTS, pinyin=[ref_utils.convert_char_to_pinyin([t]) for t in FRONT_END_TEXTS],
+                 sentences=[ref_generate.split_sentences(t) for t in FRONT_END_TEXTS],
+                 durations=[[rt, gt, sp, ref_generate.estimated_duration(mx.array(audio), rt, gt, sp)] for rt, gt, sp in FRONT_END_DURATIONS])
+    with open(os.path.join(HERE, "ref_text_front_end.json"), "w") as f:
+        json.dump(front, f, ensure_ascii=False)
+
+    # ---- DiT / sample on several random small configurations (inputs and the reference's trajectory per case)
+    fuzz = {}
+    for case in range(FUZZ_CASES):
+        r = np.random.default_rng(100 + case)
+        heads = int(r.choice([2, 4, 8]))
+        cfg = DiTConfig(dim=64 * heads, depth=int(r.integers(1, 4)), heads=heads, dim_head=64, ff_mult=int(r.choice([2, 4])),
+                        mel_dim=100, text_num_embeds=int(r.integers(20, 90)), text_dim=int(r.choice([64, 128])),
+                        conv_layers=int(r.choice([0, 1, 3])), conv_pos_groups=16, text_mask_padding=bool(case % 2 == 0))
+        model = build_reference_model(cfg, synthetic_weights(cfg, seed=200 + case))
+        B, n_ref = int(r.integers(1, 4)), int(r.integers(5, 20))
+        durs = np.sort(r.integers(n_ref + 6, n_ref + 40, B))[::-1].astype(np.int32).copy()
+        nt = int(r.integers(3, n_ref + 10))
+        cond = f32(r.standard_normal((B, n_ref, 100)))
+        text = r.integers(0, cfg.text_num_embeds, (B, nt)).astype(np.int32)
+        if B > 1:
+            text[-1, max(1, nt - 3):] = -1
+        lens = r.integers(max(1, n_ref - 4), n_ref + 1, B).astype(np.int32)
+        method = ["euler", "midpoint", "rk4"][case % 3]
+        cfg_strength = 0.0 if case == 4 else 2.0
+        sway = None if case == 5 else -1.0
+        # final durations follow cfm.py:301-303,317-319; the noise is drawn per element with those widths
+        final = np.maximum(np.maximum((text != -1).sum(-1), lens) + 1, durs)
+        z = [f32(r.standard_normal((100, int(d)))) for d in final]
+        with injected_random(normal=z):
+            _, traj = model.sample(mx.array(cond), mx.array(text), mx.array(durs), lens=mx.array(lens), steps=3, method=method,
+                                   cfg_strength=cfg_strength, sway_sampling_coef=sway, seed=1)
+        y0 = np.zeros((B, int(final.max()), 100), np.float32)
+        for i, zi in enumerate(z):
+            y0[i, :zi.shape[1]] = zi.T
+        c = f"case{case}_"
+        fuzz.update({c + "cfg": json.dumps(dataclasses.asdict(cfg)), c + "weights_seed": 200 + case, c + "cond": cond, c + "text": text,
+                     c + "durations": durs, c + "lens": lens, c + "y0": y0, c + "method": method, c + "cfg_strength": cfg_strength,
+                     c + "sway": np.nan if sway is None else sway, c + "traj": f32(traj)})
+    np.savez_compressed(os.path.join(HERE, "ref_sample_fuzz.npz"), cases=FUZZ_CASES, **fuzz)
+
+    # ---- F5TTS.from_pretrained (cfm.py:404-520) on a synthetic upstream checkpoint: its parameters, and those of the 8-bit file
+    class _Vocos:                                   # vocos_mlx is a third-party package: stub (cfm.py:446)
+        @classmethod
+        def from_pretrained(cls, name):
+            return cls()
+
+        def decode(self, mel):
+            return mel
+    saved = ref_cfm.fetch_from_hub, ref_cfm.DiT, ref_cfm.Vocos
+    ref_cfm.fetch_from_hub = lambda p, quantization_bits=None: Path(p)      # no network: the "hub" is a local directory
+    ref_cfm.DiT = lambda **kw: saved[1](**dict(kw, depth=CKPT_DEPTH))       # from_pretrained hard-codes the 22-block tree (cfm.py:459-469)
+    ref_cfm.Vocos = _Vocos
+    try:
+        with tempfile.TemporaryDirectory() as d:
+            upstream_checkpoint_dir(d, CKPT_DEPTH, CKPT_SEED)
+            m = ref_cfm.F5TTS.from_pretrained(d)
+            params = {k: array_digest(v) for k, v in sorted(m.parameters().items())}
+            q = ref_cfm.F5TTS.from_pretrained(d, quantization_bits=8)
+            qparams = {k: array_digest(v) for k, v in sorted(q.parameters().items())}
+            quantized = sorted(q._quantized_paths)
+    finally:
+        ref_cfm.fetch_from_hub, ref_cfm.DiT, ref_cfm.Vocos = saved
+    with open(os.path.join(HERE, "ref_from_pretrained.json"), "w") as f:
+        json.dump(dict(depth=CKPT_DEPTH, weights_seed=CKPT_SEED, hash="sha256 of dtype, shape and bytes", params=params,
+                       quantized=quantized, params_8bit=qparams), f, indent=0, sort_keys=True)
+    print("recorded:", len(front["texts"]), "texts,", FUZZ_CASES, "sample cases,", len(params), "/", len(qparams), "checkpoint parameters")
+
+
 if __name__ == "__main__":
-    main()
+    if "--only-recorded" in sys.argv[1:]:
+        recorded()
+    else:
+        main()
+        recorded()

@@ -299,3 +299,40 @@ def test_bench_flop_model_matches_survey():
     assert executed == 432_959_365_120 + 937 * 2 * (128 - 100) * 1024      # SURVEY's F_h + the K padding 100 -> 128
     assert executed < bench.flops_forward(937, hoisted=False)
     assert abs(62 * 442_304_409_600 / 1e12 - 27.423) < 1e-3                # reference-equivalent TFLOP per 32-point Euler utterance
+
+
+def test_bench_dump_outputs_fits_its_budget(tmp_path):
+    """--dump-outputs: arrays that fit are written whole in float32, in order; what no longer fits the 64 MB budget is written as a
+    fixed sample of its elements, the same one every run"""
+    import importlib
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    small = torch.arange(6, dtype=torch.float64).reshape(2, 3)
+    big = torch.randn(bench.DUMP_BYTES // 4 + 1000, generator=torch.Generator().manual_seed(3))
+    for d in ("a", "b"):
+        written = bench.dump_outputs(str(tmp_path / d), {"out": small, "trajectory": big})
+        assert written == {"out.npy": [2, 3], "trajectory_sample.npy": [bench.DUMP_BYTES // 4 - 6]}
+    a = np.load(tmp_path / "a" / "out.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, small.numpy())
+    s1, s2 = np.load(tmp_path / "a" / "trajectory_sample.npy"), np.load(tmp_path / "b" / "trajectory_sample.npy")
+    assert s1.dtype == np.float32 and np.array_equal(s1, s2) and np.isin(s1, big.numpy()).all()
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_BYTES + 1024
+
+
+def test_bench_plain_dry_run_steps_and_dump(tmp_path):
+    """A plain `bench.py --dry-run` times exactly --steps steps, prints one result line with ms_per_step, and --dump-outputs writes the
+    same seeded answer every run"""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    outs = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["higher_is_better"] is True
+        outs.append(np.load(tmp_path / d / "out.npy"))
+    assert outs[0].dtype == np.float32 and np.array_equal(outs[0], outs[1])

@@ -1596,12 +1596,16 @@ def test_real_checkpoint_tooling_on_a_synthetic_directory(tmp_path):
     assert lf["fold_on"]["mel_l1_vs_oracle"] <= MEL_L1_TOL and lf["fold_off"]["mel_l1_vs_oracle"] <= MEL_L1_TOL
     assert res["largest_operand"] < 65504.0 / 8 and any("attention q" in k for k in res["operand_peaks"]) and any("ff.ff.layers.2" in k for k in res["operand_peaks"])
     env = dict(os.environ, F5_WEIGHTS=str(mdir))
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--ode-points", "3", "--no-sub", "--no-cpu-baseline"],
-                       capture_output=True, text=True, timeout=900, env=env)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--ode-points", "3", "--full", "--no-sub",
+                        "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
     assert line["data"].startswith("REAL checkpoint") and "parity_l1" not in line and line["value"] > 0
     assert line["roofline"]["peak_measured_tflops"] > 500 and 0 < line["roofline"]["frac_of_measured"] < 1
+    out = np.load(tmp_path / "dump" / "out.npy")         # what the timed call returned: the mel, and its trajectory
+    traj = np.load(tmp_path / "dump" / "trajectory.npy")
+    assert out.dtype == traj.dtype == np.float32 and out.shape == (1, 937, 100) and traj.shape[1:] == (1, 937, 100)
+    assert np.isfinite(out).all() and np.isfinite(traj).all()
 
 
 def test_dit_call_remaining_argument_combinations(tiny_weights, tiny_x3):

@@ -4,8 +4,8 @@ The vectors come from `tests/golden/make_reference_golden.py`: the reference mod
 executed over `oracle/mlx_shim.py` (numpy emulation of the mlx primitives; MLX itself is not installable here).  They pin the
 oracle's restatement of the reference's code path; what stays unpinned is MLX's own arithmetic.
 
-`test_reference_goldens_are_current` re-runs the generator's reference calls live when /root/reference exists (build
-container) and is skipped on the GPU box, where only the committed vectors travel.
+The checks that once ran the reference live (text front-end, random small configurations, from_pretrained) compare against answers
+the generator recorded from it (`--only-recorded`): ref_text_front_end.json, ref_sample_fuzz.npz, ref_from_pretrained.json.
 """
 import json
 import os
@@ -132,28 +132,6 @@ def test_time_embedding_matches_reference_code(ref_model):
     assert out.shape == (3, cfg.dim) and torch.isfinite(out).all()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/f5_tts_mlx"), reason="reference checkout not present (GPU box)")
-def test_reference_goldens_are_current(ref_model):
-    """Live: import the reference over the shim and recompute one forward and the masks; must equal the committed vectors."""
-    import subprocess
-    import sys
-    code = r"""
-import sys, json, numpy as np
-sys.path.insert(0, %r); sys.path.insert(0, '/root/reference')
-sys.path.insert(0, %r)
-import make_reference_golden as M
-g = np.load(%r)
-cfg = M.DiTConfig(**json.loads(str(g['cfg'])))
-model = M.build_reference_model(cfg, M.synthetic_weights(cfg, seed=int(g['weights_seed'])))
-out = model.transformer(x=M.mx.array(g['x']), cond=M.mx.array(g['cond']), text=M.mx.array(g['text']), time=M.mx.array(g['time']),
-                        drop_audio_cond=False, drop_text=False, mask=M.mx.array(g['mask']))
-assert np.array_equal(np.asarray(out, dtype=np.float32), g['out_cond_masked'])
-print('LIVE-OK')
-""" % (ROOT, GOLDEN, os.path.join(GOLDEN, "ref_dit_forward.npz"))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
-    assert "LIVE-OK" in r.stdout, r.stderr[-2000:]
-
-
 def test_package_host_functions_match_reference_code():
     """the product's host-side mirrors (f5_tts_mlx_amd.utils, no GPU needed): index paths bit-exact vs utils.py's outputs"""
     from f5_tts_mlx_amd import utils as U
@@ -198,89 +176,42 @@ def test_sample_duration_clamps_match_reference_code(ref_model):
     assert float((out - torch.from_numpy(g["out"])).abs().max()) < TRAJ_TOL
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/f5_tts_mlx"), reason="reference checkout not present (GPU box)")
 def test_text_front_end_matches_reference_code_live():
-    """convert_char_to_pinyin / split_sentences / estimated_duration of the package vs the reference's own functions (live, over
-    the shim; jieba's segmentation of single-byte text is the package's emulation on both sides)"""
-    import subprocess
-    import sys
-    code = r"""
-import sys, numpy as np
-sys.path.insert(0, %r); sys.path.insert(0, '/root/reference')
-from oracle import mlx_shim; mx, nn = mlx_shim.install()
-from f5_tts_mlx_amd import utils as U, generate as G
-sys.modules['jieba'].cut = U._ascii_segments
-import f5_tts_mlx.utils as RU, f5_tts_mlx.generate as RG
-texts = ["Some call me nature, others call me mother nature. Hello;world", "“q” ‘x’", "x,yz a:b 'cd' \"ef\" 3.5%% done; ok",
-         "", "a", " ab  cd ", "it's 12:30pm - really?!", "One fish. Two fish! Red fish", "no terminator"]
-for t in texts:
-    assert RU.convert_char_to_pinyin([t]) == U.convert_char_to_pinyin([t]), t
-    assert RG.split_sentences(t) == G.split_sentences(t), t
-audio = np.zeros(127987, np.float32)
-for ref_text, gen_text, speed in (("Some call me nature.", "Hello there; general Kenobi", 1.3), ("abc", "。，、；：？！ x", 1.0)):
-    assert RG.estimated_duration(mx.array(audio), ref_text, gen_text, speed) == G.estimated_duration(audio, ref_text, gen_text, speed)
-print('LIVE-OK')
-""" % (ROOT,)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert "LIVE-OK" in r.stdout, (r.stdout[-500:], r.stderr[-2000:])
+    """convert_char_to_pinyin / split_sentences / estimated_duration of the package vs the reference's own functions, as recorded from
+    them over the shim (tests/golden/ref_text_front_end.json; jieba's segmentation of single-byte text is the package's emulation on
+    both sides)"""
+    from f5_tts_mlx_amd import generate as G
+    from f5_tts_mlx_amd import utils as U
+    g = json.load(open(os.path.join(GOLDEN, "ref_text_front_end.json"), encoding="utf-8"))
+    assert len(g["texts"]) == len(g["pinyin"]) == len(g["sentences"]) == 9 and len(g["durations"]) == 2
+    for t, pinyin, sentences in zip(g["texts"], g["pinyin"], g["sentences"]):
+        assert U.convert_char_to_pinyin([t]) == pinyin, t
+        assert G.split_sentences(t) == sentences, t
+    audio = np.zeros(127987, np.float32)
+    for ref_text, gen_text, speed, want in g["durations"]:
+        assert G.estimated_duration(audio, ref_text, gen_text, speed) == want, (ref_text, gen_text)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/f5_tts_mlx"), reason="reference checkout not present (GPU box)")
 def test_oracle_vs_reference_code_live_fuzz():
-    """Live, build container only: the reference's DiT / sample run over the shim on several random small configurations (widths,
-    depths, heads, text-conv depth incl. 0, batch, lengths, ragged masks, solvers, CFG on/off) against the oracle on the same
-    weights and inputs.  Complements the committed vectors, which are one configuration."""
-    import subprocess
-    import sys
-    code = r"""
-import sys, json, numpy as np, torch
-sys.path.insert(0, %r); sys.path.insert(0, %r); sys.path.insert(0, '/root/reference'); sys.path.insert(0, %r)
-import make_reference_golden as M
-from oracle import f5_oracle as O
-mx = M.mx
-worst = 0.0
-for case in range(6):
-    r = np.random.default_rng(100 + case)
-    heads = int(r.choice([2, 4, 8]))
-    cfg = M.DiTConfig(dim=64 * heads, depth=int(r.integers(1, 4)), heads=heads, dim_head=64, ff_mult=int(r.choice([2, 4])),
-                      mel_dim=100, text_num_embeds=int(r.integers(20, 90)), text_dim=int(r.choice([64, 128])),
-                      conv_layers=int(r.choice([0, 1, 3])), conv_pos_groups=16, text_mask_padding=bool(case %% 2 == 0))
-    w = M.synthetic_weights(cfg, seed=200 + case)
-    model = M.build_reference_model(cfg, w)
-    orc = O.DiTOracle(cfg, w, dtype=torch.float32)
-    B, n_ref = int(r.integers(1, 4)), int(r.integers(5, 20))
-    durs = np.sort(r.integers(n_ref + 6, n_ref + 40, B))[::-1].astype(np.int32).copy()
-    nt = int(r.integers(3, n_ref + 10))
-    cond = r.standard_normal((B, n_ref, 100)).astype(np.float32)
-    text = r.integers(0, cfg.text_num_embeds, (B, nt)).astype(np.int32)
-    if B > 1:
-        text[-1, max(1, nt - 3):] = -1
-    lens = r.integers(max(1, n_ref - 4), n_ref + 1, B).astype(np.int32)
-    method = ["euler", "midpoint", "rk4"][case %% 3]
-    cfg_strength = 0.0 if case == 4 else 2.0
-    sway = None if case == 5 else -1.0
-    # final durations follow cfm.py:301-303,317-319; the noise is drawn per element with those widths
-    text_lens = (text != -1).sum(-1)
-    final = np.maximum(np.maximum(text_lens, lens) + 1, durs)
-    z = [r.standard_normal((100, int(d))).astype(np.float32) for d in final]
-    with M.injected_random(normal=z):
-        out, traj = model.sample(mx.array(cond), mx.array(text), mx.array(durs), lens=mx.array(lens), steps=3, method=method,
-                                 cfg_strength=cfg_strength, sway_sampling_coef=sway, seed=1)
-    y0 = torch.zeros((B, int(final.max()), 100))
-    for i, zi in enumerate(z):
-        y0[i, :zi.shape[1]] = torch.from_numpy(zi.T)
-    o_out, o_traj = O.sample(orc, torch.from_numpy(cond), torch.from_numpy(text), torch.from_numpy(durs), lens=torch.from_numpy(lens),
-                             steps=3, method=method, cfg_strength=cfg_strength, sway_sampling_coef=sway, y0=y0)
-    ref = torch.from_numpy(np.asarray(traj, dtype=np.float32))
-    assert ref.shape == o_traj.shape, (case, ref.shape, o_traj.shape)
-    err = float((o_traj - ref).abs().max()) / max(1.0, float(ref.abs().max()))
-    worst = max(worst, err)
-    assert err < 2e-4, (case, err, cfg)
-print('LIVE-OK worst', worst)
-""" % (ROOT, os.path.join(ROOT, "tests"), GOLDEN)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900)
-    assert "LIVE-OK" in r.stdout, (r.stdout[-800:], r.stderr[-3000:])
-    print(r.stdout.strip().splitlines()[-1])
+    """The reference's DiT / sample, run over the shim on several random small configurations (widths, depths, heads, text-conv depth
+    incl. 0, batch, lengths, ragged masks, solvers, CFG on/off; tests/golden/ref_sample_fuzz.npz holds each case's inputs and the
+    reference's trajectory) against the oracle on the same weights and inputs.  Complements ref_sample.npz, which is one configuration."""
+    g = np.load(os.path.join(GOLDEN, "ref_sample_fuzz.npz"))
+    worst = 0.0
+    for case in range(int(g["cases"])):
+        c = lambda k: g[f"case{case}_{k}"]   # noqa: E731
+        cfg = DiTConfig(**json.loads(str(c("cfg"))))
+        orc = O.DiTOracle(cfg, synthetic_weights(cfg, seed=int(c("weights_seed"))), dtype=torch.float32)
+        sway = None if np.isnan(float(c("sway"))) else float(c("sway"))
+        _, o_traj = O.sample(orc, torch.from_numpy(c("cond")), torch.from_numpy(c("text")), torch.from_numpy(c("durations")),
+                             lens=torch.from_numpy(c("lens")), steps=3, method=str(c("method")), cfg_strength=float(c("cfg_strength")),
+                             sway_sampling_coef=sway, y0=torch.from_numpy(c("y0")))
+        ref = torch.from_numpy(c("traj"))
+        assert ref.shape == o_traj.shape, (case, ref.shape, o_traj.shape)
+        err = float((o_traj - ref).abs().max()) / max(1.0, float(ref.abs().max()))
+        worst = max(worst, err)
+        assert err < 2e-4, (case, err, cfg)
+    print("worst", worst)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -310,70 +241,27 @@ def _upstream_checkpoint(weights):
     return out
 
 
-_LIVE_FROM_PRETRAINED = r"""
-import json, sys, numpy as np
-from pathlib import Path
-sys.path.insert(0, %(root)r); sys.path.insert(0, '/root/reference')
-from oracle import mlx_shim; mx, nn = mlx_shim.install()
-class _Vocos:                                   # vocos_mlx is a third-party package: stub (cfm.py:446)
-    @classmethod
-    def from_pretrained(cls, name): return cls()
-    def decode(self, mel): return mel
-sys.modules['vocos_mlx'].Vocos = _Vocos
-import f5_tts_mlx.cfm as RC
-RC.fetch_from_hub = lambda p, quantization_bits=None: Path(p)      # no network: the "hub" is a local directory
-depth = %(depth)d
-if depth != 22:                                 # from_pretrained hard-codes the 335M tree (cfm.py:459-469); a shallower tree exercises
-    _DiT = RC.DiT                               # the same per-key code in a fraction of the time (F5_FULL_DEPTH=1 runs all 22 blocks)
-    RC.DiT = lambda **kw: _DiT(**dict(kw, depth=depth))
-from safetensors.numpy import load_file
-from f5_tts_mlx_amd.weights import convert_upstream_weights, dequantize_mlx_checkpoint
-d = %(dir)r
-# ---- full precision, convert_weights=True (the default): cfm.py:477-508
-m = RC.F5TTS.from_pretrained(d)
-ref = {k: np.asarray(v) for k, v in m.parameters().items()}
-ours = convert_upstream_weights(load_file(d + '/model_v1.safetensors'))
-assert set(ref) == set(ours), (sorted(set(ref) - set(ours))[:5], sorted(set(ours) - set(ref))[:5])
-for k in ref:
-    assert ref[k].shape == ours[k].shape and ref[k].dtype == ours[k].dtype and np.array_equal(ref[k], ours[k]), k
-keymap = {k: list(v.shape) for k, v in sorted(ours.items())}
-# ---- 8-bit file: nn.quantize's predicate decides which modules expect (weight uint32, scales, biases); cfm.py:510-515
-q = RC.F5TTS.from_pretrained(d, quantization_bits=8)
-qpaths = sorted(q._quantized_paths)
-qfile = load_file(d + '/model_v1_8b.safetensors')
-ours_q = sorted(k[:-7] for k in qfile if k.endswith('.scales'))
-assert qpaths == ours_q, (qpaths[:3], ours_q[:3], len(qpaths), len(ours_q))
-qref = {k: np.asarray(v) for k, v in q.parameters().items()}
-assert set(qref) == set(qfile) and all(np.array_equal(qref[k], qfile[k]) for k in qfile)
-deq = dequantize_mlx_checkpoint(qfile, 8)
-assert set(deq) == set(ours) and all(deq[k].shape == ours[k].shape for k in ours)
-json.dump(dict(keymap=keymap, quantized=qpaths), open(d + '/result.json', 'w'))
-print('LIVE-OK', len(ref), len(qpaths))
-"""
+def array_digest(a) -> str:
+    """sha256 of an array's dtype, shape and bytes: how tests/golden/ref_from_pretrained.json records the reference's parameters"""
+    import hashlib
+    a = np.ascontiguousarray(np.asarray(a))
+    return hashlib.sha256(str(a.dtype).encode() + str(a.shape).encode() + a.tobytes()).hexdigest()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/f5_tts_mlx"), reason="reference checkout not present (GPU box)")
-def test_checkpoint_conversion_matches_reference_from_pretrained_live(tmp_path):
-    """The reference's own `F5TTS.from_pretrained` (unmodified, over the mlx emulation; hub access and the third-party vocoder
-    stubbed) loads a synthetic UPSTREAM-named 335M checkpoint directory: its key renames / axis swaps (cfm.py:477-508) and the
-    strict load into the reference's module tree define the truth; `weights.convert_upstream_weights` must yield the same
-    names and arrays bit for bit.  Then the 8-bit path: `nn.quantize` with the reference's predicate (cfm.py:510-515) decides
-    which Linears expect packed weights; a file written with the package's rule must load strictly, and the two module sets
-    must be equal.  The resulting name -> shape map is compared with the committed tests/golden/ref_checkpoint_keymap.json."""
+def upstream_checkpoint_dir(dirname, depth, seed):
+    """A synthetic UPSTREAM-named 335M checkpoint directory cut to `depth` blocks (what tests/golden/make_reference_golden.py handed
+    the reference's from_pretrained): vocab.txt, model_v1.safetensors (`synthetic_weights(seed)` through _upstream_checkpoint) and
+    model_v1_8b.safetensors, the MLX 8-bit file written with the package's rule."""
     import dataclasses
-    import subprocess
-    import sys
     from safetensors.numpy import save_file
     from f5_tts_mlx_amd.weights import F5TTS_335M, quantize_mlx_affine
     vocab_text = open(os.path.join(ROOT, "f5_tts_mlx_amd", "assets", "vocab.txt")).read()
-    nvocab = len(vocab_text.split("\n"))
-    depth = 22 if os.environ.get("F5_FULL_DEPTH") == "1" else 2
-    cfg = dataclasses.replace(F5TTS_335M, text_num_embeds=nvocab - 1, depth=depth)
-    w = synthetic_weights(cfg, seed=9)
+    cfg = dataclasses.replace(F5TTS_335M, text_num_embeds=len(vocab_text.split("\n")) - 1, depth=depth)
+    w = synthetic_weights(cfg, seed=seed)
     w["transformer.rotary_embed.inv_freq"] = (1.0 / (10000 ** (np.arange(0, 64, 2, dtype=np.float32) / 64))).astype(np.float32)
-    up = _upstream_checkpoint(w)
-    (tmp_path / "vocab.txt").write_text(vocab_text)
-    save_file(up, str(tmp_path / "model_v1.safetensors"))
+    with open(os.path.join(dirname, "vocab.txt"), "w") as f:
+        f.write(vocab_text)
+    save_file(_upstream_checkpoint(w), os.path.join(dirname, "model_v1.safetensors"))
     q = {}
     for k, v in w.items():          # the package's rule for an MLX 8-bit file: Linear weights whose input width is a multiple of 64
         if k.endswith(".weight") and v.ndim == 2 and v.shape[1] % 64 == 0 and "text_embed.text_embed" not in k:
@@ -381,17 +269,37 @@ def test_checkpoint_conversion_matches_reference_from_pretrained_live(tmp_path):
             q[k], q[k[:-7] + ".scales"], q[k[:-7] + ".biases"] = pk, sc, bi
         else:
             q[k] = v
-    save_file(q, str(tmp_path / "model_v1_8b.safetensors"))
-    del up, q
-    r = subprocess.run([sys.executable, "-c", _LIVE_FROM_PRETRAINED % dict(root=ROOT, dir=str(tmp_path), depth=depth)],
-                       capture_output=True, text=True, timeout=1800)
-    assert "LIVE-OK" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
-    got = json.load(open(tmp_path / "result.json"))
+    save_file(q, os.path.join(dirname, "model_v1_8b.safetensors"))
+
+
+def test_checkpoint_conversion_matches_reference_from_pretrained_live(tmp_path):
+    """The reference's own `F5TTS.from_pretrained` (unmodified, over the mlx emulation; hub access and the third-party vocoder
+    stubbed) loaded a synthetic UPSTREAM-named 335M checkpoint directory (upstream_checkpoint_dir, 2 blocks): its key renames / axis
+    swaps (cfm.py:477-508) and the strict load into the reference's module tree define the truth, recorded as digests of every
+    parameter in tests/golden/ref_from_pretrained.json; `weights.convert_upstream_weights` must yield the same names and arrays bit
+    for bit.  Then the 8-bit path: `nn.quantize` with the reference's predicate (cfm.py:510-515) decided which Linears expect packed
+    weights; the file written with the package's rule must hold exactly those modules and exactly the arrays the reference's strict
+    load ended up with.  The resulting name -> shape map is compared with the committed tests/golden/ref_checkpoint_keymap.json."""
+    from safetensors.numpy import load_file
+    from f5_tts_mlx_amd.weights import convert_upstream_weights, dequantize_mlx_checkpoint
+    rec = json.load(open(os.path.join(GOLDEN, "ref_from_pretrained.json")))
+    depth = rec["depth"]
+    upstream_checkpoint_dir(str(tmp_path), depth, rec["weights_seed"])
+    # ---- full precision, convert_weights=True (the default): cfm.py:477-508
+    ours = convert_upstream_weights(load_file(str(tmp_path / "model_v1.safetensors")))
+    got = {k: array_digest(v) for k, v in ours.items()}
+    assert set(got) == set(rec["params"]), (sorted(set(rec["params"]) - set(got))[:5], sorted(set(got) - set(rec["params"]))[:5])
+    assert [k for k in got if got[k] != rec["params"][k]] == []
+    # ---- 8-bit file: nn.quantize's predicate decides which modules expect (weight uint32, scales, biases); cfm.py:510-515
+    qfile = load_file(str(tmp_path / "model_v1_8b.safetensors"))
+    assert sorted(k[:-7] for k in qfile if k.endswith(".scales")) == rec["quantized"]
+    assert {k: array_digest(v) for k, v in qfile.items()} == rec["params_8bit"]
+    deq = dequantize_mlx_checkpoint(qfile, 8)
+    assert set(deq) == set(ours) and all(deq[k].shape == ours[k].shape for k in ours)
     want = json.load(open(os.path.join(GOLDEN, "ref_checkpoint_keymap.json")))      # written from a full-depth (22 blocks) run
-    if depth != 22:
-        keep = lambda k: ".transformer_blocks." not in k or int(k.split(".transformer_blocks.")[1].split(".")[0]) < depth
-        want = dict(keymap={k: v for k, v in want["keymap"].items() if keep(k)}, quantized=[k for k in want["quantized"] if keep(k)])
-    assert got == want, "tests/golden/ref_checkpoint_keymap.json is stale: regenerate it with F5_FULL_DEPTH=1 from result.json"
+    keep = lambda k: ".transformer_blocks." not in k or int(k.split(".transformer_blocks.")[1].split(".")[0]) < depth   # noqa: E731
+    want = dict(keymap={k: v for k, v in want["keymap"].items() if keep(k)}, quantized=[k for k in want["quantized"] if keep(k)])
+    assert dict(keymap={k: list(v.shape) for k, v in sorted(ours.items())}, quantized=rec["quantized"]) == want
 
 
 def test_checkpoint_conversion_matches_committed_reference_keymap():

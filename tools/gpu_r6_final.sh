@@ -11,8 +11,8 @@ timeout 2700 python -m pytest tests -m gpu -q -rA --tb=short -p no:cacheprovider
 grep -E "^\[(ln_fold|f16 range|f16 saturation|bf16 \+ ln_fold|batch32|batch 32 vs oracle|full-size|ragged|mid batch|one-utterance|batch_sentences)" $OUT/pytest.txt | sort -u > $OUT/gpu_tests_printed_figures.txt
 echo "pytest exit $?" >> $OUT/pytest.txt; grep -E "passed|failed" $OUT/pytest.txt | tail -2; grep -E "^FAILED" $OUT/pytest.txt | head
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1; tail -2 $OUT/smoke.txt
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; cut -c1-300 $OUT/bench_default.json
-timeout 600 python bench.py --config c5 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_c5_mxfp8.json 2> $OUT/bench_c5.err; cut -c1-300 $OUT/bench_c5_mxfp8.json
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; cut -c1-300 $OUT/bench_default.json
+timeout 600 python bench.py --config c5 --steps 3 --warmup 1 --full --no-cpu-baseline > $OUT/bench_c5_mxfp8.json 2> $OUT/bench_c5.err; cut -c1-300 $OUT/bench_c5_mxfp8.json
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_b1 -o b1 -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-sub > $R/$OUT/prof_b1.json 2> $R/$OUT/prof_b1.err
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_b32 -o b32 -- python $R/bench.py --batch 32 --steps 3 --warmup 1 --no-cpu-baseline --no-sub > $R/$OUT/prof_b32.json 2> $R/$OUT/prof_b32.err
