@@ -1383,14 +1383,10 @@ extern "C" int f5_dit_forward(f5_engine* e, const f5_sample_args* a, const float
 // ------------------------------------------------------------------------------------------------
 // Test hooks.  They live in both kernel builds (bf16 / fp16 operands) and are process-wide: meant for the op-level tests and the
 // A/B tools, which set them once; a change bumps g_knob_epoch, so no cached hipGraph captured under other values is replayed.
-// The PRODUCT library keeps only the hooks that choose among the kernels sample() itself can reach (tile shapes, attention
-// workgroup shapes, conv-pos pipeline step, tile numbering); everything that selects an experiment exists in the lab build only
-// (F5_LAB=1 bash build.sh: superseded / rejected kernels, ablations, stream-K, priorities).
+// They choose only among the kernels sample() itself can reach (tile shapes, attention workgroup shapes, conv-pos pipeline step,
+// tile numbering).
 #define F5_DECL_KNOB(v) namespace f5bf { extern int v; } namespace f5hf { extern int v; }
 #define F5_SET_BOTH(v, x) do { f5bf::v = (x); f5hf::v = (x); ++g_knob_epoch; } while (0)
-#ifndef F5_LAB
-#define F5_LAB 0
-#endif
 F5_DECL_KNOB(f5_convpos_tps)
 F5_DECL_KNOB(f5_convpos_xcd_map)
 F5_DECL_KNOB(f5_attn_wide)
@@ -1402,7 +1398,6 @@ F5_DECL_KNOB(f5_gemm_nband)
 F5_DECL_KNOB(f5_gemm_qkv_small_tile)
 F5_DECL_KNOB(f5_gemm_debug_flags)
 F5_DECL_KNOB(f5_gemm_tile_override)
-extern "C" int f5_lab_build(void) { return F5_LAB; }      // 1 = this library also carries the experiments
 extern "C" int f5_op_set_operand_type(int fp16) {
     F5_REQUIRE(fp16 == 0 || fp16 == 1, "operand type must be 0 (bf16) or 1 (fp16)");
     g_ops.h = fp16 != 0;
@@ -1444,11 +1439,7 @@ extern "C" int f5_debug_set_q_premul(int on) {
     return 0;
 }
 extern "C" int f5_debug_set_attn_wide(int v) {
-#if F5_LAB
-    F5_REQUIRE(v >= -1 && v <= 2, "attention wide-workgroup switch must be -1 (auto), 0, 1 (256-query workgroups) or 2 (lab: role-split 512-query workgroups)");
-#else
     F5_REQUIRE(v >= -1 && v <= 1, "attention wide-workgroup switch must be -1 (auto), 0 or 1 (256-query workgroups)");
-#endif
     F5_SET_BOTH(f5_attn_wide, v);
     return 0;
 }
@@ -1489,65 +1480,10 @@ extern "C" int f5_debug_set_gemm_flags(int v) {
 }
 extern "C" int f5_debug_set_gemm_tile(int sel) {
     F5_REQUIRE(sel >= 0 && sel <= 14, "gemm tile override must be 0 (auto) .. 14");
-    F5_REQUIRE(F5_LAB || sel != 7, "gemm tile 7 (128x256, two workgroups per CU) exists in the lab build only");
+    F5_REQUIRE(sel != 7, "gemm tile 7 does not exist (tiles are 0 .. 6 and 8 .. 14)");
     F5_SET_BOTH(f5_gemm_tile_override, sel);
     return 0;
 }
-#if F5_LAB
-F5_DECL_KNOB(f5_attn_version)
-F5_DECL_KNOB(f5_attn_ablation)
-F5_DECL_KNOB(f5_attn_variant)
-F5_DECL_KNOB(f5_attn_prio)
-F5_DECL_KNOB(f5_gemm_big_kernel)
-F5_DECL_KNOB(f5_gemm128_pad_lds)
-F5_DECL_KNOB(f5_gemm_v3_stagger)
-F5_DECL_KNOB(f5_gemm_v3_prio)
-F5_DECL_KNOB(f5_gemm_streamk)
-extern "C" int f5_debug_set_attn_version(int v) {
-    F5_REQUIRE(v >= 1 && v <= 6, "attention version must be 1..6");
-    F5_SET_BOTH(f5_attn_version, v);
-    return 0;
-}
-extern "C" int f5_debug_set_attn_variant(int v) {
-    F5_REQUIRE(v >= 0 && v <= 63, "attention variant bits: 1 = single-issue softmax VALU, 2 = one workgroup per CU, 4 = 2-D block numbering, 8 = eager rescale, 16 = per-tile maximum (v2w) in the large-grid kernel, 32 = role-split kernel keeps Q in LDS");
-    F5_SET_BOTH(f5_attn_variant, v);
-    return 0;
-}
-extern "C" int f5_debug_set_attn_ablation(int v) {
-    F5_SET_BOTH(f5_attn_ablation, v);
-    return 0;
-}
-extern "C" int f5_debug_set_attn_prio(int v) {
-    F5_REQUIRE(v >= 0 && v <= 2, "attention priority scheme must be 0 (MFMA clusters), 1 (none) or 2 (softmax section)");
-    F5_SET_BOTH(f5_attn_prio, v);
-    return 0;
-}
-extern "C" int f5_debug_set_gemm_streamk(int v) {
-    F5_REQUIRE(v >= 0 && v <= 2, "stream-K switch must be 0 (off), 1 (full) or 2 (hybrid)");
-    if (v != 0) {
-        RC(f5bf::f5_gemm_streamk_init());   // scratch on the CURRENT device; call outside of any stream capture
-        RC(f5hf::f5_gemm_streamk_init());
-    }
-    F5_SET_BOTH(f5_gemm_streamk, v);
-    return 0;
-}
-extern "C" int f5_debug_gemm_streamk_error() { return f5bf::f5_gemm_streamk_error() | f5hf::f5_gemm_streamk_error(); }
-extern "C" int f5_debug_set_gemm_big_kernel(int v, int stagger_cycles) {
-    F5_REQUIRE(v >= 2 && v <= 5, "big GEMM kernel must be 2 (256x256 role-split), 3 (128x256 v3), 4 (256x256 lock-step) or 5 (128x256 prefetching, two per CU)");
-    F5_SET_BOTH(f5_gemm_big_kernel, v);
-    F5_SET_BOTH(f5_gemm_v3_stagger, stagger_cycles);
-    return 0;
-}
-extern "C" int f5_debug_set_gemm128_pad(int bytes) {
-    F5_SET_BOTH(f5_gemm128_pad_lds, bytes);
-    return 0;
-}
-extern "C" int f5_debug_set_gemm_v3_prio(int v) {
-    F5_REQUIRE(v >= 0 && v <= 2, "128x256 GEMM priority scheme must be 0 (MFMA clusters), 1 (none) or 2 (epilogue)");
-    F5_SET_BOTH(f5_gemm_v3_prio, v);
-    return 0;
-}
-#endif  // F5_LAB
 
 // op-level twins of the LN fold (gemm.hpp fold_*): what run_dit sets on its block GEMMs, for the per-op entry points
 static struct {

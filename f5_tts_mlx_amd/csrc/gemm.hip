@@ -14,12 +14,6 @@
 #include "gemm_dev.hpp"
 #include "rowops.hpp"     // f5_sat_flag_host
 #include "lnrow.hpp"
-#ifndef F5_LAB
-#define F5_LAB 0
-#endif
-#if F5_LAB
-#include "gemm_lab_dev.hpp"
-#endif
 
 namespace F5_NS {
 
@@ -303,12 +297,6 @@ __global__ __launch_bounds__(256) void f5_gemm_kernel(F5GemmArgs p, int tiles_n,
                                           n0 + wn * (32 * NB), lane);
         return;
     }
-#if F5_LAB
-    if (EPI == EPI_RESID_GATE && p.ln_counter == nullptr && (p.debug_flags & 8) != 0) {    // experiment: residual update by L2 atomics
-        atomic_epilogue_resid<MB, NB>(p, acc, m0 + wm * (32 * MB), n0 + wn * (32 * NB), lane);
-        return;
-    }
-#endif
     gemm_epilogue<EPI, MB, NB>(p, acc, m0, n0, wm, wn, lane);
     if (EPI == EPI_RESID_GATE && p.ln_counter) resid_ln_tail(p, tm, BMt, (p.N + BNt - 1) / BNt);
 }
@@ -337,8 +325,8 @@ static int ring_order(const F5GemmArgs& a, int tiles_m, int tiles_n) {
     return gemm_mfast(a) ? -tiles_m : tiles_n;
 }
 
-// ABL (timing experiments only, results are garbage; tools/ring_ablate.py): 1 = no operand loads after the prologue, 2 = no MFMAs,
-// 4 = no LDS fragment reads, 8 = no workgroup barrier -- what a K step of a lone workgroup is made of
+// ABL (timing ablations, results are garbage; every launch here passes 0, which compiles none of them in): 1 = no operand loads after
+// the prologue, 2 = no MFMAs, 4 = no LDS fragment reads, 8 = no workgroup barrier -- what a K step of a lone workgroup is made of
 // FOLD (round 6, batch-1-sized launches of the LN fold, gemm.hpp): 1 = EPI_RESID_GATE writes the folded operand and its slice statistics
 // (staged_epilogue_resid with its loads requested before the K loop), 2 = EPI_GELU_TANH is a fold consumer that merges the producer's statistics itself (fold_stats), on
 // transposed wave tiles like the large kernels
@@ -618,12 +606,6 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void f5_gemm_ring_kernel(F5GemmA
                                           n0 + wn * (32 * NB), lane);
         return;
     }
-#if F5_LAB
-    if (EPI == EPI_RESID_GATE && p.ln_counter == nullptr && (p.debug_flags & 8) != 0) {    // experiment: residual update by L2 atomics
-        atomic_epilogue_resid<MB, NB>(p, acc, m0 + wm * (32 * MB), n0 + wn * (32 * NB), lane);
-        return;
-    }
-#endif
     if constexpr (FOLD == 1) {
         // staging area behind the K-split reduction area (other waves of the group may still be reading theirs)
         constexpr int RED_BYTES = (KS - 1) * WM * WN * MB * NB * 16 * 64 * 4;
@@ -704,39 +686,17 @@ static int launch_ring8(const F5GemmArgs& a, hipStream_t stream) {
 // (tools/qkv_tiles_bench.py): 27.0-28.1 / 24.7-24.8 us against 25.5-27.2 us for the register-staged 64x128 default, and
 // 22.3-23.1 us at M = 937 where only 96 workgroups exist: a lone workgroup takes ~1.4 us per K tile whatever the fill, three
 // times its MFMA time -- neither L2 bytes nor occupancy is what bounds this shape.  Kept as overrides, not selected.
-template <int EPI, int MB, int NB, int WM, int WN, int KS = 1, int ABL = 0>
+template <int EPI, int MB, int NB, int WM, int WN>
 static int launch_ring_wide(const F5GemmArgs& a, hipStream_t stream) {
     constexpr int BMt = 32 * MB * WM, BNt = 32 * NB * WN;
     F5_REQUIRE(a.N % BNt == 0, "gemm: this tile needs N %% %d == 0", BNt);
     const int tiles_m = f5_cdiv(a.M, BMt), tiles_n = a.N / BNt;
     const int ntiles = tiles_m * tiles_n;
     const int order = ring_order(a, tiles_m, tiles_n);
-    hipLaunchKernelGGL((f5_gemm_ring_kernel<EPI, MB, NB, 3, WM, WN, KS, ABL>), dim3(ntiles), dim3(64 * WM * WN * KS), 0, stream, a, order,
-                       ntiles);
+    hipLaunchKernelGGL((f5_gemm_ring_kernel<EPI, MB, NB, 3, WM, WN>), dim3(ntiles), dim3(64 * WM * WN), 0, stream, a, order, ntiles);
     F5_LAUNCH_CHECK();
     return 0;
 }
-#if F5_LAB
-// timing-only ablations of the ring main loop (debug flags bits 4-7), bf16 epilogue, tile 13 (128x256, 8 waves) and tile 10
-// (64x128, two K groups of 4 waves)
-template <int ABL>
-static int launch_ring_ablate(const F5GemmArgs& a, int sel, hipStream_t stream) {
-    return sel == 13 ? launch_ring_wide<EPI_BF16, 1, 4, 4, 2, 1, ABL>(a, stream) : launch_ring_wide<EPI_BF16, 1, 2, 2, 2, 2, ABL>(a, stream);
-}
-static int launch_ring_ablate(const F5GemmArgs& a, int sel, int abl, hipStream_t stream) {
-    switch (abl) {
-        case 1: return launch_ring_ablate<1>(a, sel, stream);
-        case 2: return launch_ring_ablate<2>(a, sel, stream);
-        case 4: return launch_ring_ablate<4>(a, sel, stream);
-        case 8: return launch_ring_ablate<8>(a, sel, stream);
-        case 6: return launch_ring_ablate<6>(a, sel, stream);     // loads + barrier only
-        case 7: return launch_ring_ablate<7>(a, sel, stream);     // barrier + loop skeleton
-        case 9: return launch_ring_ablate<9>(a, sel, stream);     // LDS reads + MFMAs, no loads, no barrier
-        case 15: return launch_ring_ablate<15>(a, sel, stream);   // loop skeleton
-        default: f5_set_error("gemm: ablation %d is not instantiated", abl); return 2;
-    }
-}
-#endif  // F5_LAB
 
 template <int EPI, int MB, int NB>
 static int launch_cfg(const F5GemmArgs& a, hipStream_t stream) {
@@ -750,15 +710,8 @@ static int launch_cfg(const F5GemmArgs& a, hipStream_t stream) {
 // tile shape: the largest of 128x128 / 64x128 / 64x64 that still gives the 256 CUs >= 1.5 workgroups each
 // (small-batch shapes such as M = 1874 are otherwise a fraction of one wave of tiles)
 int f5_gemm_tile_override = 0;  // 0 auto, 1 = 128x128, 2 = 64x128, 3 = 64x64, 4 = 256x256 v2, 5 = 64x128 ring, 6 = 64x64 ring,
-                                // 7 = 128x256 v3, 8 = 128x192 8-wave ring, 9 = 128x128 8-wave ring, 10 / 11 = 64x128 / 128x128 split-K ring
+                                // 8 = 128x192 8-wave ring, 9 = 128x128 8-wave ring, 10 / 11 = 64x128 / 128x128 split-K ring
 int f5_gemm_debug_flags = 0;
-#if F5_LAB
-int f5_gemm_big_kernel = 2;       // large shapes: 2 = 256x256 role-split schedule (gemm256.hip, the product kernel), 3 = 128x256 v3 (2 WG/CU),
-                                  // 4 = 256x256 lock-step (rounds 1-2), 5 = 128x256 with in-wave fragment prefetch (gemm128.hip)
-extern int f5_gemm_streamk;
-int f5_launch_gemm_lab_v2(const F5GemmArgs& a, int epi, hipStream_t stream);   // gemm_lab.hip
-int f5_launch_gemm_lab_v3(const F5GemmArgs& a, int epi, hipStream_t stream);
-#endif
 int f5_gemm_qkv_small_tile = 0;   // small-M QKV projection with pair-major tables: 0 = auto tiles, 12 / 13 = 8-wave 128x256 ring, transposed q / k
 int f5_gemm_ring_default = 1;   // auto mode: small tiles use the global_load_lds ring kernel
 // the large-shape kernels (256x256, 128x256) have no fused LN tail (at those sizes LN-modulate is HBM-bound, not launch-bound)
@@ -766,7 +719,7 @@ static bool gemm_uses_big_kernel(const F5GemmArgs& a) {
     const long t256 = (long)f5_cdiv(a.M, 256) * (a.N / 256);
     const bool v2ok = (a.N % 256 == 0) && (a.M >= 256);
     const int sel = f5_gemm_tile_override;
-    return sel == 7 || sel == 4 || (sel == 0 && v2ok && t256 >= 512);     // (7 = the lab build's 128x256 kernel)
+    return sel == 4 || (sel == 0 && v2ok && t256 >= 512);
 }
 bool f5_gemm_resid_ln_fusable(const F5GemmArgs& a) {
     return !gemm_uses_big_kernel(a) && a.N % 256 == 0 && a.N >= 256 && a.N <= 1024 && a.ldo == a.N && a.M <= 64 * 65536;
@@ -776,9 +729,6 @@ bool f5_gemm_resid_ln_fusable(const F5GemmArgs& a) {
 bool f5_gemm_runs_staged(const F5GemmArgs& a, int epi) {
     if (!(epi == EPI_RESID_GATE || epi == EPI_QKV_ROPE || epi == EPI_GELU_TANH) || a.ln_counter != nullptr || a.N % 256 != 0) return false;
     const int sel = f5_gemm_tile_override;
-#if F5_LAB
-    if (sel == 7 || f5_gemm_big_kernel != 2 || f5_gemm_streamk) return false;
-#endif
     const long t256 = (long)f5_cdiv(a.M, 256) * (a.N / 256);
     const long t128 = (long)f5_cdiv(a.M, 128) * f5_cdiv(a.N, 128);
     if (sel == 4 || (sel == 0 && a.M >= 256 && t256 >= 512)) return a.M >= 256;
@@ -1050,30 +1000,10 @@ static int launch_epi(const F5GemmArgs& a, hipStream_t stream) {
     int sel = f5_gemm_tile_override;
     const long t256 = (long)f5_cdiv(a.M, 256) * (a.N / 256);
     const bool v2ok = (a.N % 256 == 0) && (a.M >= 256);
-#if F5_LAB
-    if (sel == 7 || (sel == 0 && v2ok && t256 >= 512 && f5_gemm_big_kernel == 3)) {
-        F5_REQUIRE(v2ok && a.K % 32 == 0, "gemm: the 128x256 kernel needs N %% 256 == 0 and M >= 256");
-        return f5_launch_gemm_lab_v3(a, EPI, stream);
-    }
-#endif
     if (sel == 4 || (sel == 0 && v2ok && t256 >= 512)) {
         F5_REQUIRE(v2ok, "gemm: the 256x256 kernel needs N %% 256 == 0 and M >= 256");
-#if F5_LAB
-        F5_REQUIRE((a.x16_out == nullptr && a.fold_rowf == nullptr) || (f5_gemm_big_kernel == 2 && !f5_gemm_streamk),
-                   "gemm: the LN fold needs the product 256x256 kernel");
-        if (f5_gemm_big_kernel == 4 || f5_gemm_streamk) return f5_launch_gemm_lab_v2(a, EPI, stream);      // lock-step predecessor (A/B)
-        if constexpr (EPI == EPI_F32 || EPI == EPI_BF16 || EPI == EPI_GELU_TANH || EPI == EPI_RESID_GATE || EPI == EPI_QKV_ROPE) {
-            if (f5_gemm_big_kernel == 5) return f5_launch_gemm128(a, EPI, stream);              // 128x256, two workgroups per CU
-        }
-#endif
         return f5_launch_gemm256(a, EPI, stream);
     }
-#if F5_LAB
-    if constexpr (EPI == EPI_BF16) {
-        const int abl = (a.debug_flags >> 4) & 15;
-        if (abl && (sel == 13 || sel == 10) && a.N % 256 == 0) return launch_ring_ablate(a, sel, abl, stream);
-    }
-#endif
     if constexpr (EPI == EPI_F32 || EPI == EPI_BF16 || EPI == EPI_GELU_TANH || EPI == EPI_RESID_GATE || EPI == EPI_QKV_ROPE) {
         // role-split 128 x 256 tiles (gemm_rs128.hip): forced by tile 14, or by the QKV-only knob at batch-1-sized shapes
         long t128x256 = (long)f5_cdiv(a.M, 128) * (a.N / 256);
@@ -1131,7 +1061,7 @@ static int launch_epi(const F5GemmArgs& a, hipStream_t stream) {
         if (a.N % 128 == 0 && t128 >= 176 && t128 <= 256) return launch_ring8<EPI, 2>(a, stream);
         if (t64x128 >= 176 && t64x128 <= 256) return launch_ring_ks2<EPI, 1>(a, stream);
     }
-    if (sel == 0 || sel == 4 || sel == 7) sel = t128 >= 384 ? 1 : (t64x128 >= 384 ? 2 : 3);
+    if (sel == 0 || sel == 4) sel = t128 >= 384 ? 1 : (t64x128 >= 384 ? 2 : 3);
     if (EPI == EPI_QKV_ROPE && sel == 3) sel = 2;
     if (EPI == EPI_QKV_ROPE && sel == 6) sel = 5;  // the V^T / head mapping wants >= one whole head per tile column
     if (sel == 5) return launch_ring<EPI, 1, 2>(a, stream);

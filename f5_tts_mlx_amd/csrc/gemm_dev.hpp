@@ -8,20 +8,6 @@ namespace F5_NS {
 
 #define BK 64
 
-// Measurement build only (F5_PROBE=1 bash build.sh -> libf5tts_hip_probe.so, tools/r5_epilogue_probe.py): ablation switches of the
-// staged epilogues, read from F5GemmArgs::debug_flags.  In the product build they are compile-time false and leave no code.
-#ifndef F5_PROBE
-#define F5_PROBE 0
-#endif
-#define F5_PROBE_NOSTORE(p_) (F5_PROBE && ((p_).debug_flags & 0x10000))   // the epilogue runs, its global stores do not (q / k / FF1 / x)
-#define F5_PROBE_NOVSTORE(p_) (F5_PROBE && ((p_).debug_flags & 0x8000))   // the same for the transposed V tiles of the QKV projection
-#define F5_PROBE_NOMATH(p_) (F5_PROBE && ((p_).debug_flags & 0x20000))    // no GELU / rotation arithmetic (and no table loads)
-#define F5_PROBE_NT(p_) (F5_PROBE && ((p_).debug_flags & 0x40000))        // residual stream read / written non-temporally
-template <typename T>
-__device__ __forceinline__ void f5_probe_sink(const T& v) {
-    asm volatile("" ::"v"(v));
-}
-
 // ---- packed-f32 epilogue arithmetic (round 5).  The staged epilogues are bound by the VALU ISSUE rate of their two waves per SIMD (one
 // instruction per ~5.4 cycles and wave whatever its width, tools/probes/valu_rate.hip), so their per-element arithmetic -- the LN-fold
 // factors, GELU's polynomial, the rotation, the bias -- runs on element PAIRS with v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32: the same
@@ -539,9 +525,7 @@ __device__ __forceinline__ void staged_epilogue_bf16(const F5GemmArgs& p, f32x16
                         const u32x4 val = *reinterpret_cast<const u32x4*>(&reg[d * TLD + t0]);
                         const int head = head0 + (d >> 6), dd = d & 63;
                         u16* dst = dstbase + ((size_t)(b * p.heads + head) * 64 + dd) * p.npad + n;
-                        if (F5_PROBE_NOVSTORE(p)) {
-                            f5_probe_sink(val);
-                        } else if (n + 8 <= p.seq_len && grow + 8 <= p.M) {
+                        if (n + 8 <= p.seq_len && grow + 8 <= p.M) {
                             *reinterpret_cast<u32x4*>(dst) = val;       // may be only 2-byte aligned: legal on gfx950
                         } else {
 #pragma unroll
@@ -633,7 +617,7 @@ __device__ __forceinline__ void staged_epilogue_tr(const F5GemmArgs& p, f32x16 (
                     } else {
                         v[h] = a + c2h;
                     }
-                    if (EPI == EPI_GELU_TANH && !F5_PROBE_NOMATH(p)) v[h] = f5_gelu_tanh2(v[h]);
+                    if (EPI == EPI_GELU_TANH) v[h] = f5_gelu_tanh2(v[h]);
                     if (EPI == EPI_GELU_ERF_BF16) v[h] = f5_f32x2{f5_gelu_erf(v[h][0]), f5_gelu_erf(v[h][1])};
                 }
                 const int so = lcol * LD + nb * 32 + rg * 8 + hi * 4;
@@ -652,9 +636,7 @@ __device__ __forceinline__ void staged_epilogue_tr(const F5GemmArgs& p, f32x16 (
         for (int i = 0; i < 32 / RPI; ++i) {
             const int lrow = i * RPI + lane / CPR, chunk = lane % CPR;
             const int grow = rowblk + lrow;
-            if (F5_PROBE_NOSTORE(p)) {
-                f5_probe_sink(back[i]);
-            } else if (grow < p.M) {
+            if (grow < p.M) {
                 const size_t off = (size_t)grow * p.ldob + colbase + chunk * 8;
                 *reinterpret_cast<u32x4*>(p.out_bf[0] + off) = back[i];
                 if (two) *reinterpret_cast<u32x4*>(p.out_bf[1] + off) = *reinterpret_cast<const u32x4*>(&rl[lrow * LD + chunk * 8]);
@@ -718,20 +700,15 @@ __device__ __forceinline__ void staged_epilogue_tr_rope(const F5GemmArgs& p, f32
 #pragma unroll
             for (int rg = 0; rg < 4; ++rg) {
                 const int c = colbase + nb * 32 + rg * 8 + hi * 4;
-                if (F5_PROBE_NOMATH(p)) {
-                    c0[rg] = c1[rg] = 1.0f;
-                    s0[rg] = s1[rg] = 0.0f;
-                } else {
-                    // features c .. c + 3 of a 64-wide head = rotation pairs 2g, 2g + 1 with g = ((c & 63) >> 2): its hi part is in loff
-                    const int g0 = (((colbase & 63) + nb * 32 + rg * 8) & 63) >> 2;   // wave-uniform (colbase is a multiple of 32)
-                    gcchar* gb = tb + (size_t)g0 * gstep;
-                    asm volatile("" : "+v"(loff));                                   // (keeps the zero-extension next to the load: saddr form)
-                    const f32x4 cs = *(gcf32x4*)(gb + loff);
-                    c0[rg] = cs[0];
-                    c1[rg] = cs[1];
-                    s0[rg] = cs[2];
-                    s1[rg] = cs[3];
-                }
+                // features c .. c + 3 of a 64-wide head = rotation pairs 2g, 2g + 1 with g = ((c & 63) >> 2): its hi part is in loff
+                const int g0 = (((colbase & 63) + nb * 32 + rg * 8) & 63) >> 2;   // wave-uniform (colbase is a multiple of 32)
+                gcchar* gb = tb + (size_t)g0 * gstep;
+                asm volatile("" : "+v"(loff));                                   // (keeps the zero-extension next to the load: saddr form)
+                const f32x4 cs = *(gcf32x4*)(gb + loff);
+                c0[rg] = cs[0];
+                c1[rg] = cs[1];
+                s0[rg] = cs[2];
+                s1[rg] = cs[3];
                 if (FOLD) {
                     const f32x4 c1q = *reinterpret_cast<const f32x4*>(&fl[c - colbase]), c2q = *reinterpret_cast<const f32x4*>(&fl[W + c - colbase]);
                     const f5_f32x2 lo = f5_fma2(nr1v, f5_f32x2{c1q[0], c1q[1]}, f5_f32x2{c2q[0], c2q[1]});
@@ -777,9 +754,7 @@ __device__ __forceinline__ void staged_epilogue_tr_rope(const F5GemmArgs& p, f32
         for (int i = 0; i < 32 / RPI; ++i) {
             const int lrow = i * RPI + lane / CPR, chunk = lane % CPR;
             const int grow = rowblk + lrow;
-            if (F5_PROBE_NOSTORE(p)) {
-                f5_probe_sink(back[i]);
-            } else if (grow < p.M) {
+            if (grow < p.M) {
                 const size_t off = (size_t)grow * p.ldob + colbase + chunk * 8;
                 *reinterpret_cast<u32x4*>(p.out_bf[0] + off) = back[i];
                 if (two) *reinterpret_cast<u32x4*>(p.out_bf[1] + off) = *reinterpret_cast<const u32x4*>(&rl[lrow * LD + chunk * 8]);
@@ -866,10 +841,6 @@ __device__ __forceinline__ void staged_epilogue_resid(const F5GemmArgs& p, f32x1
             }
             const int grow = rowblk + i * RPI + lane / CPR;
             const bool ok = grow < p.M;
-            if (F5_PROBE_NT(p))
-                xr[i] = ok ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p.out_f32 + (size_t)grow * p.ldo + colbase + chunk * 4))
-                           : f32x4{0.f, 0.f, 0.f, 0.f};
-            else
             xr[i] = ok ? *reinterpret_cast<const f32x4*>(p.out_f32 + (size_t)grow * p.ldo + colbase + chunk * 4)
                        : f32x4{0.f, 0.f, 0.f, 0.f};
             kraw[i] = (ok && p.rowkeep != nullptr) ? (uint32_t)p.rowkeep[grow] : 1u;
@@ -896,10 +867,6 @@ __device__ __forceinline__ void staged_epilogue_resid(const F5GemmArgs& p, f32x1
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = xr[i][e] + g4[e] * (kraw[i] != 0u ? v[e] : 0.0f);   // a select, like gemm_epilogue: a non-finite
                                                                                                   // accumulator of a masked row must not reach x
-            if (F5_PROBE_NOSTORE(p)) f5_probe_sink(o);
-            else if (F5_PROBE_NT(p)) {
-                if (grow < p.M) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(p.out_f32 + (size_t)grow * p.ldo + colbase + chunk * 4));
-            } else
             if (grow < p.M) *reinterpret_cast<f32x4*>(p.out_f32 + (size_t)grow * p.ldo + colbase + chunk * 4) = o;
             if (CPR == 16 && p.x16_out != nullptr) {          // (64-column wave tiles only: the launcher refuses the others)
                 // LN fold (F5GemmArgs): (x - m)(1 + s) in the operand type is the next GEMM's A operand, m = the row's mean at the

@@ -259,25 +259,23 @@ int f5_op_istft(const float* x, int ldx, const float* window, float* frames_scra
 uint16_t f5_debug_f2h_bits(float f);
 float f5_debug_h_bits2f(uint16_t h);
 uint16_t f5_debug_f2bf_bits(float f);
-/* ---- test hooks of the product library.  Process-wide (set them once, before the calls they should affect); they choose among
- * kernels that sample() itself reaches by shape, so that small test shapes can exercise every shipped tile path.  Hooks that select
- * experiments (superseded kernels, ablations, stream-K, priorities) exist in the lab build only: include/f5tts_hip_lab.h,
- * `F5_LAB=1 bash f5_tts_mlx_amd/csrc/build.sh`; f5_lab_build() tells which library is loaded. */
-int f5_lab_build(void);
+/* ---- test hooks.  Process-wide (set them once, before the calls they should affect); they choose among kernels that sample()
+ * itself reaches by shape, so that small test shapes can exercise every shipped tile path. */
 /* force the GEMM block tile: 0 auto, 1 = 128x128, 2 = 64x128, 3 = 64x64 (register-staged), 4 = 256x256 (gemm256.hip), 5 / 6 = ring
  * 64x128 / 64x64, 8 / 9 = 8-wave ring 128x192 / 128x128, 10 / 11 = in-workgroup split-K 64x128 / 128x128, 12 / 13 = 8-wave ring
- * 128x256 with 64x64 / 32x128 wave tiles (7 = the lab build's 128x256 two-per-CU kernel) */
+ * 128x256 with 64x64 / 32x128 wave tiles */
 int f5_debug_set_gemm_tile(int sel);
 /* GEMM flag bits, OR-ed into every GEMM launch of the process (an engine's own: f5_engine_set_option "gemm_flags"):
  * bit 0: skip the epilogue of the 256x256 kernel (timing only; results are garbage);
  * bit 1: small-tile kernels use the direct (2-byte store) epilogue instead of the LDS-staged one;
+ * bit 3 (8): routes the residual update exactly like bit 8 (the two are tested together);
  * bit 8 (256): the small-tile ring kernels load x / bias / gate / keep of the residual update in the epilogue instead of
  *            requesting them before the K loop (A/B of the default; identical bits);
  * bit 12 (4096): the role-split 128x256 kernel numbers its tiles as an XCD-chunked list (M fastest) instead of dealing a 2 x 4
  *            grid of tile blocks to the XCDs (A/B of the default; identical bits);
  * bit 14 (16384): the 256x256 kernel accumulates 16-bit-output tiles (FF1, plain 16-bit, q / k of QKV) in the straight order with
  *            2-byte staging writes instead of transposed with 8-byte ones (A/B; identical bits for FF1 / plain);
- * lab build only: bit 3 (8) residual update by no-return L2 atomics, bits 9-11 x-tile prefetch, bits 4-7 ring-loop ablations */
+ * bits 4-7 and 9-11 are read nowhere. */
 int f5_debug_set_gemm_flags(int v);
 /* ring GEMM tile numbering: 0 auto (band-major one-round launches whose A fits an L2, else m / n fastest), 1 n fastest, 2 m fastest,
  * 3 band-major (bands of 4 column tiles) wherever the tile grid allows */

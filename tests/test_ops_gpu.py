@@ -203,31 +203,6 @@ def test_attention_ragged_mask(lib, nseg):
     _attention_case(lib, 3, 2, 200, [200, 130, 1], nseg, seed=7)
 
 
-@pytest.mark.lab
-@pytest.mark.parametrize("version", [5, 6])
-@pytest.mark.parametrize("N", [1, 63, 64, 65, 130, 257, 499, 937])
-def test_attention_pipelined_kernel_shapes(lib, version, N):
-    """the in-wave software-pipelined kernel (attention.hip v5; 6 = the same without pinned instruction groups): every tile
-    count parity (1, 2, odd, even), partial last tiles, query blocks beyond the sequence"""
-    E.check(lib.f5_debug_set_attn_version(version))
-    try:
-        _attention_case(lib, 1, 2, N, None, 1, seed=N)
-    finally:
-        E.check(lib.f5_debug_set_attn_version(2))
-
-
-@pytest.mark.lab
-@pytest.mark.parametrize("version", [5])
-def test_attention_pipelined_kernel_ragged_and_batched(lib, version):
-    E.check(lib.f5_debug_set_attn_version(version))
-    try:
-        _attention_case(lib, 3, 2, 200, [200, 130, 1], 1, seed=7)
-        _attention_case(lib, 2, 16, 937, [937, 600], 1, seed=8)
-        test_attention_softmax_spike(lib, hp=0)
-    finally:
-        E.check(lib.f5_debug_set_attn_version(2))
-
-
 def test_attention_softmax_spike(lib, hp=1, premul=False, N=300, spikes=((70, 30.0), (200, 60.0))):
     """force large running-max jumps across KV tiles (online-softmax rescale path)."""
     B, H, D = 1, 2, 128
@@ -644,19 +619,6 @@ def test_attention_path_with_v2_qkv(lib, force_v2, nseg):
     _attention_case(lib, 2, 4, 300, [300, 211], nseg, seed=21)     # D = 256: QKV GEMM runs on the 256x256 kernel
 
 
-@pytest.mark.lab
-@pytest.mark.parametrize("ver", [1, 3, 4])
-def test_attention_other_kernel_versions(lib, ver):
-    """the older kernels stay selectable through the debug hook (A/B benchmarking); default is version 2"""
-    E.check(lib.f5_debug_set_attn_version(ver))
-    try:
-        _attention_case(lib, 2, 2, 333, [333, 100], 1, seed=5)
-        _attention_case(lib, 1, 2, 130, None, 3, seed=6)
-        _attention_case(lib, 1, 2, 937, None, 1, seed=7)
-    finally:
-        E.check(lib.f5_debug_set_attn_version(2))
-
-
 def test_attention_wide_workgroups(lib, mode=1):
     """256-query workgroups, two query blocks per wave (the large-grid bf16 kernel), forced on small problems: ragged key
     lengths, sequence tails inside the second query block, one-tile sequences"""
@@ -742,46 +704,6 @@ def test_attention_pipelined_v2p_large_grid_matches_v2f(lib):
     _with_pipelined_attention(lib, lambda: _attention_case(lib, 8, 16, 937, [937, 936, 900, 641, 640, 500, 65, 937], 1, seed=12, premul=True))
 
 
-@pytest.mark.lab
-@pytest.mark.parametrize("premul", [False, True])
-@pytest.mark.parametrize("q_in_lds", [False, True])
-def test_attention_role_split_kernel(lib, q_in_lds, premul):
-    """f5_attn2r_kernel (lab: measured slower than f5_attn2f, kept as the evidence): 512-query workgroups of 8 waves, the two
-    wave groups alternate MFMA and softmax segments one barrier apart.  Same cases as the shipped large-grid kernel: plain,
-    ragged, one-tile and partial-tile sequences, waves entirely past the sequence, spikes that force the exact path."""
-    E.check(lib.f5_debug_set_attn_wide(2))
-    E.check(lib.f5_debug_set_attn_kvsplit(1))
-    E.check(lib.f5_debug_set_attn_variant(32 if q_in_lds else 0))
-    try:
-        _attention_case(lib, 1, 2, 50, None, 1, seed=1, premul=premul)
-        _attention_case(lib, 3, 2, 200, [200, 130, 1], 1, seed=7, premul=premul)
-        _attention_case(lib, 2, 4, 300, [300, 211], 1, seed=21, premul=premul)
-        _attention_case(lib, 1, 2, 937, None, 1, seed=8, premul=premul)
-        _attention_case(lib, 6, 16, 1100, [1100, 1099, 513, 512, 64, 7], 1, seed=9, premul=premul)
-        for N, spikes in ((300, ((70, 30.0), (200, 60.0))), (937, ((936, 400.0),)), (500, ((3, 100.0),)), (700, ((64, 50.0), (65, 90.0), (640, 20.0)))):
-            test_attention_softmax_spike(lib, hp=0, premul=premul, N=N, spikes=spikes)
-    finally:
-        E.check(lib.f5_debug_set_attn_variant(0))
-        E.check(lib.f5_debug_set_attn_wide(-1))
-        E.check(lib.f5_debug_set_attn_kvsplit(-1))
-
-
-@pytest.mark.lab
-def test_attention_tile_maximum_kernels_still_selectable(lib):
-    """attention variant bit 16 = the kernels of round 1 / early round 2 (tile maximum on every tile), kept for A/B runs"""
-    E.check(lib.f5_debug_set_attn_variant(16))
-    try:
-        for wide in (1, -1):
-            E.check(lib.f5_debug_set_attn_wide(wide))
-            E.check(lib.f5_debug_set_attn_kvsplit(1 if wide == 1 else -1))
-            _attention_case(lib, 2, 4, 300, [300, 211], 1, seed=21)
-            _attention_case(lib, 1, 2, 937, None, 1, seed=8, premul=True)
-    finally:
-        E.check(lib.f5_debug_set_attn_variant(0))
-        E.check(lib.f5_debug_set_attn_wide(-1))
-        E.check(lib.f5_debug_set_attn_kvsplit(-1))
-
-
 @pytest.mark.parametrize("ks", [1, 2, 4])
 def test_attention_kv_split(lib, ks):
     """in-workgroup KV split (small-batch kernel): every split factor gives the one-pass result, including groups that
@@ -797,7 +719,7 @@ def test_attention_kv_split(lib, ks):
         E.check(lib.f5_debug_set_attn_kvsplit(-1))
 
 
-@pytest.mark.parametrize("tile", [0, 1, 2, 3, 4, 5, 6, pytest.param(7, marks=pytest.mark.lab), 8, 9, 10, 11, 14])
+@pytest.mark.parametrize("tile", [0, 1, 2, 3, 4, 5, 6, 8, 9, 10, 11, 14])
 @pytest.mark.parametrize("nseg", [1, 3])
 def test_gemm_resid_gate(lib, tile, nseg):
     """x += gate * ((A W^T + b) * keep[row])  (dit.py:172-173, 319, 323) on both GEMM kernels."""
@@ -1243,50 +1165,6 @@ def test_gemm_resid_gate_fused_ln_is_bit_identical(lib, tile, nseg):
         E.check(lib.f5_debug_set_gemm_tile(0))
 
 
-@pytest.mark.lab
-@pytest.mark.parametrize("nseg", [1, 3])
-@pytest.mark.parametrize("tile", [0, 2, 4, 5, 9, 10])
-def test_gemm_resid_gate_atomic_vs_load_add_store(lib, tile, nseg):
-    """Experiment kept behind gemm flag 8 (measured slower than the default load / add / store): the residual update
-    x += gate * v on the L2's atomic units (global_atomic_add_f32 without return, one add per element per launch).  It must be
-    deterministic (two launches from the same x: identical bits) and agree with the default form to the rounding of the product
-    (a few ulp of the operands), for the small-tile kernels and the 256x256 kernel, with row masking, ragged M (guarded tiles)
-    and interior tiles."""
-    E.check(lib.f5_debug_set_gemm_tile(tile))
-    try:
-        for (M, N, K) in ((1874, 1024, 1024), (700, 512, 256), (2100, 1024, 128), (333, 512, 192)):
-            r = rng(M + N + K + tile + nseg)
-            a, w, bias = randn(r, M, K), randn(r, N, K, scale=K ** -0.5), randn(r, N, scale=0.1)
-            gate, x0 = randn(r, N), randn(r, M, N, scale=2.0)
-            keep = torch.from_numpy((r.random(M) > 0.3).astype(np.uint8))
-            a_hi, a_lo = split_bf16(a.to(DEV))
-            w_hi, w_lo = split_bf16(w.to(DEV))
-            bias_d, gate_d, keep_d = bias.to(DEV), gate.to(DEV), keep.to(DEV)
-            res = {}
-            # 256 = the ring kernels load x / bias / gate / keep in the epilogue instead of before the K loop (same arithmetic:
-            # identical bits); 2048 = the 256x256 kernel touches its x tile before the main loop (prefetch experiment: no effect
-            # on the values)
-            for name, flags in (("atomic", 8), ("atomic2", 8), ("rmw", 0), ("late_loads", 256), ("prefetch", 2048)):
-                E.check(lib.f5_debug_set_gemm_flags(flags))
-                x = x0.to(DEV).clone()
-                E.check(lib.f5_op_gemm_resid_gate(P(a_hi), P(a_lo), P(w_hi), P(w_lo), P(bias_d), P(gate_d), P(keep_d), P(x), M, N, K, K,
-                                                  K, N, nseg, stream()), "gemm_resid_gate")
-                sync()
-                res[name] = x.cpu()
-            assert torch.equal(res["atomic"], res["atomic2"]), "atomic residual update is not deterministic"
-            assert torch.equal(res["rmw"], res["late_loads"]), "early and late residual loads differ"
-            assert torch.equal(res["rmw"], res["prefetch"]), "x-tile prefetch changed the result"
-            d = (res["atomic"].double() - res["rmw"].double()).abs()
-            scale = float(res["rmw"].abs().max())
-            print(f"[resid atomic vs rmw] tile={tile} nseg={nseg} {M}x{N}x{K}: max |d| = {float(d.max()):.3e} (max |x| = {scale:.2f})")
-            assert float(d.max()) <= 4e-7 * scale
-            # rows that are masked out must not change at all
-            assert torch.equal(res["atomic"][keep == 0], x0[keep == 0])
-    finally:
-        E.check(lib.f5_debug_set_gemm_tile(0))
-        E.check(lib.f5_debug_set_gemm_flags(0))
-
-
 @pytest.mark.parametrize("tile", [1, 2, 3, 5, 6])
 def test_gemm_all_small_tile_kernels(lib, tile):
     """every block-tile variant (register-staged 128x128 / 64x128 / 64x64 and the global_load_lds ring 64x128 / 64x64)"""
@@ -1380,93 +1258,3 @@ def test_gemm_wide_ring_kernels(lib, tile):
     finally:
         E.check(lib.f5_debug_set_gemm_tile(0))
 
-
-@pytest.mark.lab
-def test_gemm_streamk_schedule(lib):
-    """256x256 kernel under the stream-K schedule (>= one tile per CU): split tiles are handed over through the partial-tile
-    scratch; every epilogue; bitwise run-to-run determinism; agreement with the one-tile-per-workgroup schedule."""
-    r = rng(4242)
-    M, N, K = 4200, 4096, 192                      # 17 x 16 = 272 tiles of 3 K-steps over 256 CUs -> most tiles are split
-    a, w, bias = randn(r, M, K), randn(r, N, K, scale=K ** -0.5), randn(r, N, scale=0.1)
-    refbf = (bf16r(a).double() @ bf16r(w).double().T) + bias.double()
-    ref32 = a.double() @ w.double().T + bias.double()
-    outs = {}
-    for sk in (1, 2, 0, 1, 2):
-        E.check(lib.f5_debug_set_gemm_streamk(sk))
-        try:
-            out, _, _ = _gemm(lib, a, w, bias, 0, 1)
-            mx, _, _ = report(f"gemm stream-K={sk} {M}x{N}x{K}", out, refbf)
-            assert mx <= 2e-4 * max(1.0, float(refbf.abs().max()))
-            if sk in outs:
-                assert torch.equal(out, outs[sk]), "stream-K schedule must be bitwise reproducible"
-            outs[sk] = out
-            out3, _, _ = _gemm(lib, a, w, bias, 0, 3)
-            assert float((out3.double() - ref32).abs().max()) <= 5e-5 * max(1.0, float(ref32.abs().max()))
-            _, hi, lo = _gemm(lib, a, w, bias, 2, 3)
-            refg = F.gelu(ref32, approximate="tanh")
-            assert float((join(hi, lo).double() - refg).abs().max()) <= 1e-4 * max(1.0, float(refg.abs().max()))
-        finally:
-            E.check(lib.f5_debug_set_gemm_streamk(0))
-    assert float((outs[0] - outs[2]).abs().max()) <= 1e-5 * max(1.0, float(refbf.abs().max()))
-    assert float((outs[0] - outs[1]).abs().max()) <= 1e-5 * max(1.0, float(refbf.abs().max()))
-    # fused residual epilogue + QKV epilogue under the hybrid schedule
-    E.check(lib.f5_debug_set_gemm_streamk(2))
-    gate, x0 = randn(r, N), randn(r, M, N)
-    keep = torch.from_numpy((r.random(M) > 0.3).astype(np.uint8))
-    a_hi, a_lo = split_bf16(a.to(DEV))
-    w_hi, w_lo = split_bf16(w.to(DEV))
-    bias_d, gate_d, keep_d, x = bias.to(DEV), gate.to(DEV), keep.to(DEV), x0.to(DEV).clone()
-    E.check(lib.f5_op_gemm_resid_gate(P(a_hi), P(a_lo), P(w_hi), P(w_lo), P(bias_d), P(gate_d), P(keep_d), P(x), M, N, K, K, K, N, 3,
-                                      stream()), "gemm_resid_gate")
-    sync()
-    ref = x0.double() + gate.double() * (ref32 * keep.double()[:, None])
-    assert float((x.cpu().double() - ref).abs().max()) <= 5e-5 * max(1.0, float(ref.abs().max()))
-    # QKV + RoPE + head split + attention on top: D = 1280 (N = 3840 = 15 tiles), M = 5 x 900 -> 18 x 15 = 270 tiles
-    try:
-        _attention_case(lib, 5, 20, 900, [900, 850, 900, 411, 77], 1, seed=33)
-        E.check(lib.f5_debug_set_gemm_streamk(1))
-        _attention_case(lib, 5, 20, 900, [900, 850, 900, 411, 77], 1, seed=34)
-    finally:
-        E.check(lib.f5_debug_set_gemm_streamk(0))
-    assert lib.f5_debug_gemm_streamk_error() == 0
-
-
-@pytest.fixture
-def force_v3(lib):
-    E.check(lib.f5_debug_set_gemm_tile(7))
-    yield
-    E.check(lib.f5_debug_set_gemm_tile(0))
-
-
-@pytest.mark.lab
-@pytest.mark.parametrize("M,N,K", [(256, 256, 32), (300, 512, 96), (1874, 1024, 1024), (700, 768, 2048)])
-def test_gemm_v3_f32_out(lib, force_v3, M, N, K):
-    r = rng(M + N + K + 3)
-    a, w, bias = randn(r, M, K), randn(r, N, K, scale=K ** -0.5), randn(r, N, scale=0.1)
-    refbf = (bf16r(a).double() @ bf16r(w).double().T) + bias.double()
-    out, _, _ = _gemm(lib, a, w, bias, 0, 1) if K % 64 == 0 else (None, None, None)
-    if out is not None:
-        mx, _, _ = report(f"gemm v3 bf16 {M}x{N}x{K}", out, refbf)
-        assert mx <= 2e-4 * max(1.0, float(refbf.abs().max()))
-        out3, _, _ = _gemm(lib, a, w, bias, 0, 3)
-        ref32 = a.double() @ w.double().T + bias.double()
-        assert float((out3.double() - ref32).abs().max()) <= 5e-5 * max(1.0, float(ref32.abs().max()))
-
-
-@pytest.mark.lab
-@pytest.mark.parametrize("epi", [1, 2, 8])
-def test_gemm_v3_bf16_epilogues(lib, force_v3, epi):
-    r = rng(50 + epi)
-    M, N, K = 777, 512, 256
-    a, w, bias = randn(r, M, K), randn(r, N, K, scale=K ** -0.5), randn(r, N, scale=0.1)
-    pre = a.double() @ w.double().T + bias.double()
-    ref = pre if epi == 1 else (F.gelu(pre, approximate="tanh") if epi == 2 else F.gelu(pre))
-    _, out_hi, out_lo = _gemm(lib, a, w, bias, epi, 3)
-    mx, _, _ = report(f"gemm v3 epilogue {epi}", join(out_hi, out_lo), ref)
-    assert mx <= 1e-4
-
-
-@pytest.mark.lab
-@pytest.mark.parametrize("nseg", [1, 3])
-def test_attention_path_with_v3_qkv(lib, force_v3, nseg):
-    _attention_case(lib, 2, 4, 300, [300, 211], nseg, seed=22)

@@ -130,7 +130,7 @@ def compile_to_asm(src, flags=()):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     with tempfile.TemporaryDirectory() as d:
         o = os.path.join(d, "k.s")
-        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DF5_LAB=0", *flags, "-S", "--cuda-device-only", src, "-o", o]
+        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *flags, "-S", "--cuda-device-only", src, "-o", o]
         subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
         return open(o).read()
 
