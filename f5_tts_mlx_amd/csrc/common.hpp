@@ -45,6 +45,12 @@ void f5_set_error(const char* fmt, ...);
         }                                                                                         \
     } while (0)
 
+// ---- test hook (f5_debug_last_gemm_kernel): name of the kernel the most recent f5_launch_gemm of the process launched, "" when it
+// refused the launch.  Written by the launchers on the host only; one variable for both operand builds (defined in engine.hip).
+namespace f5dbg {
+extern const char* last_gemm_kernel;
+}
+
 // ---- host-side float <-> 16-bit operand bits (weight upload), round to nearest even -----------------------
 // bf16: same rounding as torch's .to(bfloat16); fp16: same as torch's .to(float16) except that finite values beyond
 // +-65504 saturate instead of becoming inf (the device producers saturate too, op16.hpp).

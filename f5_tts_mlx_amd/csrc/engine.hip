@@ -1478,6 +1478,19 @@ extern "C" int f5_debug_set_gemm_flags(int v) {
     F5_SET_BOTH(f5_gemm_debug_flags, v);
     return 0;
 }
+namespace f5dbg {
+const char* last_gemm_kernel = "";
+}
+// name of the kernel the most recent f5_launch_gemm of the process resolved to ("" = it refused the launch); returns its length
+extern "C" int f5_debug_last_gemm_kernel(char* buf, int n) {
+    const char* s = f5dbg::last_gemm_kernel;
+    const int len = (int)strlen(s);
+    if (buf != nullptr && n > 0) {
+        strncpy(buf, s, (size_t)n - 1);
+        buf[n - 1] = 0;
+    }
+    return len;
+}
 extern "C" int f5_debug_set_gemm_tile(int sel) {
     F5_REQUIRE(sel >= 0 && sel <= 14, "gemm tile override must be 0 (auto) .. 14");
     F5_REQUIRE(sel != 7, "gemm tile 7 does not exist (tiles are 0 .. 6 and 8 .. 14)");

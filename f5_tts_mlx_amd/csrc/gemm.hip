@@ -631,6 +631,8 @@ static int launch_ring(const F5GemmArgs& a, hipStream_t stream) {
     const int order = ring_order(a, tiles_m, tiles_n);
     // ring depth: keep TWO workgroups per CU (<= 80 KB of LDS each): 64x64 tiles take 4 stages (64 KB), 64x128 take 3 (72 KB)
     constexpr int NST = (MB + NB) * 8 * 4 <= 80 ? 4 : 3;
+    static_assert(MB == 1 && (NB == 1 || NB == 2), "name below");
+    f5dbg::last_gemm_kernel = NB == 2 ? "ring<1,2>" : "ring<1,1>";
     hipLaunchKernelGGL((f5_gemm_ring_kernel<EPI, MB, NB, NST>), dim3(ntiles), dim3(256), 0, stream, a, order, ntiles);
     F5_LAUNCH_CHECK();
     return 0;
@@ -649,8 +651,11 @@ static int launch_ring_ks2(const F5GemmArgs& a, hipStream_t stream) {
     const int ntiles = tiles_m * tiles_n;
     const int order = ring_order(a, tiles_m, tiles_n);
     constexpr int NST = MB == 1 ? 3 : 2;
+    static_assert(MB == 1 || MB == 2, "name below");
+    f5dbg::last_gemm_kernel = MB == 1 ? "ring_ks2<1>" : "ring_ks2<2>";
     if constexpr (EPI == EPI_RESID_GATE && MB == 1) {
         if (a.x16_out != nullptr) {                       // LN-fold producer (f5_gemm_fold_small has checked the preconditions)
+            f5dbg::last_gemm_kernel = "ring_ks2<1>+fold_producer";
             hipLaunchKernelGGL((f5_gemm_ring_kernel<EPI, MB, 2, NST, 2, 2, 2, 0, 1>), dim3(ntiles), dim3(512), 0, stream, a, order, ntiles);
             F5_LAUNCH_CHECK();
             return 0;
@@ -668,8 +673,11 @@ static int launch_ring8(const F5GemmArgs& a, hipStream_t stream) {
     const int ntiles = tiles_m * tiles_n;
     const int order = ring_order(a, tiles_m, tiles_n);
     constexpr int NST = (BMt + BNt) * 64 * 2 * 4 <= 128 * 1024 ? 4 : 3;
+    static_assert(NB == 2 || NB == 3, "name below");
+    f5dbg::last_gemm_kernel = NB == 3 ? "ring8<3>" : "ring8<2>";
     if constexpr (EPI == EPI_GELU_TANH && NB == 2) {
         if (a.fold_stats != nullptr) {                    // LN-fold consumer, statistics form (f5_gemm_fold_small has checked the preconditions)
+            f5dbg::last_gemm_kernel = "ring8<2>+fold_consumer";
             hipLaunchKernelGGL((f5_gemm_ring_kernel<EPI, 1, NB, NST, 4, 2, 1, 0, 2>), dim3(ntiles), dim3(512), 0, stream, a, order, ntiles);
             F5_LAUNCH_CHECK();
             return 0;
@@ -693,6 +701,8 @@ static int launch_ring_wide(const F5GemmArgs& a, hipStream_t stream) {
     const int tiles_m = f5_cdiv(a.M, BMt), tiles_n = a.N / BNt;
     const int ntiles = tiles_m * tiles_n;
     const int order = ring_order(a, tiles_m, tiles_n);
+    static_assert((MB == 2 && NB == 2 && WM == 2 && WN == 4) || (MB == 1 && NB == 4 && WM == 4 && WN == 2), "name below");
+    f5dbg::last_gemm_kernel = MB == 2 ? "ring_wide<2,2,2,4>" : "ring_wide<1,4,4,2>";
     hipLaunchKernelGGL((f5_gemm_ring_kernel<EPI, MB, NB, 3, WM, WN>), dim3(ntiles), dim3(64 * WM * WN), 0, stream, a, order, ntiles);
     F5_LAUNCH_CHECK();
     return 0;
@@ -702,6 +712,8 @@ template <int EPI, int MB, int NB>
 static int launch_cfg(const F5GemmArgs& a, hipStream_t stream) {
     const int tiles_m = f5_cdiv(a.M, 64 * MB), tiles_n = f5_cdiv(a.N, 64 * NB);
     const int ntiles = tiles_m * tiles_n;
+    static_assert((MB == 1 || MB == 2) && (NB == 1 || NB == 2) && MB <= NB, "name below");
+    f5dbg::last_gemm_kernel = MB == 2 ? "cfg<2,2>" : (NB == 2 ? "cfg<1,2>" : "cfg<1,1>");
     hipLaunchKernelGGL((f5_gemm_kernel<EPI, MB, NB>), dim3(ntiles), dim3(256), 0, stream, a, tiles_n, ntiles);
     F5_LAUNCH_CHECK();
     return 0;
@@ -1079,6 +1091,7 @@ static int launch_epi(const F5GemmArgs& a, hipStream_t stream) {
 
 int f5_launch_gemm(const F5GemmArgs& a_in, int epi, hipStream_t stream) {
     F5GemmArgs a = a_in;
+    f5dbg::last_gemm_kernel = "";              // a refused launch reports no kernel
     a.debug_flags |= f5_gemm_debug_flags;      // process-wide flags on top of the caller's (an engine's own option)
     if (a.sat_flag == nullptr) a.sat_flag = f5_sat_flag_host;      // fp16 range detector of the 16-bit epilogues (op16.hpp), or null
     F5_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0 && a.K % BK == 0, "gemm: bad shape M=%d N=%d K=%d (K must be a multiple of %d)",

@@ -265,6 +265,12 @@ uint16_t f5_debug_f2bf_bits(float f);
  * 64x128 / 64x64, 8 / 9 = 8-wave ring 128x192 / 128x128, 10 / 11 = in-workgroup split-K 64x128 / 128x128, 12 / 13 = 8-wave ring
  * 128x256 with 64x64 / 32x128 wave tiles */
 int f5_debug_set_gemm_tile(int sel);
+/* which kernel did it run?  Copies (at most n - 1 characters + NUL) a short stable name of the kernel the most recent GEMM launch of
+ * the process resolved to and returns the name's length: family plus the template parameters that tell instantiations apart --
+ * cfg<2,2> / cfg<1,2> / cfg<1,1> (register-staged), ring<1,2> / ring<1,1>, ring8<3> / ring8<2> (+fold_consumer), ring_ks2<1> (+fold_producer)
+ * / ring_ks2<2>, ring_wide<2,2,2,4> / ring_wide<1,4,4,2>, gemm256 and rs128 (+qk_tr, +fold_rowf / +fold_stats).  "" after a launch that
+ * was refused.  Host side only: nothing reaches a kernel.  The operand type is f5_op_get_operand_type's. */
+int f5_debug_last_gemm_kernel(char* buf, int n);
 /* GEMM flag bits, OR-ed into every GEMM launch of the process (an engine's own: f5_engine_set_option "gemm_flags"):
  * bit 0: skip the epilogue of the 256x256 kernel (timing only; results are garbage);
  * bit 1: small-tile kernels use the direct (2-byte store) epilogue instead of the LDS-staged one;

@@ -2,9 +2,11 @@
 
 The op tests of test_ops_gpu.py are written against "the operand type": here a fixture switches both the test helpers
 (f5test.operand_mode: buffers and reference rounding become torch.float16) and the library's f5_op_* entry points to fp16
-and re-runs a representative subset of them -- every MFMA kernel family (small-tile, ring, 8-wave ring, 256x256 GEMMs with
-each fused epilogue; the attention kernels incl. ragged masks and the online-softmax rescale path; the conv position
-embedding) and the 16-bit producers (LN-modulate, depthwise conv + LN, GRN).
+and re-runs them with the parameter lists of the bf16 tests -- every MFMA kernel family (small-tile, ring, 8-wave ring, split-K ring,
+wide ring, 256x256 and role-split 128x256 GEMMs with each fused epilogue; the attention kernels incl. ragged masks, the KV split and
+the online-softmax rescale path; the conv position embedding) and the 16-bit producers (LN-modulate, depthwise conv + LN, GRN).
+The fp16 kernels are separately compiled code (the f5_sat clamp, sat_flag, other MFMA and convert instructions), and the bounds of
+the shared test bodies follow the operand type (test_ops_gpu.eps_op / tol16): an fp16 kernel that loses three significand bits fails.
 """
 import numpy as np
 import pytest
@@ -105,7 +107,7 @@ def test_gemm_resid_gate_f16(lib, tile):
     T.test_gemm_resid_gate(lib, tile, 1)
 
 
-@pytest.mark.parametrize("tile", [1, 2, 5])
+@pytest.mark.parametrize("tile", [1, 2, 3, 5, 6])
 def test_gemm_small_tile_kernels_f16(lib, tile):
     T.test_gemm_all_small_tile_kernels(lib, tile)
 
@@ -133,6 +135,82 @@ def test_gemm_rs128_several_rounds_all_epilogues_f16(lib, tile):
 @pytest.mark.parametrize("stress", range(len(T.FOLD_STRESS)))
 def test_ln_modulate_folded_into_the_gemms_around_it_f16(lib, tile, stress):
     T.test_ln_modulate_folded_into_the_gemms_around_it(lib, tile, stress)
+
+
+force_v2 = T.force_v2
+
+
+@pytest.mark.parametrize("tile", [8, 9, 10, 11])
+def test_gemm_ring8_kernels_f16(lib, tile):
+    T.test_gemm_ring8_kernels(lib, tile)
+
+
+@pytest.mark.parametrize("tile", [12, 13])
+def test_gemm_wide_ring_kernels_f16(lib, tile):
+    T.test_gemm_wide_ring_kernels(lib, tile)
+
+
+@pytest.mark.parametrize("tile", [0, 1, 2, 4, 5])
+@pytest.mark.parametrize("nseg", [1, 3])
+def test_gemm_addrows_f16(lib, tile, nseg):
+    T.test_gemm_addrows(lib, tile, nseg)
+
+
+@pytest.mark.parametrize("M,N,K", [(256, 256, 64), (300, 512, 128), (1000, 256, 192), (1874, 1024, 1024), (700, 768, 2048)])
+def test_gemm_v2_f32_out_f16(lib, force_v2, M, N, K):
+    T.test_gemm_v2_f32_out(lib, None, M, N, K)
+
+
+@pytest.mark.parametrize("nseg", [1, 3])
+@pytest.mark.parametrize("epi", [1, 2, 8])
+def test_gemm_v2_16bit_epilogues_transposed_tile_f16(lib, force_v2, epi, nseg):
+    """incl. the only op-level run of EPI_GELU_ERF_BF16 (the Vocos epilogue) on this kernel"""
+    T.test_gemm_v2_16bit_epilogues_transposed_tile(lib, None, epi, nseg)
+
+
+def test_gemm_v2_band_major_tile_numbering_f16(lib, force_v2):
+    T.test_gemm_v2_band_major_tile_numbering(lib, None)
+
+
+@pytest.mark.parametrize("tile", [0, 5, 9, 10])
+def test_gemm_ring_band_major_numbering_same_bits_f16(lib, tile):
+    T.test_gemm_ring_band_major_numbering_same_bits(lib, tile)
+
+
+@pytest.mark.parametrize("nseg", [1, 3])
+def test_qkv_transposed_tiles_256_kernel_f16(lib, force_v2, nseg):
+    T.test_qkv_transposed_tiles_256_kernel(lib, None, nseg)
+
+
+@pytest.mark.parametrize("nseg", [1, 3])
+@pytest.mark.parametrize("tile", [9, 12, 13, "knob12", "knob13"])
+def test_qkv_transposed_wave_tiles_ring8_f16(lib, tile, nseg):
+    T.test_qkv_transposed_wave_tiles_ring8(lib, tile, nseg)
+
+
+@pytest.mark.parametrize("nseg", [1, 3])
+def test_attention_path_with_v2_qkv_f16(lib, force_v2, nseg):
+    T.test_attention_path_with_v2_qkv(lib, None, nseg)
+
+
+@pytest.mark.parametrize("ks", [1, 2, 4])
+def test_attention_kv_split_f16(lib, ks):
+    T.test_attention_kv_split(lib, ks)
+
+
+@pytest.mark.parametrize("premul", [False, True])
+@pytest.mark.parametrize("path", ["wide", "split2", "split4", "auto"])
+def test_attention_without_tile_maximum_f16(lib, path, premul):
+    T.test_attention_without_tile_maximum(lib, path, premul)
+
+
+def test_attention_wide_workgroups_f16(lib):
+    T.test_attention_wide_workgroups(lib)
+
+
+@pytest.mark.parametrize("B,N,dim", [(1, 31, 256), (3, 100, 1024)])
+def test_grn_f16(lib, B, N, dim):
+    T.test_grn(lib, B, N, dim)
 
 
 def _flag():
