@@ -1831,6 +1831,61 @@ extern "C" int f5_op_cfg_axpy(const float* pred, const float* null_pred, float c
     o.mel_dim = mel_dim;
     return g_ops.ode_stage(o, (hipStream_t)stream);
 }
+// the whole stage kernel (rowops.hpp F5OdeArgs, field by field; saturation goes to the word of f5_debug_set_op_sat_flag)
+extern "C" int f5_op_ode_stage(const float* pred, const float* null_pred, float cfg, const float* cfg_ptr, const float* base,
+                               const float* dt_dev, float coef, float divisor, int mode, float* kstore, const float* k1,
+                               const float* k2, const float* k3, float* out, void* xin_hi, void* xin_lo, int rows, int mel_dim,
+                               void* stream) {
+    F5OdeArgs o;
+    memset(&o, 0, sizeof(o));
+    o.pred = pred;
+    o.null_pred = null_pred;
+    o.cfg = cfg;
+    o.cfg_ptr = cfg_ptr;
+    o.base = base;
+    o.dt_ptr = dt_dev;
+    o.coef = coef;
+    o.divisor = divisor;
+    o.mode = mode;
+    o.kstore = kstore;
+    o.k1 = k1;
+    o.k2 = k2;
+    o.k3 = k3;
+    o.out = out;
+    o.xin_hi = (op16_t*)xin_hi;
+    o.xin_lo = (op16_t*)xin_lo;
+    o.rows = rows;
+    o.mel_dim = mel_dim;
+    F5_REQUIRE(pred != nullptr && base != nullptr && dt_dev != nullptr && out != nullptr, "ode_stage: null pred / base / dt / out");
+    F5_REQUIRE(mode == 0 || (mode == 1 && k1 != nullptr && k2 != nullptr && k3 != nullptr), "ode_stage: mode 1 needs k1, k2 and k3");
+    return g_ops.ode_stage(o, (hipStream_t)stream);
+}
+extern "C" int f5_op_pack_cond_text(const float* cond, const int32_t* lens, const float* text_emb, void* out_hi, void* out_lo, int B,
+                                    int seq_len, int mel_dim, int dt, int null_keeps_cond, void* stream) {
+    return g_ops.pack_cond_text(cond, lens, text_emb, (op16_t*)out_hi, (op16_t*)out_lo, B, seq_len, mel_dim, dt, null_keeps_cond,
+                                (hipStream_t)stream);
+}
+extern "C" int f5_op_pack_x(const float* y, void* out_hi, void* out_lo, int rows, int mel_dim, void* stream) {
+    F5_REQUIRE(mel_dim <= 128, "pack_x: mel_dim must be <= 128");
+    return g_ops.pack_x(y, (op16_t*)out_hi, (op16_t*)out_lo, rows, mel_dim, (hipStream_t)stream);
+}
+extern "C" int f5_op_splice(const float* cond, const float* y, const int32_t* lens, float* out, int B, int seq_len, int mel_dim,
+                            void* stream) {
+    return f5_launch_splice(cond, y, lens, out, B, seq_len, mel_dim, (hipStream_t)stream);
+}
+extern "C" int f5_op_rowkeep(const int32_t* dur, uint8_t* keep, int nbatch, int seq_len, void* stream) {
+    return f5_launch_rowkeep(dur, keep, nbatch, seq_len, (hipStream_t)stream);
+}
+extern "C" int f5_op_copy_words(const void* src, void* dst, size_t nwords, void* stream) {
+    F5_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 3) == 0, "copy_words: pointers must be 4-byte aligned");
+    return f5_launch_copy_words(src, dst, nwords, (hipStream_t)stream);
+}
+extern "C" int f5_op_stage_words(const uint32_t* host_words, size_t nwords, uint32_t* dst, void* stream) {
+    return f5_launch_stage_words(host_words, nwords, dst, (hipStream_t)stream);
+}
+extern "C" int f5_op_zero_vt_pad(void* vt, size_t rows, int seq_len, int npad, void* stream) {
+    return g_ops.zero_vt_pad((op16_t*)vt, rows, seq_len, npad, (hipStream_t)stream);
+}
 
 // x[row][col] += gate[col] * ((A W^T + bias)[row][col] * keep[row])   (dit.py:319,323; Vocos layer scale + residual)
 extern "C" int f5_op_gemm_resid_gate(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias,

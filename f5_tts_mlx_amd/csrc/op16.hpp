@@ -55,10 +55,11 @@ __device__ __forceinline__ float f5_sat(float f) {
 }
 __device__ inline op16_t f5_f2op(float f) { return static_cast<op16_t>(f5_sat(f)); }
 __device__ inline float f5_op2f(op16_t h) { return static_cast<float>(h); }
-// hi/lo split for the 3-pass precision mode: x ~= hi + lo
+// hi/lo split for the 3-pass precision mode: x ~= hi + lo.  The residual saturates like hi does: beyond 2 x 65504 it leaves the fp16
+// range as well (in range it is below half a unit of hi and the clamp changes no bit)
 __device__ inline void f5_split(float f, op16_t& hi, op16_t& lo) {
     hi = static_cast<op16_t>(f5_sat(f));
-    lo = static_cast<op16_t>(f - static_cast<float>(hi));
+    lo = static_cast<op16_t>(f5_sat(f - static_cast<float>(hi)));
 }
 // pack two floats into an operand pair (element 0 in the low half): one v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32 (RNE)
 __device__ inline uint32_t f5_pack2(float a, float b) {
@@ -117,10 +118,12 @@ __device__ inline void f5_split(float f, op16_t& hi, op16_t& lo, f5_sat_t& t) {
     f5_sat_see(t, f);
     f5_split(f, hi, lo);
 }
+// the lo halves of f5_pack2's pair: the residual of the CLAMPED hi half (an unclamped cast is inf beyond the fp16 range and the
+// residual -inf), itself saturating; the same bits as before for values in range
 __device__ inline uint32_t f5_pack2_lo(float a, float b) {
-    const float ra = a - static_cast<float>(static_cast<op16_t>(a));
-    const float rb = b - static_cast<float>(static_cast<op16_t>(b));
-    return f5_pack2_bounded(ra, rb);
+    const float ra = a - static_cast<float>(static_cast<op16_t>(f5_sat(a)));
+    const float rb = b - static_cast<float>(static_cast<op16_t>(f5_sat(b)));
+    return f5_pack2(ra, rb);
 }
 #endif
 }  // namespace F5_NS

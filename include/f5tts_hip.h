@@ -219,6 +219,30 @@ int f5_op_skinny_gemm(const float* a, const float* w, const float* b, float* out
 /* cfm.py:56,364: out = base + (coef*dt/divisor) * cfg(pred, null) */
 int f5_op_cfg_axpy(const float* pred, const float* null_pred, float cfg, const float* base, const float* dt_dev, float coef,
                    float divisor, float* out, void* xin_hi, void* xin_lo, int rows, int mel_dim, void* stream);
+/* cfm.py:38-122, :364, the whole ODE stage: k = pred + (pred - null_pred) * cfg (pred alone when null_pred is NULL; cfg_ptr, a
+ * device scalar, replaces cfg when not NULL), kstore = k when not NULL, a = coef * dt / divisor;
+ * mode 0: out = base + a * k; mode 1 (RK4 final, cfm.py:117): out = base + a * (k1 + 2 k2 + 2 k3 + k).
+ * (xin_hi, xin_lo): `out` as 16-bit operands [rows][128], zero padded (either may be NULL) */
+int f5_op_ode_stage(const float* pred, const float* null_pred, float cfg, const float* cfg_ptr, const float* base, const float* dt_dev,
+                    float coef, float divisor, int mode, float* kstore, const float* k1, const float* k2, const float* k3, float* out,
+                    void* xin_hi, void* xin_lo, int rows, int mel_dim, void* stream);
+/* dit.py:250 (A operand of the hoisted input projection): [2][B][seq_len][128 + dt] 16-bit operands = [cond, zero padded to 128 | text_emb];
+ * branch 0: cond where n < lens[b] (step_cond, cfm.py:331), branch 1: cond dropped (dit.py:249) unless null_keeps_cond;
+ * cond [B][seq_len][mel_dim <= 128], text_emb [2][B][seq_len][dt] */
+int f5_op_pack_cond_text(const float* cond, const int32_t* lens, const float* text_emb, void* out_hi, void* out_lo, int B, int seq_len,
+                         int mel_dim, int dt, int null_keeps_cond, void* stream);
+/* dit.py:250, the x part: y [rows][mel_dim <= 128] fp32 -> 16-bit operands [rows][128], zero padded */
+int f5_op_pack_x(const float* y, void* out_hi, void* out_lo, int rows, int mel_dim, void* stream);
+/* cfm.py:395-397: out = where(n < lens[b], cond, y), all [B][seq_len][mel_dim] */
+int f5_op_splice(const float* cond, const float* y, const int32_t* lens, float* out, int B, int seq_len, int mel_dim, void* stream);
+/* lens_to_mask of the durations (utils.py:39, cfm.py:334): keep[b][n] = n < dur[b] */
+int f5_op_rowkeep(const int32_t* dur, uint8_t* keep, int nbatch, int seq_len, void* stream);
+/* the staging kernels sample() uses in place of mx.array(...) / copies: device -> device copy of nwords 32-bit words (4-byte aligned
+ * pointers; 16-byte accesses when both allow it), host words -> device through kernel arguments */
+int f5_op_copy_words(const void* src, void* dst, size_t nwords, void* stream);
+int f5_op_stage_words(const uint32_t* host_words, size_t nwords, uint32_t* dst, void* stream);
+/* V^T [rows][npad] 16-bit operands: zeroes the pad columns [seq_len, npad) (no reference line: the reference has no padded V^T) */
+int f5_op_zero_vt_pad(void* vt, size_t rows, int seq_len, int npad, void* stream);
 
 /* Initial noise of F5TTS.sample (cfm.py:369-375) on the device: for each batch element the channel-major draw
  * `mx.random.seed(seed); mx.random.normal((mel, dur))`, zero padded to N frames, laid out [B][N][mel].  The generator follows

@@ -49,7 +49,7 @@ def _to_op(x: torch.Tensor) -> torch.Tensor:
 def split_bf16(x: torch.Tensor):
     """fp32 -> (hi, lo) operand pair (bf16, or fp16 under operand_mode("f16")), same encoding as csrc/op16.hpp f5_split."""
     hi = _to_op(x)
-    lo = (x - hi.to(torch.float32)).to(_OP["dtype"])
+    lo = _to_op(x - hi.to(torch.float32))      # saturates like hi: beyond 2 x 65504 the residual leaves the fp16 range too
     return hi.contiguous(), lo.contiguous()
 
 

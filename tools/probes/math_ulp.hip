@@ -1,0 +1,82 @@
+// Largest ULP error of the device math functions the row kernels call (csrc/rowops.hip: rsqrtf, expf, log1pf, sinf, cosf, powf, plus
+// sqrtf and SiLU), against fp64 on the host, over 2^21 arguments per function in the ranges those kernels produce plus the exact grids
+// of the time / rotation / position tables.  tests/rowops_matrix.py grants four times the figures this prints (its docstring has the
+// table): re-run after a ROCm update and refresh both.  hipcc --offload-arch=gfx950 -O3 math_ulp.hip -o bin/math_ulp
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdio>
+#include <vector>
+#include <random>
+__global__ void k(const float* x, float* y, int n, int fn) {
+    int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float v = x[i], r;
+    switch (fn) {
+        case 0: r = rsqrtf(v); break;
+        case 1: r = expf(v); break;
+        case 2: r = log1pf(v); break;
+        case 3: r = sinf(v); break;
+        case 4: r = cosf(v); break;
+        case 5: r = powf(10000.0f, v); break;
+        case 6: r = 1.0f / powf(10000.0f, v); break;
+        case 7: r = sqrtf(v); break;
+        default: r = v / (1.0f + expf(-v)); break;
+    }
+    y[i] = r;
+}
+static double ref(int fn, double v) {
+    switch (fn) {
+        case 0: return 1.0 / std::sqrt(v);
+        case 1: return std::exp(v);
+        case 2: return std::log1p(v);
+        case 3: return std::sin(v);
+        case 4: return std::cos(v);
+        case 5: return std::pow(10000.0, v);
+        case 6: return 1.0 / std::pow(10000.0, v);
+        case 7: return std::sqrt(v);
+        default: return v / (1.0 + std::exp(-v));
+    }
+}
+int main() {
+    const char* names[] = {"rsqrtf", "expf", "log1pf", "sinf", "cosf", "powf(1e4,x)", "1/powf(1e4,x)", "sqrtf", "silu"};
+    std::mt19937_64 g(1);
+    const int n = 1 << 21;
+    float *dx, *dy;
+    if (hipMalloc(&dx, n * 4) != hipSuccess || hipMalloc(&dy, n * 4) != hipSuccess) return 2;
+    for (int fn = 0; fn < 9; ++fn) {
+        std::vector<float> x(n), y(n);
+        std::uniform_real_distribution<double> u(0.0, 1.0);
+        for (int i = 0; i < n; ++i) {
+            double t = u(g);
+            switch (fn) {
+                case 0: case 7: x[i] = (float)std::pow(10.0, -6.0 + 15.0 * t); break;   // var + eps, sums of squares
+                case 1: x[i] = (float)(-30.0 + 50.0 * t); break;                     // softplus argument, time frequencies
+                case 2: x[i] = (float)std::exp(-30.0 + 50.0 * t); break;            // exp(mean), mean <= 20
+                case 3: case 4: x[i] = (float)(4096.0 * t); break;                   // angles of the tables
+                case 5: case 6: x[i] = (float)t; break;                              // 2 j / dim
+                default: x[i] = (float)(-20.0 + 40.0 * t); break;
+            }
+        }
+        // the grids the kernels really use
+        int q = 0;
+        if (fn == 5 || fn == 6) for (int d : {4, 64, 100, 128, 256, 512, 516, 1024}) for (int j = 0; j < d / 2; ++j) x[q++] = (float)(2 * j) / (float)d;
+        if (fn == 1) for (int half : {2, 127, 128, 512}) { float step = logf(10000.0f) / (float)(half - 1); for (int j = 0; j < half; ++j) x[q++] = (float)j * -step; }
+        if (fn == 3 || fn == 4) for (int d : {64, 128, 512}) for (int j = 0; j < d / 2; ++j) { float inv = 1.0f / powf(10000.0f, (float)(2 * j) / (float)d); for (int p = 0; p < 4096 && q < n / 2; p += 7) x[q++] = (float)p * inv; }
+        if (hipMemcpy(dx, x.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess) return 3;
+        hipLaunchKernelGGL(k, dim3(n / 256), dim3(256), 0, 0, dx, dy, n, fn);
+        if (hipMemcpy(y.data(), dy, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return 3;
+        double worst = 0, worst_abs = 0; float wx = 0;
+        for (int i = 0; i < n; ++i) {
+            double r = ref(fn, (double)x[i]);
+            if (r == 0.0 || !std::isfinite(r)) continue;
+            int e; std::frexp(r, &e);                       // |r| in [2^(e-1), 2^e)
+            double ulp = std::ldexp(1.0, e - 24);
+            if (std::fabs(r) < 1.17549435e-38) ulp = std::ldexp(1.0, -149);
+            double err = std::fabs((double)y[i] - r) / ulp;
+            if (err > worst) { worst = err; wx = x[i]; }
+            worst_abs = std::fmax(worst_abs, std::fabs((double)y[i] - r));
+        }
+        printf("%-14s max_ulp %.3f at x=%.9g  max_abs %.3e\n", names[fn], worst, wx, worst_abs);
+    }
+    return 0;
+}
