@@ -13,18 +13,7 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 #define F5_WAVE 64
 
-// GEMM epilogues (csrc/gemm.hip); "BF16" in a name means "the 16-bit operand type of the build" (bf16 or fp16, op16.hpp)
-enum F5Epi : int {
-    EPI_F32 = 0,         // out_f32 = acc + bias
-    EPI_BF16 = 1,        // out_bf  = bf16(acc + bias)
-    EPI_GELU_TANH = 2,   // out_bf  = bf16(gelu_tanh(acc + bias))                 (dit.py:94-99)
-    EPI_GELU_ERF = 3,    // out_f32 = gelu_erf(acc + bias)                        (convnext_v2.py:50-51)
-    EPI_RESID_GATE = 4,  // out_f32 += gate[col] * ((acc + bias) * keep[row])     (dit.py:172-173,319,323)
-    EPI_QKV_ROPE = 5,    // q,k: rope(acc + bias) -> qk[row][col]; v -> vt[b,h][d][n] (dit.py:136-158)
-    EPI_ADDROWS = 6,     // out_f32 = acc + addrows[row][col]; out_bf = bf16(same)  (dit.py:250 split GEMM)
-    EPI_RESID_KEEP = 7,  // out_f32 = (resid[row][col] + acc + bias) * keep[row]  (convnext_v2.py:53-54, dit.py:225)
-    EPI_GELU_ERF_BF16 = 8,  // out_bf = bf16(gelu_erf(acc + bias))              (Vocos ConvNeXt block)
-};
+#include "gemm_route.hpp"   // F5Epi and the GEMM routing function (host only, no HIP types)
 
 // ---- error handling (never throw across the C ABI) -------------------------------------------
 void f5_set_error(const char* fmt, ...);
@@ -45,10 +34,11 @@ void f5_set_error(const char* fmt, ...);
         }                                                                                         \
     } while (0)
 
-// ---- test hook (f5_debug_last_gemm_kernel): name of the kernel the most recent f5_launch_gemm of the process launched, "" when it
-// refused the launch.  Written by the launchers on the host only; one variable for both operand builds (defined in engine.hip).
+// ---- test hook (f5_debug_last_gemm_kernel): the kernel the most recent f5_launch_gemm of the process launched, as the word of
+// gemm_route.hpp f5_gemm_reached, 0 when it refused the launch.  Written by f5_launch_gemm on the host only; one variable for both
+// operand builds (defined in engine.hip).
 namespace f5dbg {
-extern const char* last_gemm_kernel;
+extern int last_gemm_kernel;
 }
 
 // ---- host-side float <-> 16-bit operand bits (weight upload), round to nearest even -----------------------

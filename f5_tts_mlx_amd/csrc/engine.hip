@@ -557,7 +557,7 @@ static Workspace plan_workspace(const f5_engine* e, int B, int N, int nt, int st
     }
     // LN fold buffers only where the fold can run (a superset of ln_fold_state(): that one also knows the branch count of the call):
     // one-pass 16-bit operand modes, the option not 0, and -- in the automatic mode -- enough rows for it to be chosen with both branches
-    // (... or few enough for the single-round kernels of the batch-1-sized route, gemm.hpp f5_gemm_fold_small: <= 2 048 rows at width 1024)
+    // (... or few enough for the single-round kernels of the batch-1-sized route, gemm_route.hpp f5_gemm_fold_small: <= 2 048 rows at width 1024)
     w.fold_planned = np == 1 && e->prec != F5_PREC_MXFP8 && e->opt.ln_fold != 0 &&
                      (e->opt.ln_fold == 1 || (long)M2 >= LN_FOLD_AUTO_ROWS || ((long)M2 <= LN_FOLD_SMALL_ROWS && LN_FOLD_SMALL_AUTO));
     const size_t fp = w.fold_planned ? 1 : 0;
@@ -649,17 +649,17 @@ static int ln_fold_state(const Ctx& c) {
               (e->opt.gemm_flags & 16384) == 0 && cf.depth >= 1;
     bool small = ok && D == 1024 && e->opt.fold_stats != 0 && (e->opt.gemm_flags & (8 | 256)) == 0;   // the single-round kernels: statistics form only
     if (ok) {
-        F5GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.M = M;
-        g.seq_len = c.N;
-        g.nseg = 1;
-        const int shapes[4][3] = {{3 * D, D, EPI_QKV_ROPE}, {D, D, EPI_RESID_GATE}, {FF, D, EPI_GELU_TANH}, {D, FF, EPI_RESID_GATE}};
+        F5GemmQuery q = {};
+        q.M = M;
+        q.seq_len = c.N;
+        q.nseg = 1;
+        q.g4 = true;             // (e->opt.qkv_tr is part of `ok`)
+        const int shapes[4][2] = {{3 * D, EPI_QKV_ROPE}, {D, EPI_RESID_GATE}, {FF, EPI_GELU_TANH}, {D, EPI_RESID_GATE}};
         for (const auto& sh : shapes) {
-            g.N = sh[0];
-            g.K = sh[1];
-            ok = ok && c.ops.gemm_runs_staged(g, sh[2]);
-            small = small && c.ops.gemm_fold_small(g, sh[2], true);
+            q.N = sh[0];
+            q.epi = sh[1];
+            ok = ok && f5_gemm_runs_staged(q);
+            small = small && f5_gemm_fold_small(q);
         }
     }
     if (e->opt.ln_fold < 0 && !(M >= LN_FOLD_AUTO_ROWS && ok) && !(small && LN_FOLD_SMALL_AUTO)) return 0;
@@ -915,7 +915,7 @@ static int run_dit(const Ctx& c, int j) {
     const float* mf = mod + (size_t)L * 6 * D;  // final adaLN: (scale, shift) order, dit.py:287
     bool h_ready = false;
     auto fuse_ln = [&](F5GemmArgs& g, const float* scale, const float* shift) -> bool {
-        if (!e->opt.fuse_ln || w.lncnt_words == 0 || !K.gemm_resid_ln_fusable(g)) return false;
+        if (!e->opt.fuse_ln || w.lncnt_words == 0 || !f5_gemm_resid_ln_fusable(f5bf::f5_gemm_query(g, EPI_RESID_GATE), g.ldo)) return false;
         g.ln_counter = c.p<int>(w.lncnt);
         g.ln_scale = scale;
         g.ln_shift = shift;
@@ -1387,17 +1387,15 @@ extern "C" int f5_dit_forward(f5_engine* e, const f5_sample_args* a, const float
 // tile numbering).
 #define F5_DECL_KNOB(v) namespace f5bf { extern int v; } namespace f5hf { extern int v; }
 #define F5_SET_BOTH(v, x) do { f5bf::v = (x); f5hf::v = (x); ++g_knob_epoch; } while (0)
+#define F5_SET_ROUTE_KNOB(v, x) do { f5dbg::gemm_knobs.v = (x); ++g_knob_epoch; } while (0)    // gemm_route.hpp: one object for both builds
 F5_DECL_KNOB(f5_convpos_tps)
 F5_DECL_KNOB(f5_convpos_xcd_map)
 F5_DECL_KNOB(f5_attn_wide)
 F5_DECL_KNOB(f5_attn_kvsplit)
 F5_DECL_KNOB(f5_attn_pipe)
-F5_DECL_KNOB(f5_gemm_ring_default)
 F5_DECL_KNOB(f5_gemm_order)
 F5_DECL_KNOB(f5_gemm_nband)
-F5_DECL_KNOB(f5_gemm_qkv_small_tile)
 F5_DECL_KNOB(f5_gemm_debug_flags)
-F5_DECL_KNOB(f5_gemm_tile_override)
 extern "C" int f5_op_set_operand_type(int fp16) {
     F5_REQUIRE(fp16 == 0 || fp16 == 1, "operand type must be 0 (bf16) or 1 (fp16)");
     g_ops.h = fp16 != 0;
@@ -1455,7 +1453,7 @@ extern "C" int f5_debug_set_attn_kvsplit(int v) {
 }
 extern "C" int f5_debug_set_gemm_qkv_tile(int v) {
     F5_REQUIRE(v == 0 || v == 1 || v == 12 || v == 13 || v == 14, "small-M QKV tile must be 0 (auto), 1 (small tiles), 12 / 13 (8-wave 128x256 ring) or 14 (role-split 128x256)");
-    F5_SET_BOTH(f5_gemm_qkv_small_tile, v);
+    F5_SET_ROUTE_KNOB(qkv_tile, v);
     return 0;
 }
 extern "C" int f5_debug_set_gemm_nband(int v) {
@@ -1464,7 +1462,7 @@ extern "C" int f5_debug_set_gemm_nband(int v) {
     return 0;
 }
 extern "C" int f5_debug_set_gemm_ring(int v) {
-    F5_SET_BOTH(f5_gemm_ring_default, v ? 1 : 0);
+    F5_SET_ROUTE_KNOB(ring, v ? 1 : 0);
     return 0;
 }
 extern "C" int f5_debug_set_gemm_order(int v) {
@@ -1479,22 +1477,39 @@ extern "C" int f5_debug_set_gemm_flags(int v) {
     return 0;
 }
 namespace f5dbg {
-const char* last_gemm_kernel = "";
+int last_gemm_kernel = 0;
+}
+static int copy_name(const std::string& s, char* buf, int n) {
+    if (buf != nullptr && n > 0) {
+        strncpy(buf, s.c_str(), (size_t)n - 1);
+        buf[n - 1] = 0;
+    }
+    return (int)s.size();
 }
 // name of the kernel the most recent f5_launch_gemm of the process resolved to ("" = it refused the launch); returns its length
 extern "C" int f5_debug_last_gemm_kernel(char* buf, int n) {
-    const char* s = f5dbg::last_gemm_kernel;
-    const int len = (int)strlen(s);
-    if (buf != nullptr && n > 0) {
-        strncpy(buf, s, (size_t)n - 1);
-        buf[n - 1] = 0;
+    return copy_name(f5_gemm_kernel_name(f5dbg::last_gemm_kernel), buf, n);
+}
+// The route (gemm_route.hpp) a GEMM launch of this shape would take under the current knobs and process-wide flags, without launching
+// anything or touching a device.  variant_bits: 1 = group-major rotation tables, 2 = fused LN tail, 4 = LN-fold producer, 8 = consumer in
+// the statistics form, 16 = consumer with row factors.  -> length of the kernel name (as f5_debug_last_gemm_kernel would report it), or
+// -1 when the launch would be refused (f5_last_error says why); facts (optional): bit 0 staged, 1 fold-small, 2 resid-LN-fusable
+extern "C" int f5_debug_gemm_route(int epi, int M, int N, int nseg, int seq_len, int variant_bits, int debug_flags, char* name, int n, int* facts) {
+    F5_REQUIRE(epi >= EPI_F32 && epi <= EPI_GELU_ERF_BF16 && M >= 1 && N >= 1, "gemm route: bad epilogue %d or shape M=%d N=%d", epi, M, N);
+    const F5GemmQuery q = {epi, M, N, nseg, seq_len, (variant_bits & 1) != 0, (variant_bits & 2) != 0, (unsigned)(variant_bits >> 2) & 7u,
+                           debug_flags | f5bf::f5_gemm_debug_flags};     // (F5_SET_BOTH keeps the fp16 build's copy equal)
+    const F5GemmRoute r = f5_gemm_route(q);
+    if (facts != nullptr) *facts = (r.staged ? 1 : 0) | (r.fold_small ? 2 : 0) | (r.ln_fusable ? 4 : 0);
+    if (r.kernel == F5K_NONE) {
+        f5_set_error("%s", r.refused);
+        return -1;
     }
-    return len;
+    return copy_name(f5_gemm_kernel_name(f5_gemm_reached(r.kernel, q)), name, n);
 }
 extern "C" int f5_debug_set_gemm_tile(int sel) {
     F5_REQUIRE(sel >= 0 && sel <= 14, "gemm tile override must be 0 (auto) .. 14");
     F5_REQUIRE(sel != 7, "gemm tile 7 does not exist (tiles are 0 .. 6 and 8 .. 14)");
-    F5_SET_BOTH(f5_gemm_tile_override, sel);
+    F5_SET_ROUTE_KNOB(tile, sel);
     return 0;
 }
 
@@ -1564,11 +1579,9 @@ extern "C" int f5_op_fold_consts(const void* w_hi, int ldw, const float* bias, c
     return g_ops.fold_consts((const op16_t*)w_hi, ldw, bias, scale, shift, vec_stride, nvec, c1, c2, out_stride, N, K, (hipStream_t)stream);
 }
 
-extern "C" int f5_op_gemm(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias,
-                          float* out_f32, void* out_bf_hi, void* out_bf_lo, int M, int N, int K, int lda, int ldw, int ldo,
-                          int nseg, int epi, void* stream) {
-    F5_REQUIRE(epi == EPI_F32 || epi == EPI_BF16 || epi == EPI_GELU_TANH || epi == EPI_GELU_ERF || epi == EPI_GELU_ERF_BF16,
-               "f5_op_gemm supports epilogues 0-3 and 8 only");
+// operands, shape and bias of an f5_op_* GEMM (what gemm_base() is to the engine's launches)
+static F5GemmArgs op_gemm_base(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, int lda, int ldw, int M, int N, int K,
+                               int nseg, const float* bias) {
     F5GemmArgs g;
     memset(&g, 0, sizeof(g));
     g.A[0] = (const op16_t*)a_hi;
@@ -1582,6 +1595,15 @@ extern "C" int f5_op_gemm(const void* a_hi, const void* a_lo, const void* w_hi, 
     g.K = K;
     g.nseg = nseg;
     g.bias = bias;
+    return g;
+}
+
+extern "C" int f5_op_gemm(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias,
+                          float* out_f32, void* out_bf_hi, void* out_bf_lo, int M, int N, int K, int lda, int ldw, int ldo,
+                          int nseg, int epi, void* stream) {
+    F5_REQUIRE(epi == EPI_F32 || epi == EPI_BF16 || epi == EPI_GELU_TANH || epi == EPI_GELU_ERF || epi == EPI_GELU_ERF_BF16,
+               "f5_op_gemm supports epilogues 0-3 and 8 only");
+    F5GemmArgs g = op_gemm_base(a_hi, a_lo, w_hi, w_lo, lda, ldw, M, N, K, nseg, bias);
     g.out_f32 = out_f32;
     g.ldo = ldo;
     g.out_bf[0] = (op16_t*)out_bf_hi;
@@ -1672,19 +1694,7 @@ extern "C" int f5_op_attention(const void* qk_hi, const void* qk_lo, const void*
 extern "C" int f5_op_qkv_rope(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias,
                               const float* rope_cos, const float* rope_sin, void* qk_hi, void* qk_lo, void* vt_hi, void* vt_lo,
                               int B, int seq_len, int npad, int heads, int dmodel, int nseg, void* stream) {
-    F5GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A[0] = (const op16_t*)a_hi;
-    g.A[1] = (const op16_t*)a_lo;
-    g.W[0] = (const op16_t*)w_hi;
-    g.W[1] = (const op16_t*)w_lo;
-    g.lda = dmodel;
-    g.ldw = dmodel;
-    g.M = B * seq_len;
-    g.N = 3 * dmodel;
-    g.K = dmodel;
-    g.nseg = nseg;
-    g.bias = bias;
+    F5GemmArgs g = op_gemm_base(a_hi, a_lo, w_hi, w_lo, dmodel, dmodel, B * seq_len, 3 * dmodel, dmodel, nseg, bias);
     g.out_bf[0] = (op16_t*)qk_hi;
     g.out_bf[1] = (op16_t*)qk_lo;
     g.ldob = 2 * dmodel;
@@ -1773,19 +1783,7 @@ extern "C" int f5_op_text_embed_nomask(const int32_t* text, int nt, const float*
 extern "C" int f5_op_gemm_resid_keep(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias,
                                      const float* resid, const uint8_t* rowkeep, float* out, int M, int N, int K, int lda, int ldw,
                                      int ldo, int nseg, void* stream) {
-    F5GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A[0] = (const op16_t*)a_hi;
-    g.A[1] = (const op16_t*)a_lo;
-    g.W[0] = (const op16_t*)w_hi;
-    g.W[1] = (const op16_t*)w_lo;
-    g.lda = lda;
-    g.ldw = ldw;
-    g.M = M;
-    g.N = N;
-    g.K = K;
-    g.nseg = nseg;
-    g.bias = bias;
+    F5GemmArgs g = op_gemm_base(a_hi, a_lo, w_hi, w_lo, lda, ldw, M, N, K, nseg, bias);
     g.resid = resid;
     g.ldres = ldo;
     g.rowkeep = rowkeep;
@@ -1891,19 +1889,7 @@ extern "C" int f5_op_zero_vt_pad(void* vt, size_t rows, int seq_len, int npad, v
 extern "C" int f5_op_gemm_resid_gate(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias,
                                      const float* gate, const uint8_t* rowkeep, float* x, int M, int N, int K, int lda, int ldw,
                                      int ldx, int nseg, void* stream) {
-    F5GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A[0] = (const op16_t*)a_hi;
-    g.A[1] = (const op16_t*)a_lo;
-    g.W[0] = (const op16_t*)w_hi;
-    g.W[1] = (const op16_t*)w_lo;
-    g.lda = lda;
-    g.ldw = ldw;
-    g.M = M;
-    g.N = N;
-    g.K = K;
-    g.nseg = nseg;
-    g.bias = bias;
+    F5GemmArgs g = op_gemm_base(a_hi, a_lo, w_hi, w_lo, lda, ldw, M, N, K, nseg, bias);
     g.gate = gate;
     g.rowkeep = rowkeep;
     g.out_f32 = x;
@@ -1927,19 +1913,7 @@ extern "C" int f5_op_gemm_resid_gate_ln(const void* a_hi, const void* a_lo, cons
                                         const float* gate, const uint8_t* rowkeep, float* x, const float* ln_scale,
                                         const float* ln_shift, void* h_hi, void* h_lo, int* counters, int M, int N, int K, int lda,
                                         int ldw, int nseg, void* stream) {
-    F5GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A[0] = (const op16_t*)a_hi;
-    g.A[1] = (const op16_t*)a_lo;
-    g.W[0] = (const op16_t*)w_hi;
-    g.W[1] = (const op16_t*)w_lo;
-    g.lda = lda;
-    g.ldw = ldw;
-    g.M = M;
-    g.N = N;
-    g.K = K;
-    g.nseg = nseg;
-    g.bias = bias;
+    F5GemmArgs g = op_gemm_base(a_hi, a_lo, w_hi, w_lo, lda, ldw, M, N, K, nseg, bias);
     g.gate = gate;
     g.rowkeep = rowkeep;
     g.out_f32 = x;
@@ -1958,18 +1932,7 @@ extern "C" int f5_op_gemm_resid_gate_ln(const void* a_hi, const void* a_lo, cons
 extern "C" int f5_op_gemm_addrows(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* addrows,
                                   int a_row_mod, float* out_f32, void* out_hi, void* out_lo, int M, int N, int K, int lda, int ldw,
                                   int ldo, int nseg, void* stream) {
-    F5GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A[0] = (const op16_t*)a_hi;
-    g.A[1] = (const op16_t*)a_lo;
-    g.W[0] = (const op16_t*)w_hi;
-    g.W[1] = (const op16_t*)w_lo;
-    g.lda = lda;
-    g.ldw = ldw;
-    g.M = M;
-    g.N = N;
-    g.K = K;
-    g.nseg = nseg;
+    F5GemmArgs g = op_gemm_base(a_hi, a_lo, w_hi, w_lo, lda, ldw, M, N, K, nseg, nullptr);
     g.a_row_mod = a_row_mod;
     g.addrows = addrows;
     g.ldadd = ldo;

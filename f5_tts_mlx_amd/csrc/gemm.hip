@@ -624,86 +624,15 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void f5_gemm_ring_kernel(F5GemmA
     if (EPI == EPI_RESID_GATE && p.ln_counter) resid_ln_tail(p, tm, BMt, (p.N + BNt - 1) / BNt);
 }
 
-template <int EPI, int MB, int NB>
+// every launch of the ring kernel: wave tile 32 MB x 32 NB, WM x WN waves per wave group, KS wave groups that split the K range, NST
+// stages of the LDS ring per group; the tiles are numbered by ring_order.  (The route sends the tiles that need whole column tiles --
+// 128x192, 128x128 8-wave, 128x256 -- only shapes whose N is a multiple of the tile width.)
+template <int EPI, int MB, int NB, int NST, int WM = 2, int WN = 2, int KS = 1, int FOLD = 0>
 static int launch_ring(const F5GemmArgs& a, hipStream_t stream) {
-    const int tiles_m = f5_cdiv(a.M, 64 * MB), tiles_n = f5_cdiv(a.N, 64 * NB);
+    const int tiles_m = f5_cdiv(a.M, 32 * MB * WM), tiles_n = f5_cdiv(a.N, 32 * NB * WN);
     const int ntiles = tiles_m * tiles_n;
     const int order = ring_order(a, tiles_m, tiles_n);
-    // ring depth: keep TWO workgroups per CU (<= 80 KB of LDS each): 64x64 tiles take 4 stages (64 KB), 64x128 take 3 (72 KB)
-    constexpr int NST = (MB + NB) * 8 * 4 <= 80 ? 4 : 3;
-    static_assert(MB == 1 && (NB == 1 || NB == 2), "name below");
-    f5dbg::last_gemm_kernel = NB == 2 ? "ring<1,2>" : "ring<1,1>";
-    hipLaunchKernelGGL((f5_gemm_ring_kernel<EPI, MB, NB, NST>), dim3(ntiles), dim3(256), 0, stream, a, order, ntiles);
-    F5_LAUNCH_CHECK();
-    return 0;
-}
-
-// 8-wave ring kernel for ONE round of workgroups on a small-M problem (M = 2*937 rows at batch 1): 4 x 2 waves, wave tile
-// 32 x 32*NB, block tile 128 x 64*NB (NB = 3: 128x192 -> 15 x 16 = 240 workgroups for the QKV projection, NB = 2: 128x128 ->
-// 240 for FF1).  One workgroup per CU with 8 waves and 3-4 K tiles in flight moves a third less L2->LDS traffic than the
-// 64x128 tiles (the bound there: tools/b1_decompose.py) without leaving CUs idle.
-// in-workgroup split-K ring kernels (tile overrides 10 / 11): 64x128 tile, 2 x (2x2 waves, wave tile 32x64), 3 stages per group
-// (out-proj / FF2 at batch 1: 240 workgroups, K chain halved); 128x128 tile, 2 x (2x2 waves, wave tile 64x64), 2 stages
-template <int EPI, int MB>
-static int launch_ring_ks2(const F5GemmArgs& a, hipStream_t stream) {
-    constexpr int BMt = 64 * MB, BNt = 128;
-    const int tiles_m = f5_cdiv(a.M, BMt), tiles_n = f5_cdiv(a.N, BNt);
-    const int ntiles = tiles_m * tiles_n;
-    const int order = ring_order(a, tiles_m, tiles_n);
-    constexpr int NST = MB == 1 ? 3 : 2;
-    static_assert(MB == 1 || MB == 2, "name below");
-    f5dbg::last_gemm_kernel = MB == 1 ? "ring_ks2<1>" : "ring_ks2<2>";
-    if constexpr (EPI == EPI_RESID_GATE && MB == 1) {
-        if (a.x16_out != nullptr) {                       // LN-fold producer (f5_gemm_fold_small has checked the preconditions)
-            f5dbg::last_gemm_kernel = "ring_ks2<1>+fold_producer";
-            hipLaunchKernelGGL((f5_gemm_ring_kernel<EPI, MB, 2, NST, 2, 2, 2, 0, 1>), dim3(ntiles), dim3(512), 0, stream, a, order, ntiles);
-            F5_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    hipLaunchKernelGGL((f5_gemm_ring_kernel<EPI, MB, 2, NST, 2, 2, 2>), dim3(ntiles), dim3(512), 0, stream, a, order, ntiles);
-    F5_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int EPI, int NB>
-static int launch_ring8(const F5GemmArgs& a, hipStream_t stream) {
-    constexpr int BMt = 128, BNt = 64 * NB;
-    const int tiles_m = f5_cdiv(a.M, BMt), tiles_n = a.N / BNt;
-    const int ntiles = tiles_m * tiles_n;
-    const int order = ring_order(a, tiles_m, tiles_n);
-    constexpr int NST = (BMt + BNt) * 64 * 2 * 4 <= 128 * 1024 ? 4 : 3;
-    static_assert(NB == 2 || NB == 3, "name below");
-    f5dbg::last_gemm_kernel = NB == 3 ? "ring8<3>" : "ring8<2>";
-    if constexpr (EPI == EPI_GELU_TANH && NB == 2) {
-        if (a.fold_stats != nullptr) {                    // LN-fold consumer, statistics form (f5_gemm_fold_small has checked the preconditions)
-            f5dbg::last_gemm_kernel = "ring8<2>+fold_consumer";
-            hipLaunchKernelGGL((f5_gemm_ring_kernel<EPI, 1, NB, NST, 4, 2, 1, 0, 2>), dim3(ntiles), dim3(512), 0, stream, a, order, ntiles);
-            F5_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    hipLaunchKernelGGL((f5_gemm_ring_kernel<EPI, 1, NB, NST, 4, 2>), dim3(ntiles), dim3(512), 0, stream, a, order, ntiles);
-    F5_LAUNCH_CHECK();
-    return 0;
-}
-
-// 128x256 ring tiles for ONE round on the QKV projection at batch 1 (M = 1874, N = 3072: 15 x 12 = 180 workgroups), two
-// wave layouts (tile overrides 12 / 13): 8 waves of 64x64 and 8 waves of 32x128, i.e. 1.0 / 1.25 KB of LDS fragment reads
-// per MFMA against 1.5 for the 64x128 tile of 4 waves of 32x64, and half the L2->LDS bytes per flop.  Measured in-graph
-// (tools/qkv_tiles_bench.py): 27.0-28.1 / 24.7-24.8 us against 25.5-27.2 us for the register-staged 64x128 default, and
-// 22.3-23.1 us at M = 937 where only 96 workgroups exist: a lone workgroup takes ~1.4 us per K tile whatever the fill, three
-// times its MFMA time -- neither L2 bytes nor occupancy is what bounds this shape.  Kept as overrides, not selected.
-template <int EPI, int MB, int NB, int WM, int WN>
-static int launch_ring_wide(const F5GemmArgs& a, hipStream_t stream) {
-    constexpr int BMt = 32 * MB * WM, BNt = 32 * NB * WN;
-    F5_REQUIRE(a.N % BNt == 0, "gemm: this tile needs N %% %d == 0", BNt);
-    const int tiles_m = f5_cdiv(a.M, BMt), tiles_n = a.N / BNt;
-    const int ntiles = tiles_m * tiles_n;
-    const int order = ring_order(a, tiles_m, tiles_n);
-    static_assert((MB == 2 && NB == 2 && WM == 2 && WN == 4) || (MB == 1 && NB == 4 && WM == 4 && WN == 2), "name below");
-    f5dbg::last_gemm_kernel = MB == 2 ? "ring_wide<2,2,2,4>" : "ring_wide<1,4,4,2>";
-    hipLaunchKernelGGL((f5_gemm_ring_kernel<EPI, MB, NB, 3, WM, WN>), dim3(ntiles), dim3(64 * WM * WN), 0, stream, a, order, ntiles);
+    hipLaunchKernelGGL((f5_gemm_ring_kernel<EPI, MB, NB, NST, WM, WN, KS, 0, FOLD>), dim3(ntiles), dim3(64 * WM * WN * KS), 0, stream, a, order, ntiles);
     F5_LAUNCH_CHECK();
     return 0;
 }
@@ -712,61 +641,12 @@ template <int EPI, int MB, int NB>
 static int launch_cfg(const F5GemmArgs& a, hipStream_t stream) {
     const int tiles_m = f5_cdiv(a.M, 64 * MB), tiles_n = f5_cdiv(a.N, 64 * NB);
     const int ntiles = tiles_m * tiles_n;
-    static_assert((MB == 1 || MB == 2) && (NB == 1 || NB == 2) && MB <= NB, "name below");
-    f5dbg::last_gemm_kernel = MB == 2 ? "cfg<2,2>" : (NB == 2 ? "cfg<1,2>" : "cfg<1,1>");
     hipLaunchKernelGGL((f5_gemm_kernel<EPI, MB, NB>), dim3(ntiles), dim3(256), 0, stream, a, tiles_n, ntiles);
     F5_LAUNCH_CHECK();
     return 0;
 }
 
-// tile shape: the largest of 128x128 / 64x128 / 64x64 that still gives the 256 CUs >= 1.5 workgroups each
-// (small-batch shapes such as M = 1874 are otherwise a fraction of one wave of tiles)
-int f5_gemm_tile_override = 0;  // 0 auto, 1 = 128x128, 2 = 64x128, 3 = 64x64, 4 = 256x256 v2, 5 = 64x128 ring, 6 = 64x64 ring,
-                                // 8 = 128x192 8-wave ring, 9 = 128x128 8-wave ring, 10 / 11 = 64x128 / 128x128 split-K ring
 int f5_gemm_debug_flags = 0;
-int f5_gemm_qkv_small_tile = 0;   // small-M QKV projection with pair-major tables: 0 = auto tiles, 12 / 13 = 8-wave 128x256 ring, transposed q / k
-int f5_gemm_ring_default = 1;   // auto mode: small tiles use the global_load_lds ring kernel
-// the large-shape kernels (256x256, 128x256) have no fused LN tail (at those sizes LN-modulate is HBM-bound, not launch-bound)
-static bool gemm_uses_big_kernel(const F5GemmArgs& a) {
-    const long t256 = (long)f5_cdiv(a.M, 256) * (a.N / 256);
-    const bool v2ok = (a.N % 256 == 0) && (a.M >= 256);
-    const int sel = f5_gemm_tile_override;
-    return sel == 4 || (sel == 0 && v2ok && t256 >= 512);
-}
-bool f5_gemm_resid_ln_fusable(const F5GemmArgs& a) {
-    return !gemm_uses_big_kernel(a) && a.N % 256 == 0 && a.N >= 256 && a.N <= 1024 && a.ldo == a.N && a.M <= 64 * 65536;
-}
-
-// mirrors launch_epi's two staged routes (a drift makes f5_launch_gemm fail loudly, never compute something else)
-bool f5_gemm_runs_staged(const F5GemmArgs& a, int epi) {
-    if (!(epi == EPI_RESID_GATE || epi == EPI_QKV_ROPE || epi == EPI_GELU_TANH) || a.ln_counter != nullptr || a.N % 256 != 0) return false;
-    const int sel = f5_gemm_tile_override;
-    const long t256 = (long)f5_cdiv(a.M, 256) * (a.N / 256);
-    const long t128 = (long)f5_cdiv(a.M, 128) * f5_cdiv(a.N, 128);
-    if (sel == 4 || (sel == 0 && a.M >= 256 && t256 >= 512)) return a.M >= 256;
-    const bool qkv_rows_ok = epi != EPI_QKV_ROPE || (a.seq_len > 0 && a.M % a.seq_len == 0);
-    return qkv_rows_ok && (sel == 14 || (sel == 0 && t128 >= 384));
-}
-
-// The batch-1-sized route of the LN fold (round 6): true when f5_launch_gemm sends this launch to the single-round kernel that implements
-// the fold for its role -- EPI_RESID_GATE: the 64 x 128 split-K ring kernel with the preloaded residual epilogue (producer: x16_out /
-// stats_out), EPI_GELU_TANH: the 8-wave 128 x 128 ring kernel (consumer, statistics form only: fold_stats), EPI_QKV_ROPE: one round of
-// role-split 128 x 256 tiles (consumer; `qkv_tr` = the group-major rotation tables will be set).  Same rules as launch_epi below.
-bool f5_gemm_fold_small(const F5GemmArgs& a, int epi, bool qkv_tr) {
-    if (f5_gemm_tile_override != 0 || !f5_gemm_ring_default || a.ln_counter != nullptr || a.nseg != 1 || a.N % 256 != 0 || a.M < 1) return false;
-    const long t256 = (long)f5_cdiv(a.M, 256) * (a.N / 256);
-    const long t128 = (long)f5_cdiv(a.M, 128) * f5_cdiv(a.N, 128);
-    const long t64x128 = (long)f5_cdiv(a.M, 64) * f5_cdiv(a.N, 128);
-    if ((a.M >= 256 && t256 >= 512) || t128 >= 384) return false;                 // the staged multi-round kernels take these
-    if (epi == EPI_QKV_ROPE) {
-        if (!qkv_tr || a.seq_len <= 0 || a.M % a.seq_len != 0 || f5_gemm_qkv_small_tile != 0) return false;
-        const long t = (long)(a.M / a.seq_len) * f5_cdiv(a.seq_len, 128) * (a.N / 256);
-        return t >= 176 && t <= 256;
-    }
-    if (epi == EPI_GELU_TANH) return t128 >= 176 && t128 <= 256;
-    if (epi == EPI_RESID_GATE) return !(t128 >= 176 && t128 <= 256) && t64x128 >= 176 && t64x128 <= 256 && (a.debug_flags & (8 | 256)) == 0;
-    return false;
-}
 
 // ---- constants of the LN fold (gemm.hpp): one wave holds FC_ROWS weight rows in registers as fp32 and streams every modulation
 // vector past them (the vectors are L2-resident: nvec x 2 x K floats)
@@ -1001,97 +881,57 @@ int f5_launch_fold_consts(const op16_t* w, int ldw, const float* bias, const flo
     return 0;
 }
 
+// the launcher of a route (gemm_route.hpp).  The route never names a kernel that lacks the epilogue, so the `if constexpr` guards only
+// keep those pairs from being instantiated: falling out of the switch is an error, not a fallback.
 template <int EPI>
-static int launch_epi(const F5GemmArgs& a, hipStream_t stream) {
-    if (a.ln_counter) {
-        F5_REQUIRE(EPI == EPI_RESID_GATE && f5_gemm_resid_ln_fusable(a) && a.ln_scale && a.ln_shift && a.ln_out[0],
-                   "gemm: the fused LN tail needs EPI_RESID_GATE on a small-tile shape (f5_gemm_resid_ln_fusable) and ln_* set");
+static int launch_epi(const F5GemmArgs& a, F5GemmKernel kern, hipStream_t stream) {
+    constexpr bool RS128 = EPI == EPI_F32 || EPI == EPI_BF16 || EPI == EPI_GELU_TANH || EPI == EPI_RESID_GATE || EPI == EPI_QKV_ROPE;
+    constexpr bool WIDE = EPI == EPI_QKV_ROPE || EPI == EPI_BF16 || EPI == EPI_GELU_TANH;
+    switch (kern) {                 // launch_ring<EPI, MB, NB, NST, WM = 2, WN = 2, KS = 1, FOLD = 0>
+        case F5K_GEMM256: return f5_launch_gemm256(a, EPI, stream);
+        case F5K_RS128: if constexpr (RS128) return f5_launch_gemm_rs128(a, EPI, stream); else break;
+        // 128x256 ring tiles for ONE round on the QKV projection at batch 1 (M = 1874, N = 3072: 15 x 12 = 180 workgroups), two
+        // wave layouts (tile overrides 12 / 13): 8 waves of 64x64 and 8 waves of 32x128, i.e. 1.0 / 1.25 KB of LDS fragment reads
+        // per MFMA against 1.5 for the 64x128 tile of 4 waves of 32x64, and half the L2->LDS bytes per flop.  Measured in-graph
+        // (tools/qkv_tiles_bench.py): 27.0-28.1 / 24.7-24.8 us against 25.5-27.2 us for the register-staged 64x128 default, and
+        // 22.3-23.1 us at M = 937 where only 96 workgroups exist: a lone workgroup takes ~1.4 us per K tile whatever the fill, three
+        // times its MFMA time -- neither L2 bytes nor occupancy is what bounds this shape.  Kept as overrides, not selected.
+        case F5K_RING_WIDE_2224: if constexpr (WIDE) return launch_ring<EPI, 2, 2, 3, 2, 4>(a, stream); else break;
+        case F5K_RING_WIDE_1442: if constexpr (WIDE) return launch_ring<EPI, 1, 4, 3, 4, 2>(a, stream); else break;
+        // in-workgroup split-K ring kernels (tile overrides 10 / 11): 64x128 tile, 2 x (2x2 waves, wave tile 32x64), 3 stages per group
+        // (out-proj / FF2 at batch 1: 240 workgroups, K chain halved); 128x128 tile, 2 x (2x2 waves, wave tile 64x64), 2 stages
+        case F5K_RING_KS2_1:
+            if constexpr (EPI == EPI_RESID_GATE) {                   // LN-fold producer (the route has checked that this is a fold_small launch)
+                if (a.x16_out != nullptr) return launch_ring<EPI, 1, 2, 3, 2, 2, 2, 1>(a, stream);
+            }
+            return launch_ring<EPI, 1, 2, 3, 2, 2, 2>(a, stream);
+        case F5K_RING_KS2_2: return launch_ring<EPI, 2, 2, 2, 2, 2, 2>(a, stream);
+        // 8-wave ring kernel for ONE round of workgroups on a small-M problem (M = 2*937 rows at batch 1): 4 x 2 waves, wave tile
+        // 32 x 32*NB, block tile 128 x 64*NB (NB = 3: 128x192 -> 15 x 16 = 240 workgroups for the QKV projection, NB = 2: 128x128 ->
+        // 240 for FF1).  One workgroup per CU with 8 waves and 3-4 K tiles in flight moves a third less L2->LDS traffic than the
+        // 64x128 tiles (the bound there: tools/b1_decompose.py) without leaving CUs idle.  Ring depth: 4 stages where they fit 128 KB
+        // of LDS ((128 + 64 NB) x 64 x 2 bytes each: 128x128), else 3
+        case F5K_RING8_3: return launch_ring<EPI, 1, 3, 3, 4, 2>(a, stream);
+        case F5K_RING8_2:
+            if constexpr (EPI == EPI_GELU_TANH) {                    // LN-fold consumer, statistics form (the route has checked that this is a fold_small launch)
+                if (a.fold_stats != nullptr) return launch_ring<EPI, 1, 2, 4, 4, 2, 1, 2>(a, stream);
+            }
+            return launch_ring<EPI, 1, 2, 4, 4, 2>(a, stream);
+        // ring depth: keep TWO workgroups per CU (<= 80 KB of LDS each): 64x64 tiles take 4 stages (64 KB), 64x128 take 3 (72 KB)
+        case F5K_RING_1_2: return launch_ring<EPI, 1, 2, 3>(a, stream);
+        case F5K_RING_1_1: return launch_ring<EPI, 1, 1, 4>(a, stream);
+        case F5K_CFG_2_2: return launch_cfg<EPI, 2, 2>(a, stream);
+        case F5K_CFG_1_2: return launch_cfg<EPI, 1, 2>(a, stream);
+        case F5K_CFG_1_1: return launch_cfg<EPI, 1, 1>(a, stream);
+        case F5K_NONE: break;
     }
-    const long t128 = (long)f5_cdiv(a.M, 128) * f5_cdiv(a.N, 128);
-    const long t64x128 = (long)f5_cdiv(a.M, 64) * f5_cdiv(a.N, 128);
-    int sel = f5_gemm_tile_override;
-    const long t256 = (long)f5_cdiv(a.M, 256) * (a.N / 256);
-    const bool v2ok = (a.N % 256 == 0) && (a.M >= 256);
-    if (sel == 4 || (sel == 0 && v2ok && t256 >= 512)) {
-        F5_REQUIRE(v2ok, "gemm: the 256x256 kernel needs N %% 256 == 0 and M >= 256");
-        return f5_launch_gemm256(a, EPI, stream);
-    }
-    if constexpr (EPI == EPI_F32 || EPI == EPI_BF16 || EPI == EPI_GELU_TANH || EPI == EPI_RESID_GATE || EPI == EPI_QKV_ROPE) {
-        // role-split 128 x 256 tiles (gemm_rs128.hip): forced by tile 14, or by the QKV-only knob at batch-1-sized shapes
-        long t128x256 = (long)f5_cdiv(a.M, 128) * (a.N / 256);
-        if (EPI == EPI_QKV_ROPE && a.seq_len > 0) t128x256 = (long)(a.M / a.seq_len) * f5_cdiv(a.seq_len, 128) * (a.N / 256);   // per-element row tiles
-        // QKV at batch-1-sized shapes: one round of role-split 128 x 256 tiles when they fill >= 70 % of the CUs (M = 2 x 937: 192 tiles,
-        // 22.0 vs 27.3 us for the 64 x 128 register-staged tiles, sample() 78.3 -> 73.7-76.4 ms; smaller grids stay with the small
-        // tiles: M = 3 x 431 22.4 vs 18.4 us).  f5_gemm_qkv_small_tile: 0 = this rule, 14 = whenever one round, 12 / 13 = lock-step ring.
-        // (the role-split QKV epilogue deals row tiles per batch element: it needs whole sequences, other shapes keep the small tiles)
-        const bool qkv_rows_ok = EPI != EPI_QKV_ROPE || (a.seq_len > 0 && a.M % a.seq_len == 0);
-        const bool qkv14 = EPI == EPI_QKV_ROPE && sel == 0 && qkv_rows_ok && a.rope_g4k != nullptr && t128x256 <= 256 &&
-                           (f5_gemm_qkv_small_tile == 14 || (f5_gemm_qkv_small_tile == 0 && t128x256 >= 176));
-        // MID sizes (batch 2 ... 16: more than one round of small tiles, too few 256 x 256 tiles to fill the chip twice): the role-split
-        // 128 x 256 kernel in several rounds instead of the register-staged 128 x 128 kernel of round 1, which is where the `t128 >= 384`
-        // fallback below used to send them.  sample() with it forced on every block GEMM (tile 14): batch 2 121.6 -> 110.1 ms, batch 3
-        // 167.7 -> 154.5, batch 4 203.7 -> 166.5; equal to the 256 x 256 kernel at batch 8 (328.5 vs 327.4) and 16 (642.5 vs 650.6), whose
-        // N = 1024 GEMMs (t256 < 512) fell to the small kernels as well (profiles/r03/mid_batch_dispatch.txt)
-        const bool mid = sel == 0 && t128 >= 384 && a.N % 256 == 0 && a.ln_counter == nullptr && qkv_rows_ok;
-        if ((sel == 14 || qkv14 || mid) && a.N % 256 == 0 && a.ln_counter == nullptr) return f5_launch_gemm_rs128(a, EPI, stream);
-        if (sel == 14) sel = 0;
-    }
-    {
-        // the small single-round kernels implement the fold for exactly the launches f5_gemm_fold_small names (statistics form)
-        const bool small = f5_gemm_fold_small(a, EPI, true);
-        F5_REQUIRE((a.x16_out == nullptr || (small && EPI == EPI_RESID_GATE)) && a.fold_rowf == nullptr &&
-                       (a.fold_stats == nullptr || (small && EPI == EPI_GELU_TANH)),
-                   "gemm: the LN fold (x16_out / fold_rowf / fold_stats) needs a launch on the 256x256 or the role-split 128x256 kernel "
-                   "(f5_gemm_runs_staged), or one of the batch-1-sized launches of f5_gemm_fold_small in the statistics form");
-    }
-    if constexpr (EPI == EPI_QKV_ROPE) {
-        // batch-1-sized QKV projection with pair-major tables: one round of 8-wave 128 x 256 tiles with transposed q / k wave tiles
-        // (f5_gemm_qkv_small_tile = 13 / 12) instead of 64 x 128 register-staged tiles (0)
-        if (sel == 0 && (f5_gemm_qkv_small_tile == 12 || f5_gemm_qkv_small_tile == 13) && a.rope_g4k != nullptr && a.N % 256 == 0) {
-            const long t128x256 = (long)f5_cdiv(a.M, 128) * (a.N / 256);
-            if (t128x256 <= 256) sel = f5_gemm_qkv_small_tile;
-        }
-    }
-    if (sel == 12 || sel == 13) {
-        if constexpr (EPI == EPI_QKV_ROPE || EPI == EPI_BF16 || EPI == EPI_GELU_TANH) {
-            if (a.N % 256 == 0)
-                return sel == 12 ? launch_ring_wide<EPI, 2, 2, 2, 4>(a, stream) : launch_ring_wide<EPI, 1, 4, 4, 2>(a, stream);
-        }
-        sel = 0;
-    }
-    if (sel == 10) return launch_ring_ks2<EPI, 1>(a, stream);
-    if (sel == 11) return launch_ring_ks2<EPI, 2>(a, stream);
-    if (sel == 8 || sel == 9) {
-        const int bn = sel == 8 ? 192 : 128;
-        if (a.N % bn == 0) return sel == 8 ? launch_ring8<EPI, 3>(a, stream) : launch_ring8<EPI, 2>(a, stream);
-        sel = 0;
-    }
-    if (sel == 0 && f5_gemm_ring_default) {
-        // one round of 8-wave workgroups (measured at M = 937 / 1874, tools/ring8_bench.py): 128x128 tiles when they fill
-        // 70-100 % of the CUs (FF1 at batch 1: 15.0 vs 17.5 us), else 64x128 tiles with the K tiles split over two wave
-        // groups (out-proj 12.4 vs 13.4 us, FF2 18.2 vs 20-21 us)
-        if (a.N % 128 == 0 && t128 >= 176 && t128 <= 256) return launch_ring8<EPI, 2>(a, stream);
-        if (t64x128 >= 176 && t64x128 <= 256) return launch_ring_ks2<EPI, 1>(a, stream);
-    }
-    if (sel == 0 || sel == 4) sel = t128 >= 384 ? 1 : (t64x128 >= 384 ? 2 : 3);
-    if (EPI == EPI_QKV_ROPE && sel == 3) sel = 2;
-    if (EPI == EPI_QKV_ROPE && sel == 6) sel = 5;  // the V^T / head mapping wants >= one whole head per tile column
-    if (sel == 5) return launch_ring<EPI, 1, 2>(a, stream);
-    if (sel == 6) return launch_ring<EPI, 1, 1>(a, stream);
-    if (sel == 1) return launch_cfg<EPI, 2, 2>(a, stream);
-    if (f5_gemm_ring_default) {
-        // the ring kernels hold 2 workgroups per CU (512 slots); the register-staged 64x128 kernel needs only 48 KB of
-        // LDS (3 per CU, 768 slots): prefer it when that turns two rounds of tiles into one (QKV at M = 2*937: 720 tiles)
-        if (sel == 2 && t64x128 > 512 && t64x128 <= 768) return launch_cfg<EPI, 1, 2>(a, stream);
-        return sel == 2 ? launch_ring<EPI, 1, 2>(a, stream) : launch_ring<EPI, 1, 1>(a, stream);
-    }
-    if (sel == 2) return launch_cfg<EPI, 1, 2>(a, stream);
-    return launch_cfg<EPI, 1, 1>(a, stream);
+    f5_set_error("gemm: route %d does not exist for epilogue %d", (int)kern, EPI);
+    return 2;
 }
 
-int f5_launch_gemm(const F5GemmArgs& a_in, int epi, hipStream_t stream) {
+// checks, routes and launches; *reached = what f5_debug_last_gemm_kernel is to report when this returns 0
+static int route_and_launch(const F5GemmArgs& a_in, int epi, hipStream_t stream, int* reached) {
     F5GemmArgs a = a_in;
-    f5dbg::last_gemm_kernel = "";              // a refused launch reports no kernel
     a.debug_flags |= f5_gemm_debug_flags;      // process-wide flags on top of the caller's (an engine's own option)
     if (a.sat_flag == nullptr) a.sat_flag = f5_sat_flag_host;      // fp16 range detector of the 16-bit epilogues (op16.hpp), or null
     F5_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0 && a.K % BK == 0, "gemm: bad shape M=%d N=%d K=%d (K must be a multiple of %d)",
@@ -1120,30 +960,43 @@ int f5_launch_gemm(const F5GemmArgs& a_in, int epi, hipStream_t stream) {
         F5_REQUIRE(epi != EPI_QKV_ROPE || (a.rope_g4k && a.dmodel % 256 == 0), "gemm(qkv): the LN fold needs the transposed q / k tiles");
         a.bias = nullptr;                             // inside fold_c2
     }
-    switch (epi) {
-        case EPI_F32: return launch_epi<EPI_F32>(a, stream);
-        case EPI_BF16: return launch_epi<EPI_BF16>(a, stream);
-        case EPI_GELU_TANH: return launch_epi<EPI_GELU_TANH>(a, stream);
-        case EPI_GELU_ERF: return launch_epi<EPI_GELU_ERF>(a, stream);
-        case EPI_RESID_GATE: return launch_epi<EPI_RESID_GATE>(a, stream);
-        case EPI_QKV_ROPE:
-            F5_REQUIRE(a.dmodel % 128 == 0 && a.N == 3 * a.dmodel, "gemm(qkv): N must be 3*dmodel, dmodel %% 128 == 0");
-            F5_REQUIRE(a.rope_cos && a.rope_sin, "gemm(qkv): token-major rotation tables missing");
-            if (a.rope_g4k || a.rope_g4q) {
-                // group-major tables = transposed q / k tiles on the staged kernels: every 256-column tile must lie inside one of the
-                // q | k | v ranges, the bias is read as 16-byte quads; gemm flag 16384 = A/B against the straight tiles
-                F5_REQUIRE(a.rope_g4q && a.rope_g4k && ((reinterpret_cast<uintptr_t>(a.rope_g4q) | reinterpret_cast<uintptr_t>(a.rope_g4k)) & 15) == 0 &&
-                               (size_t)a.seq_len * 16 * 16 < (1ull << 31),
-                           "gemm(qkv): group-major rotation tables incomplete / not 16-byte aligned");
-                const bool ok = a.dmodel % 256 == 0 && (a.bias == nullptr || (reinterpret_cast<uintptr_t>(a.bias) & 15) == 0) &&
-                                (f5_gemm_debug_flags & 16384) == 0;
-                if (!ok) a.rope_g4q = a.rope_g4k = nullptr;
-            }
-            return launch_epi<EPI_QKV_ROPE>(a, stream);
-        case EPI_ADDROWS: return launch_epi<EPI_ADDROWS>(a, stream);
-        case EPI_RESID_KEEP: return launch_epi<EPI_RESID_KEEP>(a, stream);
-        case EPI_GELU_ERF_BF16: return launch_epi<EPI_GELU_ERF_BF16>(a, stream);
-        default: f5_set_error("gemm: unknown epilogue %d", epi); return 2;
+    F5_REQUIRE(epi >= EPI_F32 && epi <= EPI_GELU_ERF_BF16, "gemm: unknown epilogue %d", epi);
+    if (epi == EPI_QKV_ROPE) {
+        F5_REQUIRE(a.dmodel % 128 == 0 && a.N == 3 * a.dmodel, "gemm(qkv): N must be 3*dmodel, dmodel %% 128 == 0");
+        F5_REQUIRE(a.rope_cos && a.rope_sin, "gemm(qkv): token-major rotation tables missing");
+        if (a.rope_g4k || a.rope_g4q) {
+            // group-major tables = transposed q / k tiles on the staged kernels: every 256-column tile must lie inside one of the
+            // q | k | v ranges, the bias is read as 16-byte quads; gemm flag 16384 = A/B against the straight tiles
+            F5_REQUIRE(a.rope_g4q && a.rope_g4k && ((reinterpret_cast<uintptr_t>(a.rope_g4q) | reinterpret_cast<uintptr_t>(a.rope_g4k)) & 15) == 0 &&
+                           (size_t)a.seq_len * 16 * 16 < (1ull << 31),
+                       "gemm(qkv): group-major rotation tables incomplete / not 16-byte aligned");
+            const bool ok = a.dmodel % 256 == 0 && (a.bias == nullptr || (reinterpret_cast<uintptr_t>(a.bias) & 15) == 0) &&
+                            (f5_gemm_debug_flags & 16384) == 0;
+            if (!ok) a.rope_g4q = a.rope_g4k = nullptr;
+        }
     }
+    F5_REQUIRE(a.ln_counter == nullptr || (a.ldo == a.N && a.ln_scale && a.ln_shift && a.ln_out[0]), "%s", F5_GEMM_MSG_LN_TAIL);
+    const F5GemmQuery q = f5_gemm_query(a, epi);
+    const F5GemmRoute r = f5_gemm_route(q);
+    F5_REQUIRE(r.kernel != F5K_NONE, "%s", r.refused);
+    *reached = f5_gemm_reached(r.kernel, q);
+    switch (epi) {
+        case EPI_F32: return launch_epi<EPI_F32>(a, r.kernel, stream);
+        case EPI_BF16: return launch_epi<EPI_BF16>(a, r.kernel, stream);
+        case EPI_GELU_TANH: return launch_epi<EPI_GELU_TANH>(a, r.kernel, stream);
+        case EPI_GELU_ERF: return launch_epi<EPI_GELU_ERF>(a, r.kernel, stream);
+        case EPI_RESID_GATE: return launch_epi<EPI_RESID_GATE>(a, r.kernel, stream);
+        case EPI_QKV_ROPE: return launch_epi<EPI_QKV_ROPE>(a, r.kernel, stream);
+        case EPI_ADDROWS: return launch_epi<EPI_ADDROWS>(a, r.kernel, stream);
+        case EPI_RESID_KEEP: return launch_epi<EPI_RESID_KEEP>(a, r.kernel, stream);
+        default: return launch_epi<EPI_GELU_ERF_BF16>(a, r.kernel, stream);
+    }
+}
+
+int f5_launch_gemm(const F5GemmArgs& a, int epi, hipStream_t stream) {
+    int reached = 0;
+    const int rc = route_and_launch(a, epi, stream, &reached);
+    f5dbg::last_gemm_kernel = rc == 0 ? reached : 0;       // a launch that was refused, or failed, reports no kernel
+    return rc;
 }
 }  // namespace F5_NS

@@ -52,7 +52,7 @@ struct F5GemmArgs {
     const float* rope_g4k;
     int debug_flags;          // bit 0: skip the epilogue (timing experiments only)
     int nband;                // 256x256 kernel: > 0 = tiles numbered band-major, bands of nband column tiles (set by the launcher)
-    // ---- EPI_RESID_GATE only, small-tile kernels only (f5_gemm_resid_ln_fusable): LN-modulate of the NEXT sub-layer fused
+    // ---- EPI_RESID_GATE only, small-tile kernels only (gemm_route.hpp f5_gemm_resid_ln_fusable): LN-modulate of the NEXT sub-layer fused
     // behind the residual update.  The workgroup that completes a row block (last of its tiles_n column tiles to finish, found
     // with one agent-scope atomic counter per row block) re-reads the block's rows of x and writes
     // ln_out = LN(x) * (1 + ln_scale) + ln_shift.  Needs N == ldo == the LN width (256 / 512 / 768 / 1024).
@@ -108,12 +108,12 @@ struct F5GemmArgs {
 };
 
 int f5_launch_gemm(const F5GemmArgs& a, int epi, hipStream_t stream);
-// true when f5_launch_gemm runs this launch on a kernel with the LDS-staged epilogues (256x256 / role-split 128x256): the only ones
-// that implement the x16_out / stats_out / fold_* fields (f5_launch_gemm fails loudly for the others)
-bool f5_gemm_runs_staged(const F5GemmArgs& a, int epi);
-// true when f5_launch_gemm runs this launch on the batch-1-sized (single-round) kernel that implements the LN fold for its role:
-// producer (EPI_RESID_GATE), or consumer in the statistics form (EPI_GELU_TANH, EPI_QKV_ROPE with group-major rotation tables = qkv_tr)
-bool f5_gemm_fold_small(const F5GemmArgs& a, int epi, bool qkv_tr);
+// what f5_gemm_route (gemm_route.hpp) reads of a launch.  f5_launch_gemm routes on it after OR-ing in the process-wide flags and clearing
+// unusable group-major tables; the engine asks f5_gemm_runs_staged / f5_gemm_fold_small / f5_gemm_resid_ln_fusable with it beforehand.
+inline F5GemmQuery f5_gemm_query(const F5GemmArgs& a, int epi) {
+    const unsigned fold = (a.x16_out ? F5_FOLD_PRODUCER : 0u) | (a.fold_stats ? F5_FOLD_STATS : 0u) | (a.fold_rowf ? F5_FOLD_ROWF : 0u);
+    return {epi, a.M, a.N, a.nseg, a.seq_len, a.rope_g4k != nullptr, a.ln_counter != nullptr, fold, a.debug_flags};
+}
 // row factors of the fold: rowf[r] = (rstd, rstd * (mean - m)) of row r from its nslice slice statistics (stats[slice][ld][2] =
 // (sum d, centred sum of squares) of d = x - m; width = 64 nslice).  row_shift (optional, [M]): on entry m (what the producer
 // subtracted; null = 0), on exit the row's mean -- the shift of the next folded operand.
@@ -133,8 +133,6 @@ int f5_launch_fold_consts(const op16_t* w, int ldw, const float* bias, const flo
 int f5_launch_gemm256(const F5GemmArgs& a, int epi, hipStream_t stream);
 // batch-1-sized shapes: role-split 128 x 256 tiles, one round of 8-wave workgroups (gemm_rs128.hip)
 int f5_launch_gemm_rs128(const F5GemmArgs& a, int epi, hipStream_t stream);
-// true when f5_launch_gemm(a, EPI_RESID_GATE) would run a small-tile kernel that implements the fused LN tail (a.ln_* unset or set)
-bool f5_gemm_resid_ln_fusable(const F5GemmArgs& a);
 
 // MX-fp8 GEMM (256x256x128 tiles, v_mfma_scale_f32_32x32x64_f8f6f4): M >= 1, N % 256 == 0, K % 128 == 0.
 // epi: EPI_F32, EPI_BF16, EPI_GELU_TANH (fp8 + scales out), EPI_RESID_GATE, EPI_QKV_ROPE.

@@ -346,10 +346,6 @@ static int launch256(const F5GemmArgs& a, hipStream_t stream) {
     // (f5_launch_gemm has checked the fold's preconditions: transposed q / k tiles, K = 1024 for the statistics form)
     const int fold = !CAN_FOLD ? 0 : (ab.fold_stats != nullptr ? 2 : (ab.fold_rowf != nullptr ? 1 : 0));
     constexpr bool QT = EPI == EPI_QKV_ROPE;
-    {
-        static const char* const names[2][3] = {{"gemm256", "gemm256+fold_rowf", "gemm256+fold_stats"}, {"gemm256+qk_tr", "gemm256+qk_tr+fold_rowf", "gemm256+qk_tr+fold_stats"}};
-        f5dbg::last_gemm_kernel = names[EPI == EPI_QKV_ROPE && ab.rope_g4k != nullptr][fold];
-    }
     if (EPI == EPI_QKV_ROPE && ab.rope_g4k != nullptr) {
         if (fold == 2) hipLaunchKernelGGL((f5_gemm256_kernel<EPI, QT, CAN_FOLD ? 2 : 0>), dim3(ntiles), dim3(512), 0, stream, ab, tiles_n, nfull, tiles_mf);
         else if (fold == 1) hipLaunchKernelGGL((f5_gemm256_kernel<EPI, QT, CAN_FOLD ? 1 : 0>), dim3(ntiles), dim3(512), 0, stream, ab, tiles_n, nfull, tiles_mf);
@@ -363,7 +359,8 @@ static int launch256(const F5GemmArgs& a, hipStream_t stream) {
     return 0;
 }
 
-// Preconditions (checked by f5_launch_gemm): N % 256 == 0, M >= 256, K % 64 == 0, operands below 2 GiB (32-bit byte offsets)
+// Preconditions (checked by f5_launch_gemm): N % 256 == 0, M >= 256, K % 64 == 0, operands below 2 GiB (32-bit byte offsets).  The
+// requirements below are assertions, not decisions: gemm_route.hpp f5_gemm_route refuses the shapes that would miss them
 int f5_launch_gemm256(const F5GemmArgs& a, int epi, hipStream_t stream) {
     F5_REQUIRE(a.N % 256 == 0 && a.M >= 256 && a.K % BK == 0, "gemm256: needs N %% 256 == 0, M >= 256, K %% 64 == 0");
     F5_REQUIRE((size_t)(a.a_row_mod > 0 ? a.a_row_mod : a.M) * a.lda < (1ull << 31) && (size_t)(a.N + 256) * a.ldw < (1ull << 31),

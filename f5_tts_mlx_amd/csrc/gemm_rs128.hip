@@ -311,10 +311,6 @@ static int launch_rs128(const F5GemmArgs& a, hipStream_t stream) {
     // (f5_launch_gemm has checked the fold's preconditions: transposed q / k tiles, K = 1024 for the statistics form)
     const int fold = !CAN_FOLD ? 0 : (ab.fold_stats != nullptr ? 2 : (ab.fold_rowf != nullptr ? 1 : 0));
     constexpr bool QT = EPI == EPI_QKV_ROPE;
-    {
-        static const char* const names[2][3] = {{"rs128", "rs128+fold_rowf", "rs128+fold_stats"}, {"rs128+qk_tr", "rs128+qk_tr+fold_rowf", "rs128+qk_tr+fold_stats"}};
-        f5dbg::last_gemm_kernel = names[EPI == EPI_QKV_ROPE && ab.rope_g4k != nullptr][fold];
-    }
     if (EPI == EPI_QKV_ROPE && ab.rope_g4k != nullptr) {
         if (fold == 2) hipLaunchKernelGGL((f5_gemm_rs128_kernel<EPI, QT, CAN_FOLD ? 2 : 0>), dim3(ntiles), dim3(512), 0, stream, ab, tiles_n, ntiles, tiles_m);
         else if (fold == 1) hipLaunchKernelGGL((f5_gemm_rs128_kernel<EPI, QT, CAN_FOLD ? 1 : 0>), dim3(ntiles), dim3(512), 0, stream, ab, tiles_n, ntiles, tiles_m);
@@ -328,7 +324,9 @@ static int launch_rs128(const F5GemmArgs& a, hipStream_t stream) {
     return 0;
 }
 
-// Preconditions (checked by f5_launch_gemm): N % 256 == 0, K % 64 == 0, operands below 2 GiB (32-bit byte offsets)
+// Preconditions (checked by f5_launch_gemm): N % 256 == 0, K % 64 == 0, operands below 2 GiB (32-bit byte offsets).  The requirements
+// below are assertions, not decisions: gemm_route.hpp f5_gemm_route sends only launches here that meet them (a ragged M % seq_len of
+// the QKV projection is refused there, with the same words)
 int f5_launch_gemm_rs128(const F5GemmArgs& a, int epi, hipStream_t stream) {
     F5_REQUIRE(a.N % 256 == 0 && a.M >= 1 && a.K % BK == 0, "gemm_rs128: needs N %% 256 == 0, K %% 64 == 0");
     F5_REQUIRE(epi != EPI_QKV_ROPE || (a.seq_len > 0 && a.M % a.seq_len == 0), "gemm_rs128(qkv): M must be a multiple of seq_len");

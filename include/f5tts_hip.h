@@ -287,7 +287,8 @@ uint16_t f5_debug_f2bf_bits(float f);
  * itself reaches by shape, so that small test shapes can exercise every shipped tile path. */
 /* force the GEMM block tile: 0 auto, 1 = 128x128, 2 = 64x128, 3 = 64x64 (register-staged), 4 = 256x256 (gemm256.hip), 5 / 6 = ring
  * 64x128 / 64x64, 8 / 9 = 8-wave ring 128x192 / 128x128, 10 / 11 = in-workgroup split-K 64x128 / 128x128, 12 / 13 = 8-wave ring
- * 128x256 with 64x64 / 32x128 wave tiles */
+ * 128x256 with 64x64 / 32x128 wave tiles, 14 = role-split 128x256 (gemm_rs128.hip).  What a selector means for a given launch --
+ * which shapes and epilogues fall back to the automatic choice -- is written once, in csrc/gemm_route.hpp f5_gemm_route. */
 int f5_debug_set_gemm_tile(int sel);
 /* which kernel did it run?  Copies (at most n - 1 characters + NUL) a short stable name of the kernel the most recent GEMM launch of
  * the process resolved to and returns the name's length: family plus the template parameters that tell instantiations apart --
@@ -295,6 +296,14 @@ int f5_debug_set_gemm_tile(int sel);
  * / ring_ks2<2>, ring_wide<2,2,2,4> / ring_wide<1,4,4,2>, gemm256 and rs128 (+qk_tr, +fold_rowf / +fold_stats).  "" after a launch that
  * was refused.  Host side only: nothing reaches a kernel.  The operand type is f5_op_get_operand_type's. */
 int f5_debug_last_gemm_kernel(char* buf, int n);
+/* which kernel WOULD it run?  The same routing function the launcher switches over (csrc/gemm_route.hpp), asked for a launch of this
+ * epilogue and shape under the current selectors (f5_debug_set_gemm_tile / _ring / _qkv_tile) and process-wide flags; nothing is
+ * launched and no device is touched.  variant_bits: 1 = group-major rotation tables set (transposed q / k tiles), 2 = fused LN tail,
+ * 4 = LN-fold producer, 8 = LN-fold consumer in the statistics form, 16 = LN-fold consumer with row factors.  Copies the name
+ * f5_debug_last_gemm_kernel would report after the launch and returns its length, or a negative value when the launch would be refused
+ * (f5_last_error says why).  facts (may be NULL): bit 0 = staged multi-round kernel, bit 1 = single-round LN-fold launch, bit 2 = an
+ * EPI_RESID_GATE launch of this shape with ldo == N can carry the fused LN tail -- what the engine plans the LN fold with. */
+int f5_debug_gemm_route(int epi, int M, int N, int nseg, int seq_len, int variant_bits, int debug_flags, char* name, int n, int* facts);
 /* GEMM flag bits, OR-ed into every GEMM launch of the process (an engine's own: f5_engine_set_option "gemm_flags"):
  * bit 0: skip the epilogue of the 256x256 kernel (timing only; results are garbage);
  * bit 1: small-tile kernels use the direct (2-byte store) epilogue instead of the LDS-staged one;

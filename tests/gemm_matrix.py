@@ -19,7 +19,7 @@ EPI = {"F32": 0, "BF16": 1, "GELU_TANH": 2, "GELU_ERF": 3, "RESID_GATE": 4, "ADD
 EPIS = tuple(EPI)
 OUT16 = ("BF16", "GELU_TANH", "GELU_ERF_BF16")            # 16-bit output only
 RS128_EPIS = ("F32", "BF16", "GELU_TANH", "RESID_GATE")   # gemm_rs128.hip implements these (and QKV_ROPE, not in this matrix)
-WIDE_EPIS = ("BF16", "GELU_TANH")                         # launch_ring_wide is instantiated for these (and QKV_ROPE)
+WIDE_EPIS = ("BF16", "GELU_TANH")                         # the 128x256 ring tiles are instantiated for these (and QKV_ROPE)
 OPS = ("bf16", "f16")
 SELECTORS = (0, 1, 2, 3, 4, 5, 6, 8, 9, 10, 11, 12, 13, 14)
 ANY_N = (0, 1, 2, 3, 5, 6, 10, 11)
@@ -77,20 +77,32 @@ class Case:
         return (self.op, self.kernel, self.sel, self.ring, self.epi, self.nseg)
 
 
-def expected_kernel(sel, epi, M, N, ring=1):
-    """What launch_epi (csrc/gemm.hip) resolves a launch to, written out from its source; None = it refuses the launch."""
+def expected_kernel(sel, epi, M, N, ring=1, *, seq_len=0, g4=False, qkv_tile=0):
+    """What f5_launch_gemm resolves a launch to (the base name, without the +variant suffixes); None = it refuses the launch.  The rule
+    itself is csrc/gemm_route.hpp f5_gemm_route; this is its mirror, written out by hand so that the two can be compared point by
+    point (tests/test_gemm_route_host.py) and the launcher checked against it (tests/test_gemm_matrix_gpu.py).  The keyword arguments matter for epi "QKV_ROPE" only
+    (not an epilogue of this matrix): seq_len = rows per batch element, g4 = the group-major rotation tables are set, qkv_tile = the
+    f5_debug_set_gemm_qkv_tile knob."""
+    qkv = epi == "QKV_ROPE"
     t128, t64, t256 = cdiv(M, 128) * cdiv(N, 128), cdiv(M, 64) * cdiv(N, 128), cdiv(M, 256) * (N // 256)
     v2ok = N % 256 == 0 and M >= 256
     if sel == 4 or (sel == 0 and v2ok and t256 >= 512):
         return "gemm256" if v2ok else None
-    if epi in RS128_EPIS:
-        mid = sel == 0 and t128 >= 384
-        if (sel == 14 or mid) and N % 256 == 0:
-            return "rs128"
+    if epi in RS128_EPIS or qkv:
+        t128x256 = cdiv(M, 128) * (N // 256)
+        if qkv and seq_len > 0:
+            t128x256 = (M // seq_len) * cdiv(seq_len, 128) * (N // 256)       # the role-split QKV epilogue deals row tiles per batch element
+        rows_ok = not qkv or (seq_len > 0 and M % seq_len == 0)
+        qkv14 = qkv and sel == 0 and rows_ok and g4 and t128x256 <= 256 and (qkv_tile == 14 or (qkv_tile == 0 and t128x256 >= 176))
+        mid = sel == 0 and t128 >= 384 and rows_ok
+        if (sel == 14 or qkv14 or mid) and N % 256 == 0:
+            return "rs128" if rows_ok else None          # selector 14 with a ragged M % seq_len: f5_launch_gemm_rs128 refuses it
         if sel == 14:
             sel = 0
+    if qkv and sel == 0 and qkv_tile in (12, 13) and g4 and N % 256 == 0 and cdiv(M, 128) * (N // 256) <= 256:
+        sel = qkv_tile
     if sel in (12, 13):
-        if epi in WIDE_EPIS and N % 256 == 0:
+        if (epi in WIDE_EPIS or qkv) and N % 256 == 0:
             return "ring_wide<2,2,2,4>" if sel == 12 else "ring_wide<1,4,4,2>"
         sel = 0
     if sel in (10, 11):
@@ -106,6 +118,10 @@ def expected_kernel(sel, epi, M, N, ring=1):
             return "ring_ks2<1>"
     if sel in (0, 4):
         sel = 1 if t128 >= 384 else (2 if t64 >= 384 else 3)
+    if qkv and sel == 3:
+        sel = 2
+    if qkv and sel == 6:
+        sel = 5                   # the V^T / head mapping wants >= one whole head per tile column
     if sel == 5:
         return "ring<1,2>"
     if sel == 6:
@@ -166,6 +182,25 @@ def cases():
                     if sel == 2:
                         out.append(make_case(op, sel, epi, nseg, 2100, 2048, 64, note="528 tiles of 64x128: the register-staged kernel"))
     return out
+
+
+# ---- shape tables shared by the GPU matrix (tests/test_gemm_matrix_gpu.py) and the routing test on the CPU (tests/test_gemm_route_host.py)
+# forced selectors the dispatcher does not honour for this (epilogue, N): (selector, epilogue, M, N)
+FALLBACKS = [(8, "F32", 300, 256), (8, "RESID_KEEP", 300, 512), (9, "BF16", 300, 192), (12, "BF16", 300, 384), (13, "GELU_TANH", 300, 384),
+             (12, "RESID_GATE", 300, 256), (13, "F32", 300, 512), (12, "ADDROWS", 300, 256), (14, "RESID_GATE", 300, 384), (14, "F32", 300, 100),
+             (14, "ADDROWS", 300, 256), (14, "RESID_KEEP", 300, 512), (14, "GELU_ERF", 300, 256), (14, "GELU_ERF_BF16", 300, 256)]
+# selector 4 (the 256x256 kernel) at shapes it cannot run: the launch is refused
+SEL4_REFUSALS = [("sel4_M_below_256", make_case("bf16", 4, "F32", 1, 255, 256, 128)), ("sel4_N_not_256", make_case("bf16", 4, "F32", 1, 300, 384, 128)),
+                 ("sel4_N_100_resid_gate", make_case("f16", 4, "RESID_GATE", 1, 300, 100, 128))]
+# every GEMM launch of prepare / run_dit for the 335M configuration at 937 frames, M = 2 x B x 937 rows: (name, epilogue, N, K)
+PRODUCTION = [("hoisted_proj", "F32", 1024, 128 + 512), ("text_pw1", "GELU_ERF", 1024, 512), ("text_pw2", "RESID_KEEP", 512, 1024),
+              ("input_proj", "ADDROWS", 1024, 128), ("attn_out", "RESID_GATE", 1024, 1024), ("ff1", "GELU_TANH", 2048, 1024),
+              ("ff2", "RESID_GATE", 1024, 2048), ("final_proj", "F32", 100, 1024)]
+# what f5_gemm_route's comments (csrc/gemm_route.hpp) promise for the block GEMMs: batch 1 one round of 8-wave workgroups (128x128 for FF1, split-K 64x128 for
+# the out-projection and FF2), the role-split 128x256 kernel at the mid sizes, the 256x256 kernel at batch 32
+PROMISED = {1: {"attn_out": "ring_ks2<1>", "ff1": "ring8<2>", "ff2": "ring_ks2<1>", "input_proj": "ring_ks2<1>"},
+            8: {"attn_out": "rs128", "ff1": "rs128", "ff2": "rs128", "final_proj": "ring_ks2<1>"},
+            32: {"attn_out": "gemm256", "ff1": "gemm256", "ff2": "gemm256"}}
 
 
 # ---- buffers ---------------------------------------------------------------------------------------------------------------

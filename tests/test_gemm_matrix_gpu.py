@@ -1,7 +1,8 @@
 """The GEMM family against fp64, by construction: every tile selector x epilogue x operand type x nseg of csrc/gemm.hip's dispatcher,
 at shapes derived from the selector's block tile (tests/gemm_matrix.py), with leading dimensions that are never the tight ones, NaN in
 the operands' pad columns, guard bands around every output, tolerances that follow from the operand type, and the name of the kernel
-each launch resolved to (f5_debug_last_gemm_kernel) checked against what the dispatcher's source says.
+each launch resolved to (f5_debug_last_gemm_kernel) checked against what the dispatcher's source says and against the routing function
+asked without a launch (f5_debug_gemm_route, tests/test_gemm_route_host.py).
 
 Then: the coverage of (kernel, epilogue, operand type, nseg) instantiations, requests the launchers must refuse, and every GEMM launch of
 prepare / run_dit of the 335M configuration at N = 937, batch 1 ... 32.
@@ -34,6 +35,13 @@ def last_kernel(lib):
     name = buf.value.decode()
     assert n == len(name)
     return name
+
+
+def routed_kernel(lib, c):
+    """what the routing function (csrc/gemm_route.hpp) says about the case, asked without a launch; "" = it would refuse"""
+    buf = C.create_string_buffer(64)
+    n = lib.f5_debug_gemm_route(GM.EPI[c.epi], c.M, c.N, c.nseg, 0, 0, 0, buf, 64, None)
+    return buf.value.decode() if n >= 0 else ""
 
 
 def launch(lib, b):
@@ -81,6 +89,9 @@ def run_case(lib, c, rows=None):
     bad = GM.check(b, rows=rows)
     if name != c.kernel:
         bad.append(f"ran {name}, the dispatcher's source says {c.kernel}")
+    routed = routed_kernel(lib, c)
+    if name != routed:
+        bad.append(f"ran {name}, f5_debug_gemm_route says {routed!r}")
     return name, bad
 
 
@@ -113,9 +124,9 @@ def test_matrix(lib, group):
     assert not failures, failures[:5]
 
 
-# Every instantiation launch_epi / f5_launch_gemm256 / f5_launch_gemm_rs128 can produce for the eight epilogues of this matrix, written
+# Every instantiation launch_epi (csrc/gemm.hip) / f5_launch_gemm256 / f5_launch_gemm_rs128 can produce for the eight epilogues of this matrix, written
 # out from the sources: the nine small-tile / ring launchers are instantiated for every epilogue, gemm256.hip switches over all of
-# them, gemm_rs128.hip over four, launch_ring_wide is only called for two (and for EPI_QKV_ROPE, which stays with
+# them, gemm_rs128.hip over four, the 128x256 ring tiles are only instantiated for two (and for EPI_QKV_ROPE, which stays with
 # test_ops_gpu._attention_case, like the +qk_tr variants of gemm256 / rs128).
 EXPECTED = {(k, e) for k in ("cfg<2,2>", "cfg<1,2>", "cfg<1,1>", "ring<1,2>", "ring<1,1>", "ring8<3>", "ring8<2>", "ring_ks2<1>", "ring_ks2<2>", "gemm256")
             for e in GM.EPIS}
@@ -140,9 +151,7 @@ def test_matrix_reaches_every_instantiation():
 
 
 # ---- forced selectors the dispatcher does not honour: recorded under the kernel actually reached ------------------------------
-FALLBACKS = [(8, "F32", 300, 256), (8, "RESID_KEEP", 300, 512), (9, "BF16", 300, 192), (12, "BF16", 300, 384), (13, "GELU_TANH", 300, 384),
-             (12, "RESID_GATE", 300, 256), (13, "F32", 300, 512), (12, "ADDROWS", 300, 256), (14, "RESID_GATE", 300, 384), (14, "F32", 300, 100),
-             (14, "ADDROWS", 300, 256), (14, "RESID_KEEP", 300, 512), (14, "GELU_ERF", 300, 256), (14, "GELU_ERF_BF16", 300, 256)]
+FALLBACKS = GM.FALLBACKS
 
 
 @pytest.mark.parametrize("op", GM.OPS)
@@ -159,9 +168,8 @@ def test_fallbacks_compute_the_same_thing(lib, op, sel, epi, M, N):
 # ---- refusals ------------------------------------------------------------------------------------------------------------------
 def _refusal_cases():
     base = dict(op="bf16", epi="F32", nseg=1)
-    yield "sel4_M_below_256", GM.make_case(sel=4, M=255, N=256, K=128, **base), {}
-    yield "sel4_N_not_256", GM.make_case(sel=4, M=300, N=384, K=128, **base), {}
-    yield "sel4_N_100_resid_gate", GM.make_case("f16", 4, "RESID_GATE", 1, 300, 100, 128), {}
+    for name, c in GM.SEL4_REFUSALS:
+        yield name, c, {}
     yield "lda_not_8", GM.make_case(sel=0, M=100, N=256, K=128, **base), {"lda": 128 + 4}
     yield "ldw_not_8", GM.make_case(sel=5, M=100, N=256, K=128, **base), {"ldw": 128 + 12}
     yield "K_not_64", GM.make_case(sel=0, M=100, N=256, K=128, **base), {"K": 96}
@@ -210,14 +218,7 @@ def test_illegal_requests_are_refused_and_touch_nothing(lib, name, c, twist):
 # ---- production shapes -------------------------------------------------------------------------------------------------------------
 # every GEMM launch of prepare / run_dit (csrc/engine.hip) for the 335M configuration (dim 1024, ff 2048, text 512 / 1024, mel 100 padded
 # to 128) at 937 frames: M = nb x B x 937 rows with nb = 2 (conditional + null branch); (name, epilogue, N, K)
-PRODUCTION = [("hoisted_proj", "F32", 1024, 128 + 512), ("text_pw1", "GELU_ERF", 1024, 512), ("text_pw2", "RESID_KEEP", 512, 1024),
-              ("input_proj", "ADDROWS", 1024, 128), ("attn_out", "RESID_GATE", 1024, 1024), ("ff1", "GELU_TANH", 2048, 1024),
-              ("ff2", "RESID_GATE", 1024, 2048), ("final_proj", "F32", 100, 1024)]
-# what launch_epi's comments promise for the block GEMMs: batch 1 one round of 8-wave workgroups (128x128 for FF1, split-K 64x128 for
-# the out-projection and FF2), the role-split 128x256 kernel at the mid sizes, the 256x256 kernel at batch 32
-PROMISED = {1: {"attn_out": "ring_ks2<1>", "ff1": "ring8<2>", "ff2": "ring_ks2<1>", "input_proj": "ring_ks2<1>"},
-            8: {"attn_out": "rs128", "ff1": "rs128", "ff2": "rs128", "final_proj": "ring_ks2<1>"},
-            32: {"attn_out": "gemm256", "ff1": "gemm256", "ff2": "gemm256"}}
+PRODUCTION, PROMISED = GM.PRODUCTION, GM.PROMISED
 
 
 def sample_rows(M, seed):
@@ -250,6 +251,6 @@ def test_production_shapes(lib, op, B):
             failures.append((name, bad))
         want = PROMISED.get(B, {}).get(name)
         if want is not None and kernel != want:
-            failures.append((name, f"launch_epi's comments promise {want} at batch {B}, ran {kernel}"))
+            failures.append((name, f"f5_gemm_route's comments promise {want} at batch {B}, ran {kernel}"))
         torch.cuda.empty_cache()
     assert not failures, failures

@@ -53,7 +53,7 @@ def test_known_silent_fallbacks_are_named():
     assert GM.expected_kernel(12, "BF16", 300, 256) == "ring_wide<2,2,2,4>"
     assert GM.expected_kernel(8, "F32", 300, 256) == "ring<1,1>" and GM.expected_kernel(8, "F32", 300, 384) == "ring8<3>"
     assert GM.expected_kernel(4, "F32", 100, 256) is None and GM.expected_kernel(4, "F32", 300, 100) is None
-    # the auto rule at the production shapes launch_epi's comments name (M = 2 x 937 per batch element)
+    # the auto rule at the production shapes f5_gemm_route's comments name (M = 2 x 937 per batch element)
     assert GM.expected_kernel(0, "GELU_TANH", 1874, 2048) == "ring8<2>"
     assert GM.expected_kernel(0, "RESID_GATE", 1874, 1024) == "ring_ks2<1>"
     assert GM.expected_kernel(0, "ADDROWS", 1874, 1024) == "ring_ks2<1>"

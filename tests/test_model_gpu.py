@@ -863,7 +863,7 @@ def full_f16():
 @pytest.mark.parametrize("B", [2, 4, 8, 16])
 def test_fullsize_mid_batches_every_utterance_vs_oracle(full_f16, B):
     """batch 2 ... 16 at the full 335M size run the role-split 128 x 256 GEMM IN SEVERAL ROUNDS with the RESID_GATE /
-    GELU / QKV epilogues (the `mid` rule of gemm.hip launch_epi, commit 943a2ee) -- the shipped default path of those batch sizes.
+    GELU / QKV epilogues (the `mid` rule of gemm_route.hpp f5_gemm_route, commit 943a2ee) -- the shipped default path of those batch sizes.
     Here: `f16`, automatic dispatch, N = 937, 5-point Euler + sway + CFG (8 DiT forwards), EVERY utterance against the fp32 CPU
     oracle's answer for the same utterance (tests/golden/full_b16_euler5.npz, made by make_batch_golden.py: bench.py's utterances
     0..15; at equal durations the oracle's batch elements do not interact, so its first B rows are the batch-B answer)."""
