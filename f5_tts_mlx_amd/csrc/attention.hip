@@ -1346,7 +1346,8 @@ static dim3 attn_grid(const F5AttnArgs& a, int qrows) {
     return dim3(nqb * 8 * f5_cdiv(a.B * a.H, 8), 1);
 }
 
-int f5_launch_attention(const F5AttnArgs& a, hipStream_t stream) {
+// checks, routes and launches; reached = what f5_debug_last_attn_kernel is to report when this returns 0
+static int attn_launch(const F5AttnArgs& a, hipStream_t stream, int& reached) {
     F5_REQUIRE(a.B > 0 && a.H > 0 && a.seq_len > 0, "attention: bad shape");
     F5_REQUIRE(a.npad % 64 == 0 && a.npad >= a.seq_len, "attention: npad must be a multiple of 64 and >= seq_len");
     F5_REQUIRE(a.ldqk % 8 == 0 && a.ldo % 4 == 0, "attention: bad leading dims");
@@ -1369,7 +1370,9 @@ int f5_launch_attention(const F5AttnArgs& a, hipStream_t stream) {
         (f5_attn_wide >= 1 || (f5_attn_wide < 0 && (long)f5_cdiv(a.seq_len, 256) * a.B * a.H >= 512))) {
         const dim3 gw = attn_grid(a, 256);
         // f5_attn_pipe: 1 = the in-wave software-pipelined kernel (v2p, one wave per SIMD), 0 = v2f; q must be pre-multiplied
-        if ((a.pipe < 0 ? f5_attn_pipe : a.pipe) && a.q_prescaled) hipLaunchKernelGGL(f5_attn2p_kernel, gw, dim3(256), 0, stream, a);
+        const bool pipe = (a.pipe < 0 ? f5_attn_pipe : a.pipe) && a.q_prescaled;
+        reached = pipe ? F5A_V2P : (a.q_prescaled ? F5A_V2F_PRE : F5A_V2F);
+        if (pipe) hipLaunchKernelGGL(f5_attn2p_kernel, gw, dim3(256), 0, stream, a);
         else if (a.q_prescaled) hipLaunchKernelGGL(f5_attn2f_kernel<true>, gw, dim3(256), 0, stream, a);
         else hipLaunchKernelGGL(f5_attn2f_kernel<false>, gw, dim3(256), 0, stream, a);
         F5_LAUNCH_CHECK();
@@ -1378,10 +1381,13 @@ int f5_launch_attention(const F5AttnArgs& a, hipStream_t stream) {
     if (ks > 1) {
         if (a.hp) {
             F5_REQUIRE(a.qk[1] && a.vt[1] && a.out[1], "attention: bf16x3 needs lo buffers");
+            reached = F5A_V2S_HP;
             hipLaunchKernelGGL((f5_attn2s_kernel<true, 2, 2>), grid, dim3(512), 0, stream, a);
         } else if (ks >= 4) {
+            reached = F5A_V2S_KS4;
             hipLaunchKernelGGL((f5_attn2s_kernel<false, 4, 2, true>), grid, dim3(1024), 0, stream, a);
         } else {
+            reached = F5A_V2S_KS2;
             hipLaunchKernelGGL((f5_attn2s_kernel<false, 2, 3, true>), grid, dim3(512), 0, stream, a);
         }
         F5_LAUNCH_CHECK();
@@ -1389,11 +1395,20 @@ int f5_launch_attention(const F5AttnArgs& a, hipStream_t stream) {
     }
     if (a.hp) {
         F5_REQUIRE(a.qk[1] && a.vt[1] && a.out[1], "attention: bf16x3 needs lo buffers");
+        reached = F5A_V2_HP;
         hipLaunchKernelGGL((f5_attn2_kernel<true, 0>), grid, dim3(256), 0, stream, a);
     } else {
+        reached = F5A_V2;
         hipLaunchKernelGGL((f5_attn2_kernel<false, 0>), grid, dim3(256), 0, stream, a);
     }
     F5_LAUNCH_CHECK();
     return 0;
+}
+
+int f5_launch_attention(const F5AttnArgs& a, hipStream_t stream) {
+    int reached = F5A_NONE;
+    const int rc = attn_launch(a, stream, reached);
+    f5dbg::last_attn_kernel = rc == 0 ? (reached | (a.out8 ? F5A_OUT8 : 0)) : F5A_NONE;    // the one place the hook is written
+    return rc;
 }
 }  // namespace F5_NS

@@ -40,6 +40,23 @@ void f5_set_error(const char* fmt, ...);
 namespace f5dbg {
 extern int last_gemm_kernel;
 }
+// ---- test hook (f5_debug_last_attn_kernel): the same for f5_launch_attention -- one of F5AttnKernel, plus F5A_OUT8 when the launch
+// carried an MX-fp8 output, 0 when it refused the launch.  The name is composed where the hook is read (engine.hip).
+enum F5AttnKernel {
+    F5A_NONE = 0,
+    F5A_V2_HP,       // f5_attn2_kernel<true,0>
+    F5A_V2,          // f5_attn2_kernel<false,0>
+    F5A_V2F_PRE,     // f5_attn2f_kernel<true>
+    F5A_V2F,         // f5_attn2f_kernel<false>
+    F5A_V2P,         // f5_attn2p_kernel
+    F5A_V2S_HP,      // f5_attn2s_kernel<true,2,2>
+    F5A_V2S_KS2,     // f5_attn2s_kernel<false,2,3,true>
+    F5A_V2S_KS4,     // f5_attn2s_kernel<false,4,2,true>
+    F5A_OUT8 = 16
+};
+namespace f5dbg {
+extern int last_attn_kernel;
+}
 
 // ---- host-side float <-> 16-bit operand bits (weight upload), round to nearest even -----------------------
 // bf16: same rounding as torch's .to(bfloat16); fp16: same as torch's .to(float16) except that finite values beyond

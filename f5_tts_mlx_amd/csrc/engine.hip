@@ -1478,6 +1478,7 @@ extern "C" int f5_debug_set_gemm_flags(int v) {
 }
 namespace f5dbg {
 int last_gemm_kernel = 0;
+int last_attn_kernel = 0;
 }
 static int copy_name(const std::string& s, char* buf, int n) {
     if (buf != nullptr && n > 0) {
@@ -1489,6 +1490,17 @@ static int copy_name(const std::string& s, char* buf, int n) {
 // name of the kernel the most recent f5_launch_gemm of the process resolved to ("" = it refused the launch); returns its length
 extern "C" int f5_debug_last_gemm_kernel(char* buf, int n) {
     return copy_name(f5_gemm_kernel_name(f5dbg::last_gemm_kernel), buf, n);
+}
+// name of the kernel the most recent f5_launch_attention of the process launched (one per instantiation, "+f8" when the launch carried
+// the MX-fp8 output; "" = it refused the launch); returns its length
+extern "C" int f5_debug_last_attn_kernel(char* buf, int n) {
+    static const char* const names[] = {"", "f5_attn2_kernel<true,0>", "f5_attn2_kernel<false,0>", "f5_attn2f_kernel<true>", "f5_attn2f_kernel<false>",
+                                        "f5_attn2p_kernel", "f5_attn2s_kernel<true,2,2>", "f5_attn2s_kernel<false,2,3,true>",
+                                        "f5_attn2s_kernel<false,4,2,true>"};
+    const int k = f5dbg::last_attn_kernel & (F5A_OUT8 - 1);
+    std::string s = k <= F5A_V2S_KS4 ? names[k] : "";
+    if (k != F5A_NONE && (f5dbg::last_attn_kernel & F5A_OUT8)) s += "+f8";
+    return copy_name(s, buf, n);
 }
 // The route (gemm_route.hpp) a GEMM launch of this shape would take under the current knobs and process-wide flags, without launching
 // anything or touching a device.  variant_bits: 1 = group-major rotation tables, 2 = fused LN tail, 4 = LN-fold producer, 8 = consumer in
@@ -1665,9 +1677,10 @@ extern "C" int f5_debug_set_op_q_premul(float v) {
     g_op_q_premul = v;
     return 0;
 }
-extern "C" int f5_op_attention(const void* qk_hi, const void* qk_lo, const void* vt_hi, const void* vt_lo, void* out_hi,
-                               void* out_lo, const int32_t* kv_len, int B, int H, int seq_len, int npad, int dmodel, float scale,
-                               int hp, void* stream) {
+// every F5AttnArgs field from the caller (the op-level tests: leading dimensions, q pre-scaling, the v2f / v2p choice, the MX-fp8 output)
+extern "C" int f5_op_attention_ex(const void* qk_hi, const void* qk_lo, const void* vt_hi, const void* vt_lo, void* out_hi, void* out_lo,
+                                  const int32_t* kv_len, int B, int H, int seq_len, int npad, int dmodel, float scale, int hp, int ldqk,
+                                  int ldo, int q_prescaled, int pipe, void* out8, void* out8s, int ldo8, void* stream) {
     F5AttnArgs at;
     memset(&at, 0, sizeof(at));
     at.qk[0] = (const op16_t*)qk_hi;
@@ -1681,14 +1694,24 @@ extern "C" int f5_op_attention(const void* qk_hi, const void* qk_lo, const void*
     at.H = H;
     at.seq_len = seq_len;
     at.npad = npad;
-    at.ldqk = 2 * dmodel;
-    at.ldo = dmodel;
+    at.ldqk = ldqk;
+    at.ldo = ldo;
     at.dmodel = dmodel;
     at.hp = hp;
     at.scale = scale;
-    at.q_prescaled = g_op_q_premul != 0.0f && hp == 0;
-    at.pipe = -1;                                     // the process default (f5_debug_set_attn_pipe)
+    at.q_prescaled = q_prescaled;
+    at.pipe = pipe;
+    at.out8 = (uint8_t*)out8;
+    at.out8s = (uint8_t*)out8s;
+    at.ldo8 = ldo8;
     return g_ops.attention(at, (hipStream_t)stream);
+}
+extern "C" int f5_op_attention(const void* qk_hi, const void* qk_lo, const void* vt_hi, const void* vt_lo, void* out_hi,
+                               void* out_lo, const int32_t* kv_len, int B, int H, int seq_len, int npad, int dmodel, float scale,
+                               int hp, void* stream) {
+    // tight leading dimensions, q pre-scaled when the op-level twin of the engine's q_premul is set, the process default of pipe
+    return f5_op_attention_ex(qk_hi, qk_lo, vt_hi, vt_lo, out_hi, out_lo, kv_len, B, H, seq_len, npad, dmodel, scale, hp, 2 * dmodel, dmodel,
+                              g_op_q_premul != 0.0f && hp == 0, -1, nullptr, nullptr, 0, stream);
 }
 
 extern "C" int f5_op_qkv_rope(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias,

@@ -167,6 +167,14 @@ int f5_op_gemm(const void* a_hi, const void* a_lo, const void* w_hi, const void*
 /* dit.py:136-166: qk [B*n][2*dmodel] (RoPE'd q | k), vt [B*H][64][npad] -> out [B*n][dmodel] */
 int f5_op_attention(const void* qk_hi, const void* qk_lo, const void* vt_hi, const void* vt_lo, void* out_hi, void* out_lo,
                     const int32_t* kv_len, int B, int H, int seq_len, int npad, int dmodel, float scale, int hp, void* stream);
+/* the same with every field of the launch from the caller: leading dimensions of qk (ldqk % 8 == 0) and out (ldo % 4 == 0),
+ * q_prescaled (1 = q already carries scale * log2(e): scores are in exp2 units), pipe (-1 = process default, 0 = v2f, 1 = v2p where the
+ * large-grid kernels run) and the MX-fp8 output of the one-pass kernels: out8 e4m3 [B*n][ldo8] (ldo8 % 4 == 0) + out8s E8M0
+ * [B*n][dmodel/32]; with out8 set the 16-bit output is not written.  f5_op_attention is this with ldqk = 2 dmodel, ldo = dmodel,
+ * q_prescaled from f5_debug_set_op_q_premul, pipe = -1 and no fp8 output. */
+int f5_op_attention_ex(const void* qk_hi, const void* qk_lo, const void* vt_hi, const void* vt_lo, void* out_hi, void* out_lo,
+                       const int32_t* kv_len, int B, int H, int seq_len, int npad, int dmodel, float scale, int hp, int ldqk, int ldo,
+                       int q_prescaled, int pipe, void* out8, void* out8s, int ldo8, void* stream);
 /* QKV projection + bias + RoPE + head split (dit.py:136-158); B > 1 needs seq_len >= 4 */
 int f5_op_qkv_rope(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias,
                    const float* rope_cos, const float* rope_sin, void* qk_hi, void* qk_lo, void* vt_hi, void* vt_lo, int B,
@@ -296,6 +304,10 @@ int f5_debug_set_gemm_tile(int sel);
  * / ring_ks2<2>, ring_wide<2,2,2,4> / ring_wide<1,4,4,2>, gemm256 and rs128 (+qk_tr, +fold_rowf / +fold_stats).  "" after a launch that
  * was refused.  Host side only: nothing reaches a kernel.  The operand type is f5_op_get_operand_type's. */
 int f5_debug_last_gemm_kernel(char* buf, int n);
+/* the same for attention: the instantiation the most recent attention launch of the process resolved to -- f5_attn2_kernel<true,0> /
+ * <false,0>, f5_attn2f_kernel<true> / <false>, f5_attn2p_kernel, f5_attn2s_kernel<true,2,2> / <false,2,3,true> / <false,4,2,true> --
+ * with "+f8" appended when the launch carried the MX-fp8 output; "" after a launch that was refused.  Host side only. */
+int f5_debug_last_attn_kernel(char* buf, int n);
 /* which kernel WOULD it run?  The same routing function the launcher switches over (csrc/gemm_route.hpp), asked for a launch of this
  * epilogue and shape under the current selectors (f5_debug_set_gemm_tile / _ring / _qkv_tile) and process-wide flags; nothing is
  * launched and no device is touched.  variant_bits: 1 = group-major rotation tables set (transposed q / k tiles), 2 = fused LN tail,

@@ -1,7 +1,8 @@
 // Largest ULP error of the device math functions the row kernels call (csrc/rowops.hip: rsqrtf, expf, log1pf, sinf, cosf, powf, plus
-// sqrtf and SiLU), against fp64 on the host, over 2^21 arguments per function in the ranges those kernels produce plus the exact grids
-// of the time / rotation / position tables.  tests/rowops_matrix.py grants four times the figures this prints (its docstring has the
-// table): re-run after a ROCm update and refresh both.  hipcc --offload-arch=gfx950 -O3 math_ulp.hip -o bin/math_ulp
+// sqrtf and SiLU) and of the exp2 instruction behind csrc/attention.hip's softmax (__builtin_amdgcn_exp2f), against fp64 on the host,
+// over 2^21 arguments per function in the ranges those kernels produce plus the exact grids of the time / rotation / position tables.
+// tests/rowops_matrix.py and tests/attention_matrix.py grant four times the figures this prints (their docstrings have the tables):
+// re-run after a ROCm update and refresh both.  hipcc --offload-arch=gfx950 -O3 math_ulp.hip -o bin/math_ulp
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -20,6 +21,7 @@ __global__ void k(const float* x, float* y, int n, int fn) {
         case 5: r = powf(10000.0f, v); break;
         case 6: r = 1.0f / powf(10000.0f, v); break;
         case 7: r = sqrtf(v); break;
+        case 9: r = __builtin_amdgcn_exp2f(v); break;
         default: r = v / (1.0f + expf(-v)); break;
     }
     y[i] = r;
@@ -34,16 +36,17 @@ static double ref(int fn, double v) {
         case 5: return std::pow(10000.0, v);
         case 6: return 1.0 / std::pow(10000.0, v);
         case 7: return std::sqrt(v);
+        case 9: return std::exp2(v);
         default: return v / (1.0 + std::exp(-v));
     }
 }
 int main() {
-    const char* names[] = {"rsqrtf", "expf", "log1pf", "sinf", "cosf", "powf(1e4,x)", "1/powf(1e4,x)", "sqrtf", "silu"};
+    const char* names[] = {"rsqrtf", "expf", "log1pf", "sinf", "cosf", "powf(1e4,x)", "1/powf(1e4,x)", "sqrtf", "silu", "amdgcn_exp2f"};
     std::mt19937_64 g(1);
     const int n = 1 << 21;
     float *dx, *dy;
     if (hipMalloc(&dx, n * 4) != hipSuccess || hipMalloc(&dy, n * 4) != hipSuccess) return 2;
-    for (int fn = 0; fn < 9; ++fn) {
+    for (int fn = 0; fn < 10; ++fn) {
         std::vector<float> x(n), y(n);
         std::uniform_real_distribution<double> u(0.0, 1.0);
         for (int i = 0; i < n; ++i) {
@@ -54,6 +57,7 @@ int main() {
                 case 2: x[i] = (float)std::exp(-30.0 + 50.0 * t); break;            // exp(mean), mean <= 20
                 case 3: case 4: x[i] = (float)(4096.0 * t); break;                   // angles of the tables
                 case 5: case 6: x[i] = (float)t; break;                              // 2 j / dim
+                case 9: x[i] = (float)(-60.0 + 75.0 * t); break;                    // scores against the reference point, exp2 units: <= 14 on the fast paths
                 default: x[i] = (float)(-20.0 + 40.0 * t); break;
             }
         }
