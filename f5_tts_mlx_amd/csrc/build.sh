@@ -29,7 +29,7 @@ for f in $KERNELS; do
     if stale $f.hip $o 0 || [ build.sh -nt $o ]; then $HIPCC $FLAGS $(noslp $f) -DF5_F16=$v -c $f.hip -o $o & pids+=($!); fi
   done
 done
-for f in audio vocoder noise engine; do
+for f in audio vocoder duration noise engine; do
   o=$B/$f.o
   objs+=($o)
   if stale $f.hip $o 1; then $HIPCC $FLAGS -c $f.hip -o $o & pids+=($!); fi

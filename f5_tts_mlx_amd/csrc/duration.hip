@@ -1,0 +1,570 @@
+// Duration predictor behind the C ABI: (mel, text, lens) -> seconds (and frames), one call (`f5_predict_duration`), hipGraph captured.
+//
+// Reference: DurationPredictor / DurationTransformer (duration.py:97-260), reached from F5TTS.predict_duration (cfm.py:253-262, :307-308):
+//   TextEmbedding WITHOUT padding mask (duration.py:116-118)  -> text_embed kernel + ConvNeXtV2 blocks (dwconv_ln, GEMM + GELU, GRN, GEMM)
+//   Linear(mel + text -> dim) + ConvPositionEmbedding (duration.py:44-58) -> packed [mel padded to 128 | text] operand, GEMM, two conv-pos launches
+//   depth x pre-LN block, plain LayerNorm, no gates, no masks (duration.py:64-94) -> ln_modulate on a zero vector, QKV + RoPE, attention,
+//                                                                  residual epilogue on a ones vector, FF1 + GELU, FF2
+//   RMSNorm -> masked mean -> Linear(dim -> 1) -> Softplus (duration.py:137,188-190,249-251) -> duration_head kernel
+// The launch sequence is the one f5_tts_mlx_amd/duration.py `_run_ops` issues through the f5_op_* entry points -- the same kernels in the
+// same order with the same arguments -- on this handle's own Ops: nothing here reads or writes the process-wide operand type.
+#include <stdarg.h>
+
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/f5tts_hip.h"
+#include "host_common.hpp"
+
+struct DTextBlock {
+    size_t dw_w, dw_b, ln_w, ln_b, b1, gamma, beta, b2;
+    MatBF pw1, pw2;
+};
+struct DBlock {
+    MatBF qkv, o, ff1, ff2;
+    size_t bqkv, bo, bff1, bff2;
+};
+struct DGraph {
+    int B, n_in, nt;
+    const void* workspace;
+    hipGraphExec_t exec;
+    uint64_t stamp;
+    hipEvent_t done;         // recorded after every launch: an exec is only destroyed once its last replay has finished
+};
+static void destroy_dgraph(DGraph& g) {
+    if (g.done) {
+        (void)hipEventSynchronize(g.done);
+        (void)hipEventDestroy(g.done);
+    }
+    (void)hipGraphExecDestroy(g.exec);
+}
+struct DWorkspace {
+    size_t total = 0;
+    size_t status;           // THE FIRST WORD OF THE WORKSPACE: F5_STATUS_* of the last call, zeroed by every call
+    size_t lens, text, mel;  // staged caller inputs (outside the captured part)
+    size_t mask, te, ids, keep, t_nxt, tg, scratch, x, cos_t, sin_t, pred;
+    size_t tln[2], tg2[2], a0[2], xb[2], c1[2], h[2], qk[2], vt[2], ao[2], ffh[2];
+};
+
+struct f5_duration {
+    f5_duration_config cfg;
+    int np = 1;
+    Ops ops;
+    char* arena = nullptr;
+    size_t arena_need = 0, arena_bytes = 0;
+    bool finalized = false;
+    std::unordered_map<std::string, std::vector<TensorDst>> tmap;
+    size_t table, pos, bproj, norm_out, to_pred, zeros, ones;
+    std::vector<DTextBlock> tblocks;
+    MatBF proj, conv_w[2];
+    size_t conv_b[2];
+    std::vector<DBlock> blocks;
+    std::vector<DGraph> graphs;
+    uint64_t clock = 0;
+};
+
+static void dadd_f32(f5_duration* d, const std::string& name, size_t off, std::vector<int64_t> shape) {
+    TensorDst t;
+    t.kind = 0;
+    t.off = off;
+    t.shape = shape;
+    d->tmap[name].push_back(t);
+}
+static void dadd_mat(f5_duration* d, const std::string& name, const MatBF& m, int row0, int src_rows, int src_cols, int c0, int c1,
+                     int dst_c0, std::vector<int64_t> shape) {
+    TensorDst t;
+    t.kind = 1;
+    t.mat = m;
+    t.row0 = row0;
+    t.src_rows = src_rows;
+    t.src_cols = src_cols;
+    t.c0 = c0;
+    t.c1 = c1;
+    t.dst_c0 = dst_c0;
+    t.shape = shape;
+    d->tmap[name].push_back(t);
+}
+
+extern "C" int f5_duration_create(const f5_duration_config* cfg, int precision, f5_duration** out) {
+    F5_REQUIRE(cfg && out, "f5_duration_create: null argument");
+    const f5_duration_config& c = *cfg;
+    F5_REQUIRE(precision == F5_PREC_BF16 || precision == F5_PREC_BF16X3 || precision == F5_PREC_F16,
+               "duration predictor precision must be bf16, bf16x3 or f16 (got %d)", precision);
+    F5_REQUIRE(c.dim_head == 64, "duration predictor: dim_head must be 64 (got %d)", c.dim_head);
+    F5_REQUIRE(c.heads >= 1 && c.heads * c.dim_head == c.dim, "duration predictor: heads * dim_head must equal dim (%d * %d != %d)", c.heads,
+               c.dim_head, c.dim);
+    F5_REQUIRE(c.dim % 256 == 0 && c.dim <= 1024, "duration predictor: dim must be a multiple of 256 and <= 1024 (got %d)", c.dim);
+    F5_REQUIRE(c.conv_pos_groups >= 1 && c.dim % c.conv_pos_groups == 0 && (c.dim / c.conv_pos_groups == 32 || c.dim / c.conv_pos_groups == 64),
+               "duration predictor: dim / conv_pos_groups must be 32 or 64 (got %d / %d)", c.dim, c.conv_pos_groups);
+    F5_REQUIRE(c.conv_pos_kernel >= 1 && c.conv_pos_kernel % 2 == 1 && c.conv_pos_kernel <= 31,
+               "duration predictor: conv_pos_kernel must be odd and <= 31 (got %d)", c.conv_pos_kernel);
+    F5_REQUIRE(c.text_dim >= 256 && c.text_dim % 256 == 0 && c.text_dim <= 1024,
+               "duration predictor: text_dim must be a multiple of 256 and <= 1024 (got %d)", c.text_dim);
+    F5_REQUIRE(c.ff_dim >= 128 && c.ff_dim % 128 == 0, "duration predictor: ff_dim must be a multiple of 128 (got %d)", c.ff_dim);
+    F5_REQUIRE(c.mel_dim >= 1 && c.mel_dim <= 128, "duration predictor: mel_dim must be in [1, 128] (got %d)", c.mel_dim);
+    F5_REQUIRE(c.text_num_embeds >= 1, "duration predictor: text_num_embeds must be >= 1 (got %d)", c.text_num_embeds);
+    F5_REQUIRE(c.depth >= 1 && c.depth <= 64, "duration predictor: depth out of range (got %d)", c.depth);
+    F5_REQUIRE(c.conv_layers >= 1 && c.conv_layers <= 64, "duration predictor: conv_layers must be >= 1 (got %d)", c.conv_layers);
+    F5_REQUIRE(c.text_max_pos >= 4, "duration predictor: text_max_pos must be >= 4 (got %d)", c.text_max_pos);
+    f5_duration* d = new f5_duration();
+    d->cfg = c;
+    d->np = precision == F5_PREC_BF16X3 ? 2 : 1;
+    d->ops.h = precision == F5_PREC_F16;
+    const int D = c.dim, Dt = c.text_dim, TF = 2 * c.text_dim, FF = c.ff_dim, M = c.mel_dim, np = d->np;
+    const std::string p = "transformer.";
+    Bump b;
+    d->table = b.take((size_t)(c.text_num_embeds + 1) * Dt * 4);
+    d->pos = b.take((size_t)c.text_max_pos * Dt * 4);
+    dadd_f32(d, p + "text_embed.text_embed.weight", d->table, {c.text_num_embeds + 1, Dt});
+    d->tblocks.resize(c.conv_layers);
+    for (int i = 0; i < c.conv_layers; ++i) {
+        DTextBlock& t = d->tblocks[i];
+        const std::string q = p + "text_embed.text_blocks.layers." + std::to_string(i) + ".";
+        t.dw_w = b.take((size_t)Dt * 7 * 4);
+        t.dw_b = b.take((size_t)Dt * 4);
+        t.ln_w = b.take((size_t)Dt * 4);
+        t.ln_b = b.take((size_t)Dt * 4);
+        t.b1 = b.take((size_t)TF * 4);
+        t.gamma = b.take((size_t)TF * 4);
+        t.beta = b.take((size_t)TF * 4);
+        t.b2 = b.take((size_t)Dt * 4);
+        t.pw1 = alloc_mat(b, TF, Dt, np);
+        t.pw2 = alloc_mat(b, Dt, TF, np);
+        dadd_f32(d, q + "dwconv.weight", t.dw_w, {Dt, 7, 1});       // (dim, 7, 1) = the bytes of [dim][7]
+        dadd_f32(d, q + "dwconv.bias", t.dw_b, {Dt});
+        dadd_f32(d, q + "norm.weight", t.ln_w, {Dt});
+        dadd_f32(d, q + "norm.bias", t.ln_b, {Dt});
+        dadd_mat(d, q + "pwconv1.weight", t.pw1, 0, TF, Dt, 0, Dt, 0, {TF, Dt});
+        dadd_f32(d, q + "pwconv1.bias", t.b1, {TF});
+        dadd_f32(d, q + "grn.gamma", t.gamma, {1, 1, TF});
+        dadd_f32(d, q + "grn.beta", t.beta, {1, 1, TF});
+        dadd_mat(d, q + "pwconv2.weight", t.pw2, 0, Dt, TF, 0, TF, 0, {Dt, TF});
+        dadd_f32(d, q + "pwconv2.bias", t.b2, {Dt});
+    }
+    // input projection: reference input order (x | text) (duration.py:44-58) -> operand columns [x padded to 128 | text]
+    d->proj = alloc_mat(b, D, 128 + Dt, np);
+    d->bproj = b.take((size_t)D * 4);
+    dadd_mat(d, p + "input_embed.proj.weight", d->proj, 0, D, M + Dt, 0, M, 0, {D, M + Dt});
+    dadd_mat(d, p + "input_embed.proj.weight", d->proj, 0, D, M + Dt, M, M + Dt, 128, {D, M + Dt});
+    dadd_f32(d, p + "input_embed.proj.bias", d->bproj, {D});
+    // conv position embedding: the kernel works on 64-channel groups; 32-channel groups are loaded as block-diagonal 64-wide super
+    // groups (f5_duration_load_tensor)
+    const int kc = c.conv_pos_kernel, gin = D / c.conv_pos_groups;
+    for (int j = 0; j < 2; ++j) {
+        d->conv_w[j] = alloc_mat(b, D, kc * 64, np);
+        d->conv_b[j] = b.take((size_t)D * 4);
+        const std::string q = p + "input_embed.conv_pos_embed.conv1d.layers." + std::to_string(j * 2) + ".";
+        dadd_mat(d, q + "weight", d->conv_w[j], 0, D, kc * 64, 0, kc * 64, 0, {D, kc, gin});
+        dadd_f32(d, q + "bias", d->conv_b[j], {D});
+    }
+    d->blocks.resize(c.depth);
+    for (int i = 0; i < c.depth; ++i) {
+        DBlock& w = d->blocks[i];
+        const std::string q = p + "transformer_blocks." + std::to_string(i) + ".";
+        w.qkv = alloc_mat(b, 3 * D, D, np);
+        w.o = alloc_mat(b, D, D, np);
+        w.ff1 = alloc_mat(b, FF, D, np);
+        w.ff2 = alloc_mat(b, D, FF, np);
+        w.bqkv = b.take((size_t)3 * D * 4);
+        w.bo = b.take((size_t)D * 4);
+        w.bff1 = b.take((size_t)FF * 4);
+        w.bff2 = b.take((size_t)D * 4);
+        const char* nm[3] = {"to_q", "to_k", "to_v"};
+        for (int k = 0; k < 3; ++k) {
+            dadd_mat(d, q + "attn." + nm[k] + ".weight", w.qkv, k * D, D, D, 0, D, 0, {D, D});
+            dadd_f32(d, q + "attn." + nm[k] + ".bias", w.bqkv + (size_t)k * D * 4, {D});
+        }
+        dadd_mat(d, q + "attn.to_out.layers.0.weight", w.o, 0, D, D, 0, D, 0, {D, D});
+        dadd_f32(d, q + "attn.to_out.layers.0.bias", w.bo, {D});
+        dadd_mat(d, q + "ff.ff.layers.0.layers.0.weight", w.ff1, 0, FF, D, 0, D, 0, {FF, D});
+        dadd_f32(d, q + "ff.ff.layers.0.layers.0.bias", w.bff1, {FF});
+        dadd_mat(d, q + "ff.ff.layers.2.weight", w.ff2, 0, D, FF, 0, FF, 0, {D, FF});
+        dadd_f32(d, q + "ff.ff.layers.2.bias", w.bff2, {D});
+    }
+    d->norm_out = b.take((size_t)D * 4);
+    d->to_pred = b.take((size_t)D * 4);
+    dadd_f32(d, p + "norm_out.weight", d->norm_out, {D});
+    dadd_f32(d, "to_pred.layers.0.weight", d->to_pred, {1, D});
+    d->zeros = b.take((size_t)D * 4);      // scale = shift = 0: ln_modulate is the plain LayerNorm of duration.py:86,91
+    d->ones = b.take((size_t)D * 4);       // gate = 1: the gated-residual epilogue is `x = x + y`
+    d->arena_need = b.off;
+    *out = d;
+    return 0;
+}
+
+extern "C" void f5_duration_destroy(f5_duration* d) {
+    if (!d) return;
+    for (auto& g : d->graphs) destroy_dgraph(g);
+    delete d;
+}
+
+extern "C" int f5_duration_weights_bytes(f5_duration* d, size_t* bytes) {
+    F5_REQUIRE(d && bytes, "null argument");
+    *bytes = d->arena_need;
+    return 0;
+}
+
+extern "C" int f5_duration_set_weights_arena(f5_duration* d, void* dev_arena, size_t bytes, void* stream) {
+    F5_REQUIRE(d && dev_arena, "null argument");
+    F5_REQUIRE(bytes >= d->arena_need, "duration predictor weights arena too small: %zu < %zu", bytes, d->arena_need);
+    F5_REQUIRE(((uintptr_t)dev_arena & 255) == 0, "duration predictor weights arena must be 256-byte aligned");
+    d->arena = (char*)dev_arena;
+    d->arena_bytes = bytes;
+    F5_HIP_CHECK(hipMemsetAsync(dev_arena, 0, d->arena_need, (hipStream_t)stream));   // zero pads, the zero vector
+    F5_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+}
+
+// Tensor names are the reference's (the keys of duration_param_specs in f5_tts_mlx_amd/duration.py: "transformer.text_embed...",
+// "to_pred.layers.0.weight"), with or without the "duration_predictor." prefix they carry inside an F5TTS checkpoint; shapes are the
+// reference's (MLX layout).  The name and the shape are checked before the arena, so that a host can validate a checkpoint without a device.
+extern "C" int f5_duration_load_tensor(f5_duration* d, const char* name, const float* host, int ndim, const int64_t* shape) {
+    F5_REQUIRE(d && name && host && shape, "null argument");
+    std::string key(name);
+    const std::string prefix = "duration_predictor.";
+    if (key.compare(0, prefix.size(), prefix) == 0) key = key.substr(prefix.size());
+    auto it = d->tmap.find(key);
+    F5_REQUIRE(it != d->tmap.end(), "unknown duration predictor tensor name '%s'", name);
+    size_t count = 1;
+    for (TensorDst& t : it->second) {
+        F5_REQUIRE((int)t.shape.size() == ndim, "tensor '%s': expected %zu dims, got %d", name, t.shape.size(), ndim);
+        count = 1;
+        for (int i = 0; i < ndim; ++i) {
+            F5_REQUIRE(t.shape[i] == shape[i], "tensor '%s': dim %d is %lld, expected %lld", name, i, (long long)shape[i],
+                       (long long)t.shape[i]);
+            count *= (size_t)shape[i];
+        }
+    }
+    F5_REQUIRE(d->arena, "f5_duration_set_weights_arena must be called first");
+    const int D = d->cfg.dim, kc = d->cfg.conv_pos_kernel;
+    for (TensorDst& t : it->second) {
+        if (t.kind == 1 && t.shape.size() == 3 && t.shape[2] == 32) {
+            // conv-pos weight (dim, k, 32): output channel o reads the 32 input channels of ITS group; two groups share one 64-channel
+            // super group of the kernel, so o's taps go to the half of the 64 columns that holds its group, the other half stays zero
+            std::vector<float> m((size_t)D * kc * 64, 0.0f);
+            for (int o = 0; o < D; ++o) {
+                const int off = ((o / 32) % 2) * 32;
+                for (int k = 0; k < kc; ++k)
+                    memcpy(&m[((size_t)o * kc + k) * 64 + off], host + ((size_t)o * kc + k) * 32, 32 * sizeof(float));
+            }
+            RC(f5_upload_tensor(d->arena, t, m.data(), m.size(), d->np, d->ops.h));
+        } else {
+            RC(f5_upload_tensor(d->arena, t, host, count, d->np, d->ops.h));
+        }
+        t.loaded = true;
+    }
+    return 0;
+}
+
+extern "C" int f5_duration_mark_weights_loaded(f5_duration* d) {
+    F5_REQUIRE(d, "null argument");
+    for (auto& kv : d->tmap)
+        for (auto& t : kv.second) t.loaded = true;
+    return 0;
+}
+
+extern "C" int f5_duration_finalize(f5_duration* d, void* stream) {
+    F5_REQUIRE(d && d->arena, "duration predictor arena not set");
+    for (auto& kv : d->tmap)
+        for (auto& t : kv.second) F5_REQUIRE(t.loaded, "duration predictor tensor '%s' was never loaded", kv.first.c_str());
+    RC(f5_launch_text_pos_table((float*)(d->arena + d->pos), d->cfg.text_max_pos, d->cfg.text_dim, (hipStream_t)stream));
+    const std::vector<float> one((size_t)d->cfg.dim, 1.0f), zero((size_t)d->cfg.dim, 0.0f);
+    F5_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    F5_HIP_CHECK(hipMemcpy(d->arena + d->ones, one.data(), one.size() * 4, hipMemcpyHostToDevice));
+    F5_HIP_CHECK(hipMemcpy(d->arena + d->zeros, zero.data(), zero.size() * 4, hipMemcpyHostToDevice));
+    d->finalized = true;
+    return 0;
+}
+
+static int dshape_ok(const f5_duration* d, int B, int n_in, int nt) {
+    const int N = n_in > nt ? n_in : nt;
+    F5_REQUIRE(B >= 1 && n_in >= 1 && nt >= 1, "duration predictor: need B >= 1, n_in >= 1 and nt >= 1 (got B=%d n_in=%d nt=%d)", B, n_in, nt);
+    F5_REQUIRE(N >= 4, "duration predictor: need N = max(n_in, nt) >= 4 (got %d)", N);
+    F5_REQUIRE(N <= d->cfg.text_max_pos, "duration predictor: N = max(n_in, nt) = %d exceeds text_max_pos = %d", N, d->cfg.text_max_pos);
+    const int widest = d->cfg.ff_dim > 3 * d->cfg.dim ? d->cfg.ff_dim : 3 * d->cfg.dim;
+    F5_REQUIRE((size_t)B * N * widest < ((size_t)1 << 31), "duration predictor: B * N = %zu rows is too many for one call", (size_t)B * N);
+    return 0;
+}
+
+static DWorkspace dplan(const f5_duration* d, int B, int n_in, int nt) {
+    const f5_duration_config& c = d->cfg;
+    const int N = n_in > nt ? n_in : nt, npad = (N + 63) / 64 * 64;
+    const size_t rows = (size_t)B * N, D = c.dim, Dt = c.text_dim, TF = 2 * Dt, K0 = 128 + Dt;
+    Bump b;
+    DWorkspace w;
+    w.status = b.take(4);
+    w.lens = b.take((size_t)B * 4);
+    w.text = b.take(rows * 4);                       // [B][nt], nt <= N: sized by N so that the plan depends on (B, N) alone below
+    w.mel = b.take(rows * c.mel_dim * 4);            // [B][N][mel_dim], rows >= n_in zero
+    w.mask = b.take(rows);
+    w.te = b.take(2 * rows * Dt * 4);                // the text_embed kernel writes both branches (cond | dropped text)
+    w.ids = b.take(2 * rows * 4);
+    w.keep = b.take(2 * rows);
+    w.t_nxt = b.take(rows * Dt * 4);
+    w.tg = b.take(rows * TF * 4);
+    w.scratch = b.take((f5_grn_partial_floats(B, N, (int)TF) + (size_t)B * TF) * 4);
+    w.x = b.take(rows * D * 4);
+    w.cos_t = b.take((size_t)N * 32 * 4);
+    w.sin_t = b.take((size_t)N * 32 * 4);
+    w.pred = b.take((size_t)B * 4);
+    for (int p = 0; p < 2; ++p) {
+        const bool on = p < d->np;
+        w.tln[p] = on ? b.take(rows * Dt * 2) : 0;
+        w.tg2[p] = on ? b.take(rows * TF * 2) : 0;
+        w.a0[p] = on ? b.take(rows * K0 * 2) : 0;
+        w.xb[p] = on ? b.take(rows * D * 2) : 0;
+        w.c1[p] = on ? b.take(rows * D * 2) : 0;
+        w.h[p] = on ? b.take(rows * D * 2) : 0;
+        w.qk[p] = on ? b.take(rows * 2 * D * 2) : 0;
+        w.vt[p] = on ? b.take((size_t)B * c.heads * 64 * npad * 2) : 0;
+        w.ao[p] = on ? b.take(rows * D * 2) : 0;
+        w.ffh[p] = on ? b.take(rows * c.ff_dim * 2) : 0;
+    }
+    w.total = b.off;
+    return w;
+}
+
+extern "C" int f5_duration_workspace_bytes(f5_duration* d, int B, int n_in, int nt, size_t* bytes) {
+    F5_REQUIRE(d && bytes, "null argument");
+    RC(dshape_ok(d, B, n_in, nt));
+    *bytes = dplan(d, B, n_in, nt).total;
+    return 0;
+}
+
+// fp16 handles: the 16-bit packers of the launches issued inside this scope report a clamp into the call's status word (the pointer
+// travels as a kernel argument; a captured graph keeps the word of the workspace it was captured against, part of the graph key)
+struct DSatScope {
+    int* saved;
+    DSatScope(const f5_duration* d, int* status_word) : saved(f5hf::f5_sat_flag_host) {
+        if (d->ops.h) f5hf::f5_sat_flag_host = status_word;
+    }
+    ~DSatScope() { f5hf::f5_sat_flag_host = saved; }
+};
+
+// the launch sequence of DurationPredictor._run_ops (f5_tts_mlx_amd/duration.py), everything on the workspace and the arena
+static int duration_body(const f5_duration* d, const DWorkspace& w, char* ws, int B, int N, int nt, hipStream_t s) {
+    const f5_duration_config& c = d->cfg;
+    const Ops& K = d->ops;
+    const int D = c.dim, Dt = c.text_dim, TF = 2 * c.text_dim, FF = c.ff_dim, H = c.heads, K0 = 128 + c.text_dim;
+    const int rows = B * N, npad = (N + 63) / 64 * 64, nseg = d->np == 2 ? 3 : 1;
+    DSatScope sat(d, reinterpret_cast<int*>(ws + w.status));
+    auto P = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto PB = [&](const size_t (&offs)[2], int part) { return part < d->np ? reinterpret_cast<op16_t*>(ws + offs[part]) : (op16_t*)nullptr; };
+    auto A = [&](size_t off) { return reinterpret_cast<const float*>(d->arena + off); };
+    auto WM = [&](const MatBF& m, int part) {
+        return part == 0 ? reinterpret_cast<const op16_t*>(d->arena + m.hi) : (d->np == 2 ? reinterpret_cast<const op16_t*>(d->arena + m.lo) : nullptr);
+    };
+    auto gemm = [&](const op16_t* ah, const op16_t* al, int lda, const MatBF& wm, int Nn, int Kk, const float* bias) {
+        F5GemmArgs g;
+        memset(&g, 0, sizeof(g));
+        g.A[0] = ah;
+        g.A[1] = al;
+        g.W[0] = WM(wm, 0);
+        g.W[1] = WM(wm, 1);
+        g.lda = lda;
+        g.ldw = wm.ld;
+        g.M = rows;
+        g.N = Nn;
+        g.K = Kk;
+        g.nseg = nseg;
+        g.bias = bias;
+        return g;
+    };
+    uint8_t* mask = reinterpret_cast<uint8_t*>(ws + w.mask);
+    const uint32_t zero_word = 0;
+    RC(f5_launch_stage_words(&zero_word, 1, reinterpret_cast<uint32_t*>(ws + w.status), s));      // status = 0, a kernel like the rest
+    RC(K.rowkeep(reinterpret_cast<const int*>(ws + w.lens), mask, B, N, s));                     // mask = n < lens[b]
+
+    // ---- text path, no padding mask (duration.py:116-118)
+    RC(K.text_embed(reinterpret_cast<const int*>(ws + w.text), nt, A(d->table), A(d->pos), c.text_max_pos, P(w.te),
+                    reinterpret_cast<int*>(ws + w.ids), reinterpret_cast<uint8_t*>(ws + w.keep), B, N, Dt, 0, s));
+    float* t_cur = P(w.te);            // branch 0
+    float* t_nxt = P(w.t_nxt);
+    float* scratch = P(w.scratch);
+    for (const DTextBlock& k : d->tblocks) {
+        RC(K.dwconv_ln(t_cur, A(k.dw_w), A(k.dw_b), A(k.ln_w), A(k.ln_b), PB(w.tln, 0), PB(w.tln, 1), B, N, Dt, 1e-6f, s));
+        F5GemmArgs g1 = gemm(PB(w.tln, 0), PB(w.tln, 1), Dt, k.pw1, TF, Dt, A(k.b1));
+        g1.out_f32 = P(w.tg);
+        g1.ldo = TF;
+        g1.ldob = TF;
+        RC(K.gemm(g1, EPI_GELU_ERF, s));
+        RC(K.grn(P(w.tg), A(k.gamma), A(k.beta), scratch, scratch + f5_grn_partial_floats(B, N, TF), PB(w.tg2, 0), PB(w.tg2, 1), B, N, TF, s));
+        F5GemmArgs g2 = gemm(PB(w.tg2, 0), PB(w.tg2, 1), TF, k.pw2, Dt, TF, A(k.b2));
+        g2.resid = t_cur;
+        g2.ldres = Dt;
+        g2.out_f32 = t_nxt;
+        g2.ldo = Dt;
+        RC(K.gemm(g2, EPI_RESID_KEEP, s));
+        float* t = t_cur;
+        t_cur = t_nxt;
+        t_nxt = t;
+    }
+
+    // ---- input embedding: proj(concat(masked mel, text)) + conv_pos_embed (duration.py:44-58, :243-247)
+    for (int p = 0; p < d->np; ++p) RC(K.zero_vt_pad(PB(w.a0, p), (size_t)rows, 0, K0, s));     // every column: the pad [mel_dim, 128) must be 0
+    RC(K.pack_bf16(P(w.mel), mask, PB(w.a0, 0), PB(w.a0, 1), rows, c.mel_dim, K0, 0, s));
+    RC(K.pack_bf16(t_cur, nullptr, PB(w.a0, 0), PB(w.a0, 1), rows, Dt, K0, 128, s));
+    F5GemmArgs gp = gemm(PB(w.a0, 0), PB(w.a0, 1), K0, d->proj, D, K0, A(d->bproj));
+    gp.out_f32 = P(w.x);
+    gp.ldo = D;
+    gp.ldob = D;
+    RC(K.gemm(gp, EPI_F32, s));
+    RC(K.pack_bf16(P(w.x), nullptr, PB(w.xb, 0), PB(w.xb, 1), rows, D, D, 0, s));
+    for (int j = 0; j < 2; ++j) {
+        F5ConvPosArgs cp;
+        memset(&cp, 0, sizeof(cp));
+        cp.in[0] = j == 0 ? PB(w.xb, 0) : PB(w.c1, 0);
+        cp.in[1] = j == 0 ? PB(w.xb, 1) : PB(w.c1, 1);
+        cp.W[0] = WM(d->conv_w[j], 0);
+        cp.W[1] = WM(d->conv_w[j], 1);
+        cp.bias = A(d->conv_b[j]);
+        cp.B = B;
+        cp.seq_len = N;
+        cp.C = D;
+        cp.groups = D / 64;
+        cp.taps = c.conv_pos_kernel;
+        cp.ld = D;
+        cp.ldo = D;
+        cp.nseg = nseg;
+        cp.mode = j;                                  // 0: c1 = 16-bit(mish(.)); 1: x += mish(.)
+        cp.out_bf[0] = j == 0 ? PB(w.c1, 0) : nullptr;
+        cp.out_bf[1] = j == 0 ? PB(w.c1, 1) : nullptr;
+        cp.out_f32 = j == 0 ? nullptr : P(w.x);
+        RC(K.convpos(cp, s));
+    }
+
+    // ---- pre-LN transformer blocks without modulation / gates / masks (duration.py:64-94)
+    RC(K.rope_table(P(w.cos_t), P(w.sin_t), N, 64, s));
+    for (int p = 0; p < d->np; ++p) RC(K.zero_vt_pad(PB(w.vt, p), (size_t)B * H * 64, N, npad, s));   // columns < N: every QKV epilogue
+    for (const DBlock& k : d->blocks) {
+        RC(K.ln_modulate(P(w.x), A(d->zeros), A(d->zeros), PB(w.h, 0), PB(w.h, 1), rows, D, 1e-6f, s));
+        RC(K.qkv_rope(PB(w.h, 0), PB(w.h, 1), WM(k.qkv, 0), WM(k.qkv, 1), A(k.bqkv), P(w.cos_t), P(w.sin_t), PB(w.qk, 0), PB(w.qk, 1),
+                      PB(w.vt, 0), PB(w.vt, 1), B, N, npad, H, D, nseg, s));
+        F5AttnArgs at;
+        memset(&at, 0, sizeof(at));
+        at.qk[0] = PB(w.qk, 0);
+        at.qk[1] = PB(w.qk, 1);
+        at.vt[0] = PB(w.vt, 0);
+        at.vt[1] = PB(w.vt, 1);
+        at.out[0] = PB(w.ao, 0);
+        at.out[1] = PB(w.ao, 1);
+        at.B = B;
+        at.H = H;
+        at.seq_len = N;
+        at.npad = npad;
+        at.ldqk = 2 * D;
+        at.ldo = D;
+        at.dmodel = D;
+        at.hp = d->np == 2;
+        at.scale = 0.125f;
+        at.pipe = -1;
+        RC(K.attention(at, s));
+        F5GemmArgs go = gemm(PB(w.ao, 0), PB(w.ao, 1), D, k.o, D, D, A(k.bo));
+        go.gate = A(d->ones);
+        go.out_f32 = P(w.x);
+        go.ldo = D;
+        RC(K.gemm(go, EPI_RESID_GATE, s));
+        RC(K.ln_modulate(P(w.x), A(d->zeros), A(d->zeros), PB(w.h, 0), PB(w.h, 1), rows, D, 1e-6f, s));
+        F5GemmArgs g1 = gemm(PB(w.h, 0), PB(w.h, 1), D, k.ff1, FF, D, A(k.bff1));
+        g1.out_bf[0] = PB(w.ffh, 0);
+        g1.out_bf[1] = PB(w.ffh, 1);
+        g1.ldo = FF;
+        g1.ldob = FF;
+        RC(K.gemm(g1, EPI_GELU_TANH, s));
+        F5GemmArgs g2 = gemm(PB(w.ffh, 0), PB(w.ffh, 1), FF, k.ff2, D, FF, A(k.bff2));
+        g2.gate = A(d->ones);
+        g2.out_f32 = P(w.x);
+        g2.ldo = D;
+        RC(K.gemm(g2, EPI_RESID_GATE, s));
+    }
+
+    // ---- RMSNorm -> masked mean -> Linear(dim -> 1) -> Softplus (duration.py:137,188-190,249-251)
+    RC(K.duration_head(P(w.x), A(d->norm_out), A(d->to_pred), mask, P(w.pred), B, N, D, 1e-5f, s));
+    return 0;
+}
+
+// Replaces `self._duration_predictor(cond, text)` and the frame arithmetic of F5TTS.predict_duration (cfm.py:253-262).
+extern "C" int f5_predict_duration(f5_duration* d, const f5_duration_args* a, void* stream) {
+    F5_REQUIRE(d && a, "f5_predict_duration: null argument");
+    F5_REQUIRE(a->mel && a->text && a->seconds && a->workspace, "f5_predict_duration: null mel / text / seconds / workspace");
+    F5_REQUIRE(d->finalized, "duration predictor weights are not finalized");
+    const int B = a->B, n_in = a->n_in, nt = a->nt;
+    RC(dshape_ok(d, B, n_in, nt));
+    F5_REQUIRE(a->frames == nullptr || (a->speed > 0.0f && a->frame_rate > 0.0f), "duration predictor: frames need frame_rate > 0 and speed > 0");
+    F5_REQUIRE(((uintptr_t)a->workspace & 255) == 0, "duration predictor workspace must be 256-byte aligned");
+    F5_REQUIRE((((uintptr_t)a->mel | (uintptr_t)a->text | (uintptr_t)a->seconds | (uintptr_t)a->frames) & 3) == 0,
+               "duration predictor: mel / text / seconds / frames must be 4-byte aligned");
+    const DWorkspace w = dplan(d, B, n_in, nt);
+    F5_REQUIRE(a->workspace_bytes >= w.total, "duration predictor workspace too small: %zu < %zu", a->workspace_bytes, w.total);
+    const int N = n_in > nt ? n_in : nt, mel = d->cfg.mel_dim;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)a->workspace;
+    void* workspace = a->workspace;
+    // caller buffers are staged outside the graph: the captured nodes only reference the workspace and the arena, so a replay serves
+    // new mel / text / lens of the same shape
+    std::vector<uint32_t> lens((size_t)B);
+    for (int b = 0; b < B; ++b) lens[b] = (uint32_t)(a->lens ? a->lens[b] : N);
+    RC(f5_launch_stage_words(lens.data(), lens.size(), reinterpret_cast<uint32_t*>(ws + w.lens), s));
+    RC(f5_launch_copy_words(a->text, ws + w.text, (size_t)B * nt, s));
+    if (n_in == N) {
+        RC(f5_launch_copy_words(a->mel, ws + w.mel, (size_t)B * N * mel, s));
+    } else {
+        // duration.py:218-220: the mel is zero padded to the text length.  The staging buffer seen as B rows of 16-bit words: the
+        // columns behind an utterance's n_in frames are zeroed, the frames themselves copied
+        RC(d->ops.zero_vt_pad(reinterpret_cast<op16_t*>(ws + w.mel), (size_t)B, n_in * mel * 2, N * mel * 2, s));
+        for (int b = 0; b < B; ++b)
+            RC(f5_launch_copy_words(a->mel + (size_t)b * n_in * mel, ws + w.mel + (size_t)b * N * mel * 4, (size_t)n_in * mel, s));
+    }
+    if (a->use_graph) {
+        hipGraphExec_t exec = nullptr;
+        for (auto& g : d->graphs)
+            if (g.B == B && g.n_in == n_in && g.nt == nt && g.workspace == workspace) {
+                exec = g.exec;
+                g.stamp = ++d->clock;
+            }
+        if (!exec) {
+            while (d->graphs.size() >= 8) {
+                size_t lru = 0;
+                for (size_t i = 1; i < d->graphs.size(); ++i)
+                    if (d->graphs[i].stamp < d->graphs[lru].stamp) lru = i;
+                destroy_dgraph(d->graphs[lru]);
+                d->graphs.erase(d->graphs.begin() + lru);
+            }
+            hipGraph_t graph = nullptr;
+            F5_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+            const int rc = duration_body(d, w, ws, B, N, nt, s);
+            const hipError_t ec = hipStreamEndCapture(s, &graph);
+            if (rc) {
+                if (graph) (void)hipGraphDestroy(graph);
+                return rc;
+            }
+            F5_HIP_CHECK(ec);
+            F5_HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+            (void)hipGraphDestroy(graph);
+            hipEvent_t done = nullptr;
+            F5_HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+            d->graphs.push_back({B, n_in, nt, workspace, exec, ++d->clock, done});
+        }
+        F5_HIP_CHECK(hipGraphLaunch(exec, s));
+        for (auto& g : d->graphs)
+            if (g.exec == exec) F5_HIP_CHECK(hipEventRecord(g.done, s));
+    } else {
+        RC(duration_body(d, w, ws, B, N, nt, s));
+    }
+    // frame_rate / speed are by-value scalars: they stay outside the graph, like the copies to the caller
+    if (a->frames) RC(d->ops.seconds_to_frames(reinterpret_cast<const float*>(ws + w.pred), a->frames, B, a->frame_rate, a->speed, s));
+    RC(f5_launch_copy_words(ws + w.pred, a->seconds, (size_t)B, s));
+    return 0;
+}
+
+// Status word of the last f5_predict_duration on the workspace of `a` (its first 32-bit word): F5_STATUS_SATURATED = a producer of a
+// 16-bit operand clamped a value beyond +-65 504 (precision f16; always 0 in the bf16 modes).  Synchronises `stream`.
+extern "C" int f5_duration_status(f5_duration* d, const f5_duration_args* a, int* flags, void* stream) {
+    F5_REQUIRE(d && a && flags && a->workspace && a->workspace_bytes >= 4, "null argument");
+    F5_HIP_CHECK(hipMemcpyAsync(flags, (const char*)a->workspace, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    F5_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int f5_duration_graph_count(f5_duration* d) { return d ? (int)d->graphs.size() : -1; }

@@ -1,4 +1,4 @@
-// Host-side plumbing shared by the engine (engine.hip) and the vocoder (vocoder.hip): declarations of both kernel builds, the
+// Host-side plumbing shared by the engine (engine.hip), the vocoder (vocoder.hip) and the duration predictor (duration.hip): declarations of both kernel builds, the
 // operand-type dispatch, the weights-arena bump allocator and the fp32 -> 16-bit upload.
 #pragma once
 #include <string>
@@ -36,6 +36,7 @@ using f5bf::f5_launch_quantize_mx_bf16;
 using f5bf::f5_launch_rope_table;
 using f5bf::f5_launch_rope_table_g4;
 using f5bf::f5_launch_rowkeep;
+using f5bf::f5_launch_seconds_to_frames;
 using f5bf::f5_launch_stage_words;
 using f5bf::f5_launch_copy_words;
 using f5bf::f5_launch_skinny_gemm;
@@ -115,6 +116,54 @@ struct Ops {
                   hipStream_t s) const {
         return h ? f5hf::f5_launch_pack_bf16(src, rowkeep, H(hi), H(lo), rows, cols, ld, col0, s)
                  : f5bf::f5_launch_pack_bf16(src, rowkeep, hi, lo, rows, cols, ld, col0, s);
+    }
+    // fused QKV projection + RoPE + V transpose on token-major rotation tables (what f5_op_qkv_rope launches with its hooks unset)
+    int qkv_rope(const op16_t* a_hi, const op16_t* a_lo, const op16_t* w_hi, const op16_t* w_lo, const float* bias, const float* rope_cos,
+                 const float* rope_sin, op16_t* qk_hi, op16_t* qk_lo, op16_t* vt_hi, op16_t* vt_lo, int B, int seq_len, int npad, int heads,
+                 int dmodel, int nseg, hipStream_t s) const {
+        F5GemmArgs g;
+        memset(&g, 0, sizeof(g));
+        g.A[0] = a_hi;
+        g.A[1] = a_lo;
+        g.W[0] = w_hi;
+        g.W[1] = w_lo;
+        g.lda = dmodel;
+        g.ldw = dmodel;
+        g.M = B * seq_len;
+        g.N = 3 * dmodel;
+        g.K = dmodel;
+        g.nseg = nseg;
+        g.bias = bias;
+        g.out_bf[0] = qk_hi;
+        g.out_bf[1] = qk_lo;
+        g.ldob = 2 * dmodel;
+        g.rope_cos = rope_cos;
+        g.rope_sin = rope_sin;
+        g.seq_len = seq_len;
+        g.npad = npad;
+        g.heads = heads;
+        g.dmodel = dmodel;
+        g.vt[0] = vt_hi;
+        g.vt[1] = vt_lo;
+        return gemm(g, EPI_QKV_ROPE, s);
+    }
+    // launches without 16-bit operands: one build serves both operand types
+    int text_embed(const int* text, int nt, const float* table, const float* pos_table, int max_pos, float* out, int* ids_out,
+                   uint8_t* keep_out, int B, int seq_len, int dim, int mask_padding, hipStream_t s) const {
+        return f5_launch_text_embed(text, nt, table, pos_table, max_pos, out, ids_out, keep_out, B, seq_len, dim, mask_padding, s);
+    }
+    int rope_table(float* cos_t, float* sin_t, int seq_len, int dim_head, hipStream_t s) const {
+        return f5_launch_rope_table(cos_t, sin_t, seq_len, dim_head, s);
+    }
+    int rowkeep(const int* dur, uint8_t* keep, int nbatch, int seq_len, hipStream_t s) const {
+        return f5_launch_rowkeep(dur, keep, nbatch, seq_len, s);
+    }
+    int duration_head(const float* x, const float* g, const float* w, const uint8_t* mask, float* out, int B, int seq_len, int dim,
+                      float eps, hipStream_t s) const {
+        return f5_launch_duration_head(x, g, w, mask, out, B, seq_len, dim, eps, s);
+    }
+    int seconds_to_frames(const float* seconds, int* frames, int B, float frame_rate, float speed, hipStream_t s) const {
+        return f5_launch_seconds_to_frames(seconds, frames, B, frame_rate, speed, s);
     }
 };
 

@@ -836,7 +836,7 @@ int f5_launch_im2col7(const float* x, op16_t* out_hi, op16_t* out_lo, int nbatch
 // fp32 [rows][cols] (optionally row-masked) -> bf16 (hi, lo) at column offset col0 of a [rows][ld] matrix
 __global__ __launch_bounds__(256) void pack_bf16_kernel(const float* __restrict__ src, const uint8_t* __restrict__ rowkeep,
                                                         op16_t* __restrict__ out_hi, op16_t* __restrict__ out_lo, int cols, int ld,
-                                                        int col0, size_t total) {
+                                                        int col0, size_t total, int* sat_flag) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const size_t row = i / cols;
@@ -844,16 +844,18 @@ __global__ __launch_bounds__(256) void pack_bf16_kernel(const float* __restrict_
     float v = src[i];
     if (rowkeep != nullptr && rowkeep[row] == 0) v = 0.0f;
     op16_t h, l;
-    f5_split(v, h, l);
+    f5_sat_t trk;
+    f5_split(v, h, l, trk);
     out_hi[row * ld + col0 + c] = h;
     if (out_lo) out_lo[row * ld + col0 + c] = l;
+    f5_sat_commit(trk, sat_flag);
 }
 int f5_launch_pack_bf16(const float* src, const uint8_t* rowkeep, op16_t* out_hi, op16_t* out_lo, int rows, int cols, int ld,
                         int col0, hipStream_t s) {
     F5_REQUIRE(col0 >= 0 && col0 + cols <= ld, "pack_bf16: column range out of bounds");
     const size_t total = (size_t)rows * cols;
     hipLaunchKernelGGL(pack_bf16_kernel, dim3(f5_cdiv((long)total, 256)), dim3(256), 0, s, src, rowkeep, out_hi, out_lo, cols, ld,
-                       col0, total);
+                       col0, total, f5_sat_flag_host);
     F5_LAUNCH_CHECK();
     return 0;
 }
@@ -895,6 +897,24 @@ __global__ __launch_bounds__(256) void duration_head_kernel(const float* __restr
 int f5_launch_duration_head(const float* x, const float* g, const float* w, const uint8_t* mask, float* out, int B, int seq_len,
                             int dim, float eps, hipStream_t s) {
     hipLaunchKernelGGL(duration_head_kernel, dim3(B), dim3(256), 0, s, x, g, w, mask, out, seq_len, dim, eps);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+
+// seconds -> frames (cfm.py:253-262: `(duration_in_sec * frame_rate / speed).astype(int32)`), one thread per utterance.  Two separately
+// rounded fp32 operations -- the product, then a TRUE division (no reciprocal, no contraction: the bits of an elementwise fp32
+// multiply followed by an fp32 divide) -- and the conversion truncates toward zero.
+__global__ __launch_bounds__(64) void seconds_to_frames_kernel(const float* __restrict__ seconds, int* __restrict__ frames, int B,
+                                                               float frame_rate, float speed) {
+#pragma clang fp contract(off) reciprocal(off)
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const float prod = seconds[b] * frame_rate;
+    frames[b] = (int)__fdiv_rn(prod, speed);
+}
+int f5_launch_seconds_to_frames(const float* seconds, int* frames, int B, float frame_rate, float speed, hipStream_t s) {
+    F5_REQUIRE(B >= 1 && speed != 0.0f, "seconds_to_frames: need B >= 1 and speed != 0");
+    hipLaunchKernelGGL(seconds_to_frames_kernel, dim3(f5_cdiv(B, 64)), dim3(64), 0, s, seconds, frames, B, frame_rate, speed);
     F5_LAUNCH_CHECK();
     return 0;
 }

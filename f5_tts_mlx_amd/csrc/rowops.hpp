@@ -108,6 +108,8 @@ int f5_launch_pack_bf16(const float* src, const uint8_t* rowkeep, op16_t* out_hi
                         int col0, hipStream_t s);
 int f5_launch_duration_head(const float* x, const float* g, const float* w, const uint8_t* mask, float* out, int B, int seq_len,
                             int dim, float eps, hipStream_t s);
+// frames[b] = (int32)(seconds[b] * frame_rate / speed): fp32 multiply, fp32 division, truncation toward zero (cfm.py:253-262)
+int f5_launch_seconds_to_frames(const float* seconds, int* frames, int B, float frame_rate, float speed, hipStream_t s);
 // MX-fp8 variants (engine precision mxfp8): LN + modulation straight to e4m3 + E8M0 scales; bf16 rows -> MX-fp8 (weights)
 int f5_launch_ln_modulate_f8(const float* x, const float* scale, const float* shift, uint8_t* q, uint8_t* qs, int rows, int dim,
                              float eps, hipStream_t s);

@@ -4,12 +4,16 @@
 reference's `DurationPredictor(DurationTransformer(dim=512, depth=8, heads=8, text_dim=512, ff_mult=2, conv_layers=2))`
 (cfm.py:429-438): TextEmbedding WITHOUT padding mask, `Linear(mel+text -> dim)` + ConvPositionEmbedding, 8 pre-LN blocks
 (plain LayerNorm, no adaLN, no gates), RMSNorm, masked mean over time, `Linear(dim -> 1, no bias)` + Softplus = seconds.
-Every layer is one HIP kernel launch through the C ABI (`f5_op_*`); Python only sequences them.
+Two ways to run it.  `native=True`: the whole prediction is ONE C-ABI call (`f5_predict_duration`, csrc/duration.hip): weights arena
++ workspaces owned here, the launch sequence captured as a hipGraph per (batch, frames, text columns), a status word for the fp16
+range, no process-wide operand switch.  `native=False` (the default, measured 7-10 % faster: DESIGN.md section 10): the
+Python-sequenced path (`_run_ops`: one `f5_op_*` launch per layer), the yardstick of the native one -- the same bits.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional
+import warnings
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -67,6 +71,24 @@ def synthetic_duration_weights(seed: int = 11, **kw) -> Dict[str, np.ndarray]:
     return out
 
 
+class F5DurationConfig(C.Structure):     # include/f5tts_hip.h f5_duration_config
+    _fields_ = [(n, C.c_int32) for n in ("dim", "depth", "heads", "dim_head", "ff_dim", "mel_dim", "text_num_embeds", "text_dim",
+                                         "conv_layers", "conv_pos_kernel", "conv_pos_groups", "text_max_pos")]
+
+
+class F5DurationArgs(C.Structure):       # include/f5tts_hip.h f5_duration_args
+    _fields_ = [("B", C.c_int32), ("n_in", C.c_int32), ("nt", C.c_int32),
+                ("mel", C.c_void_p), ("text", C.c_void_p), ("lens", C.c_void_p),
+                ("frame_rate", C.c_float), ("speed", C.c_float),
+                ("seconds", C.c_void_p), ("frames", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("use_graph", C.c_int32)]
+
+
+NATIVE_DEFAULT = False      # DurationPredictor.native: the measurement behind it is in DESIGN.md section 10
+MAX_WORKSPACES = 8          # workspaces kept per predictor, one per (B, n_in, nt): what the handle keeps graphs for
+
+
 def _split(x: torch.Tensor, two: bool, dtype: torch.dtype = torch.bfloat16):
     """fp32 -> 16-bit MFMA operand (bf16, or fp16 saturated at +-65504 like the device producers) + optional residual."""
     hi = (x.clamp(-65504.0, 65504.0) if dtype == torch.float16 else x).to(dtype)
@@ -91,6 +113,44 @@ class DurationTransformer:
         self.two = precision == "bf16x3"
         self.nseg = 3 if self.two else 1
         self.w = None
+        self.lib = None
+        self._h = C.c_void_p()          # f5_duration handle (csrc/duration.hip), created by load_weights
+        self.arena = None
+
+    def __del__(self):
+        try:
+            if self.lib is not None and self._h.value:
+                self.lib.f5_duration_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+    def c_config(self) -> F5DurationConfig:
+        return F5DurationConfig(self.dim, self.depth, self.heads, self.dim // self.heads, self.ff_dim, self.mel_dim, self.text_num_embeds,
+                                self.text_dim, self.conv_layers, 31, 16, 4096)
+
+    def _load_native(self, g: Dict[str, np.ndarray], names) -> None:
+        """The same tensors behind the C ABI: handle, arena (a torch tensor), every tensor by its reference name."""
+        lib = self.lib = E.load_library()
+        lib.f5_duration_destroy.restype = None
+        if self._h.value:
+            lib.f5_duration_destroy(self._h)
+            self._h = C.c_void_p()
+        cfg = self.c_config()
+        with torch.cuda.device(self.device):
+            E.check(lib.f5_duration_create(C.byref(cfg), E.PRECISIONS[self.precision], C.byref(self._h)), "f5_duration_create")
+            nbytes = C.c_size_t()
+            E.check(lib.f5_duration_weights_bytes(self._h, C.byref(nbytes)), "f5_duration_weights_bytes")
+            self.arena = E._aligned_bytes(nbytes.value, self.device)
+            st = E.stream_ptr(self.device)
+            E.check(lib.f5_duration_set_weights_arena(self._h, E.ptr(self.arena), C.c_size_t(self.arena.numel()), st),
+                    "f5_duration_set_weights_arena")
+            for name in names:
+                a = np.ascontiguousarray(g[name], dtype=np.float32)
+                shape = (C.c_int64 * a.ndim)(*a.shape)
+                E.check(lib.f5_duration_load_tensor(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), a.ndim, shape),
+                        f"f5_duration_load_tensor({name})")
+            E.check(lib.f5_duration_finalize(self._h, st), "f5_duration_finalize")
 
     def load_weights(self, weights: Dict[str, np.ndarray]) -> None:
         dev, two = self.device, self.two
@@ -148,6 +208,8 @@ class DurationTransformer:
         W["zeros"] = torch.zeros(self.dim, device=dev)
         W["ones"] = torch.ones(self.dim, device=dev)
         self.w = W
+        self._load_native(g, [name for name, _ in duration_param_specs(self.dim, self.depth, self.mel_dim, self.text_num_embeds,
+                                                                       self.text_dim, self.conv_layers, self.ff_dim // self.dim)])
 
 
 class DurationPredictor:
@@ -160,11 +222,20 @@ class DurationPredictor:
         self.transformer = transformer
         self.dim = transformer.dim
         self._vocab_char_map = vocab_char_map
+        self.native = NATIVE_DEFAULT    # what __call__ does when it is not told (F5TTS.predict_duration does not tell)
+        self.last_status = 0            # F5_STATUS_* of the last native call (engine.STATUS_SATURATED: an fp16 operand was clamped)
+        self._warned = False
+        self._workspaces: Dict[Tuple[int, int, int], torch.Tensor] = {}
+        self._stream = None             # side stream of the graph path
 
     def load_weights(self, weights) -> None:
         self.transformer.load_weights(dict(weights))
 
-    def __call__(self, inp: torch.Tensor, text, *, lens: Optional[torch.Tensor] = None, return_loss=False) -> torch.Tensor:
+    def __call__(self, inp: torch.Tensor, text, *, lens: Optional[torch.Tensor] = None, return_loss=False, native: Optional[bool] = None,
+                 use_graph: bool = True) -> torch.Tensor:
+        """seconds (b,) fp32.  native=True: one `f5_predict_duration` call (hipGraph replay when use_graph); native=False: the
+        Python-sequenced launches of `_run_ops`; None: this instance's `native` attribute (NATIVE_DEFAULT unless set)."""
+        native = self.native if native is None else native
         if return_loss:
             raise NotImplementedError("training loss (duration.py:229-260) is out of scope")
         T = self.transformer
@@ -181,6 +252,8 @@ class DurationPredictor:
             text = list_str_to_idx(text, self._vocab_char_map) if exists(self._vocab_char_map) else list_str_to_tensor(text)
             assert text.shape[0] == batch
         text = torch.as_tensor(text).to(torch.int32)
+        if native:
+            return self.predict_native(inp, text, lens=lens, frame_rate=None, use_graph=use_graph)[0]
         if seq_len < text.shape[1]:                         # duration.py:218-220
             pad = torch.zeros((batch, text.shape[1] - seq_len, inp.shape[2]), device=dev)
             inp = torch.cat([inp, pad], dim=1)              # plumbing: zero padding of the input buffer
@@ -194,6 +267,70 @@ class DurationPredictor:
 
         with E.operand_type(T.precision):                  # the f5_op_* entry points take this model's operand type
             return self._run_ops(lib, dev, ns, W, T, inp, text, text_d, mask_d, batch, seq_len)
+
+    def _workspace(self, B: int, n_in: int, nt: int) -> torch.Tensor:
+        key = (B, n_in, nt)
+        ws = self._workspaces.pop(key, None)
+        if ws is None:
+            T = self.transformer
+            nbytes = C.c_size_t()
+            E.check(T.lib.f5_duration_workspace_bytes(T._h, B, n_in, nt, C.byref(nbytes)), "f5_duration_workspace_bytes")
+            while len(self._workspaces) >= MAX_WORKSPACES:                  # least recently used first (dict order)
+                self._workspaces.pop(next(iter(self._workspaces)))
+            ws = E._aligned_bytes(nbytes.value, T.device)
+        self._workspaces[key] = ws
+        return ws
+
+    def predict_native(self, mel: torch.Tensor, text: torch.Tensor, *, lens: Optional[torch.Tensor] = None,
+                       frame_rate: Optional[float] = 93.0, speed: float = 1.0, use_graph: bool = True,
+                       workspace: Optional[torch.Tensor] = None):
+        """One `f5_predict_duration` call: mel (b, n_in, mel_dim) fp32, text (b, nt) int32 (-1 padded), lens host (b,) or None
+        -> (seconds (b,) fp32, frames (b,) int32 = (int32)(seconds * frame_rate / speed), or None when frame_rate is None).
+        Sets `last_status`."""
+        T = self.transformer
+        if not T._h.value:
+            raise RuntimeError("duration predictor weights not loaded")
+        lib, dev = T.lib, T.device
+        mel = mel.to(dev, torch.float32).contiguous()
+        text = text.to(dev, torch.int32).contiguous()
+        B, n_in, nt = mel.shape[0], mel.shape[1], text.shape[1]
+        assert mel.shape[2] == T.mel_dim and text.shape[0] == B
+        ws = self._workspace(B, n_in, nt) if workspace is None else workspace
+        c_lens = None
+        if exists(lens):
+            host = torch.as_tensor(lens).to("cpu", torch.int64).tolist()
+            assert len(host) == B
+            c_lens = (C.c_int32 * B)(*[int(v) for v in host])
+        seconds = torch.empty((B,), dtype=torch.float32, device=dev)
+        frames = torch.empty((B,), dtype=torch.int32, device=dev) if frame_rate is not None else None
+        args = F5DurationArgs(B, n_in, nt, mel.data_ptr(), text.data_ptr(), None if c_lens is None else C.cast(c_lens, C.c_void_p),
+                              float(frame_rate or 0.0), float(speed), seconds.data_ptr(), None if frames is None else frames.data_ptr(),
+                              ws.data_ptr(), ws.numel(), int(bool(use_graph)))
+        cur = torch.cuda.current_stream(dev)
+        run = cur
+        if use_graph:                                       # hipGraph capture is illegal on the legacy default stream
+            if self._stream is None:
+                self._stream = torch.cuda.Stream(device=dev)
+            run = self._stream
+            run.wait_stream(cur)
+        flags = C.c_int(0)
+        with torch.cuda.device(dev), torch.cuda.stream(run):
+            sp = C.c_void_p(run.cuda_stream)
+            E.check(lib.f5_predict_duration(T._h, C.byref(args), sp), "f5_predict_duration")
+            if T.precision == "f16":                        # the other operand types have fp32's range: nothing can set the word
+                E.check(lib.f5_duration_status(T._h, C.byref(args), C.byref(flags), sp), "f5_duration_status")
+        if run is not cur:
+            cur.wait_stream(run)
+            for t in (mel, text, seconds, frames):
+                if t is not None:
+                    t.record_stream(run)
+        self.last_status = int(flags.value)
+        if (self.last_status & E.STATUS_SATURATED) and not self._warned:
+            self._warned = True
+            warnings.warn("duration predictor: a 16-bit operand left the fp16 range (clamped at +-65504); the predicted duration is finite "
+                          "but not reliable -- load the predictor with precision 'bf16x3' or 'bf16' for this input", RuntimeWarning,
+                          stacklevel=2)
+        return seconds, frames
 
     def _run_ops(self, lib, dev, ns, W, T, inp, text, text_d, mask_d, batch, seq_len):
         B, N, D, Dt, H = batch, seq_len, T.dim, T.text_dim, T.heads

@@ -428,6 +428,66 @@ int f5_vocode(f5_vocoder* v, const float* mel, int B, int N, float* wave, void* 
 int f5_op_istft_batch(const float* x, int ldx, const float* window, float* frames_scratch, float* wave, int B, int nframes,
                       int n_fft, int hop, void* stream);
 
+/* ---- duration predictor behind one call (replaces `self._duration_predictor(cond, text)` and the frame arithmetic of
+ * F5TTS.predict_duration, cfm.py:253-262, :307-308; model: duration.py:97-260; wiring cfm.py:429-438) ---------------------------
+ * DurationPredictor(DurationTransformer): TextEmbedding without padding mask (duration.py:116-118), Linear(mel + text -> dim) +
+ * ConvPositionEmbedding (duration.py:44-58), `depth` pre-LN blocks with plain LayerNorm (duration.py:64-94), RMSNorm, masked mean,
+ * Linear(dim -> 1) + Softplus = seconds (duration.py:137,188-190,249-251).  Same ownership rules as the engine and the vocoder: the
+ * caller allocates the weights arena and the workspace.  Tensors are loaded by their reference (MLX-layout) names and shapes --
+ * "transformer.text_embed.text_embed.weight", "transformer.transformer_blocks.3.attn.to_q.weight", "to_pred.layers.0.weight" ... --
+ * with or without the "duration_predictor." prefix of an F5TTS checkpoint; the loader pads the matrices to 128 rows, lays
+ * input_embed.proj out as [x padded to 128 | text] columns, stacks to_q / to_k / to_v and expands 32-channel conv-pos groups to the
+ * block-diagonal 64-channel groups the kernel works on.  f5_duration_load_tensor checks name and shape before it needs the arena. */
+typedef struct f5_duration f5_duration;
+typedef struct f5_duration_config {       /* duration.py:97-158 */
+    int32_t dim;               /* 512 */
+    int32_t depth;             /* 8 */
+    int32_t heads;             /* 8 */
+    int32_t dim_head;          /* 64 (only 64 is supported by the attention kernel) */
+    int32_t ff_dim;            /* dim * ff_mult = 1024 */
+    int32_t mel_dim;           /* 100 (<= 128) */
+    int32_t text_num_embeds;   /* 2545 (embedding table has +1 rows, duration.py:116) */
+    int32_t text_dim;          /* 512 (a multiple of 256) */
+    int32_t conv_layers;       /* 2 (>= 1) */
+    int32_t conv_pos_kernel;   /* 31 */
+    int32_t conv_pos_groups;   /* 16 (dim / groups must be 32 or 64) */
+    int32_t text_max_pos;      /* 4096 */
+} f5_duration_config;
+int f5_duration_create(const f5_duration_config* cfg, int precision, f5_duration** out);   /* F5_PREC_BF16 / _BF16X3 / _F16; plans only, no device */
+void f5_duration_destroy(f5_duration* d);   /* also destroys every cached hipGraphExec */
+int f5_duration_weights_bytes(f5_duration* d, size_t* bytes);
+int f5_duration_set_weights_arena(f5_duration* d, void* dev_arena, size_t bytes, void* stream);
+int f5_duration_load_tensor(f5_duration* d, const char* name, const float* host_data, int ndim, const int64_t* shape);
+int f5_duration_mark_weights_loaded(f5_duration* d);   /* arena content arrived by a broadcast */
+int f5_duration_finalize(f5_duration* d, void* stream);   /* refuses a missing tensor by name, builds the text positional table (rope.py:63-73) */
+/* N = max(n_in, nt) (duration.py:218-220); needs B >= 1, n_in >= 1, nt >= 1, 4 <= N <= text_max_pos */
+int f5_duration_workspace_bytes(f5_duration* d, int B, int n_in, int nt, size_t* bytes);
+typedef struct f5_duration_args {
+    int32_t B;                 /* utterances                                                                 */
+    int32_t n_in;              /* mel frames of the input                                                    */
+    int32_t nt;                /* text columns                                                               */
+    const float* mel;          /* dev  [B][n_in][mel_dim] (duration.py:203-206 turns a raw wave into this)   */
+    const int32_t* text;       /* dev  [B][nt] token ids, -1 padded (utils.py:124-133)                       */
+    const int32_t* lens;       /* host [B] (duration.py:222-226) or NULL = every row is N = max(n_in, nt) long */
+    float frame_rate;          /* sample_rate // hop_length = 93 (cfm.py:260)                                */
+    float speed;               /* cfm.py:261                                                                 */
+    float* seconds;            /* dev  [B]                                                                   */
+    int32_t* frames;           /* dev  [B] or NULL: (int32)(seconds * frame_rate / speed), an fp32 product, an fp32 division, truncation */
+    void* workspace;           /* dev, f5_duration_workspace_bytes, 256-byte aligned                         */
+    size_t workspace_bytes;
+    int32_t use_graph;         /* != 0: the launch sequence is captured per (B, n_in, nt, workspace) and replayed, <= 8 graphs kept (LRU) */
+} f5_duration_args;
+/* mel / text / lens are staged into the workspace and seconds / frames copied out by kernels OUTSIDE the captured part: a replay
+ * serves new inputs of the same shape.  The handle carries its own operand type: the process-wide one (f5_op_set_operand_type) is
+ * neither read nor written.  Handles are not re-entrant. */
+int f5_predict_duration(f5_duration* d, const f5_duration_args* args, void* stream);
+/* Status word of the last f5_predict_duration on the workspace of `args` (the FIRST 32-bit word of the workspace, zeroed by every call):
+ * F5_STATUS_SATURATED (precision f16) = a producer of a 16-bit MFMA operand -- the packed input, the text path, conv-pos, LayerNorm,
+ * q / k / v, the GELU output -- clamped a value beyond +-65 504: the seconds are finite and wrong; use bf16x3 or bf16 for this input.
+ * Synchronises `stream`.  No reference counterpart. */
+int f5_duration_status(f5_duration* d, const f5_duration_args* args, int* flags, void* stream);
+int f5_duration_graph_count(f5_duration* d);
+
 #ifdef __cplusplus
 }
 #endif
