@@ -12,15 +12,20 @@
 //         transposed in HBM ([b*h][64][npad], written by the QKV GEMM epilogue).
 //   O^T's C layout again has query = lane&31, so the online-softmax rescale is a per-lane multiply.
 //
-// Block = 4 waves x 32 queries = 128 queries; KV tile = 64 keys, double-buffered in LDS (padded rows:
-// K 144 B, V^T 136 B => conflict-free ds_read_b128 / ds_read_b64).  bf16x3 mode (HP) carries hi/lo
-// for Q, K, V and splits P in registers: 3 MFMAs per product.
+// A wave owns 32 queries (or two blocks of 32); the KV tile is 64 keys.  K and V^T tiles go HBM -> LDS with
+// global_load_lds into a ring of tiles, counted vmcnt, ONE barrier per tile, no staging VGPRs.  LDS images are
+// lane-linear 128-byte rows, so the 16-byte XOR swizzle chunk ^= (row>>1)&7 is applied to the SOURCE address
+// and again on every read.  bf16x3 mode (HP) carries hi/lo for Q, K, V and splits P in registers: 3 MFMAs per
+// product.
+//
+// Four kernels share the pieces defined in front of them:
+//   f5_attn2_kernel   32 queries per wave, per-tile maximum; bf16 and bf16x3
+//   f5_attn2s_kernel  the same with KS wave groups that split the KV range inside the workgroup (small grids)
+//   f5_attn2f_kernel  large grids: 64 queries per wave, no per-tile maximum
+//   f5_attn2p_kernel  f5_attn2f_kernel's arithmetic, software-pipelined inside the wave
 #include "attention.hpp"
 
 namespace F5_NS {
-
-#define KLD 72   // K  tile row stride in elements (144 B)
-#define VLD 68   // V^T tile row stride in elements (136 B)
 
 // workgroup -> (query block, batch*head).  Workgroups are dealt to the 8 XCDs round-robin by their linear id, and every query
 // block of a head streams that head's whole K / V^T: with a plain (x = query block, y = head) numbering the query blocks of
@@ -41,13 +46,76 @@ __device__ __forceinline__ bool attn_block_map(const F5AttnArgs& p, int qrows, i
     bh = (s / nqb) * 8 + (blockIdx.x & 7);
     return bh < p.B * p.H;
 }
-// =================================================================================================
-// v2: same math / layouts, but K and V^T tiles go HBM -> LDS with global_load_lds into a ring of NST
-// tiles (3 for bf16: two tiles in flight while one is consumed; 2 for bf16x3), counted vmcnt, ONE barrier per
-// tile, no staging VGPRs (=> 3 workgroups per CU for bf16).  LDS images are lane-linear 128-byte rows, so the
-// 16-byte XOR swizzle chunk ^= (row>>1)&7 is applied to the SOURCE address and again on every read.  The
-// O rescale is skipped when no lane's running max moved (exact: alpha == 1 for every lane).
-// =================================================================================================
+
+// the whole argument block in ONE scalar-load clause (left alone the compiler loads each field where it is first used: three or
+// four dependent s_load / s_waitcnt rounds in the prologue of a kernel that is one latency chain at batch 1).  SCALE: the kernel
+// reads p.scale (q not pre-multiplied)
+template <bool SCALE>
+__device__ __forceinline__ void attn_pin_args(const F5AttnArgs& p) {
+    if (SCALE)
+        asm volatile("" ::"s"(p.qk[0]), "s"(p.vt[0]), "s"(p.out[0]), "s"(p.kv_len), "s"(p.B), "s"(p.H), "s"(p.seq_len), "s"(p.npad), "s"(p.ldqk),
+                     "s"(p.ldo), "s"(p.dmodel), "s"(p.scale), "s"(p.out8));
+    else
+        asm volatile("" ::"s"(p.qk[0]), "s"(p.vt[0]), "s"(p.out[0]), "s"(p.kv_len), "s"(p.B), "s"(p.H), "s"(p.seq_len), "s"(p.npad), "s"(p.ldqk),
+                     "s"(p.ldo), "s"(p.dmodel), "s"(p.out8));
+}
+
+// Q^T fragments (the B operand of S^T = K Q^T) of NQB 32-query blocks starting at query q0, NP parts (hi, lo) each, into
+// qf[qb * NP + part]: query row q0 + 32 qb + lq of this lane, clamped to the last row of the sequence (a block past the end computes
+// on a copy of it and stores nothing)
+template <int NQB, int NP>
+__device__ __forceinline__ void attn_load_q(op16x8 (&qf)[NQB * NP][4], const F5AttnArgs& p, size_t rowbase, int q0, int lq, int h, int hi) {
+#pragma unroll
+    for (int qb = 0; qb < NQB; ++qb) {
+        int qr = q0 + qb * 32 + lq;
+        if (qr > p.seq_len - 1) qr = p.seq_len - 1;
+#pragma unroll
+        for (int pp = 0; pp < NP; ++pp)
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+                qf[qb * NP + pp][ks] = *reinterpret_cast<const op16x8*>(p.qk[pp] + (rowbase + qr) * p.ldqk + h * 64 + ks * 16 + hi * 8);
+    }
+}
+
+// The compiler does not see hand-counted `s_waitcnt vmcnt(N)` (inline asm).  Q fragments loaded from global memory before a tile
+// loop are first USED inside the loop, so the compiler's own wait for them lands in the loop body -- as vmcnt(0) on every
+// iteration, draining the K / V^T prefetch each time.  A use it can see, placed before the loop, keeps that wait in the prologue.
+#define ATTN_PIN_Q(qf_, n0_, n1_)                                                                            \
+    _Pragma("unroll") for (int a_ = 0; a_ < (n0_); ++a_)                                                     \
+        _Pragma("unroll") for (int b_ = 0; b_ < (n1_); ++b_) asm volatile("" ::"v"((qf_)[a_][b_]));
+
+__device__ __forceinline__ void attn_glds16(const op16_t* gptr, op16_t* lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),
+                                     (__attribute__((address_space(3))) void*)(lds_wave_base), 16, 0, 0);
+}
+__device__ __forceinline__ int attn_swz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 1) & 7)) << 3); }
+// K tile rows are stored PERMUTED: LDS row i of a 32-key block holds key (i&3) + 4*(i>>3) + 16*((i>>2)&1).  In the
+// S^T = K Q^T accumulator layout lane-half hi then owns the 16 CONSECUTIVE keys 16*hi + r (r = register index), so
+// the P operand of a 16-key MFMA step is 8 consecutive keys and the matching V^T fragment is ONE ds_read_b128
+// (no bank conflicts, no register shuffles) instead of two ds_read_b64 halves.
+__device__ __forceinline__ int attn_kperm(int i) { return (i & 32) | ((i & 3) + 4 * ((i >> 3) & 3) + 16 * ((i >> 2) & 1)); }
+
+// workgroup barrier the compiler moves no memory access across (the global_load_lds writes and the LDS reads are invisible to it)
+__device__ __forceinline__ void attn_barrier() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+// top of a tile: wait for this thread's own loads of the tile, then make every wave's part visible.  ahead: the next tile's four
+// loads were issued behind them and may stay in flight (three-stage ring)
+__device__ __forceinline__ void attn_wait_barrier(bool ahead) {
+    if (ahead) {
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    attn_barrier();
+}
+
+// Row sums up to this take the fast path of the kernels without a per-tile maximum (f5_attn2f_kernel has the reasoning): if a
+// lane's partial sum of a tile is <= 2^14, every p of it is, inside half's range with the usual relative rounding
+constexpr float ATTN_SUM_LIMIT = 16384.0f;
+
 // O^T accumulators of one 32-query block -> MX-fp8: the 64 head dims are two MX blocks (db = 0, 1); a lane holds 16 values of
 // each (the other 16 sit in lane ^ 32), 4 consecutive d per accumulator row group -> one 4-byte store each.
 __device__ __forceinline__ void attn_store_f8(const F5AttnArgs& p, const f32x16 (&o)[2], float inv, size_t row, int h, int hi) {
@@ -66,6 +134,30 @@ __device__ __forceinline__ void attn_store_f8(const F5AttnArgs& p, const f32x16 
                 f5_pack4_fp8(o[db][rg * 4 + 0] * sc, o[db][rg * 4 + 1] * sc, o[db][rg * 4 + 2] * sc, o[db][rg * 4 + 3] * sc);
         }
         if (hi == 0) p.out8s[row * (size_t)(p.dmodel >> 5) + h * 2 + db] = (uint8_t)e8;
+    }
+}
+// end of a 32-query block: O^T / l of query row qr (lane halves hold partial row sums) -> out[0], with the residual in out[1] when
+// HP and the buffer is given, or MX-fp8 (one-pass kernels only)
+template <bool HP>
+__device__ __forceinline__ void attn_store_block(const F5AttnArgs& p, const f32x16 (&o)[2], float l_run, size_t rowbase, int qr, int h,
+                                                 int hi) {
+    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+    const float inv = 1.0f / l_tot;
+    if (!HP && p.out8) {
+        if (qr < p.seq_len) attn_store_f8(p, o, inv, rowbase + qr, h, hi);
+    } else if (qr < p.seq_len) {
+#pragma unroll
+        for (int db = 0; db < 2; ++db)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) {
+                const int d = db * 32 + 8 * rg + 4 * hi;
+                const float v0 = o[db][rg * 4 + 0] * inv, v1 = o[db][rg * 4 + 1] * inv;
+                const float v2 = o[db][rg * 4 + 2] * inv, v3 = o[db][rg * 4 + 3] * inv;
+                const size_t off = (rowbase + qr) * p.ldo + h * 64 + d;
+                *reinterpret_cast<u32x2*>(p.out[0] + off) = u32x2{f5_pack2_bounded(v0, v1), f5_pack2_bounded(v2, v3)};
+                if (HP && p.out[1])
+                    *reinterpret_cast<u32x2*>(p.out[1] + off) = u32x2{f5_pack2_lo(v0, v1), f5_pack2_lo(v2, v3)};
+            }
     }
 }
 
@@ -88,27 +180,16 @@ __device__ __forceinline__ attn_f32x2 attn_exp_block(f32x16& s, float c2, float 
     return sum2;
 }
 
-// The compiler does not see hand-counted `s_waitcnt vmcnt(N)` (inline asm).  Q fragments loaded from global memory before a tile
-// loop are first USED inside the loop, so the compiler's own wait for them lands in the loop body -- as vmcnt(0) on every
-// iteration, draining the K / V^T prefetch each time.  A use it can see, placed before the loop, keeps that wait in the prologue.
-#define ATTN_PIN_Q(qf_, n0_, n1_)                                                                            \
-    _Pragma("unroll") for (int a_ = 0; a_ < (n0_); ++a_)                                                     \
-        _Pragma("unroll") for (int b_ = 0; b_ < (n1_); ++b_) asm volatile("" ::"v"((qf_)[a_][b_]));
-
-__device__ __forceinline__ void attn_glds16(const op16_t* gptr, op16_t* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),
-                                     (__attribute__((address_space(3))) void*)(lds_wave_base), 16, 0, 0);
-}
-__device__ __forceinline__ int attn_swz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 1) & 7)) << 3); }
-// K tile rows are stored PERMUTED: LDS row i of a 32-key block holds key (i&3) + 4*(i>>3) + 16*((i>>2)&1).  In the
-// S^T = K Q^T accumulator layout lane-half hi then owns the 16 CONSECUTIVE keys 16*hi + r (r = register index), so
-// the P operand of a 16-key MFMA step is 8 consecutive keys and the matching V^T fragment is ONE ds_read_b128
-// (no bank conflicts, no register shuffles) instead of two ds_read_b64 halves.
-__device__ __forceinline__ int attn_kperm(int i) { return (i & 32) | ((i & 3) + 4 * ((i >> 3) & 3) + 16 * ((i >> 2) & 1)); }
-
-// ABL = timing-only ablation (results are wrong unless ABL == 0): 1 no exp2, 2 no barrier/vmcnt wait, 3 no PV MFMAs,
-// 4 no S MFMAs, 5 no softmax VALU at all, 6 no K/V loads after the prologue, 7 no LDS fragment reads (CDNA4 guide: ablate before optimising); every launch here passes 0
-template <bool HP, int ABL>
+// =================================================================================================
+// v2: 128 queries per workgroup, per-tile maximum.  K and V^T tiles go HBM -> LDS with global_load_lds into a ring of NST
+// tiles (3 for bf16: two tiles in flight while one is consumed; 2 for bf16x3), counted vmcnt, ONE barrier per
+// tile, no staging VGPRs (=> 3 workgroups per CU for bf16).  The O rescale is skipped when no lane's running max
+// moved (exact: alpha == 1 for every lane).  f5_attn2s_kernel with ONE wave group computes the same bits with the same
+// registers, LDS and occupancy, but timed against this kernel (N = 937, 16 heads, medians of ten alternations, this kernel's spread in
+// brackets) it was 36.85 -> 36.97 us (0.10) at B = 6 bf16 and 53.80 -> 54.01 us (0.08) at B = 4 bf16x3, and in other builds
+// of the same source up to 1 % either way: the two stay separate kernels.
+// =================================================================================================
+template <bool HP>
 __global__ __launch_bounds__(256, HP ? 2 : 3) void f5_attn2_kernel(F5AttnArgs p) {
     constexpr int NP = HP ? 2 : 1;
     constexpr int NST = HP ? 2 : 3;
@@ -191,19 +272,8 @@ __global__ __launch_bounds__(256, HP ? 2 : 3) void f5_attn2_kernel(F5AttnArgs p)
 
     for (int j = 0; j < ntile; ++j) {
         // wait for tile j (own loads), then make every wave's part visible; tile j+1 may stay in flight (NST == 3)
-        if (ABL != 2) {
-            if (ABL == 6) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            } else if (NST == 3 && j + 1 < ntile) {
-                asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        }
-        if (ABL != 6 && j + NST - 1 < ntile) A2_ISSUE(j + NST - 1);   // slot consumed in iteration j-1: every wave is past it
+        attn_wait_barrier(NST == 3 && j + 1 < ntile);
+        if (j + NST - 1 < ntile) A2_ISSUE(j + NST - 1);   // slot consumed in iteration j-1: every wave is past it
 
         const op16_t* st = smem + (j % NST) * (NP * 2 * TILE);
         const op16_t* sK = st;
@@ -220,15 +290,8 @@ __global__ __launch_bounds__(256, HP ? 2 : 3) void f5_attn2_kernel(F5AttnArgs p)
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 const int off = attn_swz(kb * 32 + lq, ks * 2 + hi);
-                op16x8 a;
-                if (ABL == 7) a = qf[0][ks ^ 1];
-                else a = *reinterpret_cast<const op16x8*>(&sK[off]);
-                if (ABL == 4) {
-                    asm volatile("" ::"v"(a));
-                    s[kb][ks] += (float)ks;
-                } else {
-                    s[kb] = F5_MFMA32(a, qf[0][ks], s[kb], 0, 0, 0);
-                }
+                const op16x8 a = *reinterpret_cast<const op16x8*>(&sK[off]);
+                s[kb] = F5_MFMA32(a, qf[0][ks], s[kb], 0, 0, 0);
                 if (HP) {
                     const op16x8 al = *reinterpret_cast<const op16x8*>(&sKl[off]);
                     s[kb] = F5_MFMA32(al, qf[0][ks], s[kb], 0, 0, 0);
@@ -249,14 +312,12 @@ __global__ __launch_bounds__(256, HP ? 2 : 3) void f5_attn2_kernel(F5AttnArgs p)
                 }
         }
         float tmax = -INFINITY;
-        if (ABL != 5) {
 #pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
+        for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, s[kb][r]);
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        }
-        if (ABL != 5 && __any(tmax > m_run)) {          // wave-uniform: rescale only when some lane's running max moved
+            for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, s[kb][r]);
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+        if (__any(tmax > m_run)) {          // wave-uniform: rescale only when some lane's running max moved
             const float m_new = fmaxf(m_run, tmax);
             const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c2);
             m_run = m_new;
@@ -268,25 +329,10 @@ __global__ __launch_bounds__(256, HP ? 2 : 3) void f5_attn2_kernel(F5AttnArgs p)
             }
         }
         const float mc = m_run * c2;
-        float psum = 0.0f;
-        if (ABL == 0 || ABL == 2 || ABL == 3 || ABL == 4 || ABL == 6 || ABL == 7) {
-            attn_f32x2 ps2 = {0.0f, 0.0f};
-            ps2 = attn_exp_block(s[0], c2, mc, ps2);
-            ps2 = attn_exp_block(s[1], c2, mc, ps2);
-            psum = ps2[0] + ps2[1];
-        } else {
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float pv;
-                    if (ABL == 5) pv = s[kb][r];
-                    else pv = s[kb][r] * c2 - mc;
-                    s[kb][r] = pv;
-                    if (ABL != 5) psum += pv;
-                }
-        }
-        l_run += psum;
+        attn_f32x2 ps2 = {0.0f, 0.0f};
+        ps2 = attn_exp_block(s[0], c2, mc, ps2);
+        ps2 = attn_exp_block(s[1], c2, mc, ps2);
+        l_run += ps2[0] + ps2[1];
 
 #pragma unroll
         for (int ks4 = 0; ks4 < 4; ++ks4) {
@@ -305,15 +351,8 @@ __global__ __launch_bounds__(256, HP ? 2 : 3) void f5_attn2_kernel(F5AttnArgs p)
 #pragma unroll
             for (int db = 0; db < 2; ++db) {
                 const int voff = attn_swz(db * 32 + lq, 4 * kb + 2 * hi + sp);
-                op16x8 a;
-                if (ABL == 7) a = qf[0][(ks4 + db) & 3];
-                else a = *reinterpret_cast<const op16x8*>(&sV[voff]);
-                if (ABL == 3) {
-                    asm volatile("" ::"v"(a), "v"(pb));
-                    o[db][ks4] += 1.0f;
-                } else {
-                    o[db] = F5_MFMA32(a, pb, o[db], 0, 0, 0);
-                }
+                const op16x8 a = *reinterpret_cast<const op16x8*>(&sV[voff]);
+                o[db] = F5_MFMA32(a, pb, o[db], 0, 0, 0);
                 if (HP) {
                     const op16x8 al = *reinterpret_cast<const op16x8*>(&sVl[voff]);
                     o[db] = F5_MFMA32(al, pb, o[db], 0, 0, 0);
@@ -383,10 +422,7 @@ __global__ __launch_bounds__(256, 2) void f5_attn2f_kernel(F5AttnArgs p) {
     constexpr int TILE = 64 * 64;
     __shared__ __attribute__((aligned(16))) op16_t smem[NST * 2 * TILE];   // [stage][K | V^T][64*64]
 
-    // the whole argument block in ONE scalar-load clause (left alone the compiler loads each field where it is first used: three or
-    // four dependent s_load / s_waitcnt rounds in the prologue of a kernel that is one latency chain at batch 1)
-    asm volatile("" ::"s"(p.qk[0]), "s"(p.vt[0]), "s"(p.out[0]), "s"(p.kv_len), "s"(p.B), "s"(p.H), "s"(p.seq_len), "s"(p.npad), "s"(p.ldqk),
-                 "s"(p.ldo), "s"(p.dmodel), "s"(p.scale), "s"(p.out8));
+    attn_pin_args<true>(p);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hi = lane >> 5, lq = lane & 31;
@@ -402,14 +438,7 @@ __global__ __launch_bounds__(256, 2) void f5_attn2f_kernel(F5AttnArgs p) {
     const bool live = q0 < p.seq_len;
 
     op16x8 qf[2][4];
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-        int qr = q0 + qb * 32 + lq;
-        if (qr > p.seq_len - 1) qr = p.seq_len - 1;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-            qf[qb][ks] = *reinterpret_cast<const op16x8*>(p.qk[0] + (rowbase + qr) * p.ldqk + h * 64 + ks * 16 + hi * 8);
-    }
+    attn_load_q<2, 1>(qf, p, rowbase, q0, lq, h, hi);
 
     const op16_t* kptr[2];
     const op16_t* vptr[2];
@@ -478,21 +507,13 @@ __global__ __launch_bounds__(256, 2) void f5_attn2f_kernel(F5AttnArgs p) {
     }
     float m_ref[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.0f, 0.0f};   // m_ref in exp2 units (scores * c2)
     const float c2 = PRE ? 1.0f : p.scale * 1.4426950408889634f;
-    constexpr float SUM_LIMIT = 16384.0f;
 
     A2F_ISSUE(0);
     if (ntile > 1) A2F_ISSUE(1);
     ATTN_PIN_Q(qf, 2, 4);
 
     for (int j = 0; j < ntile; ++j) {
-        if (j + 1 < ntile) {
-            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        attn_wait_barrier(j + 1 < ntile);
         if (j + NST - 1 < ntile) A2F_ISSUE(j + NST - 1);
 
         const op16_t* sK = smem + (j % NST) * (2 * TILE);
@@ -516,7 +537,7 @@ __global__ __launch_bounds__(256, 2) void f5_attn2f_kernel(F5AttnArgs p) {
                     ps2 = attn_exp_block(s[qb][1], c2, m_ref[qb], ps2);
                 }
                 psum[qb] = ps2[0] + ps2[1];
-                bad = bad || !(psum[qb] <= SUM_LIMIT);
+                bad = bad || !(psum[qb] <= ATTN_SUM_LIMIT);
             }
             slow = __any(bad);
         }
@@ -574,25 +595,7 @@ __global__ __launch_bounds__(256, 2) void f5_attn2f_kernel(F5AttnArgs p) {
 #undef A2F_QK
 
 #pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-        const float l_tot = l_run[qb] + __shfl_xor(l_run[qb], 32, 64);
-        const float inv = 1.0f / l_tot;
-        const int qr = q0 + qb * 32 + lq;
-        if (p.out8) {
-            if (qr < p.seq_len) attn_store_f8(p, o[qb], inv, rowbase + qr, h, hi);
-        } else if (qr < p.seq_len) {
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int rg = 0; rg < 4; ++rg) {
-                    const int d = db * 32 + 8 * rg + 4 * hi;
-                    const float v0 = o[qb][db][rg * 4 + 0] * inv, v1 = o[qb][db][rg * 4 + 1] * inv;
-                    const float v2 = o[qb][db][rg * 4 + 2] * inv, v3 = o[qb][db][rg * 4 + 3] * inv;
-                    const size_t off = (rowbase + qr) * p.ldo + h * 64 + d;
-                    *reinterpret_cast<u32x2*>(p.out[0] + off) = u32x2{f5_pack2_bounded(v0, v1), f5_pack2_bounded(v2, v3)};
-                }
-        }
-    }
+    for (int qb = 0; qb < 2; ++qb) attn_store_block<false>(p, o[qb], l_run[qb], rowbase, q0 + qb * 32 + lq, h, hi);
 }
 
 // =================================================================================================
@@ -704,7 +707,6 @@ __device__ __forceinline__ void attn2p_half(const uint32_t (&ak)[4], const uint3
                                             op16x8 (&fn)[8], f32x16 (&s_cur)[2], f32x16 (&s_nxt)[2], f32x16 (&o)[2][2], f32x16 (&mneg)[2],
                                             const uint32_t (&p_prev)[2][8], uint32_t (&p_cur)[2][8], float (&l_run)[2], int hi,
                                             int nvalid) {
-    constexpr float SUM_LIMIT = 16384.0f;
     if (__builtin_expect(nvalid < 32, 0)) {                  // wave-uniform; only the last tile of a sequence can be partial
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb)
@@ -752,7 +754,7 @@ __device__ __forceinline__ void attn2p_half(const uint32_t (&ak)[4], const uint3
     p_cur[1][7] = f5_pack2_bounded(y0, y1);
     a2p_lds_wait(fn);                                        // requested eight or more half-slots ago
     float psum[2] = {sa[0] + sb[0], sa[1] + sb[1]};
-    if (__builtin_expect(__any(!(psum[0] <= SUM_LIMIT) || !(psum[1] <= SUM_LIMIT)) != 0, 0)) {
+    if (__builtin_expect(__any(!(psum[0] <= ATTN_SUM_LIMIT) || !(psum[1] <= ATTN_SUM_LIMIT)) != 0, 0)) {
         // wave-uniform and rare: some score of this block lies more than 14 (exp2 units) above the reference point.  Move the
         // reference point of every row to max(old, this block's maximum): O and l shrink by alpha, -m_ref and the scores of the next
         // block (already computed against the old point) shift by delta, the block's P is taken again.
@@ -795,8 +797,7 @@ __global__ __launch_bounds__(256, 1) void f5_attn2p_kernel(F5AttnArgs p) {
     constexpr int TILE = 64 * 64;
     __shared__ __attribute__((aligned(16))) op16_t smem[8 * TILE];       // K ring [4][64*64] then V^T ring [4][64*64]: 64 KB
 
-    asm volatile("" ::"s"(p.qk[0]), "s"(p.vt[0]), "s"(p.out[0]), "s"(p.kv_len), "s"(p.B), "s"(p.H), "s"(p.seq_len), "s"(p.npad), "s"(p.ldqk),
-                 "s"(p.ldo), "s"(p.dmodel), "s"(p.out8));
+    attn_pin_args<false>(p);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hi = lane >> 5, lq = lane & 31;
@@ -810,14 +811,7 @@ __global__ __launch_bounds__(256, 1) void f5_attn2p_kernel(F5AttnArgs p) {
     const bool live = q0 < p.seq_len;                       // a wave entirely past the sequence only stages tiles and keeps the barriers
 
     op16x8 qf[2][4];
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-        int qr = q0 + qb * 32 + lq;
-        if (qr > p.seq_len - 1) qr = p.seq_len - 1;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-            qf[qb][ks] = *reinterpret_cast<const op16x8*>(p.qk[0] + (rowbase + qr) * p.ldqk + h * 64 + ks * 16 + hi * 8);
-    }
+    attn_load_q<2, 1>(qf, p, rowbase, q0, lq, h, hi);
     // staging: 2 16-byte chunks of K and of V^T per thread per tile (thread q_ = i * 256 + tid fills LDS chunk q_ of the tile image);
     // source = wave-uniform tile base (SGPR pair) + a loop-invariant 32-bit lane offset
     const char* kbase = attn_uniform_ptr(p.qk[0] + rowbase * p.ldqk + p.dmodel + h * 64);     // key 0 of this head
@@ -871,12 +865,6 @@ __global__ __launch_bounds__(256, 1) void f5_attn2p_kernel(F5AttnArgs p) {
     } else {                                                 \
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     \
     }
-#define A2P_BARRIER()                              \
-    {                                              \
-        asm volatile("" ::: "memory");             \
-        __builtin_amdgcn_s_barrier();              \
-        asm volatile("" ::: "memory");             \
-    }
     // this lane's fragment addresses (LDS bytes) inside a 64 x 64 tile image of stage 0: lane part of attn_swz; the key / d block adds 32 rows
     uint32_t ak[4], av[4];
 #pragma unroll
@@ -911,11 +899,11 @@ __global__ __launch_bounds__(256, 1) void f5_attn2p_kernel(F5AttnArgs p) {
     } else {
         asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     }
-    A2P_BARRIER();
+    attn_barrier();
     if (!live) {                                             // same barriers, same staging, no arithmetic
         for (int j = 0; j < T; ++j) {
             A2P_WAIT_TOP(j);
-            A2P_BARRIER();
+            attn_barrier();
             A2P_ISSUE_GROUP(j);
         }
         return;
@@ -989,7 +977,7 @@ __global__ __launch_bounds__(256, 1) void f5_attn2p_kernel(F5AttnArgs p) {
 #define A2P_STEP(PH)                                                                                                    \
     if (j < T) {                                                                                                        \
         A2P_WAIT_TOP(j)                                                                                                 \
-        A2P_BARRIER();                                                                                                  \
+        attn_barrier();                                                                                                 \
         A2P_ISSUE_GROUP(j)                                                                                              \
         const int nv_ = kvlen - j * 64;                                                                                 \
         /* (j, 0) requests the fragments of (j, 1): K(j+1) block 0, V^T(j) first half; (j, 1) those of (j+1, 0): K(j+1) block 1, V^T(j) second half */ \
@@ -1028,7 +1016,6 @@ __global__ __launch_bounds__(256, 1) void f5_attn2p_kernel(F5AttnArgs p) {
             }
         }
     }
-#undef A2P_BARRIER
 #undef A2P_WAIT_TOP
 #undef A2P_ISSUE_GROUP
 #undef A2P_ISSUE_V
@@ -1036,25 +1023,7 @@ __global__ __launch_bounds__(256, 1) void f5_attn2p_kernel(F5AttnArgs p) {
     asm volatile(A2P_PAD : "+a"(o[0][0]), "+a"(o[0][1]), "+a"(o[1][0]), "+a"(o[1][1]));
 
 #pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-        const float l_tot = l_run[qb] + __shfl_xor(l_run[qb], 32, 64);
-        const float inv = 1.0f / l_tot;
-        const int qr = q0 + qb * 32 + lq;
-        if (p.out8) {
-            if (qr < p.seq_len) attn_store_f8(p, o[qb], inv, rowbase + qr, h, hi);
-        } else if (qr < p.seq_len) {
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int rg = 0; rg < 4; ++rg) {
-                    const int d = db * 32 + 8 * rg + 4 * hi;
-                    const float v0 = o[qb][db][rg * 4 + 0] * inv, v1 = o[qb][db][rg * 4 + 1] * inv;
-                    const float v2 = o[qb][db][rg * 4 + 2] * inv, v3 = o[qb][db][rg * 4 + 3] * inv;
-                    const size_t off = (rowbase + qr) * p.ldo + h * 64 + d;
-                    *reinterpret_cast<u32x2*>(p.out[0] + off) = u32x2{f5_pack2_bounded(v0, v1), f5_pack2_bounded(v2, v3)};
-                }
-        }
-    }
+    for (int qb = 0; qb < 2; ++qb) attn_store_block<false>(p, o[qb], l_run[qb], rowbase, q0 + qb * 32 + lq, h, hi);
 }
 
 // =================================================================================================
@@ -1074,10 +1043,7 @@ __global__ __launch_bounds__(256 * KS, 1) void f5_attn2s_kernel(F5AttnArgs p) {
     static_assert((KS - 1) * 4 * 34 * 64 * 4 <= KS * RING * 2, "merge area must fit in the rings");
     __shared__ __attribute__((aligned(16))) op16_t smem_all[KS * RING];
 
-    // the whole argument block in ONE scalar-load clause (left alone the compiler loads each field where it is first used: three or
-    // four dependent s_load / s_waitcnt rounds in the prologue of a kernel that is one latency chain at batch 1)
-    asm volatile("" ::"s"(p.qk[0]), "s"(p.vt[0]), "s"(p.out[0]), "s"(p.kv_len), "s"(p.B), "s"(p.H), "s"(p.seq_len), "s"(p.npad), "s"(p.ldqk),
-                 "s"(p.ldo), "s"(p.dmodel), "s"(p.scale), "s"(p.out8));
+    attn_pin_args<true>(p);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave_all >> 2, wave = wave_all & 3;
@@ -1159,15 +1125,9 @@ __global__ __launch_bounds__(256 * KS, 1) void f5_attn2s_kernel(F5AttnArgs p) {
     ATTN_PIN_Q(qf, NP, 4);
 
     for (int jj = 0; jj < nit; ++jj) {
-        if (NST == 3 && jj + 1 < ntg) {
-            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (jj + NST - 1 < ntg) A2S_ISSUE(jj + NST - 1);
+        // wait for tile jj (own loads), then make every wave's part visible; tile jj+1 may stay in flight (NST == 3)
+        attn_wait_barrier(NST == 3 && jj + 1 < ntg);
+        if (jj + NST - 1 < ntg) A2S_ISSUE(jj + NST - 1);   // slot consumed in iteration jj-1: every wave is past it
         if (jj >= ntg) continue;                          // wave-uniform: this group has no tile left (still meets the barrier)
 
         const op16_t* st = smem + (jj % NST) * (NP * 2 * TILE);
@@ -1217,7 +1177,7 @@ __global__ __launch_bounds__(256 * KS, 1) void f5_attn2s_kernel(F5AttnArgs p) {
             ps2 = attn_exp_block(s[0], c2, mc, ps2);
             ps2 = attn_exp_block(s[1], c2, mc, ps2);
             psum = ps2[0] + ps2[1];
-            slow = __any(!(psum <= 16384.0f));
+            slow = __any(!(psum <= ATTN_SUM_LIMIT));
             if (slow) A2S_QK();
         }
         if (slow) {
@@ -1227,7 +1187,7 @@ __global__ __launch_bounds__(256 * KS, 1) void f5_attn2s_kernel(F5AttnArgs p) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, s[kb][r]);
             tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-            if (__any(tmax > m_run)) {
+            if (__any(tmax > m_run)) {                    // wave-uniform: rescale only when some lane's running max moved
                 const float m_new = fmaxf(m_run, tmax);
                 const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c2);
                 m_run = m_new;
@@ -1346,20 +1306,12 @@ static dim3 attn_grid(const F5AttnArgs& a, int qrows) {
     return dim3(nqb * 8 * f5_cdiv(a.B * a.H, 8), 1);
 }
 
-// checks, routes and launches; reached = what f5_debug_last_attn_kernel is to report when this returns 0
-static int attn_launch(const F5AttnArgs& a, hipStream_t stream, int& reached) {
-    F5_REQUIRE(a.B > 0 && a.H > 0 && a.seq_len > 0, "attention: bad shape");
-    F5_REQUIRE(a.npad % 64 == 0 && a.npad >= a.seq_len, "attention: npad must be a multiple of 64 and >= seq_len");
-    F5_REQUIRE(a.ldqk % 8 == 0 && a.ldo % 4 == 0, "attention: bad leading dims");
-    F5_REQUIRE(a.qk[0] && a.vt[0] && (a.out[0] || a.out8), "attention: null pointer");
-    F5_REQUIRE(!a.out8 || (!a.hp && a.out8s && a.ldo8 % 4 == 0),
-               "attention: fp8 output needs the bf16 ring kernels");
-    const dim3 grid = attn_grid(a, 128);
-    const long wgs128 = (long)f5_cdiv(a.seq_len, 128) * a.B * a.H;
+// the kernel a legal launch goes to under the knobs above (bf16x3 only has the 128-query kernels)
+static F5AttnKernel attn_route(const F5AttnArgs& a) {
     // small batches: fewer workgroups than ~2 per CU -> split the KV range over 2 or 4 wave groups inside the workgroup
     int ks = f5_attn_kvsplit;
     if (ks < 0) {
-        const long wgs = wgs128;
+        const long wgs = (long)f5_cdiv(a.seq_len, 128) * a.B * a.H;
         const int ntile = f5_cdiv(a.seq_len, 64);
         // measured (tools/attn_split_bench.py, N = 937, 16 heads): 128 WGs 20.5 / 17.4 / 16.2 us for 1 / 2 / 4 groups,
         // 256 WGs 21.4 / 19.1 / 20.1, 512 WGs 31.8 / 37.3 / 38.9
@@ -1368,40 +1320,38 @@ static int attn_launch(const F5AttnArgs& a, hipStream_t stream, int& reached) {
     // large grids (one-pass modes): two query blocks per wave (256 queries per workgroup), no per-tile maximum
     if (!a.hp && ks <= 1 &&
         (f5_attn_wide >= 1 || (f5_attn_wide < 0 && (long)f5_cdiv(a.seq_len, 256) * a.B * a.H >= 512))) {
-        const dim3 gw = attn_grid(a, 256);
         // f5_attn_pipe: 1 = the in-wave software-pipelined kernel (v2p, one wave per SIMD), 0 = v2f; q must be pre-multiplied
         const bool pipe = (a.pipe < 0 ? f5_attn_pipe : a.pipe) && a.q_prescaled;
-        reached = pipe ? F5A_V2P : (a.q_prescaled ? F5A_V2F_PRE : F5A_V2F);
-        if (pipe) hipLaunchKernelGGL(f5_attn2p_kernel, gw, dim3(256), 0, stream, a);
-        else if (a.q_prescaled) hipLaunchKernelGGL(f5_attn2f_kernel<true>, gw, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL(f5_attn2f_kernel<false>, gw, dim3(256), 0, stream, a);
-        F5_LAUNCH_CHECK();
-        return 0;
+        return pipe ? F5A_V2P : (a.q_prescaled ? F5A_V2F_PRE : F5A_V2F);
     }
-    if (ks > 1) {
-        if (a.hp) {
-            F5_REQUIRE(a.qk[1] && a.vt[1] && a.out[1], "attention: bf16x3 needs lo buffers");
-            reached = F5A_V2S_HP;
-            hipLaunchKernelGGL((f5_attn2s_kernel<true, 2, 2>), grid, dim3(512), 0, stream, a);
-        } else if (ks >= 4) {
-            reached = F5A_V2S_KS4;
-            hipLaunchKernelGGL((f5_attn2s_kernel<false, 4, 2, true>), grid, dim3(1024), 0, stream, a);
-        } else {
-            reached = F5A_V2S_KS2;
-            hipLaunchKernelGGL((f5_attn2s_kernel<false, 2, 3, true>), grid, dim3(512), 0, stream, a);
-        }
-        F5_LAUNCH_CHECK();
-        return 0;
-    }
-    if (a.hp) {
-        F5_REQUIRE(a.qk[1] && a.vt[1] && a.out[1], "attention: bf16x3 needs lo buffers");
-        reached = F5A_V2_HP;
-        hipLaunchKernelGGL((f5_attn2_kernel<true, 0>), grid, dim3(256), 0, stream, a);
-    } else {
-        reached = F5A_V2;
-        hipLaunchKernelGGL((f5_attn2_kernel<false, 0>), grid, dim3(256), 0, stream, a);
+    if (ks > 1) return a.hp ? F5A_V2S_HP : (ks >= 4 ? F5A_V2S_KS4 : F5A_V2S_KS2);
+    return a.hp ? F5A_V2_HP : F5A_V2;
+}
+
+// checks, routes and launches; reached = what f5_debug_last_attn_kernel is to report when this returns 0
+static int attn_launch(const F5AttnArgs& a, hipStream_t stream, int& reached) {
+    F5_REQUIRE(a.B > 0 && a.H > 0 && a.seq_len > 0, "attention: bad shape");
+    F5_REQUIRE(a.npad % 64 == 0 && a.npad >= a.seq_len, "attention: npad must be a multiple of 64 and >= seq_len");
+    F5_REQUIRE(a.ldqk % 8 == 0 && a.ldo % 4 == 0, "attention: bad leading dims");
+    F5_REQUIRE(a.qk[0] && a.vt[0] && (a.out[0] || a.out8), "attention: null pointer");
+    F5_REQUIRE(!a.out8 || (!a.hp && a.out8s && a.ldo8 % 4 == 0),
+               "attention: fp8 output needs the bf16 ring kernels");
+    F5_REQUIRE(!a.hp || (a.qk[1] && a.vt[1] && a.out[1]), "attention: bf16x3 needs lo buffers");
+    const F5AttnKernel k = attn_route(a);
+    const dim3 grid = attn_grid(a, 128), gw = attn_grid(a, 256);
+    switch (k) {
+        case F5A_V2_HP: hipLaunchKernelGGL(f5_attn2_kernel<true>, grid, dim3(256), 0, stream, a); break;
+        case F5A_V2: hipLaunchKernelGGL(f5_attn2_kernel<false>, grid, dim3(256), 0, stream, a); break;
+        case F5A_V2F_PRE: hipLaunchKernelGGL(f5_attn2f_kernel<true>, gw, dim3(256), 0, stream, a); break;
+        case F5A_V2F: hipLaunchKernelGGL(f5_attn2f_kernel<false>, gw, dim3(256), 0, stream, a); break;
+        case F5A_V2P: hipLaunchKernelGGL(f5_attn2p_kernel, gw, dim3(256), 0, stream, a); break;
+        case F5A_V2S_HP: hipLaunchKernelGGL((f5_attn2s_kernel<true, 2, 2>), grid, dim3(512), 0, stream, a); break;
+        case F5A_V2S_KS2: hipLaunchKernelGGL((f5_attn2s_kernel<false, 2, 3, true>), grid, dim3(512), 0, stream, a); break;
+        case F5A_V2S_KS4: hipLaunchKernelGGL((f5_attn2s_kernel<false, 4, 2, true>), grid, dim3(1024), 0, stream, a); break;
+        default: break;                                   // attn_route returns one of the eight above
     }
     F5_LAUNCH_CHECK();
+    reached = k;
     return 0;
 }
 
