@@ -3,6 +3,9 @@
 `mel_filters` / `hanning` build small constant tables on the host exactly as the reference does
 (float32 arithmetic, HTK scale, no norm); the STFT + filterbank + log run in one HIP kernel
 (`f5_mel_spectrogram`, csrc/audio.hip).
+
+`resample` changes the sample rate (no reference counterpart: the reference refuses anything but 24 kHz): the polyphase table is
+built on the host in fp64 (`resample_table`), the filter runs in one HIP kernel (`f5_resample_batch`, csrc/audio.hip).
 """
 from __future__ import annotations
 
@@ -86,6 +89,98 @@ def log_mel_spectrogram(audio: torch.Tensor, sample_rate: int = 24_000, n_mels: 
         stream = _eng.stream_ptr(audio.device)
         _eng.check(lib.f5_mel_spectrogram_batch(_eng.ptr(audio), b, C.c_int64(L), _eng.ptr(window), _eng.ptr(fb), n_fft, hop_length,
                                                 n_mels, _eng.ptr(out), stream), "f5_mel_spectrogram_batch")
+    return out
+
+
+RESAMPLE_LPW = 6                     # zero crossings of the sinc kept on each side
+RESAMPLE_ROLLOFF = 0.99              # cut-off as a fraction of the lower Nyquist frequency
+
+
+def _rate(value, name: str) -> int:
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value <= 0:
+        raise ValueError(f"{name} must be a positive integer number of Hz (got {value!r})")
+    return int(value)
+
+
+def resample_taps64(orig: int, new: int):
+    """The whole filter before rounding: (h fp64 [n][2 * width + o], o, n, width, base), as include/f5tts_hip.h states it --
+    h[i][k] = sinc(pi t) cos^2(pi t / (2 lpw)) base / o, t = (-i / n + (k - width) / o) base, exactly 0 where |t| >= lpw."""
+    orig, new = _rate(orig, "orig_sr"), _rate(new, "new_sr")
+    g = math.gcd(orig, new)
+    o, n = orig // g, new // g
+    base = min(o, n) * RESAMPLE_ROLLOFF
+    width = math.ceil(RESAMPLE_LPW * o / base)
+    i = np.arange(n, dtype=np.float64)[:, None]
+    k = np.arange(2 * width + o, dtype=np.float64)[None, :]
+    t = (-i / n + (k - width) / o) * base
+    inside = np.abs(t) < RESAMPLE_LPW
+    a = np.where(t == 0.0, 1.0, np.pi * t)                           # sinc(0) = 1 without a 0 / 0
+    sinc = np.where(t == 0.0, 1.0, np.sin(a) / a)
+    h = sinc * np.cos(np.pi * t / (2 * RESAMPLE_LPW)) ** 2 * base / o
+    return np.where(inside, h, 0.0), o, n, width, base
+
+
+@lru_cache(maxsize=None)
+def resample_table(orig: int, new: int):
+    """-> (taps fp32 [T][n], first int32 [n], o, n, T, width): the compact table f5_resample_batch takes.  first[i] is the first
+    non-zero tap of phase i, T the longest non-zero run of a phase, taps[t][i] = h[i][first[i] + t] (zero past the end of a run)."""
+    h64, o, n, width, _ = resample_taps64(orig, new)
+    h = h64.astype(np.float32)                                       # the one rounding
+    nz = h != 0
+    first = nz.argmax(axis=1).astype(np.int32)
+    last = h.shape[1] - 1 - nz[:, ::-1].argmax(axis=1)
+    T = int((last - first + 1).max())
+    padded = np.concatenate([h, np.zeros((n, T), np.float32)], axis=1)
+    taps = np.ascontiguousarray(padded[np.arange(n)[None, :], first[None, :] + np.arange(T)[:, None]])
+    for a in (taps, first):
+        a.setflags(write=False)                                      # cached: handed out to every caller
+    return taps, first, o, n, T, width
+
+
+_dev_resample = {}
+
+
+def _resample_tables(device: torch.device, orig: int, new: int):
+    key = (str(device), orig, new)
+    if key not in _dev_resample:
+        taps, first = resample_table(orig, new)[:2]
+        _dev_resample[key] = (torch.from_numpy(taps.copy()).to(device), torch.from_numpy(first.copy()).to(device))
+    return _dev_resample[key]
+
+
+def resample(audio: torch.Tensor, orig_sr: int, new_sr: int, device=None) -> torch.Tensor:
+    """audio: [t] or [b, t] at orig_sr Hz (device tensor or anything torch.as_tensor accepts) -> (b, ceil(t * new_sr / orig_sr)) float32
+    on the GPU at new_sr Hz.  Hann-windowed sinc polyphase filter (include/f5tts_hip.h f5_resample_batch; figures: docs/resample.md).
+    Equal rates hand the input back and an empty input an empty result, both without a launch.  ValueError for rates that are not
+    positive integers and for a ratio the kernel refuses."""
+    orig_sr, new_sr = _rate(orig_sr, "orig_sr"), _rate(new_sr, "new_sr")
+    lib = _eng.load_library()
+    audio = torch.as_tensor(audio)
+    if device is not None:
+        audio = audio.to(device)
+    elif not audio.is_cuda:
+        audio = audio.to("cuda")                                       # host input and no device given: current GPU
+    audio = audio.to(torch.float32)
+    if audio.ndim == 1:
+        audio = audio[None]
+    if orig_sr == new_sr:
+        return audio
+    audio = audio.contiguous()
+    _, _, o, n, T, width = resample_table(orig_sr, new_sr)
+    b, L = audio.shape
+    L_out = -((-n * L) // o)
+    out = torch.empty((b, L_out), dtype=torch.float32, device=audio.device)
+    if L == 0:
+        return out
+    taps, first = _resample_tables(audio.device, orig_sr, new_sr)
+    # one launch for the whole batch, on the current stream of the device that holds the audio (as log_mel_spectrogram)
+    with torch.cuda.device(audio.device):
+        stream = _eng.stream_ptr(audio.device)
+        rc = lib.f5_resample_batch(_eng.ptr(audio), b, C.c_int64(L), _eng.ptr(taps), _eng.ptr(first), o, n, T, width, _eng.ptr(out),
+                                   C.c_int64(L_out), stream)
+    if rc != 0 and lib.f5_last_error().startswith(b"resample: ratio"):
+        raise ValueError(lib.f5_last_error().decode("utf-8", "replace"))
+    _eng.check(rc, "f5_resample_batch")
     return out
 
 

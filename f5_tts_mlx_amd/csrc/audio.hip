@@ -182,3 +182,83 @@ extern "C" int f5_op_istft(const float* x, int ldx, const float* window, float* 
                            int n_fft, int hop, void* stream) {
     return f5_op_istft_batch(x, ldx, window, frames_scratch, wave, 1, nframes, n_fft, hop, stream);
 }
+
+// =================================================================================================
+// Polyphase resampler (no reference counterpart: generate.py:147-148 refuses anything but 24 kHz).  Hann-windowed sinc, the
+// design of torchaudio's default `resample`; the table is built on the host (audio.py resample_table).  With o = orig / gcd,
+// n = new / gcd:  out[j n + i] = sum_k h[i][k] x[j o + k - width],  x = 0 outside [0, L).  The kernel gets the compact table:
+// first[i] = first non-zero tap of phase i, taps [T][n] = the T taps from there on (consecutive lanes hold consecutive phases
+// and read consecutive words).  One workgroup per RS_TILE consecutive outputs of one batch row: it stages the input span of its
+// tile into LDS once (coalesced, zero-filled by an index test), then every thread runs T FMAs per output from LDS.
+// =================================================================================================
+#define RS_TILE 1024                 // outputs per workgroup
+#define RS_LDS 8192                  // floats of LDS for the staged span
+
+// floats a tile can need: its outputs come from at most (RS_TILE - 1) / n + 2 input groups of o samples, the last of which reaches
+// first[i] + T - 1 <= 2 width + o - 1 + T - 1 past its start
+static inline int64_t resample_span_max(int o, int n, int T, int width) {
+    return ((int64_t)(RS_TILE - 1) / n + 1) * o + 2 * (int64_t)width + o + T - 1;
+}
+
+__global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ wave, long L, const float* __restrict__ taps,
+                                                       const int* __restrict__ first, int o, int n, int T, int width,
+                                                       float* __restrict__ out, long L_out) {
+    __shared__ float xs[RS_LDS];
+    const int tid = threadIdx.x;
+    wave += (long)blockIdx.y * L;                                   // batch element: waves are [B][L], outputs [B][L_out]
+    out += (long)blockIdx.y * L_out;
+    const long p0 = (long)blockIdx.x * RS_TILE;
+    const long p1 = p0 + RS_TILE < L_out ? p0 + RS_TILE : L_out;
+    const long j0 = p0 / n, j1 = (p1 - 1) / n;
+    const long g0 = j0 * o - width;                                 // sample index of xs[0]
+    const int span = (int)(j1 - j0) * o + 2 * width + o + T - 1;    // <= resample_span_max <= RS_LDS (checked on the host)
+    for (int s = tid; s < span; s += 256) {
+        const long g = g0 + s;
+        xs[s] = (g >= 0 && g < L) ? wave[g] : 0.0f;
+    }
+    __syncthreads();
+    const int fmax = 2 * width + o - 1;
+    for (long p = p0 + tid; p < p1; p += 256) {
+        const long j = p / n;
+        const int i = (int)(p - j * n);
+        int f = first[i];
+        f = f < 0 ? 0 : (f > fmax ? fmax : f);                      // a table that lies cannot take the reads out of xs
+        const float* x = xs + (int)(j - j0) * o + f;
+        const float* h = taps + i;
+        float acc = 0.0f;
+        for (int t = 0; t < T; ++t) acc = fmaf(h[(size_t)t * n], x[t], acc);
+        out[p] = acc;
+    }
+}
+
+extern "C" int f5_resample_batch(const float* wave, int B, int64_t L, const float* taps, const int32_t* first, int o, int n, int T,
+                                 int width, float* out, int64_t L_out, void* stream) {
+    F5_REQUIRE(wave && taps && first && out, "resample: null pointer");
+    F5_REQUIRE(o >= 1 && n >= 1 && T >= 1 && width >= 1, "resample: o, n, T and width must be >= 1 (got %d, %d, %d, %d)", o, n, T, width);
+    int a = o, b = n;
+    while (b) {
+        const int r = a % b;
+        a = b;
+        b = r;
+    }
+    F5_REQUIRE(a == 1, "resample: o = %d and n = %d are not coprime (gcd %d): divide the rates by their gcd", o, n, a);
+    F5_REQUIRE(T <= 2 * (int64_t)width + o, "resample: T = %d exceeds the 2 * width + o = %lld taps of a phase", T,
+               (long long)(2 * (int64_t)width + o));
+    F5_REQUIRE(B >= 1 && B <= 65535, "resample: batch %d outside 1..65535", B);
+    F5_REQUIRE(L >= 0, "resample: negative length %lld", (long long)L);
+    F5_REQUIRE(L <= (INT64_MAX - o) / n, "resample: length %lld too long for n = %d", (long long)L, n);
+    const int64_t want = ((int64_t)n * L + o - 1) / o;
+    F5_REQUIRE(L_out == want, "resample: L_out = %lld, but ceil(n * L / o) = %lld", (long long)L_out, (long long)want);
+    const int64_t need = resample_span_max(o, n, T, width);
+    F5_REQUIRE(need <= RS_LDS,
+               "resample: ratio %d:%d too large: a tile of %d outputs spans up to %lld input samples (T = %d, width = %d), the kernel "
+               "stages at most %d",
+               o, n, RS_TILE, (long long)need, T, width, RS_LDS);
+    if (L == 0) return 0;
+    const int64_t tiles = (L_out + RS_TILE - 1) / RS_TILE;
+    F5_REQUIRE(tiles <= 0x7fffffff, "resample: %lld output tiles exceed the grid", (long long)tiles);
+    hipLaunchKernelGGL(resample_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(256), 0, (hipStream_t)stream, wave, (long)L, taps,
+                       first, o, n, T, width, out, (long)L_out);
+    F5_LAUNCH_CHECK();
+    return 0;
+}

@@ -17,6 +17,7 @@ from typing import Literal, Optional
 import numpy as np
 import torch
 
+from . import audio as _audio
 from .cfm import F5TTS
 from .utils import convert_char_to_pinyin
 
@@ -87,6 +88,8 @@ def generate(
     output_path: Optional[str] = None,
     f5tts: Optional[F5TTS] = None,          # extension: reuse an already loaded model
     batch_sentences: bool = False,          # extension: all sentences as ONE ragged sample() batch instead of the reference's loop
+    resample_ref: bool = False,             # extension: accept a reference recording at any sample rate
+    output_sample_rate: Optional[int] = None,   # extension: hand back (and write) the wave at this rate instead of 24 kHz
 ):
     """generate.py:113-245.  `batch_sentences=True` (opt-in, no reference counterpart; SURVEY.md section 8(f)2 names it as the point of
     owning the app loop): the sentences of a multi-sentence text are sampled as one ragged batch -- one `sample()` call, one set of
@@ -94,7 +97,17 @@ def generate(
     key-padding mask exists (cfm.py:333-336), and GRN (convnext_v2.py:16) and the conv position embedding (dit.py:251) see the padding
     up to the longest sentence, exactly as the reference's own `sample()` behaves for a batch; what it equals is `sample()` of that
     batch (tests/test_model_gpu.py::test_generate_batch_sentences), each element vocoded on its own frames (the padded tail of a
-    shorter sentence never reaches the vocoder)."""
+    shorter sentence never reaches the vocoder).
+
+    Sample rates (both opt-in, no reference counterpart: the reference refuses a reference recording that is not 24 kHz and always
+    writes 24 kHz).  `resample_ref=True` converts a reference recording of another rate to 24 kHz on the model's device before the
+    RMS step; `output_sample_rate` converts the final wave -- after the reference trim and the concatenation of all sentences -- once,
+    and that wave is what is returned and written.  The converter (audio.resample) is a Hann-windowed sinc polyphase filter with
+    6 zero crossings and a roll-off of 0.99: the design of torchaudio's default `resample`, which the PyTorch F5-TTS front end
+    applies to its reference audio.  It is a short filter and its stop band is modest: docs/resample.md records the figures (a
+    14 kHz tone at 48 kHz comes through the conversion to 24 kHz about 22 dB down, a 10 kHz tone at 24 kHz -> 16 kHz about 45 dB)."""
+    if output_sample_rate is not None:
+        output_sample_rate = _audio._rate(output_sample_rate, "output_sample_rate")
     if f5tts is None:
         f5tts = F5TTS.from_pretrained(model_name, quantization_bits=quantization_bits)
     if getattr(f5tts, "_vocoder", None) is None:
@@ -107,10 +120,13 @@ def generate(
         ref_audio_text = DEFAULT_REF_TEXT
     else:
         audio, sr = read_wav(ref_audio_path)
-        if sr != SAMPLE_RATE:
+        if sr != SAMPLE_RATE and not resample_ref:
             raise ValueError("Reference audio must have a sample rate of 24kHz")
 
     audio = torch.from_numpy(np.asarray(audio)).to(torch.float32)
+    if sr != SAMPLE_RATE:
+        # filtered on the model's device; back on the host the rest of the function treats it like a 24 kHz file's samples
+        audio = _audio.resample(audio, int(sr), SAMPLE_RATE, device=f5tts.transformer.device)[0].cpu()
     ref_audio_duration = audio.shape[0] / SAMPLE_RATE
     print(f"Got reference audio with duration: {ref_audio_duration:.2f} seconds")
 
@@ -173,8 +189,13 @@ def generate(
     generated_duration = wave.shape[0] / SAMPLE_RATE
     print(f"Generated {generated_duration:.2f}s of audio in {datetime.datetime.now() - start_date}.")
 
+    out_rate = SAMPLE_RATE
+    if output_sample_rate is not None and output_sample_rate != SAMPLE_RATE:
+        wave = _audio.resample(wave, SAMPLE_RATE, output_sample_rate)[0]
+        out_rate = output_sample_rate
+
     if output_path is not None:
-        write_wav(output_path, wave.detach().cpu().numpy(), SAMPLE_RATE)
+        write_wav(output_path, wave.detach().cpu().numpy(), out_rate)
     return wave
 
 
@@ -206,6 +227,8 @@ def main(argv=None):
     ap.add_argument("--method", default="rk4", choices=("euler", "midpoint", "rk4"), help="ODE solver")
     ap.add_argument("--q", type=int, default=None, choices=(4, 8), help="load the MLX 4/8-bit checkpoint (model_v1_{4,8}b.safetensors).  The group-quantised weights are EXPANDED to fp32 on load and run "
                          "through the same 16-bit MFMA kernels as the full checkpoint: unlike in the reference this saves neither memory nor time here")
+    ap.add_argument("--resample-ref", action="store_true", help="accept a --ref-audio of any sample rate: it is converted to 24 kHz on the GPU")
+    ap.add_argument("--output-rate", type=int, default=None, help="sample rate of the result in Hz (default: 24000, the model's own rate)")
     ns = ap.parse_args(argv)
 
     text = ns.text
@@ -218,7 +241,8 @@ def main(argv=None):
 
     generate(text, duration=ns.duration, estimate_duration=ns.estimate_duration, model_name=ns.model, ref_audio_path=ns.ref_audio,
              ref_audio_text=ns.ref_text, steps=ns.steps, method=ns.method, cfg_strength=ns.cfg, sway_sampling_coef=ns.sway_coef,
-             speed=ns.speed, seed=ns.seed, quantization_bits=ns.q, output_path=ns.output)
+             speed=ns.speed, seed=ns.seed, quantization_bits=ns.q, output_path=ns.output, resample_ref=ns.resample_ref,
+             output_sample_rate=ns.output_rate)
 
 
 if __name__ == "__main__":

@@ -396,6 +396,23 @@ int f5_mel_spectrogram_batch(const float* wave, int B, int64_t L, const float* w
 /* the same for one waveform: wave dev [L] -> out dev [L / hop][n_mels] */
 int f5_mel_spectrogram(const float* wave, int64_t L, const float* window, const float* filterbank, int n_fft, int hop,
                        int n_mels, float* out, void* stream);
+/* Sample-rate conversion of a batch of equally long waveforms in ONE launch (no reference counterpart: generate.py:147-148 refuses
+ * anything but 24 kHz): wave dev [B][L] fp32 -> out dev [B][L_out], L_out = ceil(n L / o).  A Hann-windowed sinc polyphase filter, the
+ * design of torchaudio's default `resample`.  With g = gcd(orig, new), o = orig / g, n = new / g, base = 0.99 min(o, n),
+ * width = ceil(6 o / base):  out[j n + i] = sum_k h[i][k] x[j o + k - width]  (x = 0 outside [0, L)),  k = 0 .. 2 width + o - 1,
+ *   h[i][k] = sinc(pi t) cos^2(pi t / 12) base / o,  t = (-i / n + (k - width) / o) base,  0 where |t| >= 6,
+ * computed in fp64 and rounded once to fp32.  The caller hands over the compact table (audio.py resample_table builds it):
+ *   first dev [n] int32:  index k of the first non-zero tap of phase i
+ *   taps  dev [T][n] fp32: taps[t][i] = h[i][first[i] + t], T = longest non-zero run of a phase, shorter runs zero padded
+ * (at most 2 width + 1 taps of a phase are non-zero: T = 25 for 48 kHz -> 24 kHz, 13 of 161 for 11 025 Hz -> 24 kHz).  fp32 FMAs in
+ * tap order; B = 1 .. 65 535; L = 0 is a successful call without a launch.
+ * Ratio limit: a workgroup stages the input span of 1024 consecutive outputs in 8192 floats of LDS, so the call refuses (no launch)
+ * unless  (1023 / n + 1) o + 2 width + o + T - 1 <= 8192  (integer division) -- with the table above, down-sampling by up to 7:1 (8:1 is
+ * refused), a little less when o is large: 48 kHz -> 8 kHz (6:1), 44.1 kHz -> 8 kHz (441:80) and every pair between
+ * 8 / 11.025 / 16 / 22.05 / 24 / 32 / 44.1 / 48 kHz and 24 kHz pass.  Rates whose gcd is small are refused whatever the ratio (o near
+ * 3 500 and beyond: the span holds two groups of o samples).  Also refused: null pointers, o / n / T / width < 1, gcd(o, n) != 1, T > 2 width + o, L < 0, L_out != ceil(n L / o). */
+int f5_resample_batch(const float* wave, int B, int64_t L, const float* taps, const int32_t* first, int o, int n, int T, int width,
+                      float* out, int64_t L_out, void* stream);
 
 /* ---- vocoder: Vocos mel-24khz behind one call (replaces `self._vocoder(out)`, cfm.py:399-400; wiring cfm.py:446,471) ---------
  * The reference delegates to the third-party `vocos_mlx` package (not in its repository); this is the published Vocos
