@@ -183,6 +183,67 @@ extern "C" int f5_op_istft(const float* x, int ldx, const float* window, float* 
     return f5_op_istft_batch(x, ldx, window, frames_scratch, wave, 1, nframes, n_fft, hop, stream);
 }
 
+// Overlap-add of a padded batch: row b holds lens[b] <= nframes frames (rows stay nframes frames apart).  Its f1 clamp and its
+// envelope stop at lens[b], so sample s < hop * (lens[b] - 1) is the sum istft_ola_kernel forms for that row alone, term by term; the
+// rest of the row, up to hop * (nframes - 1), is written as 0.0f.  Frames past lens[b] are never read.
+__global__ __launch_bounds__(256) void istft_ola_ragged_kernel(const float* __restrict__ frames, const float* __restrict__ window,
+                                                               float* __restrict__ wave, int nframes, int hop, long out_len,
+                                                               const int* __restrict__ lens) {
+    const long s = (long)blockIdx.x * 256 + threadIdx.x;
+    if (s >= out_len) return;
+    frames += (long)blockIdx.y * nframes * MEL_NFFT;            // batch element
+    wave += (long)blockIdx.y * out_len;
+    int nf = lens[blockIdx.y];
+    nf = nf < 1 ? 1 : (nf > nframes ? nframes : nf);            // a length that lies cannot take the reads out of the row
+    if (s >= (long)hop * (nf - 1)) {
+        wave[s] = 0.0f;
+        return;
+    }
+    const long pos = s + MEL_NFFT / 2;                          // position in the untrimmed signal
+    int f1 = (int)(pos / hop);
+    if (f1 > nf - 1) f1 = nf - 1;
+    long f0l = (pos - MEL_NFFT) / hop + 1;
+    if (pos - MEL_NFFT < 0) f0l = 0;
+    const int f0 = (int)(f0l < 0 ? 0 : f0l);
+    float acc = 0.0f, env = 0.0f;
+    for (int f = f0; f <= f1; ++f) {
+        const int off = (int)(pos - (long)f * hop);
+        if (off >= 0 && off < MEL_NFFT) {
+            acc += frames[(long)f * MEL_NFFT + off];
+            const float w = window[off];
+            env += w * w;
+        }
+    }
+    wave[s] = acc / env;
+}
+
+// lens dev [B], 2 <= lens[b] <= nframes.  istft_frames_kernel is per frame and runs as it is, over every frame of the padded batch
+// (the padding rows of the vocoder hold finite values; whatever they transform to is not read).
+int f5_launch_istft_ragged(const float* x, int ldx, const float* window, float* frames_scratch, float* wave, int B, int nframes, int hop,
+                           const int* lens, hipStream_t s) {
+    F5_REQUIRE(x, "istft_ragged: x is null");
+    F5_REQUIRE(window, "istft_ragged: window is null");
+    F5_REQUIRE(frames_scratch, "istft_ragged: frames_scratch is null");
+    F5_REQUIRE(wave, "istft_ragged: wave is null");
+    F5_REQUIRE(lens, "istft_ragged: lens is null");
+    F5_REQUIRE(B >= 1 && B <= 65535, "istft_ragged: B = %d outside 1..65535", B);
+    F5_REQUIRE(nframes >= 2, "istft_ragged: nframes must be >= 2 (got %d)", nframes);
+    F5_REQUIRE((long)B * nframes <= 0x7fffffffL, "istft_ragged: B * nframes = %ld frames exceed the grid", (long)B * nframes);
+    F5_REQUIRE(hop > 0 && MEL_NFFT % hop == 0, "istft_ragged: hop = %d must divide n_fft", hop);
+    F5_REQUIRE(ldx >= MEL_NFFT + 2, "istft_ragged: ldx = %d below n_fft + 2", ldx);
+    hipLaunchKernelGGL(istft_frames_kernel, dim3((unsigned)(B * nframes)), dim3(256), 0, s, x, ldx, window, frames_scratch);
+    const long out_len = (long)hop * (nframes - 1);
+    hipLaunchKernelGGL(istft_ola_ragged_kernel, dim3(f5_cdiv(out_len, 256), (unsigned)B), dim3(256), 0, s, frames_scratch, window, wave,
+                       nframes, hop, out_len, lens);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int f5_op_istft_ragged(const float* x, int ldx, const float* window, float* frames_scratch, float* wave, int B, int nframes,
+                                  int n_fft, int hop, const int32_t* lens_dev, void* stream) {
+    F5_REQUIRE(n_fft == MEL_NFFT, "istft_ragged: only n_fft = 1024 is supported (got %d)", n_fft);
+    return f5_launch_istft_ragged(x, ldx, window, frames_scratch, wave, B, nframes, hop, lens_dev, (hipStream_t)stream);
+}
+
 // =================================================================================================
 // Polyphase resampler (no reference counterpart: generate.py:147-148 refuses anything but 24 kHz).  Hann-windowed sinc, the
 // design of torchaudio's default `resample`; the table is built on the host (audio.py resample_table).  With o = orig / gcd,

@@ -1784,6 +1784,12 @@ extern "C" int f5_op_dwconv_ln(const float* x, const float* dw_w, const float* d
     return g_ops.dwconv_ln(x, dw_w, dw_b, ln_w, ln_b, (op16_t*)out_hi, (op16_t*)out_lo, nbatch, seq_len, dim, 1e-6f,
                                (hipStream_t)stream);
 }
+extern "C" int f5_op_dwconv_ln_ragged(const float* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,
+                                      void* out_hi, void* out_lo, int nbatch, int seq_len, int dim, const int32_t* lens_dev,
+                                      void* stream) {
+    return g_ops.dwconv_ln_ragged(x, dw_w, dw_b, ln_w, ln_b, (op16_t*)out_hi, (op16_t*)out_lo, nbatch, seq_len, dim, 1e-6f, lens_dev,
+                                  (hipStream_t)stream);
+}
 
 extern "C" size_t f5_op_grn_scratch_floats(int nbatch, int seq_len, int dim) {
     return f5_grn_partial_floats(nbatch, seq_len, dim) + (size_t)nbatch * dim;
@@ -1973,4 +1979,8 @@ extern "C" int f5_op_layernorm(const float* x, const float* w, const float* b, f
 }
 extern "C" int f5_op_im2col7(const float* x, void* out_hi, void* out_lo, int nbatch, int seq_len, int channels, void* stream) {
     return g_ops.im2col7(x, (op16_t*)out_hi, (op16_t*)out_lo, nbatch, seq_len, channels, (hipStream_t)stream);
+}
+extern "C" int f5_op_im2col7_ragged(const float* x, void* out_hi, void* out_lo, int nbatch, int seq_len, int channels,
+                                    const int32_t* lens_dev, void* stream) {
+    return g_ops.im2col7_ragged(x, (op16_t*)out_hi, (op16_t*)out_lo, nbatch, seq_len, channels, lens_dev, (hipStream_t)stream);
 }

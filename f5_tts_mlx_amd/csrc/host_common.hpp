@@ -87,6 +87,11 @@ struct Ops {
         return h ? f5hf::f5_launch_dwconv_ln(x, dw_w, dw_b, ln_w, ln_b, H(hi), H(lo), nbatch, seq_len, dim, eps, s)
                  : f5bf::f5_launch_dwconv_ln(x, dw_w, dw_b, ln_w, ln_b, hi, lo, nbatch, seq_len, dim, eps, s);
     }
+    int dwconv_ln_ragged(const float* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b, op16_t* hi,
+                         op16_t* lo, int nbatch, int seq_len, int dim, float eps, const int* lens, hipStream_t s) const {
+        return h ? f5hf::f5_launch_dwconv_ln_ragged(x, dw_w, dw_b, ln_w, ln_b, H(hi), H(lo), nbatch, seq_len, dim, eps, lens, s)
+                 : f5bf::f5_launch_dwconv_ln_ragged(x, dw_w, dw_b, ln_w, ln_b, hi, lo, nbatch, seq_len, dim, eps, lens, s);
+    }
     int grn(const float* g, const float* gamma, const float* beta, float* partial, float* nx, op16_t* hi, op16_t* lo, int nbatch,
             int seq_len, int dim, hipStream_t s) const {
         return h ? f5hf::f5_launch_grn(g, gamma, beta, partial, nx, H(hi), H(lo), nbatch, seq_len, dim, s)
@@ -108,6 +113,11 @@ struct Ops {
     int im2col7(const float* x, op16_t* hi, op16_t* lo, int nbatch, int seq_len, int channels, hipStream_t s) const {
         return h ? f5hf::f5_launch_im2col7(x, H(hi), H(lo), nbatch, seq_len, channels, s)
                  : f5bf::f5_launch_im2col7(x, hi, lo, nbatch, seq_len, channels, s);
+    }
+    int im2col7_ragged(const float* x, op16_t* hi, op16_t* lo, int nbatch, int seq_len, int channels, const int* lens,
+                       hipStream_t s) const {
+        return h ? f5hf::f5_launch_im2col7_ragged(x, H(hi), H(lo), nbatch, seq_len, channels, lens, s)
+                 : f5bf::f5_launch_im2col7_ragged(x, hi, lo, nbatch, seq_len, channels, lens, s);
     }
     int zero_vt_pad(op16_t* vt, size_t rows, int seq_len, int npad, hipStream_t s) const {
         return h ? f5hf::f5_launch_zero_vt_pad(H(vt), rows, seq_len, npad, s) : f5bf::f5_launch_zero_vt_pad(vt, rows, seq_len, npad, s);

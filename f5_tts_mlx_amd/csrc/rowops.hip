@@ -222,6 +222,99 @@ int f5_launch_dwconv_ln(const float* x, const float* dw_w, const float* dw_b, co
     return 0;
 }
 
+// The same for a padded batch whose row b is lens[b] <= seq_len tokens long (rows stay seq_len apart): a tap at nn >= lens[b] is
+// skipped like a tap at nn >= seq_len above -- the padding is never loaded -- and a token n >= lens[b] writes zeros and reports no
+// saturation.  A valid token runs the arithmetic of dwconv_ln_kernel on its row alone, in the same order: the same bits.
+template <int NV>
+__global__ __launch_bounds__(256) void dwconv_ln_ragged_kernel(const float* __restrict__ x, const float* __restrict__ dw_w,
+                                                               const float* __restrict__ dw_b, const float* __restrict__ ln_w,
+                                                               const float* __restrict__ ln_b, op16_t* __restrict__ out_hi,
+                                                               op16_t* __restrict__ out_lo, int rows, int seq_len, float eps,
+                                                               const int* __restrict__ lens, int* sat_flag) {
+    constexpr int DIM = NV * 256;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int b = row / seq_len, n = row - b * seq_len;
+    const int len = min(max(lens[b], 0), seq_len);              // a length that lies cannot take the loads out of the row
+    if (n >= len) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = i * 256 + lane * 4;
+            *reinterpret_cast<u32x2*>(out_hi + (size_t)row * DIM + c) = u32x2{0u, 0u};
+            if (out_lo) *reinterpret_cast<u32x2*>(out_lo + (size_t)row * DIM + c) = u32x2{0u, 0u};
+        }
+        return;
+    }
+    f5_sat_t trk;
+    float y[NV][4];
+    float sum = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = i * 256 + lane * 4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) y[i][e] = dw_b[c + e];
+#pragma unroll
+        for (int t = 0; t < 7; ++t) {
+            const int nn = n + t - 3;
+            if (nn >= 0 && nn < len) {
+                const f32x4 xv = *reinterpret_cast<const f32x4*>(x + ((size_t)b * seq_len + nn) * DIM + c);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) y[i][e] += xv[e] * dw_w[(c + e) * 7 + t];
+            }
+        }
+        sum += (y[i][0] + y[i][1]) + (y[i][2] + y[i][3]);
+    }
+    const float mean = f5_wave_sum(sum) * (1.0f / DIM);
+    float sq = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float d = y[i][e] - mean;
+            sq += d * d;
+        }
+    const float rstd = rsqrtf(f5_wave_sum(sq) * (1.0f / DIM) + eps);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = i * 256 + lane * 4;
+        float z[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) z[e] = (y[i][e] - mean) * rstd * ln_w[c + e] + ln_b[c + e];
+        *reinterpret_cast<u32x2*>(out_hi + (size_t)row * DIM + c) = u32x2{f5_pack2(z[0], z[1], trk), f5_pack2(z[2], z[3], trk)};
+        if (out_lo)
+            *reinterpret_cast<u32x2*>(out_lo + (size_t)row * DIM + c) =
+                u32x2{f5_pack2_lo(z[0], z[1]), f5_pack2_lo(z[2], z[3])};
+    }
+    f5_sat_commit(trk, sat_flag);
+}
+
+int f5_launch_dwconv_ln_ragged(const float* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,
+                               op16_t* out_hi, op16_t* out_lo, int nbatch, int seq_len, int dim, float eps, const int* lens,
+                               hipStream_t s) {
+    F5_REQUIRE(x, "dwconv_ln_ragged: x is null");
+    F5_REQUIRE(dw_w && dw_b, "dwconv_ln_ragged: dw_w / dw_b is null");
+    F5_REQUIRE(ln_w && ln_b, "dwconv_ln_ragged: ln_w / ln_b is null");
+    F5_REQUIRE(out_hi, "dwconv_ln_ragged: out_hi is null");
+    F5_REQUIRE(lens, "dwconv_ln_ragged: lens is null");
+    F5_REQUIRE(nbatch >= 1, "dwconv_ln_ragged: nbatch must be >= 1 (got %d)", nbatch);
+    F5_REQUIRE(seq_len >= 2, "dwconv_ln_ragged: seq_len must be >= 2 (got %d)", seq_len);
+    F5_REQUIRE((long)nbatch * seq_len <= 0x7fffffffL, "dwconv_ln_ragged: nbatch * seq_len = %ld rows exceed 2^31 - 1", (long)nbatch * seq_len);
+    F5_REQUIRE(dim % 256 == 0 && dim >= 256 && dim <= 1024, "dwconv_ln_ragged: dim must be 256/512/768/1024 (got %d)", dim);
+    const int rows = nbatch * seq_len;
+    const dim3 grid(f5_cdiv(rows, 4)), block(256);
+#define DW_ARGS x, dw_w, dw_b, ln_w, ln_b, out_hi, out_lo, rows, seq_len, eps, lens, f5_sat_flag_host
+    switch (dim / 256) {
+        case 1: hipLaunchKernelGGL((dwconv_ln_ragged_kernel<1>), grid, block, 0, s, DW_ARGS); break;
+        case 2: hipLaunchKernelGGL((dwconv_ln_ragged_kernel<2>), grid, block, 0, s, DW_ARGS); break;
+        case 3: hipLaunchKernelGGL((dwconv_ln_ragged_kernel<3>), grid, block, 0, s, DW_ARGS); break;
+        default: hipLaunchKernelGGL((dwconv_ln_ragged_kernel<4>), grid, block, 0, s, DW_ARGS); break;
+    }
+#undef DW_ARGS
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+
 // =================================================================================================
 // GRN: Gx[b][c] = ||g[b,:,c]||_2 over the sequence; Nx = Gx / (mean_c Gx + 1e-6);
 //      out = gamma * (g * Nx) + beta + g.   Deterministic: per-chunk partial sums, fixed-order finish.
@@ -826,6 +919,43 @@ int f5_launch_im2col7(const float* x, op16_t* out_hi, op16_t* out_lo, int nbatch
     const size_t total = (size_t)nbatch * seq_len * 7 * 128;
     hipLaunchKernelGGL(im2col7_kernel, dim3(f5_cdiv((long)total, 256)), dim3(256), 0, s, x, out_hi, out_lo, seq_len, channels,
                        total);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+// The same for a padded batch whose row b is lens[b] <= seq_len frames long: a tap at a frame >= lens[b] is zero like a tap at a
+// frame >= seq_len above, and a whole output row n >= lens[b] is zero.  The value is SELECTED by the index test -- the padding is
+// never loaded, so nothing it holds (NaN included) reaches an output.
+__global__ __launch_bounds__(256) void im2col7_ragged_kernel(const float* __restrict__ x, op16_t* __restrict__ out_hi,
+                                                             op16_t* __restrict__ out_lo, int seq_len, int channels, size_t total,
+                                                             const int* __restrict__ lens) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;   // over rows * 7 * 128
+    if (i >= total) return;
+    const size_t row = i / (7 * 128);
+    const int rem = (int)(i - row * (7 * 128));
+    const int t = rem >> 7, c = rem & 127;
+    const int b = (int)(row / seq_len);
+    const int n0 = (int)(row - (size_t)b * seq_len);
+    const int n = n0 + t - 3;
+    const int len = min(max(lens[b], 0), seq_len);              // a length that lies cannot take the load out of the row
+    float v = 0.0f;
+    if (c < channels && n0 < len && n >= 0 && n < len) v = x[((size_t)b * seq_len + n) * channels + c];
+    op16_t h, l;
+    f5_split(v, h, l);
+    out_hi[i] = h;
+    if (out_lo) out_lo[i] = l;
+}
+int f5_launch_im2col7_ragged(const float* x, op16_t* out_hi, op16_t* out_lo, int nbatch, int seq_len, int channels, const int* lens,
+                             hipStream_t s) {
+    F5_REQUIRE(x, "im2col7_ragged: x is null");
+    F5_REQUIRE(out_hi, "im2col7_ragged: out_hi is null");
+    F5_REQUIRE(lens, "im2col7_ragged: lens is null");
+    F5_REQUIRE(nbatch >= 1, "im2col7_ragged: nbatch must be >= 1 (got %d)", nbatch);
+    F5_REQUIRE(seq_len >= 2, "im2col7_ragged: seq_len must be >= 2 (got %d)", seq_len);
+    F5_REQUIRE(channels >= 1 && channels <= 128, "im2col7_ragged: channels must be in [1, 128] (got %d)", channels);
+    const size_t total = (size_t)nbatch * seq_len * 7 * 128;
+    F5_REQUIRE(total / 256 < 0x7fffffffu, "im2col7_ragged: nbatch * seq_len = %zu rows exceed the grid", (size_t)nbatch * seq_len);
+    hipLaunchKernelGGL(im2col7_ragged_kernel, dim3(f5_cdiv((long)total, 256)), dim3(256), 0, s, x, out_hi, out_lo, seq_len, channels,
+                       total, lens);
     F5_LAUNCH_CHECK();
     return 0;
 }

@@ -27,6 +27,10 @@ int f5_launch_ln_modulate(const float* x, const float* scale, const float* shift
 // ConvNeXtV2 front half (convnext_v2.py:46-48): depthwise Conv1d(k=7,pad=3)+bias -> LayerNorm(affine).
 int f5_launch_dwconv_ln(const float* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,
                         op16_t* out_hi, op16_t* out_lo, int nbatch, int seq_len, int dim, float eps, hipStream_t s);
+// the same on a padded batch: row b is lens[b] (dev [nbatch], 2 .. seq_len) tokens long, the conv stops there, tokens past it write zeros
+int f5_launch_dwconv_ln_ragged(const float* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,
+                               op16_t* out_hi, op16_t* out_lo, int nbatch, int seq_len, int dim, float eps, const int* lens,
+                               hipStream_t s);
 
 // GRN (convnext_v2.py:15-18) over the SEQUENCE axis: three deterministic passes.
 int f5_launch_grn(const float* g, const float* gamma, const float* beta, float* partial, float* nx, op16_t* out_hi,
@@ -102,6 +106,9 @@ int f5_launch_layernorm(const float* x, const float* w, const float* b, float* o
                         int rows, int dim, float eps, hipStream_t s);
 // im2col for Conv1d(k=7, pad=3) on channels-last input (c <= 128): out[b*n][7*128] bf16, tap-major, zero padded
 int f5_launch_im2col7(const float* x, op16_t* out_hi, op16_t* out_lo, int nbatch, int seq_len, int channels, hipStream_t s);
+// the same on a padded batch: taps at frames >= lens[b] (dev [nbatch], 2 .. seq_len) are zero without being loaded, rows past it are zero
+int f5_launch_im2col7_ragged(const float* x, op16_t* out_hi, op16_t* out_lo, int nbatch, int seq_len, int channels, const int* lens,
+                             hipStream_t s);
 
 // duration predictor helpers
 int f5_launch_pack_bf16(const float* src, const uint8_t* rowkeep, op16_t* out_hi, op16_t* out_lo, int rows, int cols, int ld,

@@ -23,6 +23,8 @@
 
 int f5_launch_istft(const float* x, int ldx, const float* window, float* frames_scratch, float* wave, int B, int nframes, int hop,
                     hipStream_t s);   // audio.hip
+int f5_launch_istft_ragged(const float* x, int ldx, const float* window, float* frames_scratch, float* wave, int B, int nframes, int hop,
+                           const int* lens, hipStream_t s);   // audio.hip
 
 struct VBlock {
     size_t dw_w, dw_b, ln_w, ln_b, b1, b2, gamma;
@@ -30,6 +32,7 @@ struct VBlock {
 };
 struct VGraph {
     int B, N;
+    bool ragged;             // captured with the ragged launches (f5_vocode_ragged): reads the lengths staged in its workspace
     const void* workspace;
     hipGraphExec_t exec;
     uint64_t stamp;
@@ -46,6 +49,7 @@ struct VWorkspace {
     size_t total = 0;
     size_t mel, x0, x, y, frames, wave;
     size_t a0[2], h[2], g[2];
+    size_t lens;             // int32 [B], staged by f5_vocode_ragged outside the captured part; last, so the plain plan keeps its offsets
 };
 
 struct f5_vocoder {
@@ -254,6 +258,7 @@ static VWorkspace vplan(const f5_vocoder* v, int B, int N) {
         w.h[p] = p < v->np ? b.take(rows * c.dim * 2) : 0;
         w.g[p] = p < v->np ? b.take(rows * c.intermediate_dim * 2) : 0;
     }
+    w.lens = b.take((size_t)B * 4);
     w.total = b.off;
     return w;
 }
@@ -265,7 +270,9 @@ extern "C" int f5_vocoder_workspace_bytes(f5_vocoder* v, int B, int N, size_t* b
     return 0;
 }
 
-static int vocode_body(const f5_vocoder* v, const VWorkspace& w, char* ws, int B, int N, hipStream_t s) {
+// lens: dev int32 [B] (the staged copy in the workspace) = every row decoded on its own lens[b] frames: the three launches that mix
+// time steps stop there; nullptr = every row is N frames long
+static int vocode_body(const f5_vocoder* v, const VWorkspace& w, char* ws, int B, int N, const int* lens, hipStream_t s) {
     const f5_vocos_config& c = v->cfg;
     const Ops& K = v->ops;
     const int D = c.dim, I = c.intermediate_dim, NF = c.n_fft + 2, rows = B * N, nseg = v->np == 2 ? 3 : 1;
@@ -292,14 +299,20 @@ static int vocode_body(const f5_vocoder* v, const VWorkspace& w, char* ws, int B
         return g;
     };
     // embed conv as a GEMM over im2col rows
-    RC(K.im2col7(P(w.mel), PB(w.a0, 0), PB(w.a0, 1), B, N, c.n_mels, s));
+    if (lens)
+        RC(K.im2col7_ragged(P(w.mel), PB(w.a0, 0), PB(w.a0, 1), B, N, c.n_mels, lens, s));
+    else
+        RC(K.im2col7(P(w.mel), PB(w.a0, 0), PB(w.a0, 1), B, N, c.n_mels, s));
     F5GemmArgs ge = gemm(PB(w.a0, 0), PB(w.a0, 1), 7 * 128, v->w_embed, D, 7 * 128, A(v->b_embed));
     ge.out_f32 = P(w.x0);
     ge.ldo = D;
     RC(K.gemm(ge, EPI_F32, s));
     RC(K.layernorm(P(w.x0), A(v->norm_w), A(v->norm_b), P(w.x), nullptr, nullptr, rows, D, 1e-6f, s));
     for (const VBlock& k : v->blocks) {
-        RC(K.dwconv_ln(P(w.x), A(k.dw_w), A(k.dw_b), A(k.ln_w), A(k.ln_b), PB(w.h, 0), PB(w.h, 1), B, N, D, 1e-6f, s));
+        if (lens)
+            RC(K.dwconv_ln_ragged(P(w.x), A(k.dw_w), A(k.dw_b), A(k.ln_w), A(k.ln_b), PB(w.h, 0), PB(w.h, 1), B, N, D, 1e-6f, lens, s));
+        else
+            RC(K.dwconv_ln(P(w.x), A(k.dw_w), A(k.dw_b), A(k.ln_w), A(k.ln_b), PB(w.h, 0), PB(w.h, 1), B, N, D, 1e-6f, s));
         F5GemmArgs g1 = gemm(PB(w.h, 0), PB(w.h, 1), D, k.pw1, I, D, A(k.b1));
         g1.out_bf[0] = PB(w.g, 0);
         g1.out_bf[1] = PB(w.g, 1);
@@ -316,28 +329,28 @@ static int vocode_body(const f5_vocoder* v, const VWorkspace& w, char* ws, int B
     gh.out_f32 = P(w.y);
     gh.ldo = NF;
     RC(K.gemm(gh, EPI_F32, s));
-    RC(f5_launch_istft(P(w.y), NF, A(v->window), P(w.frames), P(w.wave), B, N, c.hop_length, s));
+    if (lens)
+        RC(f5_launch_istft_ragged(P(w.y), NF, A(v->window), P(w.frames), P(w.wave), B, N, c.hop_length, lens, s));
+    else
+        RC(f5_launch_istft(P(w.y), NF, A(v->window), P(w.frames), P(w.wave), B, N, c.hop_length, s));
     return 0;
 }
 
-// mel dev [B][N][n_mels] fp32 -> wave dev [B][hop * (N - 1)] fp32.  Replaces `self._vocoder(out)` (cfm.py:399-400).
-extern "C" int f5_vocode(f5_vocoder* v, const float* mel, int B, int N, float* wave, void* workspace, size_t workspace_bytes,
-                         int use_graph, void* stream) {
-    F5_REQUIRE(v && mel && wave && workspace, "f5_vocode: null argument");
-    F5_REQUIRE(v->finalized, "vocoder weights are not finalized");
-    F5_REQUIRE(B >= 1 && N >= 2, "vocoder: need B >= 1 and N >= 2 frames (got B=%d N=%d)", B, N);
-    F5_REQUIRE(((uintptr_t)workspace & 255) == 0, "vocoder workspace must be 256-byte aligned");
-    const VWorkspace w = vplan(v, B, N);
-    F5_REQUIRE(workspace_bytes >= w.total, "vocoder workspace too small: %zu < %zu", workspace_bytes, w.total);
-    hipStream_t s = (hipStream_t)stream;
+// The call behind f5_vocode (lens_host == nullptr) and f5_vocode_ragged, after their argument checks.
+static int vocode_run(f5_vocoder* v, const VWorkspace& w, const float* mel, const int32_t* lens_host, int B, int N, float* wave,
+                      void* workspace, int use_graph, hipStream_t s) {
     char* ws = (char*)workspace;
     const size_t rows = (size_t)B * N;
+    const bool ragged = lens_host != nullptr;
+    const int* lens = ragged ? reinterpret_cast<const int*>(ws + w.lens) : nullptr;
     // caller buffers are staged outside the graph: the captured nodes only reference the workspace and the arena
     RC(f5_launch_copy_words(mel, ws + w.mel, rows * v->cfg.n_mels, s));      // copy KERNELS, not memcpy nodes (rowops.hip)
+    if (ragged)                                                               // host words through kernel arguments: a replay serves new lengths
+        RC(f5_launch_stage_words(reinterpret_cast<const uint32_t*>(lens_host), (size_t)B, reinterpret_cast<uint32_t*>(ws + w.lens), s));
     if (use_graph) {
         hipGraphExec_t exec = nullptr;
         for (auto& g : v->graphs)
-            if (g.B == B && g.N == N && g.workspace == workspace) {
+            if (g.B == B && g.N == N && g.ragged == ragged && g.workspace == workspace) {
                 exec = g.exec;
                 g.stamp = ++v->clock;
             }
@@ -359,7 +372,7 @@ extern "C" int f5_vocode(f5_vocoder* v, const float* mel, int B, int N, float* w
             }
             hipGraph_t graph = nullptr;
             F5_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            const int rc = vocode_body(v, w, ws, B, N, s);
+            const int rc = vocode_body(v, w, ws, B, N, lens, s);
             const hipError_t ec = hipStreamEndCapture(s, &graph);
             if (rc) {
                 if (graph) (void)hipGraphDestroy(graph);
@@ -370,14 +383,48 @@ extern "C" int f5_vocode(f5_vocoder* v, const float* mel, int B, int N, float* w
             (void)hipGraphDestroy(graph);
             hipEvent_t done = nullptr;
             F5_HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-            v->graphs.push_back({B, N, workspace, exec, ++v->clock, done});
+            v->graphs.push_back({B, N, ragged, workspace, exec, ++v->clock, done});
         }
         F5_HIP_CHECK(hipGraphLaunch(exec, s));
         for (auto& g : v->graphs)
             if (g.exec == exec) F5_HIP_CHECK(hipEventRecord(g.done, s));
     } else {
-        RC(vocode_body(v, w, ws, B, N, s));
+        RC(vocode_body(v, w, ws, B, N, lens, s));
     }
     RC(f5_launch_copy_words(ws + w.wave, wave, (size_t)B * v->cfg.hop_length * (N - 1), s));
     return 0;
 }
+
+// mel dev [B][N][n_mels] fp32 -> wave dev [B][hop * (N - 1)] fp32.  Replaces `self._vocoder(out)` (cfm.py:399-400).
+extern "C" int f5_vocode(f5_vocoder* v, const float* mel, int B, int N, float* wave, void* workspace, size_t workspace_bytes,
+                         int use_graph, void* stream) {
+    F5_REQUIRE(v && mel && wave && workspace, "f5_vocode: null argument");
+    F5_REQUIRE(v->finalized, "vocoder weights are not finalized");
+    F5_REQUIRE(B >= 1 && N >= 2, "vocoder: need B >= 1 and N >= 2 frames (got B=%d N=%d)", B, N);
+    F5_REQUIRE(((uintptr_t)workspace & 255) == 0, "vocoder workspace must be 256-byte aligned");
+    const VWorkspace w = vplan(v, B, N);
+    F5_REQUIRE(workspace_bytes >= w.total, "vocoder workspace too small: %zu < %zu", workspace_bytes, w.total);
+    return vocode_run(v, w, mel, nullptr, B, N, wave, workspace, use_graph, (hipStream_t)stream);
+}
+
+// The same for a padded batch whose row b is lens[b] frames long (no reference counterpart: the reference vocodes the padded batch,
+// cfm.py:399-400, and its app loop never has one): row b of `wave` is what f5_vocode gives for mel[b][:lens[b]] alone, then zeros.
+extern "C" int f5_vocode_ragged(f5_vocoder* v, const float* mel, const int32_t* lens, int B, int N, float* wave, void* workspace,
+                                size_t workspace_bytes, int use_graph, void* stream) {
+    F5_REQUIRE(v, "f5_vocode_ragged: the handle is null");
+    F5_REQUIRE(mel, "f5_vocode_ragged: mel is null");
+    F5_REQUIRE(lens, "f5_vocode_ragged: lens is null");
+    F5_REQUIRE(wave, "f5_vocode_ragged: wave is null");
+    F5_REQUIRE(workspace, "f5_vocode_ragged: workspace is null");
+    F5_REQUIRE(B >= 1, "f5_vocode_ragged: B must be >= 1 (got %d)", B);
+    F5_REQUIRE(N >= 2, "f5_vocode_ragged: N must be >= 2 frames (got %d)", N);
+    for (int b = 0; b < B; ++b)
+        F5_REQUIRE(lens[b] >= 2 && lens[b] <= N, "f5_vocode_ragged: lens[%d] = %d outside 2..N = %d", b, lens[b], N);
+    F5_REQUIRE(v->finalized, "f5_vocode_ragged: vocoder weights are not finalized");
+    F5_REQUIRE(((uintptr_t)workspace & 255) == 0, "f5_vocode_ragged: workspace must be 256-byte aligned");
+    const VWorkspace w = vplan(v, B, N);
+    F5_REQUIRE(workspace_bytes >= w.total, "f5_vocode_ragged: workspace too small: %zu < %zu", workspace_bytes, w.total);
+    return vocode_run(v, w, mel, lens, B, N, wave, workspace, use_graph, (hipStream_t)stream);
+}
+
+extern "C" int f5_vocoder_graph_count(f5_vocoder* v) { return v ? (int)v->graphs.size() : 0; }

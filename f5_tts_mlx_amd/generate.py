@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import argparse
 import datetime
+import inspect
 import pkgutil
 import re
 import sys
@@ -71,6 +72,14 @@ def write_wav(path, wave: np.ndarray, sample_rate: int = SAMPLE_RATE) -> None:
     wf.write(path, sample_rate, np.asarray(wave, dtype=np.float32))
 
 
+def _takes_lens(vocoder) -> bool:
+    """does this vocoder's call accept `lens` (Vocos.decode does; a plain mel -> wave callable does not)?"""
+    try:
+        return "lens" in inspect.signature(vocoder).parameters
+    except (TypeError, ValueError):
+        return False
+
+
 def generate(
     generation_text: str,
     duration: Optional[float] = None,
@@ -90,6 +99,7 @@ def generate(
     batch_sentences: bool = False,          # extension: all sentences as ONE ragged sample() batch instead of the reference's loop
     resample_ref: bool = False,             # extension: accept a reference recording at any sample rate
     output_sample_rate: Optional[int] = None,   # extension: hand back (and write) the wave at this rate instead of 24 kHz
+    vocode_batched: bool = False,           # extension: with batch_sentences, ONE ragged vocoder call instead of one per sentence
 ):
     """generate.py:113-245.  `batch_sentences=True` (opt-in, no reference counterpart; SURVEY.md section 8(f)2 names it as the point of
     owning the app loop): the sentences of a multi-sentence text are sampled as one ragged batch -- one `sample()` call, one set of
@@ -97,7 +107,11 @@ def generate(
     key-padding mask exists (cfm.py:333-336), and GRN (convnext_v2.py:16) and the conv position embedding (dit.py:251) see the padding
     up to the longest sentence, exactly as the reference's own `sample()` behaves for a batch; what it equals is `sample()` of that
     batch (tests/test_model_gpu.py::test_generate_batch_sentences), each element vocoded on its own frames (the padded tail of a
-    shorter sentence never reaches the vocoder).
+    shorter sentence never reaches the vocoder).  `vocode_batched=True` (opt-in, only together with `batch_sentences`) makes that one
+    `decode(mel, lens=frames)` call on the padded batch instead of one call per sentence: the vocoder's three launches that mix time
+    steps stop at each sentence's own length, so the samples are those of the loop -- bit for bit while the padded batch stays on the
+    GEMM kernels its sentences reach alone (up to 896 rows), beyond that to GEMM rounding order (docs/vocode_ragged.md).  A vocoder
+    whose call takes no `lens` argument keeps the loop.
 
     Sample rates (both opt-in, no reference counterpart: the reference refuses a reference recording that is not 24 kHz and always
     writes 24 kHz).  `resample_ref=True` converts a reference recording of another rate to 24 kHz on the model's device before the
@@ -172,7 +186,11 @@ def generate(
         finally:
             f5tts._vocoder = voc
         frames = f5tts.last_durations                                 # per-element frame counts after the clamps of cfm.py:317-318
-        wave = torch.cat([voc(mel[i:i + 1, :int(frames[i])]).reshape(-1)[audio.shape[0]:] for i in range(len(sentences))], dim=0)
+        if vocode_batched and _takes_lens(voc):
+            waves = voc(mel, lens=frames)                             # (sentences, 256 * (N - 1)), row i zero past its own frames
+            wave = torch.cat([waves[i, audio.shape[0]:HOP_LENGTH * (int(frames[i]) - 1)] for i in range(len(sentences))], dim=0)
+        else:
+            wave = torch.cat([voc(mel[i:i + 1, :int(frames[i])]).reshape(-1)[audio.shape[0]:] for i in range(len(sentences))], dim=0)
     else:
         output = []
         for sentence_text in sentences:
@@ -229,6 +247,8 @@ def main(argv=None):
                          "through the same 16-bit MFMA kernels as the full checkpoint: unlike in the reference this saves neither memory nor time here")
     ap.add_argument("--resample-ref", action="store_true", help="accept a --ref-audio of any sample rate: it is converted to 24 kHz on the GPU")
     ap.add_argument("--output-rate", type=int, default=None, help="sample rate of the result in Hz (default: 24000, the model's own rate)")
+    ap.add_argument("--batch-sentences", action="store_true", help="sample all sentences of the text as one ragged batch instead of one after the other")
+    ap.add_argument("--vocode-batched", action="store_true", help="with --batch-sentences: vocode the batch in one ragged call instead of one call per sentence")
     ns = ap.parse_args(argv)
 
     text = ns.text
@@ -242,7 +262,7 @@ def main(argv=None):
     generate(text, duration=ns.duration, estimate_duration=ns.estimate_duration, model_name=ns.model, ref_audio_path=ns.ref_audio,
              ref_audio_text=ns.ref_text, steps=ns.steps, method=ns.method, cfg_strength=ns.cfg, sway_sampling_coef=ns.sway_coef,
              speed=ns.speed, seed=ns.seed, quantization_bits=ns.q, output_path=ns.output, resample_ref=ns.resample_ref,
-             output_sample_rate=ns.output_rate)
+             output_sample_rate=ns.output_rate, batch_sentences=ns.batch_sentences, vocode_batched=ns.vocode_batched)
 
 
 if __name__ == "__main__":

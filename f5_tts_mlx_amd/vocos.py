@@ -9,12 +9,13 @@ checkpoint / vocos_mlx output is available; the structure is checked against ora
 
 The whole decode is ONE C-ABI call (`f5_vocode`, csrc/vocoder.hip): weights arena + workspace owned by this object, the layer
 sequence captured as a hipGraph per (batch, frames), the ISTFT of the whole batch in two launches.  This class only owns the
-buffers and mirrors `vocos_mlx.Vocos` (`from_pretrained`, `decode`).
+buffers and mirrors `vocos_mlx.Vocos` (`from_pretrained`, `decode`).  `decode(mel, lens=...)` (no `vocos_mlx` counterpart) decodes a
+padded batch with every row on its own frames in one call (`f5_vocode_ragged`, docs/vocode_ragged.md).
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -65,6 +66,33 @@ class VocosConfig(C.Structure):
 # state-dict entries of an upstream checkpoint that are buffers of the feature extractor / ISTFT module, not parameters of the
 # decode path (the window and the mel filterbank are recomputed)
 _IGNORED_PREFIXES = ("feature_extractor.", "head.istft.")
+
+
+def validate_lens(lens, B: int, N: int) -> List[int]:
+    """The per-row frame counts of `Vocos.decode(mel, lens=...)` as a list of B Python ints with 2 <= lens[b] <= N, or a ValueError
+    that names the offending entry: checked on the host, before any library call."""
+    if isinstance(lens, torch.Tensor):
+        if lens.dtype.is_floating_point or lens.dtype.is_complex or lens.dtype == torch.bool:
+            raise ValueError(f"lens must hold integers (got a {lens.dtype} tensor)")
+        lens = lens.detach().cpu().numpy()
+    if isinstance(lens, np.ndarray):
+        if lens.dtype.kind not in "iu":
+            raise ValueError(f"lens must hold integers (got a {lens.dtype} array)")
+        if lens.ndim != 1:
+            raise ValueError(f"lens must be 1-D (got shape {tuple(lens.shape)})")
+        lens = lens.tolist()
+    if not isinstance(lens, (list, tuple)):
+        raise ValueError(f"lens must be a sequence or a 1-D integer tensor of {B} frame counts (got {type(lens).__name__})")
+    if len(lens) != B:
+        raise ValueError(f"lens has {len(lens)} entries for a batch of {B}")
+    out = []
+    for b, v in enumerate(lens):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"lens[{b}] = {v!r} is not an integer")
+        if not 2 <= int(v) <= N:
+            raise ValueError(f"lens[{b}] = {int(v)} outside 2..{N} (the batch is padded to {N} frames)")
+        out.append(int(v))
+    return out
 
 
 class Vocos:
@@ -131,20 +159,35 @@ class Vocos:
             self._workspace = E._aligned_bytes(nbytes.value, self.device)
         return self._workspace
 
-    def decode(self, mel: torch.Tensor) -> torch.Tensor:
-        """mel (b, n, 100) -> wave: 1-D (256*(n-1),) for b == 1 (what generate.py:183 slices), else (b, 256*(n-1))."""
-        mel = mel.to(self.device, torch.float32).contiguous()
+    def decode(self, mel: torch.Tensor, lens=None) -> torch.Tensor:
+        """mel (b, n, 100) -> wave: 1-D (256*(n-1),) for b == 1 (what generate.py:183 slices), else (b, 256*(n-1)).
+
+        With `lens` (a sequence or an integer tensor of b frame counts, 2 <= lens[i] <= n) row i is decoded on its first lens[i] frames
+        alone, whatever the padding behind them holds: the result is always the padded (b, 256*(n-1)) tensor, row i equal to
+        `decode(mel[i:i+1, :lens[i]])` for 256*(lens[i]-1) samples and zero beyond (docs/vocode_ragged.md)."""
         B, N, C_ = mel.shape
         assert C_ == N_MELS
+        if lens is not None:
+            lens = validate_lens(lens, B, N)
+        mel = mel.to(self.device, torch.float32).contiguous()
         ws = self._ws(B, N)
         wave = torch.empty((B, HOP * (N - 1)), device=self.device)
         cur = torch.cuda.current_stream(self.device)
         self._stream.wait_stream(cur)
         with torch.cuda.stream(self._stream):
-            E.check(self.lib.f5_vocode(self._h, E.ptr(mel), B, N, E.ptr(wave), E.ptr(ws), C.c_size_t(ws.numel()), int(self.use_graph),
-                                       C.c_void_p(self._stream.cuda_stream)), "f5_vocode")
+            if lens is None:
+                E.check(self.lib.f5_vocode(self._h, E.ptr(mel), B, N, E.ptr(wave), E.ptr(ws), C.c_size_t(ws.numel()), int(self.use_graph),
+                                           C.c_void_p(self._stream.cuda_stream)), "f5_vocode")
+            else:
+                E.check(self.lib.f5_vocode_ragged(self._h, E.ptr(mel), (C.c_int32 * B)(*lens), B, N, E.ptr(wave), E.ptr(ws),
+                                                  C.c_size_t(ws.numel()), int(self.use_graph), C.c_void_p(self._stream.cuda_stream)),
+                        "f5_vocode_ragged")
         cur.wait_stream(self._stream)
         mel.record_stream(self._stream)
-        return wave[0] if B == 1 else wave
+        return wave if lens is not None or B > 1 else wave[0]
+
+    def graph_count(self) -> int:
+        """captured hipGraphs the handle holds now"""
+        return int(self.lib.f5_vocoder_graph_count(self._h))
 
     __call__ = decode

@@ -440,10 +440,39 @@ int f5_vocoder_workspace_bytes(f5_vocoder* v, int B, int N, size_t* bytes);
 /* mel dev [B][N][n_mels] fp32 -> wave dev [B][hop * (N - 1)] fp32; use_graph != 0: captured per (B, N, workspace), <= 8 graphs kept */
 int f5_vocode(f5_vocoder* v, const float* mel, int B, int N, float* wave, void* workspace, size_t workspace_bytes, int use_graph,
               void* stream);
+/* Ragged batch (no reference counterpart: the reference vocodes the padded batch, cfm.py:399-400): row b of mel dev [B][N][n_mels]
+ * is lens[b] frames long (host [B], 2 <= lens[b] <= N) and is decoded on those frames alone -- wave dev [B][hop * (N - 1)], row b =
+ * what f5_vocode gives for mel[b][:lens[b]] by itself for hop * (lens[b] - 1) samples, exactly 0.0f beyond.  The launch sequence is
+ * f5_vocode's with the three launches that mix time steps replaced by their ragged twins (below); the rest is row-wise.  `lens` is
+ * staged into the workspace outside the captured part: one graph per (B, N, workspace, ragged) serves every set of lengths, and the
+ * graphs of f5_vocode and of this call share the handle's 8 slots without replacing each other.  Refused before any launch, each
+ * with its own message: a null pointer, B < 1, N < 2, a lens[b] outside 2 .. N, an unfinalised handle, a workspace that is too small
+ * (f5_vocoder_workspace_bytes covers both calls) or not 256-byte aligned. */
+int f5_vocode_ragged(f5_vocoder* v, const float* mel, const int32_t* lens, int B, int N, float* wave, void* workspace,
+                     size_t workspace_bytes, int use_graph, void* stream);
+int f5_vocoder_graph_count(f5_vocoder* v);   /* captured graphs the handle holds now (both calls) */
 /* ISTFT head alone (per-op entry for tests): x dev [B * nframes][ldx >= n_fft + 2] (log-magnitude | phase) ->
  * wave dev [B][hop * (nframes - 1)]; frames_scratch dev [B * nframes][n_fft]; two launches for the whole batch */
 int f5_op_istft_batch(const float* x, int ldx, const float* window, float* frames_scratch, float* wave, int B, int nframes,
                       int n_fft, int hop, void* stream);
+/* The ragged twins of f5_op_im2col7, f5_op_dwconv_ln and f5_op_istft_batch: the same arguments plus lens_dev, dev int32 [nbatch] with
+ * 2 <= lens_dev[b] <= seq_len (nframes); the buffers keep their padded shapes, rows seq_len apart.  Row b ends at lens_dev[b]:
+ *   im2col7:   a tap at a frame >= lens[b] is zero, as a tap at a frame >= seq_len is in f5_op_im2col7, and an output row
+ *              n >= lens[b] is all zeros; the value is selected by the index test, never multiplied by a mask, so nothing the
+ *              padding holds (NaN included) is loaded;
+ *   dwconv_ln: a tap at nn >= lens[b] is left out of the sum (FMA order t = 0 .. 6 as in f5_op_dwconv_ln); a token n >= lens[b]
+ *              writes zeros to out_hi / out_lo and takes no part in the saturation report;
+ *   istft:     the overlap-add of row b uses lens[b] frames in its last-frame clamp and its envelope, writes wave[b][s] for
+ *              s < hop * (lens[b] - 1) and exactly 0.0f from there to hop * (nframes - 1); frames past lens[b] are not read.
+ * A valid output is produced by the floating-point operations of the plain op run on that row's slice alone (nbatch = 1,
+ * seq_len = lens[b]), in the same order: the same bits.  Refused before a launch: null pointers, nbatch < 1, seq_len < 2 and what
+ * the plain ops refuse.  The kernels clamp a length outside the stated range to it: wrong results, no access outside the buffers. */
+int f5_op_im2col7_ragged(const float* x, void* out_hi, void* out_lo, int nbatch, int seq_len, int channels, const int32_t* lens_dev,
+                         void* stream);
+int f5_op_dwconv_ln_ragged(const float* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b, void* out_hi,
+                           void* out_lo, int nbatch, int seq_len, int dim, const int32_t* lens_dev, void* stream);
+int f5_op_istft_ragged(const float* x, int ldx, const float* window, float* frames_scratch, float* wave, int B, int nframes,
+                       int n_fft, int hop, const int32_t* lens_dev, void* stream);
 
 /* ---- duration predictor behind one call (replaces `self._duration_predictor(cond, text)` and the frame arithmetic of
  * F5TTS.predict_duration, cfm.py:253-262, :307-308; model: duration.py:97-260; wiring cfm.py:429-438) ---------------------------
