@@ -57,6 +57,20 @@ enum F5AttnKernel {
 namespace f5dbg {
 extern int last_attn_kernel;
 }
+// ---- test hook (f5_debug_last_convpos_kernel): the same for f5_launch_convpos -- 0 when it refused the launch, else
+// one of F5ConvPosKernel, plus F5CP_XCD when the 1-D "groups dealt to XCDs" numbering ran.  The name is composed in engine.hip.
+enum F5ConvPosKernel {
+    F5CP_NONE = 0,
+    F5CP_1,          // f5_convpos_kernel<false,1>
+    F5CP_2,          // f5_convpos_kernel<false,2>
+    F5CP_4,          // f5_convpos_kernel<false,4>
+    F5CP_HP1,        // f5_convpos_kernel<true,1>
+    F5CP_HP2,        // f5_convpos_kernel<true,2>
+    F5CP_XCD = 16
+};
+namespace f5dbg {
+extern int last_convpos_kernel;
+}
 
 // ---- host-side float <-> 16-bit operand bits (weight upload), round to nearest even -----------------------
 // bf16: same rounding as torch's .to(bfloat16); fp16: same as torch's .to(float16) except that finite values beyond

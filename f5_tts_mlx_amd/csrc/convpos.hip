@@ -32,8 +32,10 @@ __global__ __launch_bounds__(256) void f5_convpos_kernel(F5ConvPosArgs p) {
     // XCDs (XCD = linear id & 7) and every XCD's L2 ends up streaming ALL groups' weights.  The 1-D grid used when the group
     // count is a multiple of 8 deals groups to XCDs instead: XCD x hosts groups x, x + 8, ... with all their token tiles and
     // batch elements, so a group's weights are fetched into one L2 and shared by its workgroups.
+    // A 3-D grid has one y per group, so with a group count that is a multiple of 8 a single y means the 1-D grid.  The group
+    // count is part of the test: one group and one batch element make a 3-D grid (token tiles, 1, 1) that must not be decoded as 1-D.
     int n0, g, b;
-    if (gridDim.y == 1 && gridDim.z == 1) {
+    if (gridDim.y == 1 && (p.groups & 7) == 0) {
         const int nx = (p.seq_len + CP_ROWS - 1) / CP_ROWS;
         const int per_group = nx * p.B;
         const int s_ = blockIdx.x >> 3;
@@ -182,31 +184,40 @@ __global__ __launch_bounds__(256) void f5_convpos_kernel(F5ConvPosArgs p) {
 int f5_convpos_tps = 0;   // taps per pipeline step: 0 auto, 1 / 2 / 4 forced (f5_debug_set_convpos_tps)
 int f5_convpos_xcd_map = 1;   // 0: plain 3-D block numbering (A/B)
 int f5_launch_convpos(const F5ConvPosArgs& a, hipStream_t stream) {
+    f5dbg::last_convpos_kernel = F5CP_NONE;                // a launch that is refused, or fails, reports no kernel
     F5_REQUIRE(a.B > 0 && a.seq_len > 0 && a.groups > 0, "convpos: bad shape");
     F5_REQUIRE(a.C == a.groups * 64, "convpos: channels per group must be 64 (C=%d groups=%d)", a.C, a.groups);
     F5_REQUIRE(a.taps >= 1 && a.taps <= CP_MAXTAPS && (a.taps & 1), "convpos: taps must be odd and <= %d", CP_MAXTAPS);
     F5_REQUIRE(a.ld % 8 == 0, "convpos: ld must be a multiple of 8");
     dim3 grid(f5_cdiv(a.seq_len, CP_ROWS), a.groups, a.B);
     const long nwg = (long)grid.x * grid.y * grid.z;
-    if (a.groups % 8 == 0 && f5_convpos_xcd_map) grid = dim3((unsigned)nwg, 1, 1);      // group-per-XCD numbering (see the kernel)
+    const bool xcd = a.groups % 8 == 0 && f5_convpos_xcd_map;
+    if (xcd) grid = dim3((unsigned)nwg, 1, 1);             // group-per-XCD numbering (see the kernel)
     // taps per pipeline step: measured (tools/convpos_bench.py) 1 is best at every size once the groups are dealt to XCDs
     // (batch 1: 19.8 / 21.1 / 21.3 us for 1 / 2 / 4; batch 32: 304 / 355 / 629 us); 2 and 4 stay selectable for experiments
     int tps = f5_convpos_tps;
     if (tps == 0) tps = 1;
     F5ConvPosArgs ab = a;
     if (ab.sat_flag == nullptr) ab.sat_flag = f5_sat_flag_host;
+    int reached;
     if (a.nseg == 3) {
         F5_REQUIRE(a.in[1] && a.W[1], "convpos: bf16x3 needs lo operands");
+        // the three-pass kernel is built for 1 and 2 taps per step only: a selector of 4 runs <true, 2>
         if (tps > 1) hipLaunchKernelGGL((f5_convpos_kernel<true, 2>), grid, dim3(256), 0, stream, ab);
         else hipLaunchKernelGGL((f5_convpos_kernel<true, 1>), grid, dim3(256), 0, stream, ab);
+        reached = tps > 1 ? F5CP_HP2 : F5CP_HP1;
     } else if (tps >= 4) {
         hipLaunchKernelGGL((f5_convpos_kernel<false, 4>), grid, dim3(256), 0, stream, ab);
+        reached = F5CP_4;
     } else if (tps >= 2) {
         hipLaunchKernelGGL((f5_convpos_kernel<false, 2>), grid, dim3(256), 0, stream, ab);
+        reached = F5CP_2;
     } else {
         hipLaunchKernelGGL((f5_convpos_kernel<false, 1>), grid, dim3(256), 0, stream, ab);
+        reached = F5CP_1;
     }
     F5_LAUNCH_CHECK();
+    f5dbg::last_convpos_kernel = reached | (xcd ? F5CP_XCD : 0);
     return 0;
 }
 }  // namespace F5_NS

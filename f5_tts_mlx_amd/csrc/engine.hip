@@ -1479,6 +1479,7 @@ extern "C" int f5_debug_set_gemm_flags(int v) {
 namespace f5dbg {
 int last_gemm_kernel = 0;
 int last_attn_kernel = 0;
+int last_convpos_kernel = 0;
 }
 static int copy_name(const std::string& s, char* buf, int n) {
     if (buf != nullptr && n > 0) {
@@ -1500,6 +1501,16 @@ extern "C" int f5_debug_last_attn_kernel(char* buf, int n) {
     const int k = f5dbg::last_attn_kernel & (F5A_OUT8 - 1);
     std::string s = k <= F5A_V2S_KS4 ? names[k] : "";
     if (k != F5A_NONE && (f5dbg::last_attn_kernel & F5A_OUT8)) s += "+f8";
+    return copy_name(s, buf, n);
+}
+// name of the instantiation the most recent f5_launch_convpos of the process launched, "+xcd" appended when the 1-D block numbering
+// ran ("" = it refused the launch); returns its length
+extern "C" int f5_debug_last_convpos_kernel(char* buf, int n) {
+    static const char* const names[] = {"", "f5_convpos_kernel<false,1>", "f5_convpos_kernel<false,2>", "f5_convpos_kernel<false,4>",
+                                        "f5_convpos_kernel<true,1>", "f5_convpos_kernel<true,2>"};
+    const int k = f5dbg::last_convpos_kernel & (F5CP_XCD - 1);
+    std::string s = k <= F5CP_HP2 ? names[k] : "";
+    if (k != F5CP_NONE && (f5dbg::last_convpos_kernel & F5CP_XCD)) s += "+xcd";
     return copy_name(s, buf, n);
 }
 // The route (gemm_route.hpp) a GEMM launch of this shape would take under the current knobs and process-wide flags, without launching

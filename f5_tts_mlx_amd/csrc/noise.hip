@@ -99,6 +99,21 @@ __global__ __launch_bounds__(256) void noise_normal_kernel(const uint32_t* __res
     for (long q = i; q < npad; q += (long)gridDim.x * 256) yb[(size_t)dur * mel + q] = 0.0f;
 }
 
+// test entry point: the float path alone, on bit patterns the caller chooses (threefry reaches the clamped tails of the uniform
+// mapping about once in 3e7 values)
+__global__ __launch_bounds__(256) void noise_from_bits_kernel(const uint32_t* __restrict__ bits, size_t n, float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = f5_bits_to_normal(bits[i]);
+}
+extern "C" int f5_op_noise_from_bits(const uint32_t* bits_dev, size_t n, float* out, void* stream) {
+    F5_REQUIRE(bits_dev && out, "noise_from_bits: null pointer");
+    F5_REQUIRE(n <= (size_t)0x7fffffff * 256, "noise_from_bits: %zu values exceed the grid", n);
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(noise_from_bits_kernel, dim3((unsigned)f5_cdiv((long)n, 256)), dim3(256), 0, (hipStream_t)stream, bits_dev, n, out);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+
 // seeds: one 64-bit seed per batch element (the reference re-seeds with the SAME seed for every element, cfm.py:371-373: pass it
 // B times); durations: host ints; y0: device [B][N][mel].  Kernel-only (host scalars travel as launch arguments through a small
 // staging kernel), safe inside a stream capture.

@@ -97,6 +97,8 @@ def load_library() -> C.CDLL:
     lib.f5_debug_f2bf_bits.argtypes = [C.c_float]
     lib.f5_debug_h_bits2f.restype = C.c_float
     lib.f5_debug_h_bits2f.argtypes = [C.c_uint16]
+    lib.f5_debug_last_convpos_kernel.argtypes = [C.c_char_p, C.c_int]
+    lib.f5_op_noise_from_bits.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 

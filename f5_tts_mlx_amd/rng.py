@@ -57,8 +57,14 @@ def mlx_like_normal(seed: int, shape) -> np.ndarray:
     key = (np.uint32(seed >> 32), np.uint32(seed & 0xFFFFFFFF))
     _, sub = _split(key)
     n = int(np.prod(shape))
-    u = _bits(sub, n).astype(np.float32) / np.float32(0xFFFFFFFF)
+    return bits_to_normal(_bits(sub, n)).reshape(shape)
+
+
+def bits_to_normal(bits: np.ndarray) -> np.ndarray:
+    """uint32 random bits -> float32 normal values: the uniform mapping in float32 steps, sqrt(2) * erfinv in float64, one final
+    rounding (csrc/noise.hip f5_bits_to_normal is the device twin)."""
+    u = np.asarray(bits, dtype=np.uint32).astype(np.float32) / np.float32(0xFFFFFFFF)
     lo = np.nextafter(np.float32(-1.0), np.float32(0.0))
     u = np.minimum(u, np.nextafter(np.float32(1.0), np.float32(0.0)))
     u = (np.float32(1.0) - lo) * u + lo
-    return (np.float32(np.sqrt(2.0)) * erfinv(u.astype(np.float64))).astype(np.float32).reshape(shape)
+    return (np.float32(np.sqrt(2.0)) * erfinv(u.astype(np.float64))).astype(np.float32)

@@ -259,6 +259,9 @@ int f5_op_zero_vt_pad(void* vt, size_t rows, int seq_len, int npad, void* stream
  * seeds: one per element (the reference uses the same seed for all); durations: host; scratch_words: >= 3 * B device words. */
 int f5_noise_normal(const uint64_t* seeds, int B, const int32_t* durations, int N, int mel, float* y0, void* scratch_words,
                     void* stream);
+/* the float path of f5_noise_normal alone, for the tests: out[i] = the normal value the generator maps the 32 random bits
+ * bits_dev[i] to (f5_tts_mlx_amd/rng.py bits_to_normal), n values, both pointers on the device */
+int f5_op_noise_from_bits(const uint32_t* bits_dev, size_t n, float* out, void* stream);
 
 /* x += gate[col] * ((A W^T + bias) * keep[row])  (dit.py:319,323; also Vocos' layer-scale + residual) */
 int f5_op_gemm_resid_gate(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias,
@@ -308,6 +311,11 @@ int f5_debug_last_gemm_kernel(char* buf, int n);
  * <false,0>, f5_attn2f_kernel<true> / <false>, f5_attn2p_kernel, f5_attn2s_kernel<true,2,2> / <false,2,3,true> / <false,4,2,true> --
  * with "+f8" appended when the launch carried the MX-fp8 output; "" after a launch that was refused.  Host side only. */
 int f5_debug_last_attn_kernel(char* buf, int n);
+/* the same for the conv-pos kernel: the instantiation the most recent conv-pos launch of the process resolved to --
+ * f5_convpos_kernel<false,1> / <false,2> / <false,4> / <true,1> / <true,2> -- with "+xcd" appended when the 1-D "groups dealt to XCDs"
+ * block numbering ran; "" after a launch that was refused.  Host side only: nothing reaches a kernel.  The operand type is
+ * f5_op_get_operand_type's. */
+int f5_debug_last_convpos_kernel(char* buf, int n);
 /* which kernel WOULD it run?  The same routing function the launcher switches over (csrc/gemm_route.hpp), asked for a launch of this
  * epilogue and shape under the current selectors (f5_debug_set_gemm_tile / _ring / _qkv_tile) and process-wide flags; nothing is
  * launched and no device is touched.  variant_bits: 1 = group-major rotation tables set (transposed q / k tiles), 2 = fused LN tail,
@@ -335,7 +343,10 @@ int f5_debug_set_gemm_order(int v);
 int f5_debug_set_gemm_ring(int v);
 int f5_debug_set_gemm_qkv_tile(int sel);    /* small-M QKV projection with pair-major tables: 0 = auto (role-split 128x256 tiles when one round of >= 176), 1 = small tiles, 12 / 13 = lock-step 8-wave 128x256 ring, 14 = role-split whenever one round */
 int f5_debug_set_gemm_nband(int n);         /* 256x256 GEMM: tiles numbered in bands of n column tiles (0 = n fastest) */
-int f5_debug_set_convpos_tps(int taps);     /* conv-pos kernel: weight slabs per pipeline step, 0 = auto (4 for small grids), 1 / 2 / 4 */
+/* conv-pos kernel: weight slabs per pipeline step, 0 = auto (1 at every size), 1 / 2 / 4.  The one-pass kernel (nseg 1) is built for
+ * all three; the three-pass kernel (nseg 3) for 1 and 2 only: with nseg == 3 a selector of 2 or 4 runs f5_convpos_kernel<true,2>
+ * (f5_debug_last_convpos_kernel says which instantiation a launch ran) */
+int f5_debug_set_convpos_tps(int taps);
 int f5_debug_set_convpos_xcd_map(int on);   /* conv-pos kernel: 1 (default) = groups dealt to XCDs, 0 = plain 3-D block numbering */
 /* 256-query attention workgroups with two query blocks per wave (one-pass modes, large grids): -1 auto, 0 off, 1 force */
 int f5_debug_set_attn_wide(int v);

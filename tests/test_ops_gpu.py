@@ -279,7 +279,9 @@ def test_attention_softmax_spike(lib, hp=1, premul=False, N=300, spikes=((70, 30
 @pytest.mark.parametrize("tps", [0, 1, 2, 4])
 def test_convpos(lib, B, N, C, taps, nseg, tps):
     """tps: weight slabs (taps) per pipeline step of the kernel -- 0 = the launcher's choice, 1 / 2 / 4 forced (31 and 5 taps are
-    not multiples of 2 or 4: the last step is partial)"""
+    not multiples of 2 or 4: the last step is partial).  With nseg == 3 the launcher maps a selector of 2 or 4 to
+    f5_convpos_kernel<true,2> (there is no <true,4>): the tps=4, nseg=3 items run the same kernel as tps=2;
+    tests/test_convaudio_matrix_gpu.py asserts the mapping through f5_debug_last_convpos_kernel."""
     E.check(lib.f5_debug_set_convpos_tps(tps))
     try:
         _convpos_case(lib, B, N, C, taps, nseg)

@@ -1,8 +1,11 @@
 // Largest ULP error of the device math functions the row kernels call (csrc/rowops.hip: rsqrtf, expf, log1pf, sinf, cosf, powf, plus
-// sqrtf and SiLU) and of the exp2 instruction behind csrc/attention.hip's softmax (__builtin_amdgcn_exp2f), against fp64 on the host,
-// over 2^21 arguments per function in the ranges those kernels produce plus the exact grids of the time / rotation / position tables.
-// tests/rowops_matrix.py and tests/attention_matrix.py grant four times the figures this prints (their docstrings have the tables):
-// re-run after a ROCm update and refresh both.  hipcc --offload-arch=gfx950 -O3 math_ulp.hip -o bin/math_ulp
+// sqrtf and SiLU), of the exp2 instruction behind csrc/attention.hip's softmax and f5_mish (__builtin_amdgcn_exp2f), and of what the
+// audio and conv-pos kernels add to those (csrc/audio.hip: sincosf on the FFT twiddle grid and on ISTFT phases, logf; common.hpp
+// f5_mish: __builtin_amdgcn_rcpf), against fp64 on the host, over 2^21 arguments per function in the ranges those kernels produce plus
+// the exact grids of the time / rotation / position / twiddle tables.  abs_u is the largest absolute error in units of 2^-24 (what a
+// sine or cosine near one of its zeros is judged by).
+// tests/rowops_matrix.py, tests/attention_matrix.py and tests/convaudio_matrix.py grant four times the figures this prints (their
+// docstrings have the tables): re-run after a ROCm update and refresh all three.  hipcc --offload-arch=gfx950 -O3 math_ulp.hip -o bin/math_ulp
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -22,6 +25,10 @@ __global__ void k(const float* x, float* y, int n, int fn) {
         case 6: r = 1.0f / powf(10000.0f, v); break;
         case 7: r = sqrtf(v); break;
         case 9: r = __builtin_amdgcn_exp2f(v); break;
+        case 10: case 12: { float c; sincosf(v, &r, &c); break; }
+        case 11: case 13: { float sn; sincosf(v, &sn, &r); break; }
+        case 14: r = logf(v); break;
+        case 15: r = __builtin_amdgcn_rcpf(v); break;
         default: r = v / (1.0f + expf(-v)); break;
     }
     y[i] = r;
@@ -37,16 +44,21 @@ static double ref(int fn, double v) {
         case 6: return 1.0 / std::pow(10000.0, v);
         case 7: return std::sqrt(v);
         case 9: return std::exp2(v);
+        case 10: case 12: return std::sin(v);
+        case 11: case 13: return std::cos(v);
+        case 14: return std::log(v);
+        case 15: return 1.0 / v;
         default: return v / (1.0 + std::exp(-v));
     }
 }
 int main() {
-    const char* names[] = {"rsqrtf", "expf", "log1pf", "sinf", "cosf", "powf(1e4,x)", "1/powf(1e4,x)", "sqrtf", "silu", "amdgcn_exp2f"};
+    const char* names[] = {"rsqrtf", "expf", "log1pf", "sinf", "cosf", "powf(1e4,x)", "1/powf(1e4,x)", "sqrtf", "silu", "amdgcn_exp2f",
+                           "sincosf.sin twid", "sincosf.cos twid", "sincosf.sin ph", "sincosf.cos ph", "logf", "amdgcn_rcpf"};
     std::mt19937_64 g(1);
     const int n = 1 << 21;
     float *dx, *dy;
     if (hipMalloc(&dx, n * 4) != hipSuccess || hipMalloc(&dy, n * 4) != hipSuccess) return 2;
-    for (int fn = 0; fn < 10; ++fn) {
+    for (int fn = 0; fn < 16; ++fn) {
         std::vector<float> x(n), y(n);
         std::uniform_real_distribution<double> u(0.0, 1.0);
         for (int i = 0; i < n; ++i) {
@@ -58,6 +70,10 @@ int main() {
                 case 3: case 4: x[i] = (float)(4096.0 * t); break;                   // angles of the tables
                 case 5: case 6: x[i] = (float)t; break;                              // 2 j / dim
                 case 9: x[i] = (float)(-60.0 + 75.0 * t); break;                    // scores against the reference point, exp2 units: <= 14 on the fast paths
+                case 10: case 11: { int j = i & 511; float a = 6.2831853f * (float)j / 1024.0f; x[i] = (i & 512) ? -a : a; break; }   // the twiddle grid of the 1024-point FFTs, both directions, and nothing else
+                case 12: case 13: x[i] = (float)(-100.0 + 200.0 * t); break;        // ISTFT phases
+                case 14: x[i] = (float)std::pow(10.0, -5.0 + 19.0 * t); break;      // filterbank sums behind the 1e-5 floor, up to 1e14 (the matrix feeds 1e10 samples)
+                case 15: x[i] = (float)(2.0 * std::pow(10.0, 30.0 * t)); break;      // w (w + 2) + 2 of f5_mish, w = exp(min(x, 30))
                 default: x[i] = (float)(-20.0 + 40.0 * t); break;
             }
         }
@@ -80,7 +96,7 @@ int main() {
             if (err > worst) { worst = err; wx = x[i]; }
             worst_abs = std::fmax(worst_abs, std::fabs((double)y[i] - r));
         }
-        printf("%-14s max_ulp %.3f at x=%.9g  max_abs %.3e\n", names[fn], worst, wx, worst_abs);
+        printf("%-16s max_ulp %.3f at x=%.9g  max_abs %.3e  abs_u %.3f\n", names[fn], worst, wx, worst_abs, worst_abs * 16777216.0);
     }
     return 0;
 }
