@@ -11,7 +11,6 @@
 #include <stdarg.h>
 
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/f5tts_hip.h"
@@ -25,20 +24,6 @@ struct DBlock {
     MatBF qkv, o, ff1, ff2;
     size_t bqkv, bo, bff1, bff2;
 };
-struct DGraph {
-    int B, n_in, nt;
-    const void* workspace;
-    hipGraphExec_t exec;
-    uint64_t stamp;
-    hipEvent_t done;         // recorded after every launch: an exec is only destroyed once its last replay has finished
-};
-static void destroy_dgraph(DGraph& g) {
-    if (g.done) {
-        (void)hipEventSynchronize(g.done);
-        (void)hipEventDestroy(g.done);
-    }
-    (void)hipGraphExecDestroy(g.exec);
-}
 struct DWorkspace {
     size_t total = 0;
     size_t status;           // THE FIRST WORD OF THE WORKSPACE: F5_STATUS_* of the last call, zeroed by every call
@@ -47,44 +32,16 @@ struct DWorkspace {
     size_t tln[2], tg2[2], a0[2], xb[2], c1[2], h[2], qk[2], vt[2], ao[2], ffh[2];
 };
 
-struct f5_duration {
+struct f5_duration : WeightStore {
     f5_duration_config cfg;
-    int np = 1;
     Ops ops;
-    char* arena = nullptr;
-    size_t arena_need = 0, arena_bytes = 0;
-    bool finalized = false;
-    std::unordered_map<std::string, std::vector<TensorDst>> tmap;
     size_t table, pos, bproj, norm_out, to_pred, zeros, ones;
     std::vector<DTextBlock> tblocks;
     MatBF proj, conv_w[2];
     size_t conv_b[2];
     std::vector<DBlock> blocks;
-    std::vector<DGraph> graphs;
-    uint64_t clock = 0;
+    GraphCache graphs;       // at most 8; keyed by (B, n_in, nt).  The caller keeps one workspace per shape: nothing is purged
 };
-
-static void dadd_f32(f5_duration* d, const std::string& name, size_t off, std::vector<int64_t> shape) {
-    TensorDst t;
-    t.kind = 0;
-    t.off = off;
-    t.shape = shape;
-    d->tmap[name].push_back(t);
-}
-static void dadd_mat(f5_duration* d, const std::string& name, const MatBF& m, int row0, int src_rows, int src_cols, int c0, int c1,
-                     int dst_c0, std::vector<int64_t> shape) {
-    TensorDst t;
-    t.kind = 1;
-    t.mat = m;
-    t.row0 = row0;
-    t.src_rows = src_rows;
-    t.src_cols = src_cols;
-    t.c0 = c0;
-    t.c1 = c1;
-    t.dst_c0 = dst_c0;
-    t.shape = shape;
-    d->tmap[name].push_back(t);
-}
 
 extern "C" int f5_duration_create(const f5_duration_config* cfg, int precision, f5_duration** out) {
     F5_REQUIRE(cfg && out, "f5_duration_create: null argument");
@@ -109,14 +66,16 @@ extern "C" int f5_duration_create(const f5_duration_config* cfg, int precision, 
     F5_REQUIRE(c.text_max_pos >= 4, "duration predictor: text_max_pos must be >= 4 (got %d)", c.text_max_pos);
     f5_duration* d = new f5_duration();
     d->cfg = c;
+    d->label = "duration predictor ";
     d->np = precision == F5_PREC_BF16X3 ? 2 : 1;
-    d->ops.h = precision == F5_PREC_F16;
+    d->f16 = d->ops.h = precision == F5_PREC_F16;
+    d->graphs.purge = false;
     const int D = c.dim, Dt = c.text_dim, TF = 2 * c.text_dim, FF = c.ff_dim, M = c.mel_dim, np = d->np;
     const std::string p = "transformer.";
     Bump b;
     d->table = b.take((size_t)(c.text_num_embeds + 1) * Dt * 4);
     d->pos = b.take((size_t)c.text_max_pos * Dt * 4);
-    dadd_f32(d, p + "text_embed.text_embed.weight", d->table, {c.text_num_embeds + 1, Dt});
+    d->add_f32(p + "text_embed.text_embed.weight", d->table, {c.text_num_embeds + 1, Dt});
     d->tblocks.resize(c.conv_layers);
     for (int i = 0; i < c.conv_layers; ++i) {
         DTextBlock& t = d->tblocks[i];
@@ -131,23 +90,23 @@ extern "C" int f5_duration_create(const f5_duration_config* cfg, int precision, 
         t.b2 = b.take((size_t)Dt * 4);
         t.pw1 = alloc_mat(b, TF, Dt, np);
         t.pw2 = alloc_mat(b, Dt, TF, np);
-        dadd_f32(d, q + "dwconv.weight", t.dw_w, {Dt, 7, 1});       // (dim, 7, 1) = the bytes of [dim][7]
-        dadd_f32(d, q + "dwconv.bias", t.dw_b, {Dt});
-        dadd_f32(d, q + "norm.weight", t.ln_w, {Dt});
-        dadd_f32(d, q + "norm.bias", t.ln_b, {Dt});
-        dadd_mat(d, q + "pwconv1.weight", t.pw1, 0, TF, Dt, 0, Dt, 0, {TF, Dt});
-        dadd_f32(d, q + "pwconv1.bias", t.b1, {TF});
-        dadd_f32(d, q + "grn.gamma", t.gamma, {1, 1, TF});
-        dadd_f32(d, q + "grn.beta", t.beta, {1, 1, TF});
-        dadd_mat(d, q + "pwconv2.weight", t.pw2, 0, Dt, TF, 0, TF, 0, {Dt, TF});
-        dadd_f32(d, q + "pwconv2.bias", t.b2, {Dt});
+        d->add_f32(q + "dwconv.weight", t.dw_w, {Dt, 7, 1});       // (dim, 7, 1) = the bytes of [dim][7]
+        d->add_f32(q + "dwconv.bias", t.dw_b, {Dt});
+        d->add_f32(q + "norm.weight", t.ln_w, {Dt});
+        d->add_f32(q + "norm.bias", t.ln_b, {Dt});
+        d->add_mat(q + "pwconv1.weight", t.pw1, 0, TF, Dt, 0, Dt, 0, {TF, Dt});
+        d->add_f32(q + "pwconv1.bias", t.b1, {TF});
+        d->add_f32(q + "grn.gamma", t.gamma, {1, 1, TF});
+        d->add_f32(q + "grn.beta", t.beta, {1, 1, TF});
+        d->add_mat(q + "pwconv2.weight", t.pw2, 0, Dt, TF, 0, TF, 0, {Dt, TF});
+        d->add_f32(q + "pwconv2.bias", t.b2, {Dt});
     }
     // input projection: reference input order (x | text) (duration.py:44-58) -> operand columns [x padded to 128 | text]
     d->proj = alloc_mat(b, D, 128 + Dt, np);
     d->bproj = b.take((size_t)D * 4);
-    dadd_mat(d, p + "input_embed.proj.weight", d->proj, 0, D, M + Dt, 0, M, 0, {D, M + Dt});
-    dadd_mat(d, p + "input_embed.proj.weight", d->proj, 0, D, M + Dt, M, M + Dt, 128, {D, M + Dt});
-    dadd_f32(d, p + "input_embed.proj.bias", d->bproj, {D});
+    d->add_mat(p + "input_embed.proj.weight", d->proj, 0, D, M + Dt, 0, M, 0, {D, M + Dt});
+    d->add_mat(p + "input_embed.proj.weight", d->proj, 0, D, M + Dt, M, M + Dt, 128, {D, M + Dt});
+    d->add_f32(p + "input_embed.proj.bias", d->bproj, {D});
     // conv position embedding: the kernel works on 64-channel groups; 32-channel groups are loaded as block-diagonal 64-wide super
     // groups (f5_duration_load_tensor)
     const int kc = c.conv_pos_kernel, gin = D / c.conv_pos_groups;
@@ -155,8 +114,8 @@ extern "C" int f5_duration_create(const f5_duration_config* cfg, int precision, 
         d->conv_w[j] = alloc_mat(b, D, kc * 64, np);
         d->conv_b[j] = b.take((size_t)D * 4);
         const std::string q = p + "input_embed.conv_pos_embed.conv1d.layers." + std::to_string(j * 2) + ".";
-        dadd_mat(d, q + "weight", d->conv_w[j], 0, D, kc * 64, 0, kc * 64, 0, {D, kc, gin});
-        dadd_f32(d, q + "bias", d->conv_b[j], {D});
+        d->add_mat(q + "weight", d->conv_w[j], 0, D, kc * 64, 0, kc * 64, 0, {D, kc, gin});
+        d->add_f32(q + "bias", d->conv_b[j], {D});
     }
     d->blocks.resize(c.depth);
     for (int i = 0; i < c.depth; ++i) {
@@ -172,20 +131,20 @@ extern "C" int f5_duration_create(const f5_duration_config* cfg, int precision, 
         w.bff2 = b.take((size_t)D * 4);
         const char* nm[3] = {"to_q", "to_k", "to_v"};
         for (int k = 0; k < 3; ++k) {
-            dadd_mat(d, q + "attn." + nm[k] + ".weight", w.qkv, k * D, D, D, 0, D, 0, {D, D});
-            dadd_f32(d, q + "attn." + nm[k] + ".bias", w.bqkv + (size_t)k * D * 4, {D});
+            d->add_mat(q + "attn." + nm[k] + ".weight", w.qkv, k * D, D, D, 0, D, 0, {D, D});
+            d->add_f32(q + "attn." + nm[k] + ".bias", w.bqkv + (size_t)k * D * 4, {D});
         }
-        dadd_mat(d, q + "attn.to_out.layers.0.weight", w.o, 0, D, D, 0, D, 0, {D, D});
-        dadd_f32(d, q + "attn.to_out.layers.0.bias", w.bo, {D});
-        dadd_mat(d, q + "ff.ff.layers.0.layers.0.weight", w.ff1, 0, FF, D, 0, D, 0, {FF, D});
-        dadd_f32(d, q + "ff.ff.layers.0.layers.0.bias", w.bff1, {FF});
-        dadd_mat(d, q + "ff.ff.layers.2.weight", w.ff2, 0, D, FF, 0, FF, 0, {D, FF});
-        dadd_f32(d, q + "ff.ff.layers.2.bias", w.bff2, {D});
+        d->add_mat(q + "attn.to_out.layers.0.weight", w.o, 0, D, D, 0, D, 0, {D, D});
+        d->add_f32(q + "attn.to_out.layers.0.bias", w.bo, {D});
+        d->add_mat(q + "ff.ff.layers.0.layers.0.weight", w.ff1, 0, FF, D, 0, D, 0, {FF, D});
+        d->add_f32(q + "ff.ff.layers.0.layers.0.bias", w.bff1, {FF});
+        d->add_mat(q + "ff.ff.layers.2.weight", w.ff2, 0, D, FF, 0, FF, 0, {D, FF});
+        d->add_f32(q + "ff.ff.layers.2.bias", w.bff2, {D});
     }
     d->norm_out = b.take((size_t)D * 4);
     d->to_pred = b.take((size_t)D * 4);
-    dadd_f32(d, p + "norm_out.weight", d->norm_out, {D});
-    dadd_f32(d, "to_pred.layers.0.weight", d->to_pred, {1, D});
+    d->add_f32(p + "norm_out.weight", d->norm_out, {D});
+    d->add_f32("to_pred.layers.0.weight", d->to_pred, {1, D});
     d->zeros = b.take((size_t)D * 4);      // scale = shift = 0: ln_modulate is the plain LayerNorm of duration.py:86,91
     d->ones = b.take((size_t)D * 4);       // gate = 1: the gated-residual epilogue is `x = x + y`
     d->arena_need = b.off;
@@ -194,9 +153,7 @@ extern "C" int f5_duration_create(const f5_duration_config* cfg, int precision, 
 }
 
 extern "C" void f5_duration_destroy(f5_duration* d) {
-    if (!d) return;
-    for (auto& g : d->graphs) destroy_dgraph(g);
-    delete d;
+    delete d;      // (~GraphCache waits for the last replay of every exec)
 }
 
 extern "C" int f5_duration_weights_bytes(f5_duration* d, size_t* bytes) {
@@ -207,13 +164,7 @@ extern "C" int f5_duration_weights_bytes(f5_duration* d, size_t* bytes) {
 
 extern "C" int f5_duration_set_weights_arena(f5_duration* d, void* dev_arena, size_t bytes, void* stream) {
     F5_REQUIRE(d && dev_arena, "null argument");
-    F5_REQUIRE(bytes >= d->arena_need, "duration predictor weights arena too small: %zu < %zu", bytes, d->arena_need);
-    F5_REQUIRE(((uintptr_t)dev_arena & 255) == 0, "duration predictor weights arena must be 256-byte aligned");
-    d->arena = (char*)dev_arena;
-    d->arena_bytes = bytes;
-    F5_HIP_CHECK(hipMemsetAsync(dev_arena, 0, d->arena_need, (hipStream_t)stream));   // zero pads, the zero vector
-    F5_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    return 0;
+    return d->set_arena(dev_arena, bytes, (hipStream_t)stream);   // zero pads, the zero vector
 }
 
 // Tensor names are the reference's (the keys of duration_param_specs in f5_tts_mlx_amd/duration.py: "transformer.text_embed...",
@@ -224,21 +175,13 @@ extern "C" int f5_duration_load_tensor(f5_duration* d, const char* name, const f
     std::string key(name);
     const std::string prefix = "duration_predictor.";
     if (key.compare(0, prefix.size(), prefix) == 0) key = key.substr(prefix.size());
-    auto it = d->tmap.find(key);
-    F5_REQUIRE(it != d->tmap.end(), "unknown duration predictor tensor name '%s'", name);
-    size_t count = 1;
-    for (TensorDst& t : it->second) {
-        F5_REQUIRE((int)t.shape.size() == ndim, "tensor '%s': expected %zu dims, got %d", name, t.shape.size(), ndim);
-        count = 1;
-        for (int i = 0; i < ndim; ++i) {
-            F5_REQUIRE(t.shape[i] == shape[i], "tensor '%s': dim %d is %lld, expected %lld", name, i, (long long)shape[i],
-                       (long long)t.shape[i]);
-            count *= (size_t)shape[i];
-        }
-    }
+    std::vector<TensorDst>* dsts = nullptr;
+    size_t count = 0;
+    RC(d->lookup(key, name, &dsts));
+    RC(d->match(name, *dsts, ndim, shape, &count));
     F5_REQUIRE(d->arena, "f5_duration_set_weights_arena must be called first");
     const int D = d->cfg.dim, kc = d->cfg.conv_pos_kernel;
-    for (TensorDst& t : it->second) {
+    for (TensorDst& t : *dsts) {
         if (t.kind == 1 && t.shape.size() == 3 && t.shape[2] == 32) {
             // conv-pos weight (dim, k, 32): output channel o reads the 32 input channels of ITS group; two groups share one 64-channel
             // super group of the kernel, so o's taps go to the half of the 64 columns that holds its group, the other half stays zero
@@ -248,26 +191,23 @@ extern "C" int f5_duration_load_tensor(f5_duration* d, const char* name, const f
                 for (int k = 0; k < kc; ++k)
                     memcpy(&m[((size_t)o * kc + k) * 64 + off], host + ((size_t)o * kc + k) * 32, 32 * sizeof(float));
             }
-            RC(f5_upload_tensor(d->arena, t, m.data(), m.size(), d->np, d->ops.h));
+            RC(d->upload(t, m.data(), m.size()));
         } else {
-            RC(f5_upload_tensor(d->arena, t, host, count, d->np, d->ops.h));
+            RC(d->upload(t, host, count));
         }
-        t.loaded = true;
     }
     return 0;
 }
 
 extern "C" int f5_duration_mark_weights_loaded(f5_duration* d) {
     F5_REQUIRE(d, "null argument");
-    for (auto& kv : d->tmap)
-        for (auto& t : kv.second) t.loaded = true;
+    d->mark_all_loaded();
     return 0;
 }
 
 extern "C" int f5_duration_finalize(f5_duration* d, void* stream) {
     F5_REQUIRE(d && d->arena, "duration predictor arena not set");
-    for (auto& kv : d->tmap)
-        for (auto& t : kv.second) F5_REQUIRE(t.loaded, "duration predictor tensor '%s' was never loaded", kv.first.c_str());
+    RC(d->require_loaded());
     RC(f5_launch_text_pos_table((float*)(d->arena + d->pos), d->cfg.text_max_pos, d->cfg.text_dim, (hipStream_t)stream));
     const std::vector<float> one((size_t)d->cfg.dim, 1.0f), zero((size_t)d->cfg.dim, 0.0f);
     F5_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
@@ -332,65 +272,36 @@ extern "C" int f5_duration_workspace_bytes(f5_duration* d, int B, int n_in, int 
     return 0;
 }
 
-// fp16 handles: the 16-bit packers of the launches issued inside this scope report a clamp into the call's status word (the pointer
-// travels as a kernel argument; a captured graph keeps the word of the workspace it was captured against, part of the graph key)
-struct DSatScope {
-    int* saved;
-    DSatScope(const f5_duration* d, int* status_word) : saved(f5hf::f5_sat_flag_host) {
-        if (d->ops.h) f5hf::f5_sat_flag_host = status_word;
-    }
-    ~DSatScope() { f5hf::f5_sat_flag_host = saved; }
-};
-
 // the launch sequence of DurationPredictor._run_ops (f5_tts_mlx_amd/duration.py), everything on the workspace and the arena
 static int duration_body(const f5_duration* d, const DWorkspace& w, char* ws, int B, int N, int nt, hipStream_t s) {
     const f5_duration_config& c = d->cfg;
     const Ops& K = d->ops;
     const int D = c.dim, Dt = c.text_dim, TF = 2 * c.text_dim, FF = c.ff_dim, H = c.heads, K0 = 128 + c.text_dim;
-    const int rows = B * N, npad = (N + 63) / 64 * 64, nseg = d->np == 2 ? 3 : 1;
-    DSatScope sat(d, reinterpret_cast<int*>(ws + w.status));
-    auto P = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    auto PB = [&](const size_t (&offs)[2], int part) { return part < d->np ? reinterpret_cast<op16_t*>(ws + offs[part]) : (op16_t*)nullptr; };
-    auto A = [&](size_t off) { return reinterpret_cast<const float*>(d->arena + off); };
-    auto WM = [&](const MatBF& m, int part) {
-        return part == 0 ? reinterpret_cast<const op16_t*>(d->arena + m.hi) : (d->np == 2 ? reinterpret_cast<const op16_t*>(d->arena + m.lo) : nullptr);
-    };
-    auto gemm = [&](const op16_t* ah, const op16_t* al, int lda, const MatBF& wm, int Nn, int Kk, const float* bias) {
-        F5GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.A[0] = ah;
-        g.A[1] = al;
-        g.W[0] = WM(wm, 0);
-        g.W[1] = WM(wm, 1);
-        g.lda = lda;
-        g.ldw = wm.ld;
-        g.M = rows;
-        g.N = Nn;
-        g.K = Kk;
-        g.nseg = nseg;
-        g.bias = bias;
-        return g;
-    };
+    const int rows = B * N, npad = (N + 63) / 64 * 64;
+    const LaunchView L{d->arena, ws, d->np, d->ops};
+    const int nseg = L.nseg();
+    // fp16 handles: the 16-bit packers of the launches issued inside this scope report a clamp into the call's status word
+    SatScope sat(d->ops.h, L.p<int>(w.status));
     uint8_t* mask = reinterpret_cast<uint8_t*>(ws + w.mask);
     const uint32_t zero_word = 0;
     RC(f5_launch_stage_words(&zero_word, 1, reinterpret_cast<uint32_t*>(ws + w.status), s));      // status = 0, a kernel like the rest
     RC(K.rowkeep(reinterpret_cast<const int*>(ws + w.lens), mask, B, N, s));                     // mask = n < lens[b]
 
     // ---- text path, no padding mask (duration.py:116-118)
-    RC(K.text_embed(reinterpret_cast<const int*>(ws + w.text), nt, A(d->table), A(d->pos), c.text_max_pos, P(w.te),
+    RC(K.text_embed(reinterpret_cast<const int*>(ws + w.text), nt, L.a<float>(d->table), L.a<float>(d->pos), c.text_max_pos, L.p<float>(w.te),
                     reinterpret_cast<int*>(ws + w.ids), reinterpret_cast<uint8_t*>(ws + w.keep), B, N, Dt, 0, s));
-    float* t_cur = P(w.te);            // branch 0
-    float* t_nxt = P(w.t_nxt);
-    float* scratch = P(w.scratch);
+    float* t_cur = L.p<float>(w.te);            // branch 0
+    float* t_nxt = L.p<float>(w.t_nxt);
+    float* scratch = L.p<float>(w.scratch);
     for (const DTextBlock& k : d->tblocks) {
-        RC(K.dwconv_ln(t_cur, A(k.dw_w), A(k.dw_b), A(k.ln_w), A(k.ln_b), PB(w.tln, 0), PB(w.tln, 1), B, N, Dt, 1e-6f, s));
-        F5GemmArgs g1 = gemm(PB(w.tln, 0), PB(w.tln, 1), Dt, k.pw1, TF, Dt, A(k.b1));
-        g1.out_f32 = P(w.tg);
+        RC(K.dwconv_ln(t_cur, L.a<float>(k.dw_w), L.a<float>(k.dw_b), L.a<float>(k.ln_w), L.a<float>(k.ln_b), L.pb(w.tln, 0), L.pb(w.tln, 1), B, N, Dt, 1e-6f, s));
+        F5GemmArgs g1 = L.gemm(L.pb(w.tln, 0), L.pb(w.tln, 1), Dt, k.pw1, rows, TF, Dt, L.a<float>(k.b1));
+        g1.out_f32 = L.p<float>(w.tg);
         g1.ldo = TF;
         g1.ldob = TF;
         RC(K.gemm(g1, EPI_GELU_ERF, s));
-        RC(K.grn(P(w.tg), A(k.gamma), A(k.beta), scratch, scratch + f5_grn_partial_floats(B, N, TF), PB(w.tg2, 0), PB(w.tg2, 1), B, N, TF, s));
-        F5GemmArgs g2 = gemm(PB(w.tg2, 0), PB(w.tg2, 1), TF, k.pw2, Dt, TF, A(k.b2));
+        RC(K.grn(L.p<float>(w.tg), L.a<float>(k.gamma), L.a<float>(k.beta), scratch, scratch + f5_grn_partial_floats(B, N, TF), L.pb(w.tg2, 0), L.pb(w.tg2, 1), B, N, TF, s));
+        F5GemmArgs g2 = L.gemm(L.pb(w.tg2, 0), L.pb(w.tg2, 1), TF, k.pw2, rows, Dt, TF, L.a<float>(k.b2));
         g2.resid = t_cur;
         g2.ldres = Dt;
         g2.out_f32 = t_nxt;
@@ -402,23 +313,23 @@ static int duration_body(const f5_duration* d, const DWorkspace& w, char* ws, in
     }
 
     // ---- input embedding: proj(concat(masked mel, text)) + conv_pos_embed (duration.py:44-58, :243-247)
-    for (int p = 0; p < d->np; ++p) RC(K.zero_vt_pad(PB(w.a0, p), (size_t)rows, 0, K0, s));     // every column: the pad [mel_dim, 128) must be 0
-    RC(K.pack_bf16(P(w.mel), mask, PB(w.a0, 0), PB(w.a0, 1), rows, c.mel_dim, K0, 0, s));
-    RC(K.pack_bf16(t_cur, nullptr, PB(w.a0, 0), PB(w.a0, 1), rows, Dt, K0, 128, s));
-    F5GemmArgs gp = gemm(PB(w.a0, 0), PB(w.a0, 1), K0, d->proj, D, K0, A(d->bproj));
-    gp.out_f32 = P(w.x);
+    for (int p = 0; p < d->np; ++p) RC(K.zero_vt_pad(L.pb(w.a0, p), (size_t)rows, 0, K0, s));     // every column: the pad [mel_dim, 128) must be 0
+    RC(K.pack_bf16(L.p<float>(w.mel), mask, L.pb(w.a0, 0), L.pb(w.a0, 1), rows, c.mel_dim, K0, 0, s));
+    RC(K.pack_bf16(t_cur, nullptr, L.pb(w.a0, 0), L.pb(w.a0, 1), rows, Dt, K0, 128, s));
+    F5GemmArgs gp = L.gemm(L.pb(w.a0, 0), L.pb(w.a0, 1), K0, d->proj, rows, D, K0, L.a<float>(d->bproj));
+    gp.out_f32 = L.p<float>(w.x);
     gp.ldo = D;
     gp.ldob = D;
     RC(K.gemm(gp, EPI_F32, s));
-    RC(K.pack_bf16(P(w.x), nullptr, PB(w.xb, 0), PB(w.xb, 1), rows, D, D, 0, s));
+    RC(K.pack_bf16(L.p<float>(w.x), nullptr, L.pb(w.xb, 0), L.pb(w.xb, 1), rows, D, D, 0, s));
     for (int j = 0; j < 2; ++j) {
         F5ConvPosArgs cp;
         memset(&cp, 0, sizeof(cp));
-        cp.in[0] = j == 0 ? PB(w.xb, 0) : PB(w.c1, 0);
-        cp.in[1] = j == 0 ? PB(w.xb, 1) : PB(w.c1, 1);
-        cp.W[0] = WM(d->conv_w[j], 0);
-        cp.W[1] = WM(d->conv_w[j], 1);
-        cp.bias = A(d->conv_b[j]);
+        cp.in[0] = j == 0 ? L.pb(w.xb, 0) : L.pb(w.c1, 0);
+        cp.in[1] = j == 0 ? L.pb(w.xb, 1) : L.pb(w.c1, 1);
+        cp.W[0] = L.wm(d->conv_w[j], 0);
+        cp.W[1] = L.wm(d->conv_w[j], 1);
+        cp.bias = L.a<float>(d->conv_b[j]);
         cp.B = B;
         cp.seq_len = N;
         cp.C = D;
@@ -428,27 +339,27 @@ static int duration_body(const f5_duration* d, const DWorkspace& w, char* ws, in
         cp.ldo = D;
         cp.nseg = nseg;
         cp.mode = j;                                  // 0: c1 = 16-bit(mish(.)); 1: x += mish(.)
-        cp.out_bf[0] = j == 0 ? PB(w.c1, 0) : nullptr;
-        cp.out_bf[1] = j == 0 ? PB(w.c1, 1) : nullptr;
-        cp.out_f32 = j == 0 ? nullptr : P(w.x);
+        cp.out_bf[0] = j == 0 ? L.pb(w.c1, 0) : nullptr;
+        cp.out_bf[1] = j == 0 ? L.pb(w.c1, 1) : nullptr;
+        cp.out_f32 = j == 0 ? nullptr : L.p<float>(w.x);
         RC(K.convpos(cp, s));
     }
 
     // ---- pre-LN transformer blocks without modulation / gates / masks (duration.py:64-94)
-    RC(K.rope_table(P(w.cos_t), P(w.sin_t), N, 64, s));
-    for (int p = 0; p < d->np; ++p) RC(K.zero_vt_pad(PB(w.vt, p), (size_t)B * H * 64, N, npad, s));   // columns < N: every QKV epilogue
+    RC(K.rope_table(L.p<float>(w.cos_t), L.p<float>(w.sin_t), N, 64, s));
+    for (int p = 0; p < d->np; ++p) RC(K.zero_vt_pad(L.pb(w.vt, p), (size_t)B * H * 64, N, npad, s));   // columns < N: every QKV epilogue
     for (const DBlock& k : d->blocks) {
-        RC(K.ln_modulate(P(w.x), A(d->zeros), A(d->zeros), PB(w.h, 0), PB(w.h, 1), rows, D, 1e-6f, s));
-        RC(K.qkv_rope(PB(w.h, 0), PB(w.h, 1), WM(k.qkv, 0), WM(k.qkv, 1), A(k.bqkv), P(w.cos_t), P(w.sin_t), PB(w.qk, 0), PB(w.qk, 1),
-                      PB(w.vt, 0), PB(w.vt, 1), B, N, npad, H, D, nseg, s));
+        RC(K.ln_modulate(L.p<float>(w.x), L.a<float>(d->zeros), L.a<float>(d->zeros), L.pb(w.h, 0), L.pb(w.h, 1), rows, D, 1e-6f, s));
+        RC(K.qkv_rope(L.pb(w.h, 0), L.pb(w.h, 1), L.wm(k.qkv, 0), L.wm(k.qkv, 1), L.a<float>(k.bqkv), L.p<float>(w.cos_t), L.p<float>(w.sin_t), L.pb(w.qk, 0), L.pb(w.qk, 1),
+                      L.pb(w.vt, 0), L.pb(w.vt, 1), B, N, npad, H, D, nseg, s));
         F5AttnArgs at;
         memset(&at, 0, sizeof(at));
-        at.qk[0] = PB(w.qk, 0);
-        at.qk[1] = PB(w.qk, 1);
-        at.vt[0] = PB(w.vt, 0);
-        at.vt[1] = PB(w.vt, 1);
-        at.out[0] = PB(w.ao, 0);
-        at.out[1] = PB(w.ao, 1);
+        at.qk[0] = L.pb(w.qk, 0);
+        at.qk[1] = L.pb(w.qk, 1);
+        at.vt[0] = L.pb(w.vt, 0);
+        at.vt[1] = L.pb(w.vt, 1);
+        at.out[0] = L.pb(w.ao, 0);
+        at.out[1] = L.pb(w.ao, 1);
         at.B = B;
         at.H = H;
         at.seq_len = N;
@@ -460,27 +371,27 @@ static int duration_body(const f5_duration* d, const DWorkspace& w, char* ws, in
         at.scale = 0.125f;
         at.pipe = -1;
         RC(K.attention(at, s));
-        F5GemmArgs go = gemm(PB(w.ao, 0), PB(w.ao, 1), D, k.o, D, D, A(k.bo));
-        go.gate = A(d->ones);
-        go.out_f32 = P(w.x);
+        F5GemmArgs go = L.gemm(L.pb(w.ao, 0), L.pb(w.ao, 1), D, k.o, rows, D, D, L.a<float>(k.bo));
+        go.gate = L.a<float>(d->ones);
+        go.out_f32 = L.p<float>(w.x);
         go.ldo = D;
         RC(K.gemm(go, EPI_RESID_GATE, s));
-        RC(K.ln_modulate(P(w.x), A(d->zeros), A(d->zeros), PB(w.h, 0), PB(w.h, 1), rows, D, 1e-6f, s));
-        F5GemmArgs g1 = gemm(PB(w.h, 0), PB(w.h, 1), D, k.ff1, FF, D, A(k.bff1));
-        g1.out_bf[0] = PB(w.ffh, 0);
-        g1.out_bf[1] = PB(w.ffh, 1);
+        RC(K.ln_modulate(L.p<float>(w.x), L.a<float>(d->zeros), L.a<float>(d->zeros), L.pb(w.h, 0), L.pb(w.h, 1), rows, D, 1e-6f, s));
+        F5GemmArgs g1 = L.gemm(L.pb(w.h, 0), L.pb(w.h, 1), D, k.ff1, rows, FF, D, L.a<float>(k.bff1));
+        g1.out_bf[0] = L.pb(w.ffh, 0);
+        g1.out_bf[1] = L.pb(w.ffh, 1);
         g1.ldo = FF;
         g1.ldob = FF;
         RC(K.gemm(g1, EPI_GELU_TANH, s));
-        F5GemmArgs g2 = gemm(PB(w.ffh, 0), PB(w.ffh, 1), FF, k.ff2, D, FF, A(k.bff2));
-        g2.gate = A(d->ones);
-        g2.out_f32 = P(w.x);
+        F5GemmArgs g2 = L.gemm(L.pb(w.ffh, 0), L.pb(w.ffh, 1), FF, k.ff2, rows, D, FF, L.a<float>(k.bff2));
+        g2.gate = L.a<float>(d->ones);
+        g2.out_f32 = L.p<float>(w.x);
         g2.ldo = D;
         RC(K.gemm(g2, EPI_RESID_GATE, s));
     }
 
     // ---- RMSNorm -> masked mean -> Linear(dim -> 1) -> Softplus (duration.py:137,188-190,249-251)
-    RC(K.duration_head(P(w.x), A(d->norm_out), A(d->to_pred), mask, P(w.pred), B, N, D, 1e-5f, s));
+    RC(K.duration_head(L.p<float>(w.x), L.a<float>(d->norm_out), L.a<float>(d->to_pred), mask, L.p<float>(w.pred), B, N, D, 1e-5f, s));
     return 0;
 }
 
@@ -517,38 +428,11 @@ extern "C" int f5_predict_duration(f5_duration* d, const f5_duration_args* a, vo
             RC(f5_launch_copy_words(a->mel + (size_t)b * n_in * mel, ws + w.mel + (size_t)b * N * mel * 4, (size_t)n_in * mel, s));
     }
     if (a->use_graph) {
-        hipGraphExec_t exec = nullptr;
-        for (auto& g : d->graphs)
-            if (g.B == B && g.n_in == n_in && g.nt == nt && g.workspace == workspace) {
-                exec = g.exec;
-                g.stamp = ++d->clock;
-            }
-        if (!exec) {
-            while (d->graphs.size() >= 8) {
-                size_t lru = 0;
-                for (size_t i = 1; i < d->graphs.size(); ++i)
-                    if (d->graphs[i].stamp < d->graphs[lru].stamp) lru = i;
-                destroy_dgraph(d->graphs[lru]);
-                d->graphs.erase(d->graphs.begin() + lru);
-            }
-            hipGraph_t graph = nullptr;
-            F5_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            const int rc = duration_body(d, w, ws, B, N, nt, s);
-            const hipError_t ec = hipStreamEndCapture(s, &graph);
-            if (rc) {
-                if (graph) (void)hipGraphDestroy(graph);
-                return rc;
-            }
-            F5_HIP_CHECK(ec);
-            F5_HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(graph);
-            hipEvent_t done = nullptr;
-            F5_HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-            d->graphs.push_back({B, n_in, nt, workspace, exec, ++d->clock, done});
-        }
-        F5_HIP_CHECK(hipGraphLaunch(exec, s));
-        for (auto& g : d->graphs)
-            if (g.exec == exec) F5_HIP_CHECK(hipEventRecord(g.done, s));
+        char key[64];
+        snprintf(key, sizeof(key), "B%d n%d nt%d", B, n_in, nt);
+        GraphCache::Entry* g = d->graphs.find(key, workspace);
+        if (!g) RC(d->graphs.capture(key, workspace, s, 1, [&](int) { return duration_body(d, w, ws, B, N, nt, s); }, &g));
+        RC(GraphCache::launch(g, s));
     } else {
         RC(duration_body(d, w, ws, B, N, nt, s));
     }
@@ -567,4 +451,4 @@ extern "C" int f5_duration_status(f5_duration* d, const f5_duration_args* a, int
     return 0;
 }
 
-extern "C" int f5_duration_graph_count(f5_duration* d) { return d ? (int)d->graphs.size() : -1; }
+extern "C" int f5_duration_graph_count(f5_duration* d) { return d ? d->graphs.size() : -1; }

@@ -9,7 +9,6 @@
 #include <stdarg.h>
 
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/f5tts_hip.h"
@@ -73,15 +72,6 @@ struct Workspace {
     size_t vt_bytes;
 };
 
-struct GraphEntry {
-    std::string key;
-    hipGraphExec_t exec;     // segment 0 (the whole call when the graph is not split)
-    std::vector<hipGraphExec_t> more;   // engine option "graph_split": the further segments (one per ODE step), launched in order
-    const void* workspace;   // the captured nodes reference this buffer
-    uint64_t stamp;          // last use (LRU)
-    hipEvent_t done;         // recorded after every launch: an exec is only destroyed once its last replay has finished
-};
-
 // Per-engine launch options: everything that reaches a kernel as a by-value argument or changes the launch sequence of sample()
 // lives in the engine handle, so two engines of one process keep their own configuration (f5_engine_set_option).  The process-wide
 // f5_debug_set_* hooks only set the DEFAULTS a new engine starts from (and what the per-op entry points f5_op_* use).
@@ -108,24 +98,9 @@ static int g_live_engines = 0;   // f5_debug_set_{ln_fusion,qkv_transposed,q_pre
 // knob values is never replayed
 static int g_knob_epoch = 0;
 
-static void destroy_graph_entry(GraphEntry& g) {
-    if (g.done) {
-        (void)hipEventSynchronize(g.done);        // the exec may still be running on the stream of its last launch
-        (void)hipEventDestroy(g.done);
-    }
-    (void)hipGraphExecDestroy(g.exec);
-    for (hipGraphExec_t x : g.more) (void)hipGraphExecDestroy(x);
-}
-
-struct f5_engine {
+struct f5_engine : WeightStore {
     f5_config cfg;
     int prec;
-    int np;  // precision parts (1 or 2)
-    char* arena = nullptr;
-    size_t arena_bytes = 0;
-    size_t arena_need = 0;
-    bool finalized = false;
-    std::unordered_map<std::string, std::vector<TensorDst>> tmap;
     // arena offsets
     size_t time_w0, time_b0, time_w2, time_b2;
     size_t ada_w, ada_b;  // [(6*depth+2)*D][D], [(6*depth+2)*D]
@@ -140,10 +115,8 @@ struct f5_engine {
     size_t bout;
     Ops ops;                          // kernels of this engine's operand type
     F5Options opt = g_default_options;
-    std::vector<GraphEntry> graphs;   // cached hipGraphExecs, at most graph_cap (least recently used is destroyed)
+    GraphCache graphs;                // cached hipGraphExecs, at most f5_engine_set_graph_cache (default 8)
     std::vector<std::string> seen;    // signatures sampled once in "auto" graph mode (captured on the second sighting)
-    int graph_cap = 8;
-    uint64_t clock = 0;
 };
 
 static int nfe_per_step(int method) { return method == F5_EULER ? 1 : (method == F5_MIDPOINT ? 2 : 4); }
@@ -158,28 +131,6 @@ static MatF8 alloc_f8(Bump& b, int rows, int ld) {
     return m;
 }
 
-static void add_f32(f5_engine* e, const std::string& name, size_t off, std::vector<int64_t> shape) {
-    TensorDst d;
-    d.kind = 0;
-    d.off = off;
-    d.shape = shape;
-    e->tmap[name].push_back(d);
-}
-static void add_mat(f5_engine* e, const std::string& name, const MatBF& m, int row0, int src_rows, int src_cols, int c0, int c1,
-                    int dst_c0, std::vector<int64_t> shape) {
-    TensorDst d;
-    d.kind = 1;
-    d.mat = m;
-    d.row0 = row0;
-    d.src_rows = src_rows;
-    d.src_cols = src_cols;
-    d.c0 = c0;
-    d.c1 = c1;
-    d.dst_c0 = dst_c0;
-    d.shape = shape;
-    e->tmap[name].push_back(d);
-}
-
 static int build_arena_plan(f5_engine* e) {
     const f5_config& c = e->cfg;
     const int D = c.dim, Dt = c.text_dim, FF = c.ff_dim, TF = c.text_ff_dim, L = c.depth, np = e->np;
@@ -190,10 +141,10 @@ static int build_arena_plan(f5_engine* e) {
     e->time_b0 = b.take((size_t)D * 4);
     e->time_w2 = b.take((size_t)D * D * 4);
     e->time_b2 = b.take((size_t)D * 4);
-    add_f32(e, p + "time_embed.time_mlp.layers.0.weight", e->time_w0, {D, c.freq_embed_dim});
-    add_f32(e, p + "time_embed.time_mlp.layers.0.bias", e->time_b0, {D});
-    add_f32(e, p + "time_embed.time_mlp.layers.2.weight", e->time_w2, {D, D});
-    add_f32(e, p + "time_embed.time_mlp.layers.2.bias", e->time_b2, {D});
+    e->add_f32(p + "time_embed.time_mlp.layers.0.weight", e->time_w0, {D, c.freq_embed_dim});
+    e->add_f32(p + "time_embed.time_mlp.layers.0.bias", e->time_b0, {D});
+    e->add_f32(p + "time_embed.time_mlp.layers.2.weight", e->time_w2, {D, D});
+    e->add_f32(p + "time_embed.time_mlp.layers.2.bias", e->time_b2, {D});
     // adaLN (fp32): all blocks + final stacked so one skinny GEMM builds the whole modulation table
     const size_t ada_rows = (size_t)(6 * L + 2) * D;
     e->ada_w = b.take(ada_rows * D * 4);
@@ -201,7 +152,7 @@ static int build_arena_plan(f5_engine* e) {
     // text embedding
     e->text_table = b.take((size_t)(c.text_num_embeds + 1) * Dt * 4);
     e->text_pos = b.take((size_t)c.text_max_pos * Dt * 4);
-    add_f32(e, p + "text_embed.text_embed.weight", e->text_table, {c.text_num_embeds + 1, Dt});
+    e->add_f32(p + "text_embed.text_embed.weight", e->text_table, {c.text_num_embeds + 1, Dt});
     e->tblocks.resize(c.conv_layers);
     for (int i = 0; i < c.conv_layers; ++i) {
         TextBlockW& t = e->tblocks[i];
@@ -216,33 +167,33 @@ static int build_arena_plan(f5_engine* e) {
         t.b2 = b.take((size_t)Dt * 4);
         t.pw1 = alloc_mat(b, TF, Dt, np);
         t.pw2 = alloc_mat(b, Dt, TF, np);
-        add_f32(e, q + "dwconv.weight", t.dw_w, {Dt, 7, 1});
-        add_f32(e, q + "dwconv.bias", t.dw_b, {Dt});
-        add_f32(e, q + "norm.weight", t.ln_w, {Dt});
-        add_f32(e, q + "norm.bias", t.ln_b, {Dt});
-        add_mat(e, q + "pwconv1.weight", t.pw1, 0, TF, Dt, 0, Dt, 0, {TF, Dt});
-        add_f32(e, q + "pwconv1.bias", t.b1, {TF});
-        add_f32(e, q + "grn.gamma", t.gamma, {1, 1, TF});
-        add_f32(e, q + "grn.beta", t.beta, {1, 1, TF});
-        add_mat(e, q + "pwconv2.weight", t.pw2, 0, Dt, TF, 0, TF, 0, {Dt, TF});
-        add_f32(e, q + "pwconv2.bias", t.b2, {Dt});
+        e->add_f32(q + "dwconv.weight", t.dw_w, {Dt, 7, 1});
+        e->add_f32(q + "dwconv.bias", t.dw_b, {Dt});
+        e->add_f32(q + "norm.weight", t.ln_w, {Dt});
+        e->add_f32(q + "norm.bias", t.ln_b, {Dt});
+        e->add_mat(q + "pwconv1.weight", t.pw1, 0, TF, Dt, 0, Dt, 0, {TF, Dt});
+        e->add_f32(q + "pwconv1.bias", t.b1, {TF});
+        e->add_f32(q + "grn.gamma", t.gamma, {1, 1, TF});
+        e->add_f32(q + "grn.beta", t.beta, {1, 1, TF});
+        e->add_mat(q + "pwconv2.weight", t.pw2, 0, Dt, TF, 0, TF, 0, {Dt, TF});
+        e->add_f32(q + "pwconv2.bias", t.b2, {Dt});
     }
     // input projection, split by input segment (x | cond | text), dit.py:250
     const int M = c.mel_dim, IN = 2 * M + Dt;
     e->wx = alloc_mat(b, D, 128, np);
     e->wct = alloc_mat(b, D, 128 + Dt, np);
     e->bproj = b.take((size_t)D * 4);
-    add_mat(e, p + "input_embed.proj.weight", e->wx, 0, D, IN, 0, M, 0, {D, IN});
-    add_mat(e, p + "input_embed.proj.weight", e->wct, 0, D, IN, M, 2 * M, 0, {D, IN});
-    add_mat(e, p + "input_embed.proj.weight", e->wct, 0, D, IN, 2 * M, IN, 128, {D, IN});
-    add_f32(e, p + "input_embed.proj.bias", e->bproj, {D});
+    e->add_mat(p + "input_embed.proj.weight", e->wx, 0, D, IN, 0, M, 0, {D, IN});
+    e->add_mat(p + "input_embed.proj.weight", e->wct, 0, D, IN, M, 2 * M, 0, {D, IN});
+    e->add_mat(p + "input_embed.proj.weight", e->wct, 0, D, IN, 2 * M, IN, 128, {D, IN});
+    e->add_f32(p + "input_embed.proj.bias", e->bproj, {D});
     const int kc = c.conv_pos_kernel, gin = D / c.conv_pos_groups;
     for (int j = 0; j < 2; ++j) {
         e->conv_w[j] = alloc_mat(b, D, kc * gin, np);
         e->conv_b[j] = b.take((size_t)D * 4);
         const std::string q = p + "input_embed.conv_pos_embed.conv1d.layers." + std::to_string(j * 2) + ".";
-        add_mat(e, q + "weight", e->conv_w[j], 0, D, kc * gin, 0, kc * gin, 0, {D, kc, gin});
-        add_f32(e, q + "bias", e->conv_b[j], {D});
+        e->add_mat(q + "weight", e->conv_w[j], 0, D, kc * gin, 0, kc * gin, 0, {D, kc, gin});
+        e->add_f32(q + "bias", e->conv_b[j], {D});
     }
     e->blocks.resize(L);
     for (int i = 0; i < L; ++i) {
@@ -262,26 +213,26 @@ static int build_arena_plan(f5_engine* e) {
         w.bo = b.take((size_t)D * 4);
         w.bff1 = b.take((size_t)FF * 4);
         w.bff2 = b.take((size_t)D * 4);
-        add_f32(e, q + "attn_norm.linear.weight", e->ada_w + (size_t)i * 6 * D * D * 4, {6 * D, D});
-        add_f32(e, q + "attn_norm.linear.bias", e->ada_b + (size_t)i * 6 * D * 4, {6 * D});
+        e->add_f32(q + "attn_norm.linear.weight", e->ada_w + (size_t)i * 6 * D * D * 4, {6 * D, D});
+        e->add_f32(q + "attn_norm.linear.bias", e->ada_b + (size_t)i * 6 * D * 4, {6 * D});
         const char* nm[3] = {"to_q", "to_k", "to_v"};
         for (int k = 0; k < 3; ++k) {
-            add_mat(e, q + "attn." + nm[k] + ".weight", w.qkv, k * D, D, D, 0, D, 0, {D, D});
-            add_f32(e, q + "attn." + nm[k] + ".bias", w.bqkv + (size_t)k * D * 4, {D});
+            e->add_mat(q + "attn." + nm[k] + ".weight", w.qkv, k * D, D, D, 0, D, 0, {D, D});
+            e->add_f32(q + "attn." + nm[k] + ".bias", w.bqkv + (size_t)k * D * 4, {D});
         }
-        add_mat(e, q + "attn.to_out.layers.0.weight", w.o, 0, D, D, 0, D, 0, {D, D});
-        add_f32(e, q + "attn.to_out.layers.0.bias", w.bo, {D});
-        add_mat(e, q + "ff.ff.layers.0.layers.0.weight", w.ff1, 0, FF, D, 0, D, 0, {FF, D});
-        add_f32(e, q + "ff.ff.layers.0.layers.0.bias", w.bff1, {FF});
-        add_mat(e, q + "ff.ff.layers.2.weight", w.ff2, 0, D, FF, 0, FF, 0, {D, FF});
-        add_f32(e, q + "ff.ff.layers.2.bias", w.bff2, {D});
+        e->add_mat(q + "attn.to_out.layers.0.weight", w.o, 0, D, D, 0, D, 0, {D, D});
+        e->add_f32(q + "attn.to_out.layers.0.bias", w.bo, {D});
+        e->add_mat(q + "ff.ff.layers.0.layers.0.weight", w.ff1, 0, FF, D, 0, D, 0, {FF, D});
+        e->add_f32(q + "ff.ff.layers.0.layers.0.bias", w.bff1, {FF});
+        e->add_mat(q + "ff.ff.layers.2.weight", w.ff2, 0, D, FF, 0, FF, 0, {D, FF});
+        e->add_f32(q + "ff.ff.layers.2.bias", w.bff2, {D});
     }
-    add_f32(e, p + "norm_out.linear.weight", e->ada_w + (size_t)L * 6 * D * D * 4, {2 * D, D});
-    add_f32(e, p + "norm_out.linear.bias", e->ada_b + (size_t)L * 6 * D * 4, {2 * D});
+    e->add_f32(p + "norm_out.linear.weight", e->ada_w + (size_t)L * 6 * D * D * 4, {2 * D, D});
+    e->add_f32(p + "norm_out.linear.bias", e->ada_b + (size_t)L * 6 * D * 4, {2 * D});
     e->wout = alloc_mat(b, M, D, np);
     e->bout = b.take((size_t)M * 4);
-    add_mat(e, p + "proj_out.weight", e->wout, 0, M, D, 0, D, 0, {M, D});
-    add_f32(e, p + "proj_out.bias", e->bout, {M});
+    e->add_mat(p + "proj_out.weight", e->wout, 0, M, D, 0, D, 0, {M, D});
+    e->add_f32(p + "proj_out.bias", e->bout, {M});
     e->arena_need = b.off;
     return 0;
 }
@@ -306,7 +257,7 @@ extern "C" int f5_engine_create(const f5_config* cfg, int precision, f5_engine**
     e->cfg = c;
     e->prec = precision;
     e->np = precision == F5_PREC_BF16X3 ? 2 : 1;
-    e->ops.h = precision == F5_PREC_F16;
+    e->f16 = e->ops.h = precision == F5_PREC_F16;
     build_arena_plan(e);
     ++g_live_engines;
     *out = e;
@@ -315,62 +266,55 @@ extern "C" int f5_engine_create(const f5_config* cfg, int precision, f5_engine**
 
 extern "C" void f5_engine_destroy(f5_engine* e) {
     if (!e) return;
-    for (auto& g : e->graphs) destroy_graph_entry(g);
     --g_live_engines;
-    delete e;
+    delete e;      // (~GraphCache waits for the last replay of every exec)
 }
 
 extern "C" int f5_engine_set_graph_cache(f5_engine* e, int max_graphs) {
     F5_REQUIRE(e && max_graphs >= 1 && max_graphs <= 1024, "graph cache size must be in [1, 1024]");
-    e->graph_cap = max_graphs;
-    while ((int)e->graphs.size() > e->graph_cap) {
-        size_t lru = 0;
-        for (size_t i = 1; i < e->graphs.size(); ++i)
-            if (e->graphs[i].stamp < e->graphs[lru].stamp) lru = i;
-        destroy_graph_entry(e->graphs[lru]);
-        e->graphs.erase(e->graphs.begin() + lru);
-    }
+    e->graphs.set_cap((size_t)max_graphs);
     return 0;
+}
+
+// The engine options by name.  Switches are 0 / 1, tri-states -1 (automatic) / 0 / 1, gemm_flags is a raw word.  One table serves
+// set, get, the message that lists the names and the option part of the graph key.
+enum OptKind { OPT_SWITCH, OPT_TRI, OPT_INT };
+static const struct OptDesc {
+    const char* name;
+    int F5Options::*member;
+    OptKind kind;
+} k_options[] = {
+    {"q_premul", &F5Options::q_premul, OPT_SWITCH},     {"qkv_transposed", &F5Options::qkv_tr, OPT_SWITCH},
+    {"ln_fusion", &F5Options::fuse_ln, OPT_SWITCH},     {"gemm_flags", &F5Options::gemm_flags, OPT_INT},
+    {"attn_pipe", &F5Options::attn_pipe, OPT_TRI},      {"null_keeps_cond", &F5Options::null_keeps_cond, OPT_SWITCH},
+    {"ln_fold", &F5Options::ln_fold, OPT_TRI},          {"sat_check", &F5Options::sat_check, OPT_SWITCH},
+    {"graph_split", &F5Options::graph_split, OPT_SWITCH}, {"fold_stats", &F5Options::fold_stats, OPT_TRI},
+};
+static const OptDesc* find_option(const char* name) {
+    std::string names;
+    for (const OptDesc& o : k_options) {
+        if (strcmp(o.name, name) == 0) return &o;
+        names += names.empty() ? "" : ", ";
+        names += o.name;
+    }
+    f5_set_error("unknown engine option %s (%s)", name, names.c_str());
+    return nullptr;
 }
 extern "C" int f5_engine_set_option(f5_engine* e, const char* name, int value) {
     F5_REQUIRE(e && name, "null argument");
-    const std::string n(name);
-    if (n == "q_premul") e->opt.q_premul = value ? 1 : 0;
-    else if (n == "qkv_transposed") e->opt.qkv_tr = value ? 1 : 0;
-    else if (n == "ln_fusion") e->opt.fuse_ln = value ? 1 : 0;
-    else if (n == "gemm_flags") e->opt.gemm_flags = value;
-    else if (n == "attn_pipe") e->opt.attn_pipe = value < 0 ? -1 : (value ? 1 : 0);
-    else if (n == "null_keeps_cond") e->opt.null_keeps_cond = value ? 1 : 0;
-    else if (n == "ln_fold") e->opt.ln_fold = value < 0 ? -1 : (value ? 1 : 0);
-    else if (n == "sat_check") e->opt.sat_check = value ? 1 : 0;
-    else if (n == "graph_split") e->opt.graph_split = value ? 1 : 0;
-    else if (n == "fold_stats") e->opt.fold_stats = value < 0 ? -1 : (value ? 1 : 0);
-    else {
-        f5_set_error("unknown engine option %s (q_premul, qkv_transposed, ln_fusion, gemm_flags, attn_pipe, null_keeps_cond, ln_fold, sat_check)", name);
-        return 2;
-    }
+    const OptDesc* o = find_option(name);
+    if (!o) return 2;
+    e->opt.*o->member = o->kind == OPT_INT ? value : (o->kind == OPT_TRI && value < 0 ? -1 : (value ? 1 : 0));
     return 0;
 }
 extern "C" int f5_engine_get_option(f5_engine* e, const char* name, int* value) {
     F5_REQUIRE(e && name && value, "null argument");
-    const std::string n(name);
-    if (n == "q_premul") *value = e->opt.q_premul;
-    else if (n == "qkv_transposed") *value = e->opt.qkv_tr;
-    else if (n == "ln_fusion") *value = e->opt.fuse_ln;
-    else if (n == "gemm_flags") *value = e->opt.gemm_flags;
-    else if (n == "attn_pipe") *value = e->opt.attn_pipe;
-    else if (n == "null_keeps_cond") *value = e->opt.null_keeps_cond;
-    else if (n == "ln_fold") *value = e->opt.ln_fold;
-    else if (n == "sat_check") *value = e->opt.sat_check;
-    else if (n == "graph_split") *value = e->opt.graph_split;
-    else if (n == "fold_stats") *value = e->opt.fold_stats;
-    else {
-        f5_set_error("unknown engine option %s", name);
-        return 2;
-    }
+    const OptDesc* o = find_option(name);
+    if (!o) return 2;
+    *value = e->opt.*o->member;
     return 0;
 }
-extern "C" int f5_engine_graph_count(f5_engine* e) { return e ? (int)e->graphs.size() : -1; }
+extern "C" int f5_engine_graph_count(f5_engine* e) { return e ? e->graphs.size() : -1; }
 
 extern "C" int f5_weights_bytes(f5_engine* e, size_t* bytes) {
     F5_REQUIRE(e && bytes, "null argument");
@@ -380,38 +324,24 @@ extern "C" int f5_weights_bytes(f5_engine* e, size_t* bytes) {
 
 extern "C" int f5_set_weights_arena(f5_engine* e, void* dev_arena, size_t bytes, void* stream) {
     F5_REQUIRE(e && dev_arena, "null argument");
-    F5_REQUIRE(bytes >= e->arena_need, "weights arena too small: %zu < %zu", bytes, e->arena_need);
-    F5_REQUIRE(((uintptr_t)dev_arena & 255) == 0, "weights arena must be 256-byte aligned");
-    e->arena = (char*)dev_arena;
-    e->arena_bytes = bytes;
-    F5_HIP_CHECK(hipMemsetAsync(dev_arena, 0, e->arena_need, (hipStream_t)stream));  // zero pads
-    F5_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    return 0;
+    return e->set_arena(dev_arena, bytes, (hipStream_t)stream);
 }
 
 extern "C" int f5_load_tensor(f5_engine* e, const char* name, const float* host, int ndim, const int64_t* shape) {
     F5_REQUIRE(e && name && host && shape, "null argument");
+    // the name and the shape are checked before the arena, so that a host can validate a checkpoint without a device
+    std::vector<TensorDst>* dsts = nullptr;
+    size_t count = 0;
+    RC(e->lookup(name, name, &dsts));
+    RC(e->match(name, *dsts, ndim, shape, &count));
     F5_REQUIRE(e->arena, "f5_set_weights_arena must be called first");
-    auto it = e->tmap.find(name);
-    F5_REQUIRE(it != e->tmap.end(), "unknown tensor name '%s'", name);
-    for (TensorDst& d : it->second) {
-        F5_REQUIRE((int)d.shape.size() == ndim, "tensor '%s': expected %zu dims, got %d", name, d.shape.size(), ndim);
-        size_t count = 1;
-        for (int i = 0; i < ndim; ++i) {
-            F5_REQUIRE(d.shape[i] == shape[i], "tensor '%s': dim %d is %lld, expected %lld", name, i, (long long)shape[i],
-                       (long long)d.shape[i]);
-            count *= (size_t)shape[i];
-        }
-        RC(f5_upload_tensor(e->arena, d, host, count, e->np, e->ops.h));
-        d.loaded = true;
-    }
+    for (TensorDst& d : *dsts) RC(e->upload(d, host, count));
     return 0;
 }
 
 extern "C" int f5_mark_weights_loaded(f5_engine* e) {
     F5_REQUIRE(e, "null argument");
-    for (auto& kv : e->tmap)
-        for (auto& d : kv.second) d.loaded = true;
+    e->mark_all_loaded();
     return 0;
 }
 
@@ -426,8 +356,7 @@ extern "C" int f5_share_weights(f5_engine* e, const f5_engine* owner) {
                "f5_share_weights: the two handles differ in configuration or precision");
     e->arena = owner->arena;
     e->arena_bytes = owner->arena_bytes;
-    for (auto& kv : e->tmap)
-        for (auto& d : kv.second) d.loaded = true;
+    e->mark_all_loaded();
     e->finalized = true;
     return 0;
 }
@@ -453,16 +382,13 @@ extern "C" int f5_broadcast_weights(f5_engine* e, void* nccl_comm, int root, int
     const int ncclUint8 = 1;
     const int rc = fn(e->arena, e->arena, e->arena_need, ncclUint8, root, nccl_comm, (hipStream_t)stream);
     F5_REQUIRE(rc == 0, "ncclBroadcast failed with ncclResult_t %d", rc);
-    if (rank != root)
-        for (auto& kv : e->tmap)
-            for (auto& d : kv.second) d.loaded = true;
+    if (rank != root) e->mark_all_loaded();
     return 0;
 }
 
 extern "C" int f5_finalize_weights(f5_engine* e, void* stream) {
     F5_REQUIRE(e && e->arena, "arena not set");
-    for (auto& kv : e->tmap)
-        for (auto& d : kv.second) F5_REQUIRE(d.loaded, "tensor '%s' was never loaded", kv.first.c_str());
+    RC(e->require_loaded());
     int rc = f5_launch_text_pos_table((float*)(e->arena + e->text_pos), e->cfg.text_max_pos, e->cfg.text_dim, (hipStream_t)stream);
     if (rc) return rc;
     if (e->prec == F5_PREC_MXFP8) {
@@ -589,27 +515,13 @@ extern "C" int f5_workspace_bytes(f5_engine* e, int B, int N, int nt, int steps,
 // ------------------------------------------------------------------------------------------------
 // launch context
 // ------------------------------------------------------------------------------------------------
-struct Ctx {
+struct Ctx : LaunchView {
     f5_engine* e;
     Workspace w;
-    char* ws;
     hipStream_t s;
     int B, N, nt, nb;   // nb = branches evaluated per function evaluation (1 or 2)
     int npad;
     bool use_mask;
-    Ops ops;
-    template <typename T>
-    T* p(size_t off) const { return reinterpret_cast<T*>(ws + off); }
-    template <typename T>
-    T* a(size_t off) const { return reinterpret_cast<T*>(e->arena + off); }
-    op16_t* pb(const size_t (&offs)[2], int part) const {
-        return (part < e->np) ? reinterpret_cast<op16_t*>(ws + offs[part]) : nullptr;
-    }
-    const op16_t* wm(const MatBF& m, int part) const {
-        if (part == 0) return reinterpret_cast<const op16_t*>(e->arena + m.hi);
-        return e->np == 2 ? reinterpret_cast<const op16_t*>(e->arena + m.lo) : nullptr;
-    }
-    int nseg() const { return e->np == 2 ? 3 : 1; }
 };
 
 // factor folded into q by the QKV epilogue (0 = none): single-segment operand modes only, see run_dit
@@ -619,19 +531,7 @@ static float q_premul_factor(const f5_engine* e) {
 
 static F5GemmArgs gemm_base(const Ctx& c, const op16_t* a_hi, const op16_t* a_lo, int lda, const MatBF& w, int M, int N, int K,
                             const float* bias) {
-    F5GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A[0] = a_hi;
-    g.A[1] = a_lo;
-    g.W[0] = c.wm(w, 0);
-    g.W[1] = c.wm(w, 1);
-    g.lda = lda;
-    g.ldw = w.ld;
-    g.M = M;
-    g.N = N;
-    g.K = K;
-    g.nseg = c.nseg();
-    g.bias = bias;
+    F5GemmArgs g = c.gemm(a_hi, a_lo, lda, w, M, N, K, bias);
     g.debug_flags = c.e->opt.gemm_flags;      // this engine's own flags (f5_engine_set_option)
     return g;
 }
@@ -1053,17 +953,6 @@ static int run_dit(const Ctx& c, int j) {
     return 0;
 }
 
-// fp16 range detector (op16.hpp): while one of these is alive the 16-bit packers of every launch of the fp16 build report
-// saturation into the call's status word (bit F5_STATUS_SATURATED).  Host-side: the pointer travels as a kernel argument, a captured
-// graph keeps the status word of the workspace it was captured against (part of the graph key).
-struct SatScope {
-    int* saved;
-    SatScope(const f5_engine* e, int* status_word) : saved(f5hf::f5_sat_flag_host) {
-        if (e->prec == F5_PREC_F16 && e->opt.sat_check) f5hf::f5_sat_flag_host = status_word;
-    }
-    ~SatScope() { f5hf::f5_sat_flag_host = saved; }
-};
-
 // steps [i0, i1) of the solve; i0 == 0 also runs the per-call preparation (hoisted tables, text path, first operand pack)
 static int run_sample_body(const Ctx& c, const f5_sample_args* a, int i0 = 0, int i1 = 1 << 30) {
     const f5_config& cf = c.e->cfg;
@@ -1190,9 +1079,12 @@ static int stage_inputs(Ctx& c, const f5_sample_args* a, const float* x_override
 
 static Ctx make_ctx(f5_engine* e, const f5_sample_args* a, hipStream_t s) {
     Ctx c;
+    c.arena = e->arena;
+    c.ws = (char*)a->workspace;
+    c.np = e->np;
+    c.ops = e->ops;
     c.e = e;
     c.w = plan_workspace(e, a->B, a->N, a->nt, a->steps, a->method);
-    c.ws = (char*)a->workspace;
     c.s = s;
     c.B = a->B;
     c.N = a->N;
@@ -1200,7 +1092,6 @@ static Ctx make_ctx(f5_engine* e, const f5_sample_args* a, hipStream_t s) {
     c.nb = a->cfg_strength < 1e-5f ? 1 : 2;
     c.npad = (a->N + 63) / 64 * 64;
     c.use_mask = a->use_mask != 0;
-    c.ops = e->ops;
     return c;
 }
 
@@ -1212,7 +1103,7 @@ extern "C" int f5_sample(f5_engine* e, const f5_sample_args* a, void* stream) {
     F5_REQUIRE(a->workspace_bytes >= c.w.total, "workspace too small: %zu < %zu", a->workspace_bytes, c.w.total);
     const int mel = e->cfg.mel_dim;
     const size_t M1 = (size_t)c.B * c.N;
-    SatScope sat(e, c.p<int>(c.w.status));
+    SatScope sat(e->prec == F5_PREC_F16 && e->opt.sat_check, c.p<int>(c.w.status));
 
     // function-evaluation times and step sizes in fp32, as the solvers compute them (cfm.py:50-56,76-86,106-114)
     std::vector<float> tnfe, dts;
@@ -1236,88 +1127,31 @@ extern "C" int f5_sample(f5_engine* e, const f5_sample_args* a, void* stream) {
 
     // hipGraph cache.  The key is everything a captured node depends on BY VALUE: shapes, solver, branch count, masking and the
     // workspace address.  Per-call scalars (cfg strength, time grid, dt) are read from workspace memory staged above.
-    char key[256];
-    snprintf(key, sizeof(key), "B%d N%d nt%d st%d m%d nb%d mask%d ln%d qp%d qt%d gf%d ap%d nk%d lf%d sc%d gs%d fs%d ke%d ws%p", c.B, c.N, c.nt, a->steps, a->method, c.nb,
-             (int)c.use_mask, e->opt.fuse_ln, e->opt.q_premul, e->opt.qkv_tr, e->opt.gemm_flags, e->opt.attn_pipe, e->opt.null_keeps_cond, e->opt.ln_fold, e->opt.sat_check, e->opt.graph_split, e->opt.fold_stats, g_knob_epoch,
-             a->workspace);
-    bool graph = a->use_graph == 1;
-    if (a->use_graph == F5_GRAPH_AUTO) {
+    char shape_key[192];
+    snprintf(shape_key, sizeof(shape_key), "B%d N%d nt%d st%d m%d nb%d mask%d ke%d ws%p opt", c.B, c.N, c.nt, a->steps, a->method, c.nb,
+             (int)c.use_mask, g_knob_epoch, a->workspace);
+    std::string key(shape_key);
+    for (const OptDesc& o : k_options) key += " " + std::to_string(e->opt.*o.member);
+    const bool graph_on = a->use_graph == F5_GRAPH_ON, graph_auto = a->use_graph == F5_GRAPH_AUTO;
+    GraphCache::Entry* entry = (graph_on || graph_auto) ? e->graphs.find(key, a->workspace) : nullptr;
+    bool graph = graph_on || entry != nullptr;
+    if (graph_auto && !entry) {
         // a text-to-speech service sees a new (N, nt) on almost every call and capture + instantiate of ~5000 nodes costs more
         // than one eager pass: run a signature eagerly the first time, capture it when it comes back
-        bool cached = false;
-        for (auto& g : e->graphs) cached |= g.key == key;
-        bool seen = false;
-        for (auto& k : e->seen) seen |= k == key;
-        graph = cached || seen;
+        for (auto& k : e->seen) graph |= k == key;
         if (!graph) {
             if (e->seen.size() >= 64) e->seen.erase(e->seen.begin());
             e->seen.push_back(key);
         }
     }
     if (graph) {
-        GraphEntry* entry = nullptr;
-        for (auto& g : e->graphs)
-            if (g.key == key) {
-                entry = &g;
-                g.stamp = ++e->clock;
-            }
         if (!entry) {
-            // entries captured against another workspace are dead (the caller re-allocated it); then make room (LRU)
-            for (size_t i = 0; i < e->graphs.size();) {
-                if (e->graphs[i].workspace != a->workspace) {
-                    destroy_graph_entry(e->graphs[i]);
-                    e->graphs.erase(e->graphs.begin() + i);
-                } else {
-                    ++i;
-                }
-            }
-            while ((int)e->graphs.size() >= e->graph_cap && !e->graphs.empty()) {
-                size_t lru = 0;
-                for (size_t i = 1; i < e->graphs.size(); ++i)
-                    if (e->graphs[i].stamp < e->graphs[lru].stamp) lru = i;
-                destroy_graph_entry(e->graphs[lru]);
-                e->graphs.erase(e->graphs.begin() + lru);
-            }
             // segments: the whole call, or (graph_split) one per ODE step
             const int nseg = (e->opt.graph_split && a->steps > 2) ? a->steps - 1 : 1;
-            std::vector<hipGraphExec_t> execs;
-            auto drop = [&]() {
-                for (hipGraphExec_t x : execs) (void)hipGraphExecDestroy(x);
-            };
-            for (int sg = 0; sg < nseg; ++sg) {
-                hipGraph_t graph_h = nullptr;
-                F5_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                const int rc = nseg == 1 ? run_sample_body(c, a) : run_sample_body(c, a, sg, sg + 1);
-                const hipError_t ec = hipStreamEndCapture(s, &graph_h);
-                if (rc || ec != hipSuccess) {
-                    if (graph_h) (void)hipGraphDestroy(graph_h);
-                    drop();
-                    if (rc) return rc;
-                    F5_HIP_CHECK(ec);
-                }
-                hipGraphExec_t exec = nullptr;
-                const hipError_t ei = hipGraphInstantiate(&exec, graph_h, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(graph_h);
-                if (ei != hipSuccess) {
-                    drop();
-                    F5_HIP_CHECK(ei);
-                }
-                execs.push_back(exec);
-            }
-            hipEvent_t done = nullptr;
-            if (hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) {
-                drop();                                       // do not leak the instantiated graphs
-                f5_set_error("f5_sample: hipEventCreateWithFlags failed");
-                return 3;
-            }
-            GraphEntry ge{key, execs[0], {}, a->workspace, ++e->clock, done};
-            ge.more.assign(execs.begin() + 1, execs.end());
-            e->graphs.push_back(std::move(ge));
-            entry = &e->graphs.back();
+            RC(e->graphs.capture(key, a->workspace, s, nseg,
+                                 [&](int sg) { return nseg == 1 ? run_sample_body(c, a) : run_sample_body(c, a, sg, sg + 1); }, &entry));
         }
-        F5_HIP_CHECK(hipGraphLaunch(entry->exec, s));
-        for (hipGraphExec_t x : entry->more) F5_HIP_CHECK(hipGraphLaunch(x, s));
-        F5_HIP_CHECK(hipEventRecord(entry->done, s));
+        RC(GraphCache::launch(entry, s));
     } else {
         RC(run_sample_body(c, a));
     }
@@ -1366,7 +1200,7 @@ extern "C" int f5_dit_forward(f5_engine* e, const f5_sample_args* a, const float
     F5_REQUIRE(a->workspace_bytes >= c.w.total, "workspace too small: %zu < %zu", a->workspace_bytes, c.w.total);
     const int mel = e->cfg.mel_dim;
     const size_t M1 = (size_t)c.B * c.N;
-    SatScope sat(e, c.p<int>(c.w.status));
+    SatScope sat(e->prec == F5_PREC_F16 && e->opt.sat_check, c.p<int>(c.w.status));
     std::vector<float> tnfe(1, t), dts(1, 0.0f);
     RC(stage_inputs(c, &a2, x, tnfe, dts));
     const Ops& K = c.ops;
@@ -1602,31 +1436,12 @@ extern "C" int f5_op_fold_consts(const void* w_hi, int ldw, const float* bias, c
     return g_ops.fold_consts((const op16_t*)w_hi, ldw, bias, scale, shift, vec_stride, nvec, c1, c2, out_stride, N, K, (hipStream_t)stream);
 }
 
-// operands, shape and bias of an f5_op_* GEMM (what gemm_base() is to the engine's launches)
-static F5GemmArgs op_gemm_base(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, int lda, int ldw, int M, int N, int K,
-                               int nseg, const float* bias) {
-    F5GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A[0] = (const op16_t*)a_hi;
-    g.A[1] = (const op16_t*)a_lo;
-    g.W[0] = (const op16_t*)w_hi;
-    g.W[1] = (const op16_t*)w_lo;
-    g.lda = lda;
-    g.ldw = ldw;
-    g.M = M;
-    g.N = N;
-    g.K = K;
-    g.nseg = nseg;
-    g.bias = bias;
-    return g;
-}
-
 extern "C" int f5_op_gemm(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias,
                           float* out_f32, void* out_bf_hi, void* out_bf_lo, int M, int N, int K, int lda, int ldw, int ldo,
                           int nseg, int epi, void* stream) {
     F5_REQUIRE(epi == EPI_F32 || epi == EPI_BF16 || epi == EPI_GELU_TANH || epi == EPI_GELU_ERF || epi == EPI_GELU_ERF_BF16,
                "f5_op_gemm supports epilogues 0-3 and 8 only");
-    F5GemmArgs g = op_gemm_base(a_hi, a_lo, w_hi, w_lo, lda, ldw, M, N, K, nseg, bias);
+    F5GemmArgs g = f5_gemm_args(a_hi, a_lo, w_hi, w_lo, lda, ldw, M, N, K, nseg, bias);
     g.out_f32 = out_f32;
     g.ldo = ldo;
     g.out_bf[0] = (op16_t*)out_bf_hi;
@@ -1728,7 +1543,7 @@ extern "C" int f5_op_attention(const void* qk_hi, const void* qk_lo, const void*
 extern "C" int f5_op_qkv_rope(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias,
                               const float* rope_cos, const float* rope_sin, void* qk_hi, void* qk_lo, void* vt_hi, void* vt_lo,
                               int B, int seq_len, int npad, int heads, int dmodel, int nseg, void* stream) {
-    F5GemmArgs g = op_gemm_base(a_hi, a_lo, w_hi, w_lo, dmodel, dmodel, B * seq_len, 3 * dmodel, dmodel, nseg, bias);
+    F5GemmArgs g = f5_gemm_args(a_hi, a_lo, w_hi, w_lo, dmodel, dmodel, B * seq_len, 3 * dmodel, dmodel, nseg, bias);
     g.out_bf[0] = (op16_t*)qk_hi;
     g.out_bf[1] = (op16_t*)qk_lo;
     g.ldob = 2 * dmodel;
@@ -1823,7 +1638,7 @@ extern "C" int f5_op_text_embed_nomask(const int32_t* text, int nt, const float*
 extern "C" int f5_op_gemm_resid_keep(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias,
                                      const float* resid, const uint8_t* rowkeep, float* out, int M, int N, int K, int lda, int ldw,
                                      int ldo, int nseg, void* stream) {
-    F5GemmArgs g = op_gemm_base(a_hi, a_lo, w_hi, w_lo, lda, ldw, M, N, K, nseg, bias);
+    F5GemmArgs g = f5_gemm_args(a_hi, a_lo, w_hi, w_lo, lda, ldw, M, N, K, nseg, bias);
     g.resid = resid;
     g.ldres = ldo;
     g.rowkeep = rowkeep;
@@ -1929,7 +1744,7 @@ extern "C" int f5_op_zero_vt_pad(void* vt, size_t rows, int seq_len, int npad, v
 extern "C" int f5_op_gemm_resid_gate(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias,
                                      const float* gate, const uint8_t* rowkeep, float* x, int M, int N, int K, int lda, int ldw,
                                      int ldx, int nseg, void* stream) {
-    F5GemmArgs g = op_gemm_base(a_hi, a_lo, w_hi, w_lo, lda, ldw, M, N, K, nseg, bias);
+    F5GemmArgs g = f5_gemm_args(a_hi, a_lo, w_hi, w_lo, lda, ldw, M, N, K, nseg, bias);
     g.gate = gate;
     g.rowkeep = rowkeep;
     g.out_f32 = x;
@@ -1953,7 +1768,7 @@ extern "C" int f5_op_gemm_resid_gate_ln(const void* a_hi, const void* a_lo, cons
                                         const float* gate, const uint8_t* rowkeep, float* x, const float* ln_scale,
                                         const float* ln_shift, void* h_hi, void* h_lo, int* counters, int M, int N, int K, int lda,
                                         int ldw, int nseg, void* stream) {
-    F5GemmArgs g = op_gemm_base(a_hi, a_lo, w_hi, w_lo, lda, ldw, M, N, K, nseg, bias);
+    F5GemmArgs g = f5_gemm_args(a_hi, a_lo, w_hi, w_lo, lda, ldw, M, N, K, nseg, bias);
     g.gate = gate;
     g.rowkeep = rowkeep;
     g.out_f32 = x;
@@ -1972,7 +1787,7 @@ extern "C" int f5_op_gemm_resid_gate_ln(const void* a_hi, const void* a_lo, cons
 extern "C" int f5_op_gemm_addrows(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* addrows,
                                   int a_row_mod, float* out_f32, void* out_hi, void* out_lo, int M, int N, int K, int lda, int ldw,
                                   int ldo, int nseg, void* stream) {
-    F5GemmArgs g = op_gemm_base(a_hi, a_lo, w_hi, w_lo, lda, ldw, M, N, K, nseg, nullptr);
+    F5GemmArgs g = f5_gemm_args(a_hi, a_lo, w_hi, w_lo, lda, ldw, M, N, K, nseg, nullptr);
     g.a_row_mod = a_row_mod;
     g.addrows = addrows;
     g.ldadd = ldo;

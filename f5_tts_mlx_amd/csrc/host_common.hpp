@@ -1,7 +1,9 @@
 // Host-side plumbing shared by the engine (engine.hip), the vocoder (vocoder.hip) and the duration predictor (duration.hip): declarations of both kernel builds, the
-// operand-type dispatch, the weights-arena bump allocator and the fp32 -> 16-bit upload.
+// operand-type dispatch, the weights store (arena plan, tensor map, fp32 -> 16-bit upload), the launch view of a call, the fp16
+// saturation scope and the hipGraph cache.
 #pragma once
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 // the kernel sources are built twice (bf16 operands: namespace f5bf, fp16 operands: namespace f5hf, op16.hpp); this file is
@@ -44,6 +46,25 @@ using f5bf::f5_launch_splice;
 using f5bf::f5_launch_text_embed;
 using f5bf::f5_launch_text_pos_table;
 using f5bf::f5_launch_time_sinus;
+
+// operands, shape and bias of a GEMM launch on raw operand pointers; everything else zero
+static inline F5GemmArgs f5_gemm_args(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, int lda, int ldw, int M, int N,
+                                      int K, int nseg, const float* bias) {
+    F5GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A[0] = (const op16_t*)a_hi;
+    g.A[1] = (const op16_t*)a_lo;
+    g.W[0] = (const op16_t*)w_hi;
+    g.W[1] = (const op16_t*)w_lo;
+    g.lda = lda;
+    g.ldw = ldw;
+    g.M = M;
+    g.N = N;
+    g.K = K;
+    g.nseg = nseg;
+    g.bias = bias;
+    return g;
+}
 
 // Kernels of one operand type.  `h` selects the fp16 build.
 struct Ops {
@@ -131,19 +152,7 @@ struct Ops {
     int qkv_rope(const op16_t* a_hi, const op16_t* a_lo, const op16_t* w_hi, const op16_t* w_lo, const float* bias, const float* rope_cos,
                  const float* rope_sin, op16_t* qk_hi, op16_t* qk_lo, op16_t* vt_hi, op16_t* vt_lo, int B, int seq_len, int npad, int heads,
                  int dmodel, int nseg, hipStream_t s) const {
-        F5GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.A[0] = a_hi;
-        g.A[1] = a_lo;
-        g.W[0] = w_hi;
-        g.W[1] = w_lo;
-        g.lda = dmodel;
-        g.ldw = dmodel;
-        g.M = B * seq_len;
-        g.N = 3 * dmodel;
-        g.K = dmodel;
-        g.nseg = nseg;
-        g.bias = bias;
+        F5GemmArgs g = f5_gemm_args(a_hi, a_lo, w_hi, w_lo, dmodel, dmodel, B * seq_len, 3 * dmodel, dmodel, nseg, bias);
         g.out_bf[0] = qk_hi;
         g.out_bf[1] = qk_lo;
         g.ldob = 2 * dmodel;
@@ -248,3 +257,219 @@ static inline int f5_upload_tensor(char* arena, const TensorDst& d, const float*
                                  d.src_rows, hipMemcpyHostToDevice));
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// weight store: the arena plan of one model handle, its tensor map and the loading protocol
+// (weights_bytes -> set_arena -> load_tensor ... / mark_all_loaded -> finalize)
+// ------------------------------------------------------------------------------------------------
+struct WeightStore {
+    const char* label = "";   // prefix of the messages: "" (engine), "vocoder ", "duration predictor "
+    char* arena = nullptr;
+    size_t arena_need = 0, arena_bytes = 0;
+    bool finalized = false;
+    int np = 1;               // precision parts (1, or 2: hi + lo)
+    bool f16 = false;         // 16-bit operand type of the matrices
+    std::unordered_map<std::string, std::vector<TensorDst>> tmap;
+
+    void add_f32(const std::string& name, size_t off, std::vector<int64_t> shape) {
+        TensorDst d;
+        d.kind = 0;
+        d.off = off;
+        d.shape = shape;
+        tmap[name].push_back(d);
+    }
+    void add_mat(const std::string& name, const MatBF& m, int row0, int src_rows, int src_cols, int c0, int c1, int dst_c0,
+                 std::vector<int64_t> shape) {
+        TensorDst d;
+        d.kind = 1;
+        d.mat = m;
+        d.row0 = row0;
+        d.src_rows = src_rows;
+        d.src_cols = src_cols;
+        d.c0 = c0;
+        d.c1 = c1;
+        d.dst_c0 = dst_c0;
+        d.shape = shape;
+        tmap[name].push_back(d);
+    }
+    void add_mat(const std::string& name, const MatBF& m, int rows, int cols) { add_mat(name, m, 0, rows, cols, 0, cols, 0, {rows, cols}); }
+
+    int set_arena(void* dev_arena, size_t bytes, hipStream_t s) {
+        F5_REQUIRE(bytes >= arena_need, "%sweights arena too small: %zu < %zu", label, bytes, arena_need);
+        F5_REQUIRE(((uintptr_t)dev_arena & 255) == 0, "%sweights arena must be 256-byte aligned", label);
+        arena = (char*)dev_arena;
+        arena_bytes = bytes;
+        F5_HIP_CHECK(hipMemsetAsync(dev_arena, 0, arena_need, s));   // zero pads
+        F5_HIP_CHECK(hipStreamSynchronize(s));
+        return 0;
+    }
+    // destinations of tensor `key`; `name` is what the caller passed (the message names it)
+    int lookup(const std::string& key, const char* name, std::vector<TensorDst>** dsts) {
+        auto it = tmap.find(key);
+        F5_REQUIRE(it != tmap.end(), "unknown %stensor name '%s'", label, name);
+        *dsts = &it->second;
+        return 0;
+    }
+    // the exact-shape check of every destination; count = number of elements
+    int match(const char* name, const std::vector<TensorDst>& dsts, int ndim, const int64_t* shape, size_t* count) const {
+        for (const TensorDst& d : dsts) {
+            F5_REQUIRE((int)d.shape.size() == ndim, "tensor '%s': expected %zu dims, got %d", name, d.shape.size(), ndim);
+            for (int i = 0; i < ndim; ++i)
+                F5_REQUIRE(d.shape[i] == shape[i], "tensor '%s': dim %d is %lld, expected %lld", name, i, (long long)shape[i],
+                           (long long)d.shape[i]);
+        }
+        *count = 1;
+        for (int i = 0; i < ndim; ++i) *count *= (size_t)shape[i];
+        return 0;
+    }
+    int upload(TensorDst& d, const float* host, size_t count) {
+        RC(f5_upload_tensor(arena, d, host, count, np, f16));
+        d.loaded = true;
+        return 0;
+    }
+    void mark_all_loaded() {
+        for (auto& kv : tmap)
+            for (auto& d : kv.second) d.loaded = true;
+    }
+    int require_loaded() const {
+        for (auto& kv : tmap)
+            for (auto& d : kv.second) F5_REQUIRE(d.loaded, "%stensor '%s' was never loaded", label, kv.first.c_str());
+        return 0;
+    }
+};
+
+// ------------------------------------------------------------------------------------------------
+// launch view: typed pointers into the workspace and the arena of one call, and the GEMM argument base
+// ------------------------------------------------------------------------------------------------
+struct LaunchView {
+    const char* arena;
+    char* ws;
+    int np;
+    Ops ops;
+    template <typename T>
+    T* p(size_t off) const { return reinterpret_cast<T*>(ws + off); }
+    template <typename T>
+    const T* a(size_t off) const { return reinterpret_cast<const T*>(arena + off); }
+    op16_t* pb(const size_t (&offs)[2], int part) const { return part < np ? reinterpret_cast<op16_t*>(ws + offs[part]) : nullptr; }
+    const op16_t* wm(const MatBF& m, int part) const {
+        if (part == 0) return reinterpret_cast<const op16_t*>(arena + m.hi);
+        return np == 2 ? reinterpret_cast<const op16_t*>(arena + m.lo) : nullptr;
+    }
+    int nseg() const { return np == 2 ? 3 : 1; }
+    F5GemmArgs gemm(const op16_t* a_hi, const op16_t* a_lo, int lda, const MatBF& w, int M, int N, int K, const float* bias) const {
+        return f5_gemm_args(a_hi, a_lo, wm(w, 0), wm(w, 1), lda, w.ld, M, N, K, nseg(), bias);
+    }
+};
+
+// fp16 range detector (op16.hpp): while an active one is alive the 16-bit packers of every launch of the fp16 build report saturation
+// into the call's status word (bit F5_STATUS_SATURATED).  Host-side: the pointer travels as a kernel argument, a captured graph keeps
+// the status word of the workspace it was captured against (part of the graph key).
+struct SatScope {
+    int* saved;
+    SatScope(bool active, int* status_word) : saved(f5hf::f5_sat_flag_host) {
+        if (active) f5hf::f5_sat_flag_host = status_word;
+    }
+    ~SatScope() { f5hf::f5_sat_flag_host = saved; }
+};
+
+// ------------------------------------------------------------------------------------------------
+// hipGraph cache of one model handle: captured calls by (key, workspace), least recently used evicted
+// ------------------------------------------------------------------------------------------------
+struct GraphCache {
+    struct Entry {
+        std::string key;                    // everything a captured node depends on BY VALUE
+        const void* workspace;              // the captured nodes reference this buffer
+        std::vector<hipGraphExec_t> execs;  // the segments of the call, launched in order
+        uint64_t stamp;                     // last use (LRU)
+        hipEvent_t done;                    // recorded after every launch: an exec is only destroyed once its last replay has finished
+    };
+    std::vector<Entry> entries;
+    size_t cap = 8;
+    bool purge = true;    // an entry captured against another workspace is dead (the caller re-allocated it): dropped before an insert
+    uint64_t clock = 0;
+
+    GraphCache() = default;
+    GraphCache(const GraphCache&) = delete;
+    GraphCache& operator=(const GraphCache&) = delete;
+    ~GraphCache() { clear(); }
+
+    int size() const { return (int)entries.size(); }
+    void clear() {
+        while (!entries.empty()) erase(entries.size() - 1);
+    }
+    void set_cap(size_t n) {
+        cap = n;
+        while (entries.size() > cap) evict_lru();
+    }
+    Entry* find(const std::string& key, const void* workspace) {
+        for (Entry& g : entries)
+            if (g.workspace == workspace && g.key == key) {
+                g.stamp = ++clock;
+                return &g;
+            }
+        return nullptr;
+    }
+    // Captures body(0) ... body(nseg - 1) on `s`, one exec each, and inserts the entry.  A failure leaves nothing behind: the graph
+    // and the execs built so far are destroyed; the body's return code goes ahead of the HIP error.
+    template <typename Body>
+    int capture(const std::string& key, const void* workspace, hipStream_t s, int nseg, Body&& body, Entry** out) {
+        for (size_t i = purge ? entries.size() : 0; i-- > 0;)
+            if (entries[i].workspace != workspace) erase(i);
+        while (entries.size() >= cap && !entries.empty()) evict_lru();
+        Entry e{key, workspace, {}, 0, nullptr};
+        for (int seg = 0; seg < nseg; ++seg) {
+            hipGraph_t graph = nullptr;
+            hipGraphExec_t exec = nullptr;
+            hipError_t err = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
+            int rc = 0;
+            if (err == hipSuccess) {
+                rc = body(seg);
+                err = hipStreamEndCapture(s, &graph);
+            }
+            if (!rc && err == hipSuccess) err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+            if (graph) (void)hipGraphDestroy(graph);
+            if (rc || err != hipSuccess) {
+                destroy_execs(e);
+                if (rc) return rc;
+                f5_set_error("graph capture failed: %s (segment %d of %d)", hipGetErrorString(err), seg, nseg);
+                return 1;
+            }
+            e.execs.push_back(exec);
+        }
+        if (hipEventCreateWithFlags(&e.done, hipEventDisableTiming) != hipSuccess) {
+            destroy_execs(e);
+            f5_set_error("graph capture: hipEventCreateWithFlags failed");
+            return 3;
+        }
+        e.stamp = ++clock;
+        entries.push_back(std::move(e));
+        *out = &entries.back();
+        return 0;
+    }
+    static int launch(Entry* g, hipStream_t s) {
+        for (hipGraphExec_t x : g->execs) F5_HIP_CHECK(hipGraphLaunch(x, s));
+        F5_HIP_CHECK(hipEventRecord(g->done, s));
+        return 0;
+    }
+
+  private:
+    static void destroy_execs(Entry& g) {
+        for (hipGraphExec_t x : g.execs) (void)hipGraphExecDestroy(x);
+        g.execs.clear();
+    }
+    void erase(size_t i) {
+        Entry& g = entries[i];
+        if (g.done) {
+            (void)hipEventSynchronize(g.done);        // the exec may still be running on the stream of its last launch
+            (void)hipEventDestroy(g.done);
+        }
+        destroy_execs(g);
+        entries.erase(entries.begin() + i);
+    }
+    void evict_lru() {
+        size_t lru = 0;
+        for (size_t i = 1; i < entries.size(); ++i)
+            if (entries[i].stamp < entries[lru].stamp) lru = i;
+        erase(lru);
+    }
+};

@@ -176,6 +176,88 @@ def test_engine_handle_errors_and_sizes_without_gpu():
     assert lib.f5_engine_create(C.byref(bad), 0, C.byref(hb)) != 0 and b"dim" in lib.f5_last_error()
 
 
+ENGINE_SWITCHES = ("q_premul", "qkv_transposed", "ln_fusion", "null_keeps_cond", "sat_check", "graph_split")
+ENGINE_TRISTATES = ("attn_pipe", "ln_fold", "fold_stats")
+ENGINE_OPTIONS = ENGINE_SWITCHES + ENGINE_TRISTATES + ("gemm_flags",)
+
+
+@pytest.fixture()
+def engine_handle():
+    """an engine handle without an arena: creating one plans sizes and touches no device"""
+    lib = E.load_library()
+    lib.f5_engine_destroy.restype = None
+    h = C.c_void_p()
+    cfg = E.to_c_config(F5TTS_335M)
+    assert lib.f5_engine_create(C.byref(cfg), E.PRECISIONS["f16"], C.byref(h)) == 0
+    yield lib, h
+    lib.f5_engine_destroy(h)
+
+
+def test_engine_options_round_trip_with_their_normalisation(engine_handle):
+    lib, h = engine_handle
+
+    def put(name, value):
+        got = C.c_int(12345)
+        assert lib.f5_engine_set_option(h, name.encode(), value) == 0, lib.f5_last_error()
+        assert lib.f5_engine_get_option(h, name.encode(), C.byref(got)) == 0, lib.f5_last_error()
+        return got.value
+
+    defaults = {}
+    for name in ENGINE_OPTIONS:
+        v = C.c_int(12345)
+        assert lib.f5_engine_get_option(h, name.encode(), C.byref(v)) == 0
+        defaults[name] = v.value
+    assert defaults == dict(q_premul=1, qkv_transposed=1, ln_fusion=0, null_keeps_cond=0, sat_check=1, graph_split=0, attn_pipe=-1,
+                            ln_fold=-1, fold_stats=-1, gemm_flags=0)
+    for name in ENGINE_SWITCHES:
+        assert [put(name, v) for v in (5, 0, -7, 1)] == [1, 0, 1, 1], name
+    for name in ENGINE_TRISTATES:
+        assert [put(name, v) for v in (-7, 3, 0, -1, 1)] == [-1, 1, 0, -1, 1], name
+    assert [put("gemm_flags", v) for v in (4096, -3, 0)] == [4096, -3, 0]
+    # one option's value never leaks into another's
+    for name in ENGINE_OPTIONS:
+        put(name, 0)
+    assert put("ln_fold", 1) == 1
+    for name in ENGINE_OPTIONS:
+        v = C.c_int(12345)
+        assert lib.f5_engine_get_option(h, name.encode(), C.byref(v)) == 0 and v.value == (1 if name == "ln_fold" else 0), name
+
+
+def test_unknown_engine_option_lists_every_name(engine_handle):
+    lib, h = engine_handle
+    v = C.c_int()
+    for rc in (lib.f5_engine_set_option(h, b"no_such_option", 1), lib.f5_engine_get_option(h, b"no_such_option", C.byref(v))):
+        msg = lib.f5_last_error().decode()
+        assert rc != 0 and msg.startswith("unknown engine option no_such_option")
+        listed = [n.strip() for n in msg[msg.index("(") + 1:msg.rindex(")")].split(",")]
+        assert len(ENGINE_OPTIONS) == 10 and sorted(listed) == sorted(ENGINE_OPTIONS), msg
+    assert lib.f5_engine_set_option(h, None, 1) != 0 and lib.f5_engine_get_option(h, b"ln_fold", None) != 0
+
+
+def test_engine_load_tensor_checks_name_shape_and_arena(engine_handle):
+    lib, h = engine_handle
+    buf = (C.c_float * (1024 * 1024))()
+    ok_name = b"transformer.transformer_blocks.0.attn.to_q.weight"
+    shp = (C.c_int64 * 2)(1024, 1024)
+    assert lib.f5_load_tensor(h, ok_name, buf, 2, shp) != 0                            # right name and shape, no arena yet
+    assert lib.f5_last_error() == b"f5_set_weights_arena must be called first"
+    assert lib.f5_load_tensor(h, b"transformer.no_such.weight", buf, 2, shp) != 0
+    assert lib.f5_last_error() == b"unknown tensor name 'transformer.no_such.weight'"
+    assert lib.f5_load_tensor(h, ok_name, buf, 3, (C.c_int64 * 3)(1024, 1024, 1)) != 0
+    assert lib.f5_last_error() == b"tensor '" + ok_name + b"': expected 2 dims, got 3"
+    assert lib.f5_load_tensor(h, ok_name, buf, 2, (C.c_int64 * 2)(1024, 512)) != 0
+    assert lib.f5_last_error() == b"tensor '" + ok_name + b"': dim 1 is 512, expected 1024"
+    # a tensor that is split over several destinations (x | cond | text columns of the input projection) is checked the same way
+    proj = b"transformer.input_embed.proj.weight"
+    assert lib.f5_load_tensor(h, proj, buf, 2, (C.c_int64 * 2)(1024, 711)) != 0
+    assert lib.f5_last_error() == b"tensor '" + proj + b"': dim 1 is 711, expected 712"
+    assert lib.f5_load_tensor(h, proj, buf, 2, (C.c_int64 * 2)(1024, 712)) != 0
+    assert lib.f5_last_error() == b"f5_set_weights_arena must be called first"
+    assert lib.f5_finalize_weights(h, None) != 0 and lib.f5_last_error() == b"arena not set"
+    assert lib.f5_mark_weights_loaded(h) == 0
+    assert lib.f5_finalize_weights(h, None) != 0 and lib.f5_last_error() == b"arena not set"
+
+
 def test_f16_precision_and_host_half_conversion_without_gpu():
     """precision "f16": an engine can be created / sized without a GPU, its arena equals the bf16 one (one 16-bit copy per
     matrix), and the host-side float -> fp16 conversion used by f5_load_tensor is IEEE round-to-nearest-even with

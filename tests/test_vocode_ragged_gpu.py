@@ -256,6 +256,35 @@ def test_graph_serves_new_lengths_and_keeps_the_plain_graph_apart(vweights, mel_
     assert ve.graph_count() == 0
 
 
+def test_graph_cache_drops_a_dead_workspace_and_stays_bounded(vweights):
+    """The two rules of the vocoder's graph cache: a graph captured against a workspace the caller has since replaced is dropped before
+    the next capture, and at most 8 graphs are kept.  B = 1 and a few frames: every decode is a handful of small launches."""
+    vg = Vocos(vweights, precision="f16", device=DEV, use_graph=True)
+    ve = Vocos(vweights, precision="f16", device=DEV, use_graph=False)
+    r = np.random.default_rng(16)
+    mel = torch.from_numpy((r.standard_normal((1, 16, 100)) * 2.0 - 1.0).astype(np.float32)).to(DEV)
+
+    def same(n):
+        got = vg.decode(mel[:, :n].contiguous())
+        want = ve.decode(mel[:, :n].contiguous())
+        torch.cuda.synchronize()
+        return got.shape == (HOP * (n - 1),) and torch.equal(bits(got), bits(want))
+
+    assert vg.graph_count() == 0
+    assert same(8) and vg.graph_count() == 1
+    first = vg._workspace                          # kept alive: the larger workspace is then certain to lie at another address
+    assert same(16) and vg.graph_count() == 1      # N = 16 needs a larger workspace: the graph of N = 8 went with the old one
+    assert vg._workspace.data_ptr() != first.data_ptr()
+    second = vg._workspace.data_ptr()
+    assert same(12) and vg.graph_count() == 2      # fits the same workspace: a second graph beside the first
+    for i, n in enumerate((4, 5, 6, 7, 9, 10, 11)):
+        assert same(n), n
+        assert vg.graph_count() == min(3 + i, 8), (n, vg.graph_count())
+    assert vg._workspace.data_ptr() == second and vg.graph_count() == 8      # nine shapes on one workspace, eight graphs
+    assert same(16) and same(11) and vg.graph_count() == 8                    # evicted and kept entries both still decode right
+    assert ve.graph_count() == 0
+
+
 # ---- generate ------------------------------------------------------------------------------------------------------------------
 def test_generate_vocode_batched(tmp_path, lib, vweights):
     """generate(batch_sentences=True, vocode_batched=True) against vocode_batched=False on the text of test_generate_batch_sentences,

@@ -101,6 +101,35 @@ def test_workspace_plan_covers_the_staged_lengths(handle):
     assert lib.f5_vocoder_graph_count(handle) == 0
 
 
+def test_load_tensor_checks_name_shape_and_arena(handle):
+    lib = E.load_library()
+    buf = (C.c_float * (V.INTER * V.DIM))()
+
+    def load(name, *shape):
+        rc = lib.f5_vocoder_load_tensor(handle, name, buf, len(shape), (C.c_int64 * len(shape))(*shape))
+        return rc, lib.f5_last_error()
+
+    no_arena = b"f5_vocoder_set_weights_arena must be called first"
+    pw1 = b"backbone.convnext.3.pwconv1.weight"
+    assert load(pw1, V.INTER, V.DIM) == (2, no_arena)                                   # right name and shape, no arena yet
+    assert load(b"backbone.convnext.99.pwconv1.weight", V.INTER, V.DIM) == (2, b"unknown vocoder tensor name 'backbone.convnext.99.pwconv1.weight'")
+    assert load(pw1, V.INTER, V.DIM, 1) == (2, b"tensor '" + pw1 + b"': unexpected shape")               # wrong rank
+    assert load(pw1, V.INTER, V.DIM // 2) == (2, b"tensor '" + pw1 + b"': unexpected shape")            # wrong dimension
+    assert load(pw1, V.DIM, V.INTER) == (2, b"tensor '" + pw1 + b"': unexpected shape")                 # transposed: the same count
+    # the shapes the loader tolerates pass its shape check (and stop at the arena)
+    dw, gamma = b"backbone.convnext.0.dwconv.weight", b"backbone.convnext.0.gamma"
+    assert load(dw, V.DIM, 1, 7) == (2, no_arena) and load(dw, V.DIM, 7, 1) == (2, no_arena)
+    assert load(dw, V.DIM, 7) == (2, b"tensor '" + dw + b"': unexpected shape")
+    assert load(gamma, V.DIM) == (2, no_arena) and load(gamma, 1, 1, V.DIM) == (2, no_arena)
+    assert load(gamma, 1, V.DIM + 1) == (2, b"tensor '" + gamma + b"': unexpected shape")
+    # the embed conv weight has its own layout check
+    emb = b"backbone.embed.weight"
+    assert load(emb, V.DIM, V.N_MELS, 7) == (2, no_arena) and load(emb, V.DIM, 7, V.N_MELS) == (2, no_arena)
+    assert load(emb, V.DIM, V.N_MELS) == (2, b"tensor '" + emb + b"': expected (dim, n_mels, 7) or (dim, 7, n_mels)")
+    assert load(emb, V.DIM, 7, V.N_MELS + 1) == (2, b"tensor '" + emb + b"': expected (dim, n_mels, 7) or (dim, 7, n_mels)")
+    assert lib.f5_vocoder_finalize(handle, None) != 0 and lib.f5_last_error() == b"vocoder arena not set"
+
+
 # ---- Vocos.decode validates lens on the host -----------------------------------------------------------------------------------
 @pytest.mark.parametrize("lens", [LENS, tuple(LENS), torch.tensor(LENS), torch.tensor(LENS, dtype=torch.int32), np.array(LENS),
                                   [np.int64(v) for v in LENS]])
