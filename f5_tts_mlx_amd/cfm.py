@@ -206,6 +206,9 @@ class F5TTS:
         use_graph="auto",                        # extension: True / False / "auto" (graph from the 2nd call of a shape on)
         pad_to: Optional[int] = None,            # extension: padded length of a SHARD of a larger batch = that batch's max duration
                                                  # (the key-padding mask of cfm.py:333-336 is then built even for a one-utterance shard)
+        edit_mask: Optional[torch.Tensor] = None,  # extension (speech editing): bool (b, n), True = keep this frame of `cond`; the
+                                                 # conditioning mask becomes lens_to_mask(lens) & edit_mask -- the rule of the PyTorch
+                                                 # F5-TTS sampler, so an all-True mask is the call without it (docs/edit.md)
     ) -> tuple[torch.Tensor, torch.Tensor]:
         self.eval()
         device = self.transformer.device
@@ -258,9 +261,26 @@ class F5TTS:
 
         t = time_grid(steps, sway_sampling_coef)
 
+        # speech editing: the per-frame conditioning mask, padded with False to max_duration, cleared at n >= duration[b] and combined
+        # with the prefix rule (cond_mask of cfm.py:323-331 AND the caller's mask); lengths, clamps, noise and time grid are untouched
+        cond_keep = None
+        if edit_mask is not None:
+            edit_mask = torch.as_tensor(edit_mask)
+            if edit_mask.dtype != torch.bool or edit_mask.ndim != 2 or edit_mask.shape[0] != batch:
+                raise ValueError(f"edit_mask must be a bool tensor (b, n) with b = {batch}, got {edit_mask.dtype} {tuple(edit_mask.shape)}")
+            if edit_mask.shape[1] > max_duration and bool(edit_mask[:, max_duration:].any()):
+                raise ValueError(f"edit_mask keeps frames beyond max_duration = {max_duration}")
+            n_mask = min(int(edit_mask.shape[1]), max_duration)
+            frame = torch.arange(max_duration)[None, :]
+            cond_keep = torch.zeros((batch, max_duration), dtype=torch.bool)
+            cond_keep[:, :n_mask] = edit_mask[:, :n_mask].cpu()
+            cond_keep &= (frame < lens[:, None]) & (frame < duration[:, None])
+            cond_keep = cond_keep.to(device)
+
         out, trajectory = self.transformer.engine.sample(
             text.to(device).contiguous(), cond_p, lens.tolist(), duration.tolist(), y0, t, method=method,
-            cfg_strength=float(cfg_strength), use_mask=(batch > 1 or pad_to is not None), use_graph=use_graph, return_trajectory=True)
+            cfg_strength=float(cfg_strength), use_mask=(batch > 1 or pad_to is not None), use_graph=use_graph, return_trajectory=True,
+            cond_keep=cond_keep)
 
         if exists(self._vocoder):
             out = self._vocoder(out)

@@ -323,3 +323,87 @@ extern "C" int f5_resample_batch(const float* wave, int B, int64_t L, const floa
     F5_LAUNCH_CHECK();
     return 0;
 }
+
+// =================================================================================================
+// Waveform patch (speech editing: no reference counterpart).  The vocoded result of an edit call keeps the original samples outside
+// the edited spans: row b of `out` is laid out by a table of segments (dst_begin, dst_end, src_begin), sorted and contiguous from 0;
+// src_begin >= 0 = a KEPT segment (out = src[src_begin + s - dst_begin], selected: the source's own bits), src_begin < 0 = a
+// REGENERATED one (out = gen).  Where a kept segment meets a regenerated neighbour (the table entry before / after it, whatever its
+// length) its first / last F samples cross-fade: out = g + fade[i] (o - g), one FMA on the fp32 difference, i counted from the seam.
+// Samples past the last segment are exactly 0.0f.  The table travels as a kernel argument (copied at launch time, like
+// stage_words_kernel's words): WP_ROWS_MAX rows of at most 64 segments per launch.
+// =================================================================================================
+#define WP_SEG_MAX 64
+#define WP_WORDS 960                 // int32 words of table per launch (a kernel argument of 3 840 bytes)
+struct F5WavePatchTable {
+    int w[WP_WORDS];                 // [rows][S][3]
+};
+__global__ __launch_bounds__(256) void wave_patch_kernel(const float* __restrict__ gen, const float* __restrict__ src,
+                                                         F5WavePatchTable t, const float* __restrict__ fade, float* __restrict__ out,
+                                                         long L, long Ls, int S, int F) {
+    const long s = (long)blockIdx.x * 256 + threadIdx.x;
+    if (s >= L) return;
+    const int* seg = t.w + (size_t)blockIdx.y * S * 3;
+    gen += (long)blockIdx.y * L;                                    // the launcher offsets gen / src / out to the first row of the launch
+    src += (long)blockIdx.y * Ls;
+    out += (long)blockIdx.y * L;
+    float v = 0.0f;                                                 // past the last segment
+    for (int k = 0; k < S; ++k) {
+        const int d0 = seg[3 * k], d1 = seg[3 * k + 1], s0 = seg[3 * k + 2];
+        if (s < d0 || s >= d1) continue;
+        const float g = gen[s];
+        v = g;
+        if (s0 >= 0) {
+            const long si = (long)s0 + (s - d0);
+            if (si < Ls) {                                          // (checked on the host: a table that lies cannot take the load out of the row)
+                const float o = src[si];
+                v = o;
+                const long i0 = s - d0, i1 = (long)d1 - 1 - s;
+                if (i0 < F && k > 0 && seg[3 * (k - 1) + 2] < 0) v = fmaf(fade[i0], o - g, g);
+                else if (i1 < F && k + 1 < S && seg[3 * (k + 1) + 2] < 0) v = fmaf(fade[i1], o - g, g);
+            }
+        }
+        break;
+    }
+    out[s] = v;
+}
+
+extern "C" int f5_op_wave_patch(const float* gen, const float* src, const int32_t* segs_host, const float* fade, float* out, int B,
+                                int64_t L, int64_t Ls, int S, int F, void* stream) {
+    F5_REQUIRE(gen && src && segs_host && out && (fade || F <= 0), "wave_patch: null pointer");
+    F5_REQUIRE(B >= 1 && B <= 65535, "wave_patch: batch %d outside 1..65535", B);
+    F5_REQUIRE(S >= 1 && S <= WP_SEG_MAX, "wave_patch: S = %d segments per row outside 1..%d", S, WP_SEG_MAX);
+    F5_REQUIRE(F >= 0, "wave_patch: negative fade length F = %d", F);
+    F5_REQUIRE(L >= 0 && L <= 0x7fffffff && Ls >= 0 && Ls <= 0x7fffffff, "wave_patch: lengths L = %lld, Ls = %lld outside 0..2^31 - 1",
+               (long long)L, (long long)Ls);
+    for (int b = 0; b < B; ++b) {
+        const int32_t* t = segs_host + (size_t)b * S * 3;
+        int64_t at = 0;
+        for (int k = 0; k < S; ++k) {
+            const int64_t d0 = t[3 * k], d1 = t[3 * k + 1], s0 = t[3 * k + 2];
+            F5_REQUIRE(d0 == at && d1 >= d0,
+                       "wave_patch: row %d segment %d is [%lld, %lld) where %lld was expected: the table must be sorted and contiguous from 0",
+                       b, k, (long long)d0, (long long)d1, (long long)at);
+            F5_REQUIRE(d1 <= L, "wave_patch: row %d segment %d ends at %lld, beyond the row length L = %lld", b, k, (long long)d1, (long long)L);
+            at = d1;
+            if (s0 < 0) continue;
+            F5_REQUIRE(s0 + (d1 - d0) <= Ls, "wave_patch: row %d kept segment %d reads source samples [%lld, %lld), outside [0, %lld]", b, k,
+                       (long long)s0, (long long)(s0 + d1 - d0), (long long)Ls);
+            const int nfade = (k > 0 && t[3 * (k - 1) + 2] < 0 ? 1 : 0) + (k + 1 < S && t[3 * (k + 1) + 2] < 0 ? 1 : 0);
+            F5_REQUIRE(d1 - d0 >= (int64_t)nfade * F,
+                       "wave_patch: row %d kept segment %d is %lld samples long, shorter than its %d fade(s) of F = %d samples", b, k,
+                       (long long)(d1 - d0), nfade, F);
+        }
+    }
+    if (L == 0) return 0;
+    const int rows_max = WP_WORDS / (3 * S);
+    for (int b0 = 0; b0 < B; b0 += rows_max) {
+        const int rows = B - b0 < rows_max ? B - b0 : rows_max;
+        F5WavePatchTable t;
+        memcpy(t.w, segs_host + (size_t)b0 * S * 3, (size_t)rows * S * 3 * sizeof(int));
+        hipLaunchKernelGGL(wave_patch_kernel, dim3((unsigned)((L + 255) / 256), (unsigned)rows), dim3(256), 0, (hipStream_t)stream,
+                           gen + (size_t)b0 * L, src + (size_t)b0 * Ls, t, fade, out + (size_t)b0 * L, (long)L, (long)Ls, S, F);
+    }
+    F5_LAUNCH_CHECK();
+    return 0;
+}

@@ -70,6 +70,7 @@ struct Workspace {
     size_t foldc[2];               // c1, c2 tables, [nfe][L][3 D + FF] floats each
     bool fold_planned;
     size_t vt_bytes;
+    size_t cond_keep;              // f5_sample_edit: the per-frame conditioning mask, [B][N] bytes, BEHIND everything above (no other offset moves)
 };
 
 // Per-engine launch options: everything that reaches a kernel as a by-value argument or changes the launch sequence of sample()
@@ -500,6 +501,7 @@ static Workspace plan_workspace(const f5_engine* e, int B, int N, int nt, int st
         w.ffh8 = b.take(M2 * FF);
         w.ffh8s = b.take(M2 * (FF / 32));
     }
+    w.cond_keep = b.take(M1);
     w.total = b.off;
     return w;
 }
@@ -521,6 +523,7 @@ struct Ctx : LaunchView {
     hipStream_t s;
     int B, N, nt, nb;   // nb = branches evaluated per function evaluation (1 or 2)
     int npad;
+    bool edit = false;  // f5_sample_edit: conditioning frames are chosen by the mask at w.cond_keep instead of n < lens[b]
     bool use_mask;
 };
 
@@ -661,7 +664,11 @@ static int run_prep(const Ctx& c, int nfe) {
         cur ^= 1;
     }
     // --- hoisted part of the input projection: Hc = [cond | text] * Wct^T + b   (dit.py:249-250)
-    RC(K.pack_cond_text(c.p<float>(w.cond), c.p<int>(w.lens), c.p<float>(w.te[cur]), c.pb(w.ct, 0), c.pb(w.ct, 1), c.B,
+    if (c.edit)
+        RC(K.pack_cond_text_keep(c.p<float>(w.cond), c.p<uint8_t>(w.cond_keep), c.p<float>(w.te[cur]), c.pb(w.ct, 0), c.pb(w.ct, 1),
+                                 c.B, c.N, cf.mel_dim, Dt, e->opt.null_keeps_cond, s));
+    else
+        RC(K.pack_cond_text(c.p<float>(w.cond), c.p<int>(w.lens), c.p<float>(w.te[cur]), c.pb(w.ct, 0), c.pb(w.ct, 1), c.B,
                                 c.N, cf.mel_dim, Dt, e->opt.null_keeps_cond, s));
     F5GemmArgs gh = gemm_base(c, c.pb(w.ct, 0), c.pb(w.ct, 1), 128 + Dt, e->wct, M2, D, 128 + Dt, c.a<float>(e->bproj));
     gh.out_f32 = c.p<float>(w.hc);
@@ -1095,11 +1102,14 @@ static Ctx make_ctx(f5_engine* e, const f5_sample_args* a, hipStream_t s) {
     return c;
 }
 
-extern "C" int f5_sample(f5_engine* e, const f5_sample_args* a, void* stream) {
+// f5_sample (edit = false) and f5_sample_edit (the mask replaces n < lens[b] in the hoisted input packing and the final splice)
+static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* cond_keep, bool edit, void* stream) {
+    F5_REQUIRE(!edit || cond_keep, "f5_sample_edit: cond_keep is null");
     RC(check_args(e, a));
     F5_REQUIRE(a->y0 && a->t && a->out, "null pointer in f5_sample_args (y0/t/out)");
     hipStream_t s = (hipStream_t)stream;
     Ctx c = make_ctx(e, a, s);
+    c.edit = edit;
     F5_REQUIRE(a->workspace_bytes >= c.w.total, "workspace too small: %zu < %zu", a->workspace_bytes, c.w.total);
     const int mel = e->cfg.mel_dim;
     const size_t M1 = (size_t)c.B * c.N;
@@ -1124,12 +1134,14 @@ extern "C" int f5_sample(f5_engine* e, const f5_sample_args* a, void* stream) {
         }
     }
     RC(stage_inputs(c, a, nullptr, tnfe, dts));
+    // the mask travels like text / cond / y0: copied into the workspace outside the captured part, so one graph serves every mask of a shape
+    if (edit) RC(f5_launch_copy_bytes(cond_keep, c.ws + c.w.cond_keep, M1, s));
 
     // hipGraph cache.  The key is everything a captured node depends on BY VALUE: shapes, solver, branch count, masking and the
     // workspace address.  Per-call scalars (cfg strength, time grid, dt) are read from workspace memory staged above.
     char shape_key[192];
-    snprintf(shape_key, sizeof(shape_key), "B%d N%d nt%d st%d m%d nb%d mask%d ke%d ws%p opt", c.B, c.N, c.nt, a->steps, a->method, c.nb,
-             (int)c.use_mask, g_knob_epoch, a->workspace);
+    snprintf(shape_key, sizeof(shape_key), "B%d N%d nt%d st%d m%d nb%d mask%d edit%d ke%d ws%p opt", c.B, c.N, c.nt, a->steps, a->method,
+             c.nb, (int)c.use_mask, (int)c.edit, g_knob_epoch, a->workspace);
     std::string key(shape_key);
     for (const OptDesc& o : k_options) key += " " + std::to_string(e->opt.*o.member);
     const bool graph_on = a->use_graph == F5_GRAPH_ON, graph_auto = a->use_graph == F5_GRAPH_AUTO;
@@ -1156,9 +1168,16 @@ extern "C" int f5_sample(f5_engine* e, const f5_sample_args* a, void* stream) {
         RC(run_sample_body(c, a));
     }
     const float* ylast = c.p<float>(c.w.traj) + (size_t)(a->steps - 1) * M1 * mel;
-    RC(f5_launch_splice(c.p<float>(c.w.cond), ylast, c.p<int>(c.w.lens), a->out, c.B, c.N, mel, s));
+    if (edit)
+        RC(f5_launch_splice_keep(c.p<float>(c.w.cond), ylast, c.p<uint8_t>(c.w.cond_keep), a->out, c.B, c.N, mel, s));
+    else
+        RC(f5_launch_splice(c.p<float>(c.w.cond), ylast, c.p<int>(c.w.lens), a->out, c.B, c.N, mel, s));
     if (a->trajectory) RC(f5_launch_copy_words(c.ws + c.w.traj, a->trajectory, (size_t)a->steps * M1 * mel, s));
     return 0;
+}
+extern "C" int f5_sample(f5_engine* e, const f5_sample_args* a, void* stream) { return sample_impl(e, a, nullptr, false, stream); }
+extern "C" int f5_sample_edit(f5_engine* e, const f5_sample_args* a, const uint8_t* cond_keep_dev, void* stream) {
+    return sample_impl(e, a, cond_keep_dev, true, stream);
 }
 
 // Status word of the last f5_sample / f5_dit_forward that used this workspace (its FIRST 32-bit word, for every shape and solver):
@@ -1721,6 +1740,27 @@ extern "C" int f5_op_pack_cond_text(const float* cond, const int32_t* lens, cons
 extern "C" int f5_op_pack_x(const float* y, void* out_hi, void* out_lo, int rows, int mel_dim, void* stream) {
     F5_REQUIRE(mel_dim <= 128, "pack_x: mel_dim must be <= 128");
     return g_ops.pack_x(y, (op16_t*)out_hi, (op16_t*)out_lo, rows, mel_dim, (hipStream_t)stream);
+}
+extern "C" int f5_op_pack_cond_text_keep(const float* cond, const uint8_t* keep, const float* text_emb, void* out_hi, void* out_lo, int B,
+                                         int seq_len, int mel_dim, int dt, int null_keeps_cond, void* stream) {
+    F5_REQUIRE(cond && keep && text_emb && out_hi, "pack_cond_text_keep: null pointer");
+    F5_REQUIRE(B >= 1 && seq_len >= 1 && mel_dim >= 1 && dt >= 0, "pack_cond_text_keep: bad sizes B=%d seq_len=%d mel_dim=%d dt=%d", B, seq_len,
+               mel_dim, dt);
+    return g_ops.pack_cond_text_keep(cond, keep, text_emb, (op16_t*)out_hi, (op16_t*)out_lo, B, seq_len, mel_dim, dt, null_keeps_cond,
+                                     (hipStream_t)stream);
+}
+extern "C" int f5_op_splice_keep(const float* cond, const float* y, const uint8_t* keep, float* out, int B, int seq_len, int mel_dim,
+                                 void* stream) {
+    F5_REQUIRE(cond && y && keep && out, "splice_keep: null pointer");
+    F5_REQUIRE(B >= 1 && seq_len >= 1 && mel_dim >= 1, "splice_keep: bad sizes B=%d seq_len=%d mel_dim=%d", B, seq_len, mel_dim);
+    return f5_launch_splice_keep(cond, y, keep, out, B, seq_len, mel_dim, (hipStream_t)stream);
+}
+extern "C" int f5_op_gather_frames(const float* src, const int32_t* src_idx, float* cond_out, uint8_t* keep_out, int B, int n_src,
+                                   int seq_len, int mel_dim, void* stream) {
+    F5_REQUIRE(src && src_idx && cond_out && keep_out, "gather_frames: null pointer");
+    F5_REQUIRE(B >= 1 && n_src >= 1 && seq_len >= 1 && mel_dim >= 1, "gather_frames: bad sizes B=%d n_src=%d seq_len=%d mel_dim=%d", B, n_src,
+               seq_len, mel_dim);
+    return f5_launch_gather_frames(src, src_idx, cond_out, keep_out, B, n_src, seq_len, mel_dim, (hipStream_t)stream);
 }
 extern "C" int f5_op_splice(const float* cond, const float* y, const int32_t* lens, float* out, int B, int seq_len, int mel_dim,
                             void* stream) {

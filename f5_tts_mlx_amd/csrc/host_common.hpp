@@ -43,6 +43,9 @@ using f5bf::f5_launch_stage_words;
 using f5bf::f5_launch_copy_words;
 using f5bf::f5_launch_skinny_gemm;
 using f5bf::f5_launch_splice;
+using f5bf::f5_launch_splice_keep;
+using f5bf::f5_launch_gather_frames;
+using f5bf::f5_launch_copy_bytes;
 using f5bf::f5_launch_text_embed;
 using f5bf::f5_launch_text_pos_table;
 using f5bf::f5_launch_time_sinus;
@@ -122,6 +125,11 @@ struct Ops {
                        int mel_dim, int dt, int null_keeps_cond, hipStream_t s) const {
         return h ? f5hf::f5_launch_pack_cond_text(cond, lens, text_emb, H(hi), H(lo), B, seq_len, mel_dim, dt, null_keeps_cond, s)
                  : f5bf::f5_launch_pack_cond_text(cond, lens, text_emb, hi, lo, B, seq_len, mel_dim, dt, null_keeps_cond, s);
+    }
+    int pack_cond_text_keep(const float* cond, const uint8_t* keep, const float* text_emb, op16_t* hi, op16_t* lo, int B, int seq_len,
+                            int mel_dim, int dt, int null_keeps_cond, hipStream_t s) const {
+        return h ? f5hf::f5_launch_pack_cond_text_keep(cond, keep, text_emb, H(hi), H(lo), B, seq_len, mel_dim, dt, null_keeps_cond, s)
+                 : f5bf::f5_launch_pack_cond_text_keep(cond, keep, text_emb, hi, lo, B, seq_len, mel_dim, dt, null_keeps_cond, s);
     }
     int pack_x(const float* y, op16_t* hi, op16_t* lo, int rows, int mel_dim, hipStream_t s) const {
         return h ? f5hf::f5_launch_pack_x(y, H(hi), H(lo), rows, mel_dim, s) : f5bf::f5_launch_pack_x(y, hi, lo, rows, mel_dim, s);

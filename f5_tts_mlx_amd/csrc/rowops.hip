@@ -439,8 +439,12 @@ int f5_launch_text_embed(const int* text, int nt, const float* table, const floa
 // =================================================================================================
 // A operand of the hoisted input projection: rows [2][B*seq], cols [cond padded to 128 | text dt]
 // branch 0: cond masked by n < lens[b] (step_cond, cfm.py:331); branch 1: cond dropped (dit.py:249) unless null_keeps_cond
+// KEEP: the prefix test is replaced by a per-frame mask, keep[b][n] != 0 (speech editing: the infilling mask of cfm.py:198-224 at
+// sampling time).  The value is SELECTED by the test: a frame that is not kept is never loaded.
 // =================================================================================================
+template <bool KEEP>
 __global__ __launch_bounds__(256) void pack_cond_text_kernel(const float* __restrict__ cond, const int* __restrict__ lens,
+                                                             const uint8_t* __restrict__ keep,
                                                              const float* __restrict__ text_emb, op16_t* __restrict__ out_hi,
                                                              op16_t* __restrict__ out_lo, int B, int seq_len, int mel_dim,
                                                              int dt, int null_keeps_cond, int* sat_flag) {
@@ -448,7 +452,7 @@ __global__ __launch_bounds__(256) void pack_cond_text_kernel(const float* __rest
     const int ld = 128 + dt;
     const size_t orow = (((size_t)br * B + b) * seq_len + n) * ld;
     // null_keeps_cond: the second branch is (drop_audio_cond = False, drop_text = True) instead of (True, True), dit.py:245-247 / 209-210
-    const bool use_cond = (br == 0 || null_keeps_cond) && (n < lens[b]);
+    const bool use_cond = (br == 0 || null_keeps_cond) && (KEEP ? keep[(size_t)b * seq_len + n] != 0 : n < lens[b]);
     f5_sat_t trk;
     for (int c = threadIdx.x; c < ld; c += 256) {
         float v = 0.0f;
@@ -468,8 +472,17 @@ __global__ __launch_bounds__(256) void pack_cond_text_kernel(const float* __rest
 int f5_launch_pack_cond_text(const float* cond, const int* lens, const float* text_emb, op16_t* out_hi, op16_t* out_lo,
                              int B, int seq_len, int mel_dim, int dt, int null_keeps_cond, hipStream_t s) {
     F5_REQUIRE(mel_dim <= 128, "pack_cond_text: mel_dim must be <= 128");
-    hipLaunchKernelGGL(pack_cond_text_kernel, dim3(seq_len, B, 2), dim3(256), 0, s, cond, lens, text_emb, out_hi, out_lo, B,
-                       seq_len, mel_dim, dt, null_keeps_cond, f5_sat_flag_host);
+    hipLaunchKernelGGL(pack_cond_text_kernel<false>, dim3(seq_len, B, 2), dim3(256), 0, s, cond, lens, (const uint8_t*)nullptr, text_emb,
+                       out_hi, out_lo, B, seq_len, mel_dim, dt, null_keeps_cond, f5_sat_flag_host);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+int f5_launch_pack_cond_text_keep(const float* cond, const uint8_t* keep, const float* text_emb, op16_t* out_hi, op16_t* out_lo,
+                                  int B, int seq_len, int mel_dim, int dt, int null_keeps_cond, hipStream_t s) {
+    F5_REQUIRE(mel_dim <= 128, "pack_cond_text_keep: mel_dim must be <= 128");
+    F5_REQUIRE(keep, "pack_cond_text_keep: keep is null");
+    hipLaunchKernelGGL(pack_cond_text_kernel<true>, dim3(seq_len, B, 2), dim3(256), 0, s, cond, (const int*)nullptr, keep, text_emb,
+                       out_hi, out_lo, B, seq_len, mel_dim, dt, null_keeps_cond, f5_sat_flag_host);
     F5_LAUNCH_CHECK();
     return 0;
 }
@@ -707,6 +720,48 @@ int f5_launch_splice(const float* cond, const float* y, const int* lens, float* 
     F5_LAUNCH_CHECK();
     return 0;
 }
+// the same with a per-frame mask in place of the prefix test: out = keep[b][n] ? cond : y, selected -- the side that is not taken is
+// not loaded
+__global__ __launch_bounds__(256) void splice_keep_kernel(const float* __restrict__ cond, const float* __restrict__ y,
+                                                          const uint8_t* __restrict__ keep, float* __restrict__ out, int mel_dim,
+                                                          size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    out[i] = keep[i / mel_dim] ? cond[i] : y[i];
+}
+int f5_launch_splice_keep(const float* cond, const float* y, const uint8_t* keep, float* out, int B, int seq_len, int mel_dim,
+                          hipStream_t s) {
+    F5_REQUIRE(keep, "splice_keep: keep is null");
+    const size_t total = (size_t)B * seq_len * mel_dim;
+    hipLaunchKernelGGL(splice_keep_kernel, dim3(f5_cdiv((long)total, 256)), dim3(256), 0, s, cond, y, keep, out, mel_dim, total);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+
+// Frame gather (speech editing: an edited utterance laid out on the device in one launch): cond_out[b][n] = src[b][src_idx[b][n]] and
+// keep_out[b][n] = 1 where 0 <= src_idx[b][n] < n_src; zeros and keep 0 for every other index (-1 = "regenerate here"), which reads
+// nothing.  One thread per output element; the thread of column 0 writes the frame's keep byte.
+__global__ __launch_bounds__(256) void gather_frames_kernel(const float* __restrict__ src, const int* __restrict__ src_idx,
+                                                            float* __restrict__ cond_out, uint8_t* __restrict__ keep_out, int n_src,
+                                                            int seq_len, int mel_dim, size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const size_t row = i / mel_dim;
+    const int c = (int)(i - row * mel_dim);
+    const size_t b = row / seq_len;
+    const int idx = src_idx[row];
+    const bool valid = idx >= 0 && idx < n_src;
+    cond_out[i] = valid ? src[(b * n_src + idx) * mel_dim + c] : 0.0f;
+    if (c == 0) keep_out[row] = valid ? 1 : 0;
+}
+int f5_launch_gather_frames(const float* src, const int* src_idx, float* cond_out, uint8_t* keep_out, int B, int n_src, int seq_len,
+                            int mel_dim, hipStream_t s) {
+    const size_t total = (size_t)B * seq_len * mel_dim;
+    hipLaunchKernelGGL(gather_frames_kernel, dim3(f5_cdiv((long)total, 256)), dim3(256), 0, s, src, src_idx, cond_out, keep_out, n_src,
+                       seq_len, mel_dim, total);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
 
 // ---- per-call staging without memcpy / memset API calls --------------------------------------------------------------------
 // Everything f5_sample enqueues is a KERNEL on the caller's stream: host scalars travel as kernel arguments (copied at launch
@@ -752,6 +807,20 @@ int f5_launch_copy_words(const void* src, void* dst, size_t nwords, hipStream_t 
         hipLaunchKernelGGL(copy_words_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const uint32_t*)src, (uint32_t*)dst, nwords / 4, nwords);
     else
         hipLaunchKernelGGL(copy_words_scalar_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const uint32_t*)src, (uint32_t*)dst, nwords);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+// device -> device copy of n bytes, any alignment (the conditioning mask of f5_sample_edit: a row slice of a uint8 [B][N] tensor starts
+// at any byte)
+__global__ __launch_bounds__(256) void copy_bytes_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, size_t n) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) dst[i] = src[i];
+}
+int f5_launch_copy_bytes(const void* src, void* dst, size_t nbytes, hipStream_t s) {
+    if (nbytes == 0) return 0;
+    long blocks = f5_cdiv((long)nbytes, 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(copy_bytes_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const uint8_t*)src, (uint8_t*)dst, nbytes);
     F5_LAUNCH_CHECK();
     return 0;
 }

@@ -44,6 +44,9 @@ int f5_launch_text_embed(const int* text, int nt, const float* table, const floa
 // pack A operand of the hoisted input projection: [cond(128, zero padded) | text_embed(dt)] for both branches
 int f5_launch_pack_cond_text(const float* cond, const int* lens, const float* text_emb, op16_t* out_hi, op16_t* out_lo,
                              int B, int seq_len, int mel_dim, int dt, int null_keeps_cond, hipStream_t s);
+// the same with the prefix test n < lens[b] replaced by a per-frame mask keep (dev uint8 [B][seq_len], non-zero = conditioning frame)
+int f5_launch_pack_cond_text_keep(const float* cond, const uint8_t* keep, const float* text_emb, op16_t* out_hi, op16_t* out_lo,
+                                  int B, int seq_len, int mel_dim, int dt, int null_keeps_cond, hipStream_t s);
 
 // sinusoidal time embedding (dit.py:61-67)
 int f5_launch_time_sinus(const float* t, float* out, int n, int dim, hipStream_t s);
@@ -89,6 +92,14 @@ int f5_launch_ode_stage(const F5OdeArgs& a, hipStream_t s);
 // out = where(n < lens[b], cond, y)  (cfm.py:395-397)
 int f5_launch_splice(const float* cond, const float* y, const int* lens, float* out, int B, int seq_len, int mel_dim,
                      hipStream_t s);
+// out = where(keep[b][n] != 0, cond, y): the splice of an edited utterance (keep: dev uint8 [B][seq_len])
+int f5_launch_splice_keep(const float* cond, const float* y, const uint8_t* keep, float* out, int B, int seq_len, int mel_dim,
+                          hipStream_t s);
+// cond_out[b][n] = src[b][src_idx[b][n]], keep_out[b][n] = 1 where 0 <= src_idx[b][n] < n_src; zeros and keep 0 elsewhere (nothing read)
+int f5_launch_gather_frames(const float* src, const int* src_idx, float* cond_out, uint8_t* keep_out, int B, int n_src, int seq_len,
+                            int mel_dim, hipStream_t s);
+// device -> device copy of nbytes bytes, any alignment
+int f5_launch_copy_bytes(const void* src, void* dst, size_t nbytes, hipStream_t s);
 
 // per-call staging as kernels (no memcpy / memset API on the sampling path): host words -> device through kernel arguments,
 // device -> device word copy, zeroing of the V^T pad columns

@@ -99,6 +99,9 @@ def load_library() -> C.CDLL:
     lib.f5_debug_h_bits2f.argtypes = [C.c_uint16]
     lib.f5_debug_last_convpos_kernel.argtypes = [C.c_char_p, C.c_int]
     lib.f5_op_noise_from_bits.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    lib.f5_sample_edit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.f5_op_wave_patch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int,
+                                     C.c_int, C.c_void_p]
     _lib = lib
     return lib
 
@@ -388,20 +391,43 @@ class Engine:
         if not self.weights_ready:
             raise RuntimeError("weights not loaded")
 
+    def _check_keep(self, cond_keep, cond) -> Optional[torch.Tensor]:
+        """The conditioning mask of an edit call as the contiguous uint8 (B, N) tensor f5_sample_edit reads (bool is reinterpreted, not
+        copied); None stays None."""
+        if cond_keep is None:
+            return None
+        if not (torch.is_tensor(cond_keep) and cond_keep.is_cuda and cond_keep.dtype in (torch.bool, torch.uint8)):
+            raise TypeError("cond_keep must be a bool or uint8 CUDA tensor")
+        if tuple(cond_keep.shape) != tuple(cond.shape[:2]) or cond_keep.device != cond.device:
+            raise ValueError(f"cond_keep must be (B, N) = {tuple(cond.shape[:2])} on {cond.device}, got {tuple(cond_keep.shape)} on {cond_keep.device}")
+        cond_keep = cond_keep.contiguous()
+        return cond_keep.view(torch.uint8) if cond_keep.dtype == torch.bool else cond_keep
+
+    def _call_sample(self, a, cond_keep, st) -> None:
+        """f5_sample, or f5_sample_edit when the call carries a conditioning mask."""
+        if cond_keep is None:
+            check(self.lib.f5_sample(self._h, C.byref(a), st), "f5_sample")
+        else:
+            check(self.lib.f5_sample_edit(self._h, C.byref(a), ptr(cond_keep), st), "f5_sample_edit")
+
     def sample(self, text: torch.Tensor, cond: torch.Tensor, lens: Sequence[int], durations: Sequence[int], y0: torch.Tensor,
                t: np.ndarray, method: str = "euler", cfg_strength: float = 2.0, use_mask: Optional[bool] = None,
                use_graph=True, return_trajectory: bool = True, out: Optional[torch.Tensor] = None,
-               trajectory: Optional[torch.Tensor] = None):
+               trajectory: Optional[torch.Tensor] = None, cond_keep: Optional[torch.Tensor] = None):
         """ODE solve on the GPU. cond (B,N,mel) fp32 zero-padded to N=max(durations); text (B,nt) int32
         (-1 padded); y0 (B,N,mel).  use_graph: True / False / "auto" (eager on the first sighting of a shape
-        signature, captured hipGraph from the second on).  Returns (out (B,N,mel), trajectory (steps,B,N,mel) or None)."""
+        signature, captured hipGraph from the second on).  cond_keep (speech editing, f5_sample_edit): bool / uint8 CUDA tensor (B, N),
+        non-zero = frame n of row b is conditioning -- it replaces the prefix rule n < lens[b]; it follows the call through the re-runs,
+        the cross-check, the bf16x3 fall-back and the split halves.  Returns (out (B,N,mel), trajectory (steps,B,N,mel) or None)."""
         if method not in METHODS:
             raise ValueError(f"Unknown method: {method}")
         self._check_inputs(text, cond, lens, durations)
+        cond_keep = self._check_keep(cond_keep, cond)
         self.check_status(block=False)                 # a pending check of the previous call: resolved here if it has arrived
         if self._use_fallback:                         # an earlier call saturated fp16 / failed its cross-check: bf16x3 from now on
             return self._fallback.sample(text, cond, lens, durations, y0, t, method=method, cfg_strength=cfg_strength, use_mask=use_mask,
-                                         use_graph=use_graph, return_trajectory=return_trajectory, out=out, trajectory=trajectory)
+                                         use_graph=use_graph, return_trajectory=return_trajectory, out=out, trajectory=trajectory,
+                                         cond_keep=cond_keep)
         B, N, mel = cond.shape
         steps = int(len(t))
         assert y0.shape == cond.shape and y0.dtype == torch.float32 and y0.is_contiguous() and y0.is_cuda
@@ -409,7 +435,7 @@ class Engine:
             use_mask = B > 1                       # cfm.py:333-336
         if 0 < self.split_batch <= B and self.verify_calls == 0:
             done = self._sample_split(text, cond, lens, durations, y0, t, steps, method, cfg_strength, use_mask, use_graph,
-                                      return_trajectory, out, trajectory)
+                                      return_trajectory, out, trajectory, cond_keep)
             if done is not None:
                 return done                        # (None: a half reported its status word -- the whole call is repeated below, unsplit)
         ws = self.workspace(B, N, text.shape[1], steps, method)
@@ -419,17 +445,19 @@ class Engine:
             trajectory = torch.empty((steps, B, N, mel), dtype=torch.float32, device=self.device)
         a, keep = self._args(text, cond, lens, durations, y0, t, steps, method, cfg_strength, use_mask, use_graph, out,
                              trajectory if return_trajectory else None, ws)
-        launch = lambda: self._run_on_side_stream(lambda st: check(self.lib.f5_sample(self._h, C.byref(a), st), "f5_sample"))  # noqa: E731
+        launch = lambda: self._run_on_side_stream(lambda st: self._call_sample(a, cond_keep, st))  # noqa: E731
         launch()
         saturated = self._after_call(a, launch, f"sample(B={B}, N={N}, {method}, {steps} points)", (B, N, steps, method))
         del keep
         if saturated and self._use_fallback:           # ("sync": re-run THIS call in bf16x3, into the same output buffers)
             return self._fallback.sample(text, cond, lens, durations, y0, t, method=method, cfg_strength=cfg_strength, use_mask=use_mask,
-                                         use_graph=use_graph, return_trajectory=return_trajectory, out=out, trajectory=trajectory)
+                                         use_graph=use_graph, return_trajectory=return_trajectory, out=out, trajectory=trajectory,
+                                         cond_keep=cond_keep)
         if self.verify_calls > 0 and self.precision == "f16" and self._ensure_fallback() is not None:
             self.verify_calls -= 1
             ref, ref_traj = self._fallback.sample(text, cond, lens, durations, y0, t, method=method, cfg_strength=cfg_strength,
-                                                  use_mask=use_mask, use_graph=False, return_trajectory=return_trajectory)
+                                                  use_mask=use_mask, use_graph=False, return_trajectory=return_trajectory,
+                                                  cond_keep=cond_keep)
             self.last_verify_l1 = l1 = float((out - ref).abs().mean())
             if not (l1 <= self.verify_tol):
                 self.verify_events += 1
@@ -446,7 +474,7 @@ class Engine:
 
     # ---- two half batches on two streams ---------------------------------------------------------
     def _sample_split(self, text, cond, lens, durations, y0, t, steps, method, cfg_strength, use_mask, use_graph, return_trajectory,
-                      out, trajectory):
+                      out, trajectory, cond_keep=None):
         """sample() of a large batch as two independent half batches: this engine runs utterances [0, h) on its stream, a sibling handle
         on the same weights arena runs [h, B) on its own, each enqueued by its own host thread (the HIP runtime lets a thread run only a
         few dozen launches ahead of the GPU, so one thread cannot keep two streams fed).  Utterances do not interact (both halves keep
@@ -468,36 +496,36 @@ class Engine:
             ws = eng.workspace(b1 - b0, N, nt, steps, method)
             a, keep = eng._args(text[b0:b1], cond[b0:b1], lens[b0:b1], durations[b0:b1], y0[b0:b1], t, steps, method, cfg_strength,
                                 use_mask, use_graph, out[b0:b1], tr, ws)
-            calls.append((eng, a, keep, tr))
+            calls.append((eng, a, keep, tr, None if cond_keep is None else cond_keep[b0:b1]))     # (each half gets its rows of the mask)
 
-        def run(eng, a):
+        def run(eng, a, ck):
             torch.cuda.set_device(self.device)         # (the worker thread's current device)
-            eng._run_on_side_stream(lambda st: check(eng.lib.f5_sample(eng._h, C.byref(a), st), "f5_sample"), cur)
+            eng._run_on_side_stream(lambda st: eng._call_sample(a, ck, st), cur)
 
-        key = (B, N, nt, steps, method, use_graph, bool(use_mask), return_trajectory, cfg_strength >= 1e-5)
+        key = (B, N, nt, steps, method, use_graph, bool(use_mask), return_trajectory, cfg_strength >= 1e-5, cond_keep is not None)
         if key in self._split_seen:
-            fut = self._pool.submit(run, calls[1][0], calls[1][1])
+            fut = self._pool.submit(run, calls[1][0], calls[1][1], calls[1][4])
             try:
-                run(calls[0][0], calls[0][1])
+                run(calls[0][0], calls[0][1], calls[0][4])
             finally:
                 fut.result()
         else:
-            for eng, a, _, _ in calls:
-                run(eng, a)
+            for eng, a, _, _, ck in calls:
+                run(eng, a, ck)
             self._split_seen.add(key)
         flags = 0
         if self._status_host is not None and self.range_check != "off":
-            for eng, a, _, _ in calls:
+            for eng, a, _, _, _ in calls:
                 flags |= eng._status_word_blocking(a, cur)
         if flags & (STATUS_FOLD_OVERFLOW | STATUS_SATURATED):
             return None
         self.split_events += 1
         if return_trajectory:
             if trajectory is None:
-                trajectory = torch.cat([calls[0][-1], calls[1][-1]], dim=1)
+                trajectory = torch.cat([calls[0][3], calls[1][3]], dim=1)
             else:
-                trajectory[:, :h].copy_(calls[0][-1])
-                trajectory[:, h:].copy_(calls[1][-1])
+                trajectory[:, :h].copy_(calls[0][3])
+                trajectory[:, h:].copy_(calls[1][3])
         return out, (trajectory if return_trajectory else None)
 
     def _status_word_blocking(self, a, cur=None) -> int:

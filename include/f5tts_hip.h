@@ -126,6 +126,19 @@ typedef struct f5_sample_args {
 
 int f5_workspace_bytes(f5_engine* e, int B, int N, int nt, int steps, int method, size_t* bytes);
 int f5_sample(f5_engine* e, const f5_sample_args* args, void* stream);
+/* Speech editing: f5_sample with the conditioning chosen FRAME BY FRAME.  The reference trains the DiT as an infilling model -- its
+ * training forward zeroes an interior span of the conditioning mel and predicts that span (F5TTS.__call__, cfm.py:198-224) -- but its
+ * sampler only ever conditions on a prefix (cond_mask = lens_to_mask(lens), cfm.py:323-331, :395-397).  Here cond_keep_dev, dev uint8
+ * [B][N] (non-zero = "this frame is conditioning"), replaces the test n < lens[b] in the two places that decide between conditioning
+ * and generated frames: step_cond = where(keep, cond, 0) in the hoisted input packing (cfm.py:331) and out = where(keep, cond, y) in
+ * the final splice (cfm.py:395-397).  Values are selected, never multiplied by the mask: whatever `cond` holds at a frame that is not
+ * kept (NaN included) reaches nothing.  Everything else -- launches, noise, time grid, key-padding mask, status word -- is f5_sample's;
+ * with keep[b][n] = (n < lens[b]) the results are f5_sample's bit for bit.  `lens` in the arguments is validated as in f5_sample and
+ * otherwise unused.  The mask is copied into the workspace (behind everything f5_sample uses; f5_workspace_bytes covers both calls)
+ * outside the captured part: one hipGraph per shape signature serves every mask, and the graphs of f5_sample and f5_sample_edit share
+ * the engine's cache without replaying each other (the edit flag is part of the key).  Refused before any launch: a null mask and
+ * everything f5_sample refuses. */
+int f5_sample_edit(f5_engine* e, const f5_sample_args* args, const uint8_t* cond_keep_dev /* [B][N] */, void* stream);
 
 /* Status word of the last f5_sample / f5_dit_forward on the workspace of `args`.  It is the FIRST 32-bit word of the workspace for every
  * shape and solver (a caller may copy it itself).  bit 1 (F5_STATUS_FOLD_RAN) = the LN fold (engine option "ln_fold") ran in that call;
@@ -243,6 +256,22 @@ int f5_op_pack_cond_text(const float* cond, const int32_t* lens, const float* te
 int f5_op_pack_x(const float* y, void* out_hi, void* out_lo, int rows, int mel_dim, void* stream);
 /* cfm.py:395-397: out = where(n < lens[b], cond, y), all [B][seq_len][mel_dim] */
 int f5_op_splice(const float* cond, const float* y, const int32_t* lens, float* out, int B, int seq_len, int mel_dim, void* stream);
+/* The keep-mask twins of the two ops above (f5_sample_edit): keep dev uint8 [B][seq_len], non-zero = conditioning frame, in place of
+ * n < lens[b].  pack_cond_text_keep generalises step_cond = where(cond_mask, cond, 0) (cfm.py:331) to the interior spans the training
+ * forward masks (cfm.py:198-224): branch 0 takes cond[b][n] where keep[b][n] != 0 and zeros elsewhere, branch 1 the same when
+ * null_keeps_cond is set; 16-bit split, saturation report, text columns and both operand types as f5_op_pack_cond_text.  splice_keep
+ * generalises cfm.py:395-397: out = keep ? cond : y.  Both SELECT by the test: the side that is not taken is not loaded, so a NaN in a
+ * dropped conditioning frame does not reach the output.  Refused before a launch: null pointers (out_lo may be NULL), sizes < 1. */
+int f5_op_pack_cond_text_keep(const float* cond, const uint8_t* keep, const float* text_emb, void* out_hi, void* out_lo, int B,
+                              int seq_len, int mel_dim, int dt, int null_keeps_cond, void* stream);
+int f5_op_splice_keep(const float* cond, const float* y, const uint8_t* keep, float* out, int B, int seq_len, int mel_dim, void* stream);
+/* Frame gather (no reference counterpart; the layout step of speech editing): src dev [B][n_src][mel_dim] fp32, src_idx dev int32
+ * [B][seq_len] -> cond_out dev [B][seq_len][mel_dim], keep_out dev uint8 [B][seq_len].  An index in [0, n_src) copies that frame of the
+ * same row and sets keep to 1; any other index (-1 is the documented "regenerate here") writes zeros and keep 0 and reads nothing.
+ * One launch lays out an edited utterance: kept stretches shifted, replaced spans resized (f5_tts_mlx_amd/edit.py edit_layout builds
+ * the map). */
+int f5_op_gather_frames(const float* src, const int32_t* src_idx, float* cond_out, uint8_t* keep_out, int B, int n_src, int seq_len,
+                        int mel_dim, void* stream);
 /* lens_to_mask of the durations (utils.py:39, cfm.py:334): keep[b][n] = n < dur[b] */
 int f5_op_rowkeep(const int32_t* dur, uint8_t* keep, int nbatch, int seq_len, void* stream);
 /* the staging kernels sample() uses in place of mx.array(...) / copies: device -> device copy of nwords 32-bit words (4-byte aligned
@@ -424,6 +453,25 @@ int f5_mel_spectrogram(const float* wave, int64_t L, const float* window, const 
  * 3 500 and beyond: the span holds two groups of o samples).  Also refused: null pointers, o / n / T / width < 1, gcd(o, n) != 1, T > 2 width + o, L < 0, L_out != ceil(n L / o). */
 int f5_resample_batch(const float* wave, int B, int64_t L, const float* taps, const int32_t* first, int o, int n, int T, int width,
                       float* out, int64_t L_out, void* stream);
+
+/* Waveform patch (no reference counterpart; the last step of speech editing): puts the original samples back outside the edited spans
+ * of a vocoded edit result.  gen dev [B][L] (the vocoded result), src dev [B][Ls] (the source recording at the model's rate and scale),
+ * out dev [B][L]; segs_host host int32 [B][S][3] = (dst_begin, dst_end, src_begin) in samples, src_begin = -1 for a regenerated
+ * segment -- staged to the device through kernel arguments like f5_op_stage_words' words (no host buffer outlives the call, no
+ * synchronisation); fade dev fp32 [F] (may be NULL when F = 0).  Per row the segments are sorted, contiguous from 0 and may be empty;
+ * rows with fewer than S segments pad with empty ones.
+ *   - inside a regenerated segment out = gen; past the last segment's end out = exactly 0.0f;
+ *   - inside a kept segment out = src[src_begin + (s - dst_begin)] by selection: the source's own bits, not g + 1 (o - g);
+ *   - the first F samples of a kept segment whose predecessor in the table is regenerated: out = g + fade[i] (o - g), ONE fused
+ *     multiply-add on the fp32 difference o - g, i = s - dst_begin; the last F samples of one whose successor is regenerated: the same
+ *     with i = dst_end - 1 - s.  (Predecessor / successor = the table entry before / after, whatever its length.)
+ * The caller builds fade[i] = 0.5 (1 - cos(pi (i + 0.5) / F)) in fp64 and rounds once (f5_tts_mlx_amd/edit.py fade_table; the
+ * convention of audio.py resample_table).  F = 0 is a plain piecewise copy.  Refused on the host before any launch, each with its own
+ * message: null pointers; B < 1; S outside 1 .. 64; F < 0; L or Ls outside 0 .. 2^31 - 1; an unsorted or non-contiguous table; a
+ * segment that ends beyond L; a kept segment whose source range leaves [0, Ls]; a kept segment shorter than the fades it must hold (F
+ * with one regenerated neighbour, 2 F with two).  L = 0 is a successful call without a launch. */
+int f5_op_wave_patch(const float* gen, const float* src, const int32_t* segs_host, const float* fade, float* out, int B, int64_t L,
+                     int64_t Ls, int S, int F, void* stream);
 
 /* ---- vocoder: Vocos mel-24khz behind one call (replaces `self._vocoder(out)`, cfm.py:399-400; wiring cfm.py:446,471) ---------
  * The reference delegates to the third-party `vocos_mlx` package (not in its repository); this is the published Vocos
