@@ -184,8 +184,231 @@ def resample(audio: torch.Tensor, orig_sr: int, new_sr: int, device=None) -> tor
     return out
 
 
+# ---- many recordings in one call (no reference counterpart: the reference's sample() takes a raw wave for batch 1 only) -----------
+ENERGY_BLOCK = 240                   # samples per energy block of prepare_references: 10 ms at 24 kHz
+
+
+def _padded_batch(waves, device):
+    """[b, t] (or [t]) fp32, contiguous, on `device` (None: where it is, or the current GPU for host input)"""
+    waves = torch.as_tensor(waves)
+    if device is not None:
+        waves = waves.to(device)
+    elif not waves.is_cuda:
+        waves = waves.to("cuda")
+    waves = waves.to(torch.float32)
+    if waves.ndim == 1:
+        waves = waves[None]
+    if waves.ndim != 2:
+        raise ValueError(f"a padded batch of waveforms is [b, t], got {tuple(waves.shape)}")
+    return waves.contiguous()
+
+
+def _host_ints(values, B: int, name: str) -> list:
+    out = [int(v) for v in (values.tolist() if isinstance(values, (torch.Tensor, np.ndarray)) else values)]
+    if len(out) != B:
+        raise ValueError(f"{name} must have one entry per row ({B}), got {len(out)}")
+    return out
+
+
+def block_energy(waves: torch.Tensor, lens, block: int = ENERGY_BLOCK, device=None) -> torch.Tensor:
+    """waves [b, t] padded, lens (b,) sample counts -> (b, ceil(t / block)) fp32 on the GPU: energy[b][k] = sum of the squares of row
+    b's samples in block k that lie below lens[b] (f5_wave_block_energy in include/f5tts_hip.h states the summation order; the padding
+    is never read).  One launch, no synchronisation when `lens` is already an int32 tensor on the device."""
+    lib = _eng.load_library()
+    waves = _padded_batch(waves, device)
+    B, L = waves.shape
+    if isinstance(lens, torch.Tensor) and lens.is_cuda and lens.dtype == torch.int32 and lens.shape == (B,):
+        lens_dev = lens.contiguous()
+    else:
+        host = _host_ints(lens, B, "lens")
+        for b, n in enumerate(host):
+            if not 0 <= n <= L:
+                raise ValueError(f"lens[{b}] = {n} outside 0..{L}")
+        lens_dev = torch.tensor(host, dtype=torch.int32).to(waves.device)
+    block = int(block)
+    nblk = -(-L // block) if block > 0 else 0
+    energy = torch.empty((B, nblk), dtype=torch.float32, device=waves.device)
+    with torch.cuda.device(waves.device):
+        rc = lib.f5_wave_block_energy(_eng.ptr(waves), B, L, _eng.ptr(lens_dev), block, _eng.ptr(energy), nblk, _eng.stream_ptr(waves.device))
+    if rc != 0 and lib.f5_last_error().startswith(b"block_energy: block"):
+        raise ValueError(lib.f5_last_error().decode("utf-8", "replace"))
+    _eng.check(rc, "f5_wave_block_energy")
+    return energy
+
+
+def log_mel_spectrogram_ragged(waves: torch.Tensor, lens, begin=None, gain=None, sample_rate: int = 24_000, n_mels: int = 100,
+                               n_fft: int = 1024, hop_length: int = 256, device=None) -> torch.Tensor:
+    """waves [b, t] padded; row i is the recording waves[i, begin[i] : begin[i] + lens[i]] (begin: zeros when None), scaled by gain[i]
+    (fp32; None: not scaled at all).  -> (b, N, n_mels) fp32 on the GPU, N = the largest lens[i] // hop_length: the frames of row i
+    are the bits log_mel_spectrogram gives for a contiguous copy of gain[i] * slice, the frames past its own count exactly 0 -- the
+    zero padding sample() gives the conditioning.  One launch (f5_mel_spectrogram_ragged).  `lens` and `begin`
+    are host values (lists, arrays or CPU tensors): N comes from them, and they are checked against the row here."""
+    lib = _eng.load_library()
+    waves = _padded_batch(waves, device)
+    B, L = waves.shape
+    lens_h = _host_ints(lens, B, "lens")
+    begin_h = [0] * B if begin is None else _host_ints(begin, B, "begin")
+    for b in range(B):
+        if begin_h[b] < 0 or lens_h[b] < 0 or begin_h[b] + lens_h[b] > L:
+            raise ValueError(f"row {b}: samples [{begin_h[b]}, {begin_h[b] + lens_h[b]}) lie outside the row of {L}")
+    N = max(n // hop_length for n in lens_h)                          # so that every row's frames fit: the kernel cannot check that
+    out = torch.empty((B, N, n_mels), dtype=torch.float32, device=waves.device)
+    if N == 0:
+        return out
+    window, fb = _tables(waves.device, sample_rate, n_fft, n_mels)
+    table = torch.tensor([begin_h, lens_h], dtype=torch.int32).to(waves.device)
+    gain_dev = None
+    if gain is not None:
+        gain_dev = torch.as_tensor(np.asarray(gain.cpu() if isinstance(gain, torch.Tensor) else gain, dtype=np.float32)).reshape(-1).to(waves.device)
+        if gain_dev.numel() != B:
+            raise ValueError(f"gain must have one entry per row ({B}), got {gain_dev.numel()}")
+    with torch.cuda.device(waves.device):
+        _eng.check(lib.f5_mel_spectrogram_ragged(_eng.ptr(waves), B, L, _eng.ptr(table[0]), _eng.ptr(table[1]), _eng.ptr(gain_dev),
+                                                 _eng.ptr(window), _eng.ptr(fb), n_fft, hop_length, n_mels, _eng.ptr(out), N,
+                                                 _eng.stream_ptr(waves.device)), "f5_mel_spectrogram_ragged")
+    return out
+
+
+def silence_window(energy, lens, block: int, threshold_db: float, keep_blocks: int):
+    """The part of each recording between its first and its last loud block, `keep_blocks` blocks of margin on either side: host
+    arithmetic in fp64 on the table block_energy made, no GPU.  energy (b, nblk), lens (b,) sample counts -> (begin, length), two
+    lists of sample counts.  The level of block k is 10 log10(E_k / n_k), n_k = the samples of the row in that block (-inf for
+    E_k = 0); a block is loud when its level is above threshold_db.  begin = max(0, first_loud - keep_blocks) block, end =
+    min(row's block count, last_loud + 1 + keep_blocks) block, length = min(end, lens) - begin.  The kept samples are the recording's
+    own: no synthetic silence is added.  ValueError for a row without a loud block."""
+    e = np.asarray(energy.cpu() if isinstance(energy, torch.Tensor) else energy, dtype=np.float64)
+    if e.ndim == 1:
+        e = e[None]
+    B = e.shape[0]
+    lens = _host_ints(lens, B, "lens")
+    block, keep_blocks = int(block), int(keep_blocks)
+    if block < 1 or keep_blocks < 0:
+        raise ValueError(f"block must be >= 1 and keep_blocks >= 0 (got {block}, {keep_blocks})")
+    begin, length = [], []
+    for b in range(B):
+        nb = -(-lens[b] // block)
+        if nb > e.shape[1]:
+            raise ValueError(f"row {b}: {lens[b]} samples need {nb} blocks of {block}, the table has {e.shape[1]}")
+        k = np.arange(nb)
+        n_k = np.minimum((k + 1) * block, lens[b]) - k * block
+        with np.errstate(divide="ignore"):
+            level = 10.0 * np.log10(e[b, :nb] / n_k)
+        loud = np.nonzero(level > threshold_db)[0]
+        if loud.size == 0:
+            raise ValueError(f"row {b}: no block of {block} samples is louder than {threshold_db} dB: nothing to keep")
+        b_blk = max(0, int(loud[0]) - keep_blocks)
+        e_blk = min(nb, int(loud[-1]) + 1 + keep_blocks)
+        begin.append(b_blk * block)
+        length.append(min(e_blk * block, lens[b]) - b_blk * block)
+    return begin, length
+
+
+def reference_gain(energy, begin, length, block: int, target_rms: float = 0.1) -> np.ndarray:
+    """The level rule of generate() (generate.py:154-156: a quiet reference is scaled UP to target_rms, a loud one is left alone) on
+    the block energies: host fp64.  Mean square of row b = the energies of its kept blocks, added in increasing k, over length[b];
+    gain = float32(target_rms / rms) when rms < target_rms, else 1.0.  -> (b,) float32.  `begin` must be whole blocks and
+    begin + length end on a block boundary or at the row's end, which is what silence_window returns (and begin = 0, length = lens).
+    ValueError for rms = 0 (generate() would divide by it)."""
+    e = np.asarray(energy.cpu() if isinstance(energy, torch.Tensor) else energy, dtype=np.float64)
+    if e.ndim == 1:
+        e = e[None]
+    B = e.shape[0]
+    begin, length = _host_ints(begin, B, "begin"), _host_ints(length, B, "length")
+    block = int(block)
+    gain = np.ones(B, dtype=np.float32)
+    for b in range(B):
+        if begin[b] % block:
+            raise ValueError(f"row {b}: begin = {begin[b]} is not a whole number of blocks of {block}")
+        k0, k1 = begin[b] // block, -(-(begin[b] + length[b]) // block)
+        if length[b] <= 0 or k1 > e.shape[1]:
+            raise ValueError(f"row {b}: samples [{begin[b]}, {begin[b] + length[b]}) are empty or beyond the energy table")
+        total = 0.0
+        for v in e[b, k0:k1].tolist():                                 # increasing k, one fp64 addition each
+            total += v
+        rms = math.sqrt(total / length[b])
+        if rms == 0.0:
+            raise ValueError(f"row {b}: the kept samples are all zero (rms 0): no level to normalise")
+        if rms < target_rms:
+            gain[b] = np.float32(target_rms / rms)
+    return gain
+
+
+class References:
+    """What prepare_references hands back.  mel (b, N, n_mels) fp32 on the device, row i zero past frames[i]; frames: mel frames per
+    row; samples: kept samples per row at 24 kHz (what a generated wave is trimmed by); begin: first kept sample per row; gain:
+    float32 (b,) level factors."""
+
+    def __init__(self, mel, frames, samples, begin, gain):
+        self.mel, self.frames, self.samples, self.begin, self.gain = mel, frames, samples, begin, gain
+
+
+def prepare_references(waves, sample_rates=24_000, *, trim_silence_db: Optional[float] = None, keep_ms: float = 50, target_rms: float = 0.1,
+                       device=None) -> References:
+    """Reference recordings of different lengths, sample rates and levels -> the conditioning of a ragged sample() batch.
+    waves: a list of 1-D arrays / tensors; sample_rates: one int or one per row.  A row at another rate than 24 kHz goes through
+    `resample` by itself (its table depends on the rate); the rows are written into one padded buffer; ONE block_energy launch
+    (blocks of 240 samples = 10 ms) and ONE device-to-host copy of its table -- the only synchronisation -- give the host what the
+    silence window and the gain are computed from; ONE ragged mel launch follows.
+    trim_silence_db (default None: nothing is cut): leading and trailing silence below this level is cut (silence_window), keeping
+    keep_ms of margin on either side; -42 is the customary figure for edge trimming in the PyTorch F5-TTS front end.  The gain
+    (reference_gain: only scales up, to target_rms) is computed always, over the kept samples.
+    ValueError names the row: a ratio the resampler refuses, a row without a loud block, an all-zero row, a row that keeps fewer
+    than one frame of 256 samples."""
+    SR, hop_length = 24_000, 256
+    waves = list(waves)
+    B = len(waves)
+    if B == 0:
+        raise ValueError("prepare_references needs at least one recording")
+    rates = [sample_rates] * B if isinstance(sample_rates, (int, np.integer)) and not isinstance(sample_rates, bool) else list(sample_rates)
+    if len(rates) != B:
+        raise ValueError(f"sample_rates must be one int or one per recording ({B}), got {len(rates)}")
+    rates = [_rate(r, f"sample rate of row {i}") for i, r in enumerate(rates)]
+    rows = []
+    for i, w in enumerate(waves):
+        w = torch.as_tensor(w)
+        if w.ndim != 1:
+            raise ValueError(f"row {i}: a recording is 1-D (mono), got {tuple(w.shape)}")
+        if rates[i] != SR:
+            try:
+                w = resample(w, rates[i], SR, device=device)[0]
+            except ValueError as exc:
+                raise ValueError(f"row {i}: {exc}") from None
+        rows.append(_padded_batch(w, device)[0])
+    dev = rows[0].device
+    lens = [int(r.shape[0]) for r in rows]
+    buf = torch.zeros((B, max(max(lens), 1)), dtype=torch.float32, device=dev)
+    for i, r in enumerate(rows):
+        buf[i, :lens[i]] = r.to(dev)
+    energy = block_energy(buf, lens, ENERGY_BLOCK).cpu().numpy()       # the one synchronisation
+    if trim_silence_db is not None:
+        begin, length = silence_window(energy, lens, ENERGY_BLOCK, float(trim_silence_db), int(round(keep_ms * SR / 1000.0 / ENERGY_BLOCK)))
+    else:
+        begin, length = [0] * B, list(lens)
+    for i in range(B):
+        if length[i] < hop_length:
+            raise ValueError(f"row {i}: {length[i]} samples are kept, fewer than one frame of {hop_length}")
+    gain = reference_gain(energy, begin, length, ENERGY_BLOCK, target_rms)
+    mel = log_mel_spectrogram_ragged(buf, length, begin, gain, sample_rate=SR, hop_length=hop_length)
+    return References(mel, [n // hop_length for n in length], length, begin, gain)
+
+
+def check_resample_ratio(orig_sr: int, new_sr: int) -> None:
+    """ValueError when `resample` would refuse the pair of rates, without a launch and without a device: the library's own rule, asked
+    through a call of length 0 (which checks everything and reads nothing)."""
+    orig_sr, new_sr = _rate(orig_sr, "orig_sr"), _rate(new_sr, "new_sr")
+    if orig_sr == new_sr:
+        return
+    lib = _eng.load_library()
+    taps, first, o, n, T, width = resample_table(orig_sr, new_sr)
+    p = C.c_void_p(taps.ctypes.data)                                   # any non-null address: nothing is read at length 0
+    rc = lib.f5_resample_batch(p, 1, C.c_int64(0), p, C.c_void_p(first.ctypes.data), o, n, T, width, p, C.c_int64(0), C.c_void_p(0))
+    if rc != 0:
+        raise ValueError(lib.f5_last_error().decode("utf-8", "replace"))
+
+
 class MelSpec:
-    """audio.py:213-230."""
+    """audio.py:213-230.  Extension: `lens` (sample counts per row of a padded [b, t] batch) gives the ragged mel, each row on its own
+    samples and zero past its own frames (log_mel_spectrogram_ragged); without it the call is the reference's."""
 
     def __init__(self, sample_rate=24_000, n_fft=1024, hop_length=256, n_mels=100, device=None):
         self.device = device                # where host audio is moved to (the owning model's device); None = current GPU
@@ -194,6 +417,9 @@ class MelSpec:
         self.hop_length = hop_length
         self.n_mels = n_mels
 
-    def __call__(self, audio, **kwargs) -> torch.Tensor:
+    def __call__(self, audio, lens=None, **kwargs) -> torch.Tensor:
+        if lens is not None:
+            return log_mel_spectrogram_ragged(audio, lens, sample_rate=self.sample_rate, n_mels=self.n_mels, n_fft=self.n_fft,
+                                              hop_length=self.hop_length, device=self.device)
         return log_mel_spectrogram(audio, sample_rate=self.sample_rate, n_mels=self.n_mels, n_fft=self.n_fft,
                                    hop_length=self.hop_length, device=self.device)

@@ -182,9 +182,10 @@ class F5TTS:
         loss = masked.sum() / torch.clamp(m.sum().to(torch.float32), min=1e-6)                      # :249
         return loss.mean()
 
-    def predict_duration(self, cond, text, speed: float = 1.0):
-        """cfm.py:253-262."""
-        duration_in_sec = self._duration_predictor(cond, text)
+    def predict_duration(self, cond, text, speed: float = 1.0, lens=None):
+        """cfm.py:253-262.  Extension: `lens` (frames of conditioning per row of a padded batch) goes to the predictor when given, so
+        that it masks each row's padding; without it the call is the reference's."""
+        duration_in_sec = self._duration_predictor(cond, text) if lens is None else self._duration_predictor(cond, text, lens=lens)
         frame_rate = self._mel_spec.sample_rate // self._mel_spec.hop_length
         return (duration_in_sec * frame_rate / speed).to(torch.int32)
 
@@ -209,15 +210,23 @@ class F5TTS:
         edit_mask: Optional[torch.Tensor] = None,  # extension (speech editing): bool (b, n), True = keep this frame of `cond`; the
                                                  # conditioning mask becomes lens_to_mask(lens) & edit_mask -- the rule of the PyTorch
                                                  # F5-TTS sampler, so an all-True mask is the call without it (docs/edit.md)
+        wave_lens=None,                          # extension: sample counts (b,) of a padded raw-wave batch `cond` (b, nw): each row's mel
+                                                 # is taken on its own samples (no gain, no trim), `lens` defaults to the rows' frame counts
     ) -> tuple[torch.Tensor, torch.Tensor]:
         self.eval()
         device = self.transformer.device
         cond = torch.as_tensor(cond)
 
-        # raw wave (cfm.py:283-286): batch 1 only, like the reference's `rearrange("1 n -> n")`
+        # raw wave (cfm.py:283-286): batch 1 only, like the reference's `rearrange("1 n -> n")` -- or, with `wave_lens`, a padded batch
         if cond.ndim == 2:
-            assert cond.shape[0] == 1, "raw-wave conditioning supports batch 1 (cfm.py:284)"
-            cond = self._mel_spec(cond[0])
+            if wave_lens is not None:
+                wave_lens = [int(v) for v in torch.as_tensor(wave_lens).reshape(-1).tolist()]
+                cond = self._mel_spec(cond, lens=wave_lens)          # (b, max frames, d), row i zero past its own frames (docs/multi_voice.md)
+                if not exists(lens):
+                    lens = torch.tensor([n // self._mel_spec.hop_length for n in wave_lens], dtype=torch.int64)
+            else:
+                assert cond.shape[0] == 1, "raw-wave conditioning supports batch 1 (cfm.py:284)"
+                cond = self._mel_spec(cond[0])
             assert cond.shape[-1] == self.num_channels
 
         batch, cond_seq_len = cond.shape[:2]
@@ -228,7 +237,7 @@ class F5TTS:
                 text = list_str_to_tensor(text)
             assert text.shape[0] == batch
         if duration is None and self._duration_predictor is not None:
-            duration = self.predict_duration(cond, text, speed)
+            duration = self.predict_duration(cond, text, speed) if lens is None else self.predict_duration(cond, text, speed, lens=lens)
         max_duration_cap = int(max_duration)
         text, lens, duration, max_duration = prepare_lengths(text, cond_seq_len, batch, duration, lens, max_duration, method)
         self.last_durations = [int(d) for d in duration.tolist()]     # extension: frames per element after the clamps (cfm.py:317-318)

@@ -9,18 +9,25 @@
 #define MEL_NFFT 1024
 #define MEL_LOG2 10
 
-__global__ __launch_bounds__(256) void mel_kernel(const float* __restrict__ wave, long L, const float* __restrict__ window,
-                                                  const float* __restrict__ fb, int hop, int n_mels, float* __restrict__ out) {
+// One frame of one recording, by one workgroup of 256 threads: the body of mel_kernel and mel_ragged_kernel, so that the two cannot
+// drift.  The recording is row[lo .. hi); the frame's first sample is row[start] (start + MEL_NFFT / 2 = the frame's centre); a sample
+// outside [lo, hi) counts as zero by the index test and is not loaded.  has_gain (the same for the whole workgroup): every sample is
+// multiplied by `gain` first -- that product is rounded once to fp32, then multiplied by the window; without it there is no such
+// multiplication at all.
+__device__ __forceinline__ void mel_frame(const float* __restrict__ row, long lo, long hi, long start, bool has_gain, float gain,
+                                          const float* __restrict__ window, const float* __restrict__ fb, int n_mels,
+                                          float* __restrict__ out_frame) {
     __shared__ float re[MEL_NFFT], im[MEL_NFFT];
     __shared__ float twc[MEL_NFFT / 2], tws[MEL_NFFT / 2];
     const int tid = threadIdx.x;
-    const long frame = blockIdx.x;
-    wave += (long)blockIdx.y * L;                                   // batch element: waves are [B][L], outputs [B][frames][n_mels]
-    out += (long)blockIdx.y * (long)gridDim.x * n_mels;
-    const long start = frame * hop - MEL_NFFT / 2;
     for (int i = tid; i < MEL_NFFT; i += 256) {
         const long si = start + i;
-        const float v = (si >= 0 && si < L) ? wave[si] * window[i] : 0.0f;
+        float v = 0.0f;
+        if (si >= lo && si < hi) {
+            float x = row[si];
+            if (has_gain) x = x * gain;
+            v = x * window[i];
+        }
         const int r = (int)(__brev((unsigned)i) >> (32 - MEL_LOG2));
         re[r] = v;
         im[r] = 0.0f;
@@ -60,8 +67,96 @@ __global__ __launch_bounds__(256) void mel_kernel(const float* __restrict__ wave
         const float* f = fb + (size_t)m * nbin;
         float acc = 0.0f;
         for (int k = 0; k < nbin; ++k) acc += re[k] * f[k];
-        out[frame * n_mels + m] = logf(fmaxf(acc, 1e-5f));
+        out_frame[m] = logf(fmaxf(acc, 1e-5f));
     }
+}
+
+__global__ __launch_bounds__(256) void mel_kernel(const float* __restrict__ wave, long L, const float* __restrict__ window,
+                                                  const float* __restrict__ fb, int hop, int n_mels, float* __restrict__ out) {
+    const long frame = blockIdx.x;
+    wave += (long)blockIdx.y * L;                                   // batch element: waves are [B][L], outputs [B][frames][n_mels]
+    out += (long)blockIdx.y * (long)gridDim.x * n_mels;
+    mel_frame(wave, 0, L, frame * hop - MEL_NFFT / 2, false, 1.0f, window, fb, n_mels, out + frame * n_mels);
+}
+
+// Padded batch of recordings of different lengths: row b is wave[b][begin[b] .. begin[b] + lens[b]), F_b = lens[b] / hop frames of it
+// are mel_frame's (the bits mel_kernel gives for a contiguous copy of the slice, scaled by gain[b]); frames F_b <= n < N are exactly
+// 0.0f in every band (the zero padding sample() gives the conditioning, not log(1e-5)).  One workgroup per (frame, row): the test on
+// n is the same for all its threads.
+__global__ __launch_bounds__(256) void mel_ragged_kernel(const float* __restrict__ wave, int L, const int* __restrict__ begin,
+                                                         const int* __restrict__ lens, const float* __restrict__ gain,
+                                                         const float* __restrict__ window, const float* __restrict__ fb, int hop,
+                                                         int n_mels, float* __restrict__ out) {
+    const int b = blockIdx.y;
+    const long n = blockIdx.x;
+    int b0 = begin[b], len = lens[b];
+    b0 = b0 < 0 ? 0 : (b0 > L ? L : b0);                            // a slice that lies cannot take the reads out of the row
+    len = len < 0 ? 0 : (len > L - b0 ? L - b0 : len);
+    float* o = out + ((long)b * gridDim.x + n) * n_mels;
+    if (n >= len / hop) {
+        for (int m = threadIdx.x; m < n_mels; m += 256) o[m] = 0.0f;
+        return;
+    }
+    mel_frame(wave + (long)b * L, b0, (long)b0 + len, b0 + n * hop - MEL_NFFT / 2, gain != nullptr, gain ? gain[b] : 1.0f, window, fb,
+              n_mels, o);
+}
+
+extern "C" int f5_mel_spectrogram_ragged(const float* wave, int B, int64_t L, const int32_t* begin_dev, const int32_t* lens_dev,
+                                         const float* gain_dev, const float* window, const float* filterbank, int n_fft, int hop,
+                                         int n_mels, float* out, int N, void* stream) {
+    F5_REQUIRE(wave && begin_dev && lens_dev && window && filterbank && out, "mel_ragged: null pointer");
+    F5_REQUIRE(n_fft == MEL_NFFT, "mel_ragged: only n_fft = 1024 is supported (got %d)", n_fft);
+    F5_REQUIRE(hop > 0 && n_mels > 0 && B >= 1 && B <= 65535, "mel_ragged: bad hop / n_mels / batch");
+    F5_REQUIRE(N >= 1, "mel_ragged: N = %d frames per row must be >= 1", N);
+    F5_REQUIRE(L >= 0 && L <= 0x7fffffffLL, "mel_ragged: L = %lld outside 0..2^31 - 1", (long long)L);
+    hipLaunchKernelGGL(mel_ragged_kernel, dim3((unsigned)N, (unsigned)B), dim3(256), 0, (hipStream_t)stream, wave, (int)L, begin_dev,
+                       lens_dev, gain_dev, window, filterbank, hop, n_mels, out);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+
+// =================================================================================================
+// Block energies of a padded batch (no reference counterpart; feeds the silence window and the RMS gain of audio.prepare_references):
+// energy[b][k] = sum of wave[b][s]^2 over s in [k block, min((k + 1) block, lens[b])).  One wave (64 lanes) per block of samples, four
+// per workgroup.  Summation order, fixed by `block` and the position in the block alone: lane l runs acc = fmaf(x, x, acc) over the
+// samples l, l + 64, l + 128, ... of the block in increasing order, from acc = 0; the 64 lane sums are then combined by an xor
+// butterfly, v += shfl_xor(v, d) for d = 32, 16, 8, 4, 2, 1.  A sample at s >= lens[b] is selected away by the index test: never
+// loaded, never multiplied.
+// =================================================================================================
+__global__ __launch_bounds__(256) void block_energy_kernel(const float* __restrict__ wave, int L, const int* __restrict__ lens,
+                                                           int block, float* __restrict__ energy, int nblk) {
+    const int lane = threadIdx.x & 63;
+    const long k = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (k >= nblk) return;                                          // whole waves leave: the butterfly below stays among 64 live lanes
+    const int b = blockIdx.y;
+    int len = lens[b];
+    len = len < 0 ? 0 : (len > L ? L : len);                        // a length that lies cannot take the reads out of the row
+    const float* x = wave + (long)b * L;
+    const long s0 = k * block;
+    long s1 = s0 + block;
+    if (s1 > len) s1 = len;
+    float acc = 0.0f;
+    for (long s = s0 + lane; s < s1; s += 64) {
+        const float v = x[s];
+        acc = fmaf(v, v, acc);
+    }
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    if (lane == 0) energy[(long)b * nblk + k] = acc;
+}
+
+extern "C" int f5_wave_block_energy(const float* wave, int B, int64_t L, const int32_t* lens_dev, int block, float* energy, int nblk,
+                                    void* stream) {
+    F5_REQUIRE(wave && lens_dev && energy, "block_energy: null pointer");
+    F5_REQUIRE(B >= 1 && B <= 65535, "block_energy: B = %d outside 1..65535", B);
+    F5_REQUIRE(block >= 1 && block <= 4096, "block_energy: block = %d outside 1..4096", block);
+    F5_REQUIRE(L >= 0 && L <= 0x7fffffffLL, "block_energy: L = %lld outside 0..2^31 - 1", (long long)L);
+    const int64_t want = (L + block - 1) / block;
+    F5_REQUIRE(nblk == want, "block_energy: nblk = %d, but ceil(L / block) = %lld", nblk, (long long)want);
+    if (L == 0) return 0;
+    hipLaunchKernelGGL(block_energy_kernel, dim3((unsigned)((nblk + 3) / 4), (unsigned)B), dim3(256), 0, (hipStream_t)stream, wave,
+                       (int)L, lens_dev, block, energy, nblk);
+    F5_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int f5_mel_spectrogram_batch(const float* wave, int B, int64_t L, const float* window, const float* filterbank, int n_fft,

@@ -102,6 +102,9 @@ def load_library() -> C.CDLL:
     lib.f5_sample_edit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.f5_op_wave_patch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int,
                                      C.c_int, C.c_void_p]
+    lib.f5_wave_block_energy.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.f5_mel_spectrogram_ragged.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     _lib = lib
     return lib
 

@@ -4,6 +4,9 @@
 seconds -> frames with 93.75 frames/s, RMS normalisation that only scales UP, reference trimmed by SAMPLES).  Differences:
 WAV I/O uses scipy (soundfile is not installed), playback (`AudioPlayer`, PortAudio) is out of scope, and the function
 returns the waveform (the reference returns None).  Without `output_path` nothing is played; the wave is just returned.
+
+`generate_many(requests, ...)` (no reference counterpart; docs/multi_voice.md) runs many requests, each with its own reference
+recording, as ONE ragged `sample()` batch.
 """
 from __future__ import annotations
 
@@ -217,6 +220,144 @@ def generate(
     return wave
 
 
+def _load_reference(ref_audio_path, ref_audio_text, which: str):
+    """-> (fp32 samples, rate, transcript); None = the bundled sample and its text, as in generate()"""
+    if ref_audio_path is None:
+        audio, sr = read_wav(pkgutil.get_data("f5_tts_mlx_amd", "assets/test_en_1_ref_short.wav"))
+        return torch.from_numpy(np.asarray(audio)).to(torch.float32), int(sr), DEFAULT_REF_TEXT
+    if not ref_audio_text:
+        raise ValueError(f"{which}: a reference recording needs its transcript (ref_audio_text)")
+    audio, sr = read_wav(ref_audio_path)
+    return torch.from_numpy(np.asarray(audio)).to(torch.float32), int(sr), ref_audio_text
+
+
+def generate_many(
+    requests,
+    *,
+    steps: int = 8,
+    method: Literal["euler", "midpoint", "rk4"] = "rk4",
+    cfg_strength: float = 2.0,
+    sway_sampling_coef: float = -1.0,
+    speed: float = 1.0,
+    seed: Optional[int] = None,
+    estimate_duration: bool = False,
+    f5tts: Optional[F5TTS] = None,
+    model_name: str = "lucasnewman/f5-tts-mlx",
+    quantization_bits: Optional[int] = None,
+    trim_silence_db: Optional[float] = None,
+    output_sample_rate: Optional[int] = None,
+):
+    """Many voices in one call (no reference counterpart; docs/multi_voice.md).  requests: a list of (generation_text, ref_audio_path or
+    None, ref_audio_text); None = the bundled sample and its text.  -> a list of waves, one per request, in order.
+
+    Every sentence of every request (split_sentences; a text without sentence punctuation is one sentence) is one row of ONE ragged
+    `sample()` batch.  A row's conditioning is its request's reference, prepared by audio.prepare_references (any sample rate, level
+    scaled up to 0.1 rms, and with `trim_silence_db` -- default None: nothing is cut; -42 is the customary figure -- leading and trailing
+    silence removed); its text is ref_text + " " + sentence.  Its duration is, with `estimate_duration`, the heuristic on the request's
+    WHOLE text and its reference's kept samples (the quirk batch_sentences keeps), otherwise the duration predictor's, which gets
+    the rows' frame counts.  The batch is vocoded on each row's own frames -- one decode(mel, lens=frames) call when the vocoder
+    takes `lens`, else one call per row --, each row is trimmed by its own reference's kept sample count and the rows of a request
+    are concatenated.  Every row gets the same `seed` (the reference re-seeds per element).
+
+    It equals prepare_references -> sample(mel, text, durations, lens=frames) -> the decode -> the same slices, bit for bit; it does
+    NOT equal a loop of generate() calls bit for bit (the batch has a key-padding mask, GRN and the conv position embedding see the
+    padding, and the gain is fp64 arithmetic on fp32 block sums instead of torch's fp32 mean).
+    ValueError before any launch, naming the request: an empty list, a request without text, a reference recording without a
+    transcript, a reference at a rate the resampler refuses."""
+    requests = list(requests)
+    if not requests:
+        raise ValueError("generate_many needs at least one request")
+    if output_sample_rate is not None:
+        output_sample_rate = _audio._rate(output_sample_rate, "output_sample_rate")
+        _audio.check_resample_ratio(SAMPLE_RATE, output_sample_rate)
+    waves, rates, ref_texts, sentences = [], [], [], []
+    for i, req in enumerate(requests):
+        if len(req) != 3:
+            raise ValueError(f"request {i}: expected (generation_text, ref_audio_path, ref_audio_text), got {len(req)} items")
+        text, path, ref_text = req
+        if not isinstance(text, str) or not text.strip():
+            raise ValueError(f"request {i}: no text to generate")
+        audio, sr, ref_text = _load_reference(path, ref_text, f"request {i}")
+        try:
+            _audio.check_resample_ratio(sr, SAMPLE_RATE)
+        except ValueError as exc:
+            raise ValueError(f"request {i}: reference at {sr} Hz: {exc}") from None
+        waves.append(audio)
+        rates.append(sr)
+        ref_texts.append(ref_text)
+        sentences.append(split_sentences(text) or [text.strip()])
+
+    if f5tts is None:
+        f5tts = F5TTS.from_pretrained(model_name, quantization_bits=quantization_bits)
+    voc = getattr(f5tts, "_vocoder", None)
+    if voc is None:
+        raise RuntimeError("generate_many() needs a model with a vocoder (F5TTS(..., vocoder=...) / from_pretrained with Vocos)")
+
+    try:
+        refs = _audio.prepare_references(waves, rates, trim_silence_db=trim_silence_db, target_rms=TARGET_RMS,
+                                         device=f5tts.transformer.device)
+    except ValueError as exc:                                         # one reference per request: its rows are the requests
+        msg = str(exc)
+        raise ValueError("request " + msg[4:] if msg.startswith("row ") else msg) from None
+
+    row_req = [i for i, ss in enumerate(sentences) for _ in ss]      # request of every row
+    texts = convert_char_to_pinyin([ref_texts[i] + " " + s for i, ss in enumerate(sentences) for s in ss])
+    cond = refs.mel[torch.tensor(row_req, device=refs.mel.device)]
+    lens = torch.tensor([refs.frames[i] for i in row_req], dtype=torch.int64)
+    durs = None                                                       # duration predictor, per row, with lens (cfm.py:307-308)
+    if estimate_duration:
+        per_req = [int(estimated_duration(np.broadcast_to(np.float32(0), (refs.samples[i],)), ref_texts[i], requests[i][0], speed)
+                       * FRAMES_PER_SEC) for i in range(len(requests))]
+        durs = torch.tensor([per_req[i] for i in row_req], dtype=torch.int64)
+
+    start_date = datetime.datetime.now()
+    try:                                                              # mel frames out of sample(): each row is vocoded on its own frames
+        f5tts._vocoder = None
+        mel, _ = f5tts.sample(cond, text=texts, duration=durs, lens=lens, steps=steps, method=method, speed=speed,
+                              cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
+    finally:
+        f5tts._vocoder = voc
+    frames = f5tts.last_durations                                     # per-row frame counts after the clamps of cfm.py:317-318
+    if _takes_lens(voc):
+        decoded = voc(mel, lens=frames)                               # (rows, 256 * (N - 1)), row r zero past its own frames
+        rows = [decoded[r, refs.samples[i]:HOP_LENGTH * (int(frames[r]) - 1)] for r, i in enumerate(row_req)]
+    else:
+        rows = [voc(mel[r:r + 1, :int(frames[r])]).reshape(-1)[refs.samples[i]:] for r, i in enumerate(row_req)]
+    out = []
+    for i in range(len(requests)):
+        wave = torch.cat([rows[r] for r, q in enumerate(row_req) if q == i], dim=0)
+        if output_sample_rate is not None and output_sample_rate != SAMPLE_RATE:
+            wave = _audio.resample(wave, SAMPLE_RATE, output_sample_rate)[0]
+        out.append(wave)
+    if out[0].is_cuda:
+        torch.cuda.synchronize()
+    total = sum(w.shape[0] for w in out) / (output_sample_rate or SAMPLE_RATE)
+    print(f"Generated {total:.2f}s of audio for {len(requests)} requests ({len(row_req)} rows) in {datetime.datetime.now() - start_date}.")
+    return out
+
+
+def read_requests(path):
+    """A --requests file: one JSON object per line with "text", and optionally "ref_audio", "ref_text" and "output" (blank lines are
+    skipped) -> a list of dicts with exactly these four keys (None where a line leaves one out)."""
+    import json
+    reqs = []
+    with open(path, encoding="utf-8") as f:
+        for no, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            try:
+                obj = json.loads(line)
+            except json.JSONDecodeError as exc:
+                raise ValueError(f"{path}:{no}: not a JSON object ({exc.msg})") from None
+            if not isinstance(obj, dict) or not isinstance(obj.get("text"), str):
+                raise ValueError(f'{path}:{no}: expected an object with a "text" string')
+            unknown = set(obj) - {"text", "ref_audio", "ref_text", "output"}
+            if unknown:
+                raise ValueError(f"{path}:{no}: unknown key(s) {sorted(unknown)}")
+            reqs.append({k: obj.get(k) for k in ("text", "ref_audio", "ref_text", "output")})
+    return reqs
+
+
 # command line: the reference's flags and defaults (generate.py:248-362), table driven
 _CLI = (
     ("--model", str, "lucasnewman/f5-tts-mlx", "checkpoint: hub name or local directory"),
@@ -234,7 +375,7 @@ _CLI = (
 )
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(
         description="F5-TTS text to speech on MI355X (same flags as f5_tts_mlx.generate)",
         epilog="Text front-end: single-byte (ASCII / Latin) text is tokenised exactly like the reference; Chinese text needs "
@@ -249,7 +390,34 @@ def main(argv=None):
     ap.add_argument("--output-rate", type=int, default=None, help="sample rate of the result in Hz (default: 24000, the model's own rate)")
     ap.add_argument("--batch-sentences", action="store_true", help="sample all sentences of the text as one ragged batch instead of one after the other")
     ap.add_argument("--vocode-batched", action="store_true", help="with --batch-sentences: vocode the batch in one ragged call instead of one call per sentence")
+    ap.add_argument("--requests", default=None, metavar="FILE.jsonl",
+                    help="many voices in one batch: one JSON object per line with text, ref_audio, ref_text and output (ref_audio / ref_text "
+                         "left out: the bundled sample); excludes --text and --output")
+    ap.add_argument("--trim-silence", type=float, default=None, metavar="DB",
+                    help="with --requests: cut leading and trailing silence below DB dB off every reference (-42 is customary; default: cut nothing)")
     ns = ap.parse_args(argv)
+    if ns.requests is not None:
+        for flag, value in (("--text", ns.text), ("--output", ns.output), ("--ref-audio", ns.ref_audio), ("--ref-text", ns.ref_text),
+                            ("--duration", ns.duration)):
+            if value is not None:
+                ap.error(f"--requests excludes {flag}: every line of the file carries its own")
+    elif ns.trim_silence is not None:
+        ap.error("--trim-silence needs --requests")
+    return ns
+
+
+def main(argv=None):
+    ns = parse_args(argv)
+    if ns.requests is not None:
+        reqs = read_requests(ns.requests)
+        waves = generate_many([(r["text"], r["ref_audio"], r["ref_text"]) for r in reqs], steps=ns.steps, method=ns.method,
+                              cfg_strength=ns.cfg, sway_sampling_coef=ns.sway_coef, speed=ns.speed, seed=ns.seed,
+                              estimate_duration=ns.estimate_duration, model_name=ns.model, quantization_bits=ns.q,
+                              trim_silence_db=ns.trim_silence, output_sample_rate=ns.output_rate)
+        for r, wave in zip(reqs, waves):
+            if r["output"] is not None:
+                write_wav(r["output"], wave.detach().cpu().numpy(), ns.output_rate or SAMPLE_RATE)
+        return
 
     text = ns.text
     if text is None:

@@ -436,6 +436,35 @@ int f5_mel_spectrogram_batch(const float* wave, int B, int64_t L, const float* w
 /* the same for one waveform: wave dev [L] -> out dev [L / hop][n_mels] */
 int f5_mel_spectrogram(const float* wave, int64_t L, const float* window, const float* filterbank, int n_fft, int hop,
                        int n_mels, float* out, void* stream);
+/* The same for a padded batch of recordings of DIFFERENT lengths, in one launch (no reference counterpart: the reference's sample()
+ * takes a raw wave for batch 1 only, cfm.py:283-286).  wave dev [B][L]; begin_dev, lens_dev dev int32 [B]; gain_dev dev fp32 [B] or
+ * NULL; out dev [B][N][n_mels].  Row b is the recording wave[b][begin[b] .. begin[b] + lens[b]) and has F_b = lens[b] / hop frames.
+ *   - frame n < F_b: the bits f5_mel_spectrogram gives for a contiguous copy of that slice with every sample multiplied by gain[b]
+ *     first (the product is rounded once to fp32, then multiplied by the window; gain_dev == NULL: no multiplication at all).  The
+ *     two kernels share the frame body as one device function.  Samples outside the slice count as zero by the index test and are
+ *     not loaded (NaN there stays out);
+ *   - frame F_b <= n < N: exactly 0.0f in every band -- the zero padding sample() gives the conditioning (cfm.py:321), not log(1e-5).
+ * Refused before a launch: what f5_mel_spectrogram_batch refuses (a null pointer other than gain_dev, n_fft != 1024, hop / n_mels < 1,
+ * B outside 1 .. 65 535), N < 1, L outside 0 .. 2^31 - 1.  begin[b] / lens[b] outside the row are clamped in the kernel (begin to
+ * 0 .. L, lens to 0 .. L - begin): wrong results, no access outside the buffers -- the convention of the ragged vocoder ops.  Rows with
+ * F_b > N lose their frames past N: the lengths live on the device, the caller checks them (audio.py log_mel_spectrogram_ragged). */
+int f5_mel_spectrogram_ragged(const float* wave, int B, int64_t L, const int32_t* begin_dev, const int32_t* lens_dev,
+                              const float* gain_dev /* may be NULL */, const float* window, const float* filterbank, int n_fft, int hop,
+                              int n_mels, float* out, int N, void* stream);
+/* Block energies of a padded batch of recordings (no reference counterpart; the silence window and the RMS gain of
+ * audio.py prepare_references are host arithmetic on this table): wave dev [B][L], lens_dev dev int32 [B], energy dev [B][nblk],
+ * nblk = ceil(L / block).  energy[b][k] = sum of wave[b][s]^2 over s in [k block, min((k + 1) block, lens[b])); an empty range gives
+ * exactly 0.0f.  A sample at s >= lens[b] is never loaded: the value is selected by the index test, never multiplied by a mask, so NaN
+ * in the padding stays out.
+ * Summation order (fixed: it depends on `block` and on the position inside the block only, so row b of a batch has the bits of the
+ * same call on that row alone): one 64-lane wave per block; lane l accumulates the block's samples l, l + 64, l + 128, ... in
+ * increasing order with acc = fmaf(x, x, acc) from acc = 0; the 64 lane sums are combined by an xor butterfly,
+ * v = v + shfl_xor(v, d) for d = 32, 16, 8, 4, 2, 1.
+ * Refused on the host before any launch, each with its own message: a null pointer; B outside 1 .. 65 535; block outside 1 .. 4096;
+ * L outside 0 .. 2^31 - 1; nblk != ceil(L / block).  L = 0 is a successful call without a launch.  lens[b] outside 0 .. L is clamped in
+ * the kernel (wrong results, no access outside the buffers). */
+int f5_wave_block_energy(const float* wave, int B, int64_t L, const int32_t* lens_dev, int block, float* energy, int nblk,
+                         void* stream);
 /* Sample-rate conversion of a batch of equally long waveforms in ONE launch (no reference counterpart: generate.py:147-148 refuses
  * anything but 24 kHz): wave dev [B][L] fp32 -> out dev [B][L_out], L_out = ceil(n L / o).  A Hann-windowed sinc polyphase filter, the
  * design of torchaudio's default `resample`.  With g = gcd(orig, new), o = orig / g, n = new / g, base = 0.99 min(o, n),
