@@ -73,6 +73,21 @@ def time_grid(steps: int, sway_sampling_coef: Optional[float]) -> np.ndarray:
     return t
 
 
+def time_grid_rows(steps: int, sway_sampling_coefs) -> np.ndarray:
+    """One grid per batch row, (b, steps) float32: row i is time_grid(steps, sway_sampling_coefs[i]) (an entry may be None: linear)."""
+    return np.stack([time_grid(steps, c) for c in sway_sampling_coefs]).astype(np.float32)
+
+
+def per_row(value, batch: int, name: str):
+    """A sampling control given as a scalar (or None) or as one value per batch row -> (is_sequence, list of `batch` values)."""
+    if value is None or np.ndim(value) == 0:
+        return False, [value] * batch
+    values = list(value.tolist()) if hasattr(value, "tolist") else list(value)
+    if len(values) != batch:
+        raise ValueError(f"{name}: expected a scalar or {batch} values (one per batch row), got {len(values)}")
+    return True, values
+
+
 def prepare_lengths(text: torch.Tensor, cond_seq_len: int, batch: int, duration, lens, max_duration: int, method: str):
     """Host-side scalar logic of `F5TTS.sample` (cfm.py:288-319, :383-390) on CPU tensors.
 
@@ -182,11 +197,13 @@ class F5TTS:
         loss = masked.sum() / torch.clamp(m.sum().to(torch.float32), min=1e-6)                      # :249
         return loss.mean()
 
-    def predict_duration(self, cond, text, speed: float = 1.0, lens=None):
+    def predict_duration(self, cond, text, speed=1.0, lens=None):
         """cfm.py:253-262.  Extension: `lens` (frames of conditioning per row of a padded batch) goes to the predictor when given, so
-        that it masks each row's padding; without it the call is the reference's."""
+        that it masks each row's padding; without it the call is the reference's.  `speed` may be one value per row."""
         duration_in_sec = self._duration_predictor(cond, text) if lens is None else self._duration_predictor(cond, text, lens=lens)
         frame_rate = self._mel_spec.sample_rate // self._mel_spec.hop_length
+        if np.ndim(speed) != 0:
+            speed = torch.as_tensor(speed, dtype=torch.float32, device=duration_in_sec.device)
         return (duration_in_sec * frame_rate / speed).to(torch.int32)
 
     def sample(
@@ -230,6 +247,14 @@ class F5TTS:
             assert cond.shape[-1] == self.num_channels
 
         batch, cond_seq_len = cond.shape[:2]
+        # per-request controls (extension, docs/row_controls.md): each of cfg_strength, sway_sampling_coef, seed and speed is a scalar as in
+        # the reference or one value per batch row; an all-scalar call takes the path below untouched
+        cfg_seq, cfg_rows = per_row(cfg_strength, batch, "cfg_strength")
+        sway_seq, sway_rows = per_row(sway_sampling_coef, batch, "sway_sampling_coef")
+        seed_seq, seed_rows = per_row(seed, batch, "seed")
+        speed_seq, speed_rows = per_row(speed, batch, "speed")
+        if speed_seq:
+            speed = [float(v) for v in speed_rows]
         if isinstance(text, list):
             if exists(self._vocab_char_map):
                 text = list_str_to_idx(text, self._vocab_char_map)
@@ -263,12 +288,12 @@ class F5TTS:
         # the same `seed` for every element; without a seed every element gets fresh entropy.
         if y0 is None:
             durs = [int(d) for d in duration.tolist()]
-            seeds = [seed if exists(seed) else int(np.random.SeedSequence().entropy % (1 << 63)) for _ in durs]
+            seeds = [sd if exists(sd) else int(np.random.SeedSequence().entropy % (1 << 63)) for sd in seed_rows]
             y0 = noise_normal(seeds, durs, max_duration, self.num_channels, device)
         y0 = torch.as_tensor(y0).to(device, torch.float32).contiguous()
         assert y0.shape == (batch, max_duration, self.num_channels)
 
-        t = time_grid(steps, sway_sampling_coef)
+        t = time_grid_rows(steps, sway_rows) if sway_seq else time_grid(steps, sway_sampling_coef)
 
         # speech editing: the per-frame conditioning mask, padded with False to max_duration, cleared at n >= duration[b] and combined
         # with the prefix rule (cond_mask of cfm.py:323-331 AND the caller's mask); lengths, clamps, noise and time grid are untouched
@@ -288,7 +313,7 @@ class F5TTS:
 
         out, trajectory = self.transformer.engine.sample(
             text.to(device).contiguous(), cond_p, lens.tolist(), duration.tolist(), y0, t, method=method,
-            cfg_strength=float(cfg_strength), use_mask=(batch > 1 or pad_to is not None), use_graph=use_graph, return_trajectory=True,
+            cfg_strength=[float(v) for v in cfg_rows] if cfg_seq else float(cfg_strength), use_mask=(batch > 1 or pad_to is not None), use_graph=use_graph, return_trajectory=True,
             cond_keep=cond_keep)
 
         if exists(self._vocoder):

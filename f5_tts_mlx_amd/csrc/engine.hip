@@ -8,6 +8,8 @@
 // Per function evaluation the cond and null branches run as one batch of 2*B*N rows.
 #include <stdarg.h>
 
+#include <cmath>
+
 #include <string>
 #include <vector>
 
@@ -71,6 +73,12 @@ struct Workspace {
     bool fold_planned;
     size_t vt_bytes;
     size_t cond_keep;              // f5_sample_edit: the per-frame conditioning mask, [B][N] bytes, BEHIND everything above (no other offset moves)
+    // f5_sample_rows / f5_dit_forward_rows only (plan_workspace_rows; behind `total`: no offset of the plan above moves)
+    size_t rscal = 0, rscal_words = 0;          // per-row controls, staged per call: [tgrid nfe x B | dt steps x B | cfg B] floats
+    size_t rtgrid = 0, rdt = 0, rcfg = 0;
+    size_t rsinus = 0, rth = 0, rtemb = 0;      // time MLP of every (evaluation, row): [nfe x B] rows each
+    size_t rmod = 0;                            // adaLN table [nfe][B][(6L+2) D]
+    size_t total_rows = 0;                      // bytes of the plan including the rows part
 };
 
 // Per-engine launch options: everything that reaches a kernel as a by-value argument or changes the launch sequence of sample()
@@ -514,6 +522,37 @@ extern "C" int f5_workspace_bytes(f5_engine* e, int B, int N, int nt, int steps,
     return 0;
 }
 
+// The plan of f5_sample with the per-row part appended: the staged controls and the time / adaLN tables of every (evaluation, row) pair.
+// The fp32 scratch of the two gated projections needs no space of its own: w.qk[0] (2 M D 16-bit values = M D floats) is dead from the end
+// of a block's attention to the next block's QKV projection, which is where both projections run.
+static Workspace plan_workspace_rows(const f5_engine* e, int B, int N, int nt, int steps, int method) {
+    Workspace w = plan_workspace(e, B, N, nt, steps, method);
+    const f5_config& c = e->cfg;
+    const int nfe = (steps - 1) * nfe_per_step(method);
+    const size_t nfe1 = (size_t)(nfe > 0 ? nfe : 1), rows = nfe1 * B;
+    Bump b;
+    b.off = w.total;
+    w.rscal_words = rows + (size_t)steps * B + B;
+    w.rscal = b.take(w.rscal_words * 4);
+    w.rtgrid = w.rscal;
+    w.rdt = w.rtgrid + rows * 4;
+    w.rcfg = w.rdt + (size_t)steps * B * 4;
+    w.rsinus = b.take(rows * c.freq_embed_dim * 4);
+    w.rth = b.take(rows * c.dim * 4);
+    w.rtemb = b.take(rows * c.dim * 4);
+    w.rmod = b.take(rows * (size_t)(6 * c.depth + 2) * c.dim * 4);
+    w.total_rows = b.off;
+    return w;
+}
+
+extern "C" int f5_workspace_bytes_rows(f5_engine* e, int B, int N, int nt, int steps, int method, size_t* bytes) {
+    F5_REQUIRE(e && bytes, "null argument");
+    F5_REQUIRE(B >= 1 && N >= 1 && steps >= 1, "bad sizes B=%d N=%d steps=%d", B, N, steps);
+    F5_REQUIRE(method >= F5_EULER && method <= F5_RK4, "Unknown method: %d", method);
+    *bytes = plan_workspace_rows(e, B, N, nt, steps, method).total_rows;
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // launch context
 // ------------------------------------------------------------------------------------------------
@@ -524,6 +563,7 @@ struct Ctx : LaunchView {
     int B, N, nt, nb;   // nb = branches evaluated per function evaluation (1 or 2)
     int npad;
     bool edit = false;  // f5_sample_edit: conditioning frames are chosen by the mask at w.cond_keep instead of n < lens[b]
+    bool rows = false;  // f5_sample_rows / f5_dit_forward_rows: time and guidance strength per batch row (w.r*: plan_workspace_rows)
     bool use_mask;
 };
 
@@ -547,6 +587,14 @@ static int ln_fold_state(const Ctx& c) {
     const f5_engine* e = c.e;
     const f5_config& cf = e->cfg;
     if (e->opt.ln_fold == 0) return 0;
+    if (c.rows) {        // the fold's constants c1, c2 are built per evaluation, not per row
+        if (e->opt.ln_fold == 1) {
+            f5_set_error("ln_fold = 1: the folded LN cannot run with per-row sampling controls (its constants are per evaluation); use ln_fold = "
+                         "-1 or 0 for f5_sample_rows / f5_dit_forward_rows");
+            return -1;
+        }
+        return 0;
+    }
     const int D = cf.dim, FF = cf.ff_dim, M = c.nb * c.B * c.N;
     bool ok = e->np == 1 && e->prec != F5_PREC_MXFP8 && e->opt.qkv_tr && !e->opt.fuse_ln && D % 256 == 0 && D <= 2048 && FF % 256 == 0 &&
               (e->opt.gemm_flags & 16384) == 0 && cf.depth >= 1;
@@ -588,13 +636,15 @@ static int run_prep(const Ctx& c, int nfe) {
 
     // --- t-only tables (dit.py:61-82, 267, 286)
     if (nfe > 0) {
-        RC(f5_launch_time_sinus(c.p<float>(w.tgrid), c.p<float>(w.sinus), nfe, cf.freq_embed_dim, s));
-        RC(f5_launch_skinny_gemm(c.p<float>(w.sinus), c.a<float>(e->time_w0), c.a<float>(e->time_b0), c.p<float>(w.th), nfe, D,
-                                 cf.freq_embed_dim, 0, 1, s));
-        RC(f5_launch_skinny_gemm(c.p<float>(w.th), c.a<float>(e->time_w2), c.a<float>(e->time_b2), c.p<float>(w.temb), nfe, D, D,
-                                 0, 0, s));
-        RC(f5_launch_skinny_gemm(c.p<float>(w.temb), c.a<float>(e->ada_w), c.a<float>(e->ada_b), c.p<float>(w.mod), nfe,
-                                 (6 * L + 2) * D, D, 1, 0, s));
+        // per-row controls: one table row per (evaluation, batch row), [nfe][B] (f5_launch_skinny_gemm slices any row count by itself)
+        const int nt_rows = c.rows ? nfe * c.B : nfe;
+        const float* tg = c.p<float>(c.rows ? w.rtgrid : w.tgrid);
+        float *sinus = c.p<float>(c.rows ? w.rsinus : w.sinus), *th = c.p<float>(c.rows ? w.rth : w.th);
+        float *temb = c.p<float>(c.rows ? w.rtemb : w.temb), *modt = c.p<float>(c.rows ? w.rmod : w.mod);
+        RC(f5_launch_time_sinus(tg, sinus, nt_rows, cf.freq_embed_dim, s));
+        RC(f5_launch_skinny_gemm(sinus, c.a<float>(e->time_w0), c.a<float>(e->time_b0), th, nt_rows, D, cf.freq_embed_dim, 0, 1, s));
+        RC(f5_launch_skinny_gemm(th, c.a<float>(e->time_w2), c.a<float>(e->time_b2), temb, nt_rows, D, D, 0, 0, s));
+        RC(f5_launch_skinny_gemm(temb, c.a<float>(e->ada_w), c.a<float>(e->ada_b), modt, nt_rows, (6 * L + 2) * D, D, 1, 0, s));
     }
     const int fold = ln_fold_state(c);
     if (fold < 0) return 2;
@@ -690,7 +740,14 @@ static int run_dit(const Ctx& c, int j) {
     const int M1 = c.B * c.N, M = c.nb * M1;
     hipStream_t s = c.s;
     const Ops& K = c.ops;
-    const float* mod = c.p<float>(w.mod) + (size_t)j * (6 * L + 2) * D;
+    // per-row controls: `mod` is vector 0 of evaluation j in the [nfe][B][(6L+2) D] table; the row kernels step through the B vectors
+    const size_t vstride = (size_t)(6 * L + 2) * D;
+    const float* mod = c.rows ? c.p<float>(w.rmod) + (size_t)j * c.B * vstride : c.p<float>(w.mod) + (size_t)j * vstride;
+    // the gated projections of that route leave their fp32 result (bias included) here: q | k are dead once the attention has run
+    float* yscratch = reinterpret_cast<float*>(c.pb(w.qk, 0));
+    auto ln_rows = [&](const float* y, const float* gate, const uint8_t* keep, const float* scale, const float* shift) {
+        return K.resid_gate_ln_rows(y, c.p<float>(w.x), gate, keep, scale, shift, c.pb(w.h, 0), c.pb(w.h, 1), M, D, c.N, c.B, vstride, 1e-6f, s);
+    };
     const uint8_t* rowkeep = c.use_mask ? c.p<uint8_t>(w.rowkeep) : nullptr;
     const int* kvlen = c.use_mask ? c.p<int>(w.dur2) : nullptr;
 
@@ -822,7 +879,7 @@ static int run_dit(const Ctx& c, int j) {
     const float* mf = mod + (size_t)L * 6 * D;  // final adaLN: (scale, shift) order, dit.py:287
     bool h_ready = false;
     auto fuse_ln = [&](F5GemmArgs& g, const float* scale, const float* shift) -> bool {
-        if (!e->opt.fuse_ln || w.lncnt_words == 0 || !f5_gemm_resid_ln_fusable(f5bf::f5_gemm_query(g, EPI_RESID_GATE), g.ldo)) return false;
+        if (c.rows || !e->opt.fuse_ln || w.lncnt_words == 0 || !f5_gemm_resid_ln_fusable(f5bf::f5_gemm_query(g, EPI_RESID_GATE), g.ldo)) return false;
         g.ln_counter = c.p<int>(w.lncnt);
         g.ln_scale = scale;
         g.ln_shift = shift;
@@ -876,7 +933,8 @@ static int run_dit(const Ctx& c, int j) {
     for (int i = 0; i < L && e->prec != F5_PREC_MXFP8; ++i) {
         const BlockW& bw = e->blocks[i];
         const float* m6 = mod + (size_t)i * 6 * D;  // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-        if (!h_ready) RC(K.ln_modulate(c.p<float>(w.x), m6 + D, m6, c.pb(w.h, 0), c.pb(w.h, 1), M, D, 1e-6f, s, fold ? c.p<float>(w.lnmean) : nullptr));
+        if (!h_ready && c.rows) RC(ln_rows(nullptr, nullptr, nullptr, m6 + D, m6));
+        else if (!h_ready) RC(K.ln_modulate(c.p<float>(w.x), m6 + D, m6, c.pb(w.h, 0), c.pb(w.h, 1), M, D, 1e-6f, s, fold ? c.p<float>(w.lnmean) : nullptr));
         F5GemmArgs gq = gemm_base(c, c.pb(w.h, 0), c.pb(w.h, 1), D, bw.qkv, M, 3 * D, D, c.a<float>(bw.bqkv));
         if (h_folded) fold_consumer(gq, i, 0);
         gq.out_bf[0] = c.pb(w.qk, 0);
@@ -921,16 +979,20 @@ static int run_dit(const Ctx& c, int j) {
         RC(K.attention(at, s));
 
         F5GemmArgs go = gemm_base(c, c.pb(w.ao, 0), c.pb(w.ao, 1), D, bw.o, M, D, D, c.a<float>(bw.bo));
-        go.out_f32 = c.p<float>(w.x);
+        go.out_f32 = c.rows ? yscratch : c.p<float>(w.x);
         go.ldo = D;
-        go.gate = m6 + 2 * D;
-        go.rowkeep = rowkeep;
+        if (!c.rows) {
+            go.gate = m6 + 2 * D;
+            go.rowkeep = rowkeep;
+        }
         const bool fused_mlp_ln = fuse_ln(go, m6 + 4 * D, m6 + 3 * D);     // h = LN(x) (1 + scale_mlp) + shift_mlp in the same launch
         if (fold) fold_producer(go, m6 + 4 * D);
-        RC(K.gemm(go, EPI_RESID_GATE, s));
+        RC(K.gemm(go, c.rows ? EPI_F32 : EPI_RESID_GATE, s));
         if (fold) RC(fold_rows());
 
-        if (!fused_mlp_ln && !fold) RC(K.ln_modulate(c.p<float>(w.x), m6 + 4 * D, m6 + 3 * D, c.pb(w.h, 0), c.pb(w.h, 1), M, D, 1e-6f, s));
+        // per-row controls: x += gate_msa[row] * (keep ? y : 0), then the mlp LN-modulate, in one row kernel
+        if (c.rows) RC(ln_rows(yscratch, m6 + 2 * D, rowkeep, m6 + 4 * D, m6 + 3 * D));
+        else if (!fused_mlp_ln && !fold) RC(K.ln_modulate(c.p<float>(w.x), m6 + 4 * D, m6 + 3 * D, c.pb(w.h, 0), c.pb(w.h, 1), M, D, 1e-6f, s));
         F5GemmArgs g1 = gemm_base(c, c.pb(w.h, 0), c.pb(w.h, 1), D, bw.ff1, M, FF, D, c.a<float>(bw.bff1));
         if (fold) fold_consumer(g1, i, 3 * D);
         g1.out_bf[0] = c.pb(w.ffh, 0);
@@ -938,9 +1000,9 @@ static int run_dit(const Ctx& c, int j) {
         g1.ldob = FF;
         RC(K.gemm(g1, EPI_GELU_TANH, s));
         F5GemmArgs g2 = gemm_base(c, c.pb(w.ffh, 0), c.pb(w.ffh, 1), FF, bw.ff2, M, D, FF, c.a<float>(bw.bff2));
-        g2.out_f32 = c.p<float>(w.x);
+        g2.out_f32 = c.rows ? yscratch : c.p<float>(w.x);
         g2.ldo = D;
-        g2.gate = m6 + 5 * D;
+        if (!c.rows) g2.gate = m6 + 5 * D;
         // the LN that follows FF2: the next block's attention LN (scale_msa, shift_msa), or the final one (dit.py:287: scale, shift)
         const float* m6n = m6 + 6 * D;
         h_ready = (i + 1 < L) ? fuse_ln(g2, m6n + D, m6n) : fuse_ln(g2, mf, mf + D);
@@ -949,8 +1011,12 @@ static int run_dit(const Ctx& c, int j) {
             fold_producer(g2, m6n + D);
             h_ready = true;
         }
-        RC(K.gemm(g2, EPI_RESID_GATE, s));
+        RC(K.gemm(g2, c.rows ? EPI_F32 : EPI_RESID_GATE, s));
         if (h_folded) RC(fold_rows());
+        if (c.rows) {        // x += gate_mlp[row] * y, then the LN that follows (no row mask on FF2, as in the gated epilogue above)
+            RC(i + 1 < L ? ln_rows(yscratch, m6 + 5 * D, nullptr, m6n + D, m6n) : ln_rows(yscratch, m6 + 5 * D, nullptr, mf, mf + D));
+            h_ready = true;
+        }
     }
     if (!h_ready) RC(K.ln_modulate(c.p<float>(w.x), mf, mf + D, c.pb(w.h, 0), c.pb(w.h, 1), M, D, 1e-6f, s));
     F5GemmArgs gf = gemm_base(c, c.pb(w.h, 0), c.pb(w.h, 1), D, e->wout, M, cf.mel_dim, D, c.a<float>(e->bout));
@@ -979,7 +1045,13 @@ static int run_sample_body(const Ctx& c, const f5_sample_args* a, int i0 = 0, in
     const float* nullp = c.nb == 2 ? pred + M1 * mel : nullptr;
     float* kst = c.p<float>(w.kst);
     float* ytmp = c.p<float>(w.ytmp);
+    // per-row controls: every stage reads its row's guidance strength and the step's [B] step sizes
+    const float* dt_rows = nullptr;
+    auto stage = [&](const F5OdeArgs& o) {
+        return c.rows ? K.ode_stage_rows(o, c.p<float>(w.rcfg), dt_rows, c.N, c.B, s) : K.ode_stage(o, s);
+    };
     for (int i = i0; i + 1 < a->steps && i < i1; ++i) {
+        if (c.rows) dt_rows = c.p<float>(w.rdt) + (size_t)i * c.B;
         float* y = traj + (size_t)i * M1 * mel;
         float* ynext = traj + (size_t)(i + 1) * M1 * mel;
         F5OdeArgs o;
@@ -998,29 +1070,29 @@ static int run_sample_body(const Ctx& c, const f5_sample_args* a, int i0 = 0, in
             RC(run_dit(c, i));
             o.coef = 1.0f;
             o.out = ynext;
-            RC(K.ode_stage(o, s));
+            RC(stage(o));
         } else if (a->method == F5_MIDPOINT) {
             RC(run_dit(c, 2 * i));
             o.coef = 0.5f;
             o.out = ytmp;
-            RC(K.ode_stage(o, s));
+            RC(stage(o));
             RC(run_dit(c, 2 * i + 1));
             o.coef = 1.0f;
             o.out = ynext;
-            RC(K.ode_stage(o, s));
+            RC(stage(o));
         } else {
             RC(run_dit(c, 4 * i));
             o.coef = 0.5f;
             o.out = ytmp;
             o.kstore = kst;
-            RC(K.ode_stage(o, s));
+            RC(stage(o));
             RC(run_dit(c, 4 * i + 1));
             o.kstore = kst + M1 * mel;
-            RC(K.ode_stage(o, s));
+            RC(stage(o));
             RC(run_dit(c, 4 * i + 2));
             o.coef = 1.0f;
             o.kstore = kst + 2 * M1 * mel;
-            RC(K.ode_stage(o, s));
+            RC(stage(o));
             RC(run_dit(c, 4 * i + 3));
             o.kstore = nullptr;
             o.mode = 1;
@@ -1029,7 +1101,7 @@ static int run_sample_body(const Ctx& c, const f5_sample_args* a, int i0 = 0, in
             o.k2 = kst + M1 * mel;
             o.k3 = kst + 2 * M1 * mel;
             o.out = ynext;
-            RC(K.ode_stage(o, s));
+            RC(stage(o));
         }
     }
     return 0;
@@ -1102,28 +1174,15 @@ static Ctx make_ctx(f5_engine* e, const f5_sample_args* a, hipStream_t s) {
     return c;
 }
 
-// f5_sample (edit = false) and f5_sample_edit (the mask replaces n < lens[b] in the hoisted input packing and the final splice)
-static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* cond_keep, bool edit, void* stream) {
-    F5_REQUIRE(!edit || cond_keep, "f5_sample_edit: cond_keep is null");
-    RC(check_args(e, a));
-    F5_REQUIRE(a->y0 && a->t && a->out, "null pointer in f5_sample_args (y0/t/out)");
-    hipStream_t s = (hipStream_t)stream;
-    Ctx c = make_ctx(e, a, s);
-    c.edit = edit;
-    F5_REQUIRE(a->workspace_bytes >= c.w.total, "workspace too small: %zu < %zu", a->workspace_bytes, c.w.total);
-    const int mel = e->cfg.mel_dim;
-    const size_t M1 = (size_t)c.B * c.N;
-    SatScope sat(e->prec == F5_PREC_F16 && e->opt.sat_check, c.p<int>(c.w.status));
-
-    // function-evaluation times and step sizes in fp32, as the solvers compute them (cfm.py:50-56,76-86,106-114)
-    std::vector<float> tnfe, dts;
-    for (int i = 0; i + 1 < a->steps; ++i) {
-        const float t0 = a->t[i];
-        const float dt = a->t[i + 1] - t0;
+// function-evaluation times and step sizes of one time grid in fp32, as the solvers compute them (cfm.py:50-56,76-86,106-114)
+static void eval_times(const float* t, int steps, int method, std::vector<float>& tnfe, std::vector<float>& dts) {
+    for (int i = 0; i + 1 < steps; ++i) {
+        const float t0 = t[i];
+        const float dt = t[i + 1] - t0;
         dts.push_back(dt);
-        if (a->method == F5_EULER) {
+        if (method == F5_EULER) {
             tnfe.push_back(t0);
-        } else if (a->method == F5_MIDPOINT) {
+        } else if (method == F5_MIDPOINT) {
             tnfe.push_back(t0);
             tnfe.push_back(t0 + 0.5f * dt);
         } else {
@@ -1133,15 +1192,80 @@ static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* con
             tnfe.push_back(t0 + dt);
         }
     }
-    RC(stage_inputs(c, a, nullptr, tnfe, dts));
+}
+
+// what the per-row route refuses on top of check_args, before any launch; `what` names the call
+static int check_rows_route(const f5_engine* e, const char* what) {
+    F5_REQUIRE(e->prec != F5_PREC_MXFP8, "%s: precision mxfp8 has no per-row modulation kernels (use f16, bf16 or bf16x3)", what);
+    return 0;
+}
+
+// switches a context to the per-row route: the plan with the rows part, and both branches as soon as ANY row is guided
+static void ctx_to_rows(Ctx& c, const f5_sample_args* a, const float* cfg_rows, int ncfg) {
+    c.rows = true;
+    c.w = plan_workspace_rows(c.e, a->B, a->N, a->nt, a->steps, a->method);
+    c.nb = 1;
+    for (int b = 0; b < ncfg; ++b)
+        if (!(cfg_rows[b] < 1e-5f)) c.nb = 2;
+}
+
+// f5_sample (edit = false), f5_sample_edit (the mask replaces n < lens[b] in the hoisted input packing and the final splice) and
+// f5_sample_rows (rc != null: time grid and guidance strength per batch row)
+static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* cond_keep, bool edit, void* stream,
+                       const f5_row_controls* rc = nullptr) {
+    F5_REQUIRE(!edit || cond_keep, "f5_sample_edit: cond_keep is null");
+    RC(check_args(e, a));
+    F5_REQUIRE(a->y0 && (a->t || rc) && a->out, "null pointer in f5_sample_args (y0/t/out)");
+    hipStream_t s = (hipStream_t)stream;
+    Ctx c = make_ctx(e, a, s);
+    c.edit = edit;
+    if (rc) {
+        RC(check_rows_route(e, "f5_sample_rows"));
+        for (size_t i = 0; i < (size_t)a->B * a->steps; ++i)
+            F5_REQUIRE(std::isfinite(rc->t_rows[i]), "f5_sample_rows: t_rows[%zu][%zu] is not finite", i / a->steps, i % a->steps);
+        for (int b = 0; b < a->B; ++b) F5_REQUIRE(std::isfinite(rc->cfg_rows[b]), "f5_sample_rows: cfg_rows[%d] is not finite", b);
+        ctx_to_rows(c, a, rc->cfg_rows, a->B);
+        F5_REQUIRE(a->workspace_bytes >= c.w.total_rows, "f5_sample_rows: workspace too small: %zu < %zu (f5_workspace_bytes_rows)",
+                   a->workspace_bytes, c.w.total_rows);
+        if (ln_fold_state(c) < 0) return 2;
+    }
+    F5_REQUIRE(a->workspace_bytes >= c.w.total, "workspace too small: %zu < %zu", a->workspace_bytes, c.w.total);
+    const int mel = e->cfg.mel_dim;
+    const size_t M1 = (size_t)c.B * c.N;
+    SatScope sat(e->prec == F5_PREC_F16 && e->opt.sat_check, c.p<int>(c.w.status));
+
+    std::vector<float> tnfe, dts;
+    if (rc) {
+        // every row's own grid through the same fp32 arithmetic, laid out [nfe][B] / [steps - 1][B]; the scalar slots get row 0's
+        const int nfe = (a->steps - 1) * nfe_per_step(a->method);
+        std::vector<uint32_t> words(c.w.rscal_words, 0u);
+        float* rt = reinterpret_cast<float*>(words.data());
+        float* rd = rt + (size_t)(nfe > 0 ? nfe : 1) * c.B;
+        for (int b = 0; b < c.B; ++b) {
+            std::vector<float> tb, db;
+            eval_times(rc->t_rows + (size_t)b * a->steps, a->steps, a->method, tb, db);
+            for (size_t j = 0; j < tb.size(); ++j) rt[j * c.B + b] = tb[j];
+            for (size_t i = 0; i < db.size(); ++i) rd[i * c.B + b] = db[i];
+            if (b == 0) {
+                tnfe = tb;
+                dts = db;
+            }
+        }
+        memcpy(rd + (size_t)a->steps * c.B, rc->cfg_rows, (size_t)c.B * 4);
+        RC(stage_inputs(c, a, nullptr, tnfe, dts));
+        RC(f5_launch_stage_words(words.data(), words.size(), c.p<uint32_t>(c.w.rscal), s));
+    } else {
+        eval_times(a->t, a->steps, a->method, tnfe, dts);
+        RC(stage_inputs(c, a, nullptr, tnfe, dts));
+    }
     // the mask travels like text / cond / y0: copied into the workspace outside the captured part, so one graph serves every mask of a shape
     if (edit) RC(f5_launch_copy_bytes(cond_keep, c.ws + c.w.cond_keep, M1, s));
 
     // hipGraph cache.  The key is everything a captured node depends on BY VALUE: shapes, solver, branch count, masking and the
     // workspace address.  Per-call scalars (cfg strength, time grid, dt) are read from workspace memory staged above.
     char shape_key[192];
-    snprintf(shape_key, sizeof(shape_key), "B%d N%d nt%d st%d m%d nb%d mask%d edit%d ke%d ws%p opt", c.B, c.N, c.nt, a->steps, a->method,
-             c.nb, (int)c.use_mask, (int)c.edit, g_knob_epoch, a->workspace);
+    snprintf(shape_key, sizeof(shape_key), "B%d N%d nt%d st%d m%d nb%d mask%d edit%d rows%d ke%d ws%p opt", c.B, c.N, c.nt, a->steps,
+             a->method, c.nb, (int)c.use_mask, (int)c.edit, (int)c.rows, g_knob_epoch, a->workspace);
     std::string key(shape_key);
     for (const OptDesc& o : k_options) key += " " + std::to_string(e->opt.*o.member);
     const bool graph_on = a->use_graph == F5_GRAPH_ON, graph_auto = a->use_graph == F5_GRAPH_AUTO;
@@ -1178,6 +1302,12 @@ static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* con
 extern "C" int f5_sample(f5_engine* e, const f5_sample_args* a, void* stream) { return sample_impl(e, a, nullptr, false, stream); }
 extern "C" int f5_sample_edit(f5_engine* e, const f5_sample_args* a, const uint8_t* cond_keep_dev, void* stream) {
     return sample_impl(e, a, cond_keep_dev, true, stream);
+}
+extern "C" int f5_sample_rows(f5_engine* e, const f5_sample_args* a, const f5_row_controls* rc, void* stream) {
+    F5_REQUIRE(rc != nullptr, "f5_sample_rows: controls is null");
+    F5_REQUIRE(rc->t_rows != nullptr, "f5_sample_rows: controls.t_rows is null");
+    F5_REQUIRE(rc->cfg_rows != nullptr, "f5_sample_rows: controls.cfg_rows is null");
+    return sample_impl(e, a, rc->cond_keep_dev, rc->cond_keep_dev != nullptr, stream, rc);
 }
 
 // Status word of the last f5_sample / f5_dit_forward that used this workspace (its FIRST 32-bit word, for every shape and solver):
@@ -1222,6 +1352,41 @@ extern "C" int f5_dit_forward(f5_engine* e, const f5_sample_args* a, const float
     SatScope sat(e->prec == F5_PREC_F16 && e->opt.sat_check, c.p<int>(c.w.status));
     std::vector<float> tnfe(1, t), dts(1, 0.0f);
     RC(stage_inputs(c, &a2, x, tnfe, dts));
+    const Ops& K = c.ops;
+    RC(run_prep(c, 1));
+    RC(K.pack_x(c.p<float>(c.w.traj), c.pb(c.w.xin, 0), c.pb(c.w.xin, 1), (int)M1, mel, s));
+    RC(run_dit(c, 0));
+    RC(f5_launch_copy_words(c.ws + c.w.vel, pred, M1 * mel, s));
+    if (null_pred && c.nb == 2) RC(f5_launch_copy_words(c.ws + c.w.vel + M1 * mel * 4, null_pred, M1 * mel, s));
+    return 0;
+}
+
+// f5_dit_forward with one time per batch row (the reference's DiT takes `time` as (b,), dit.py:374-401): one batched forward where the
+// scalar entry point needs one call per distinct time.  Workspace: f5_workspace_bytes_rows with steps = 2, method = F5_EULER.
+extern "C" int f5_dit_forward_rows(f5_engine* e, const f5_sample_args* a, const float* x, const float* t_rows_host, float* pred,
+                                   float* null_pred, void* stream) {
+    RC(check_args(e, a));
+    F5_REQUIRE(x && pred, "null pointer");
+    F5_REQUIRE(t_rows_host != nullptr, "f5_dit_forward_rows: t_rows is null");
+    RC(check_rows_route(e, "f5_dit_forward_rows"));
+    for (int b = 0; b < a->B; ++b) F5_REQUIRE(std::isfinite(t_rows_host[b]), "f5_dit_forward_rows: t_rows[%d] is not finite", b);
+    hipStream_t s = (hipStream_t)stream;
+    f5_sample_args a2 = *a;
+    a2.steps = 2;
+    a2.method = F5_EULER;
+    Ctx c = make_ctx(e, &a2, s);
+    ctx_to_rows(c, &a2, &a2.cfg_strength, 1);
+    F5_REQUIRE(a->workspace_bytes >= c.w.total_rows, "f5_dit_forward_rows: workspace too small: %zu < %zu (f5_workspace_bytes_rows)",
+               a->workspace_bytes, c.w.total_rows);
+    if (ln_fold_state(c) < 0) return 2;
+    const int mel = e->cfg.mel_dim;
+    const size_t M1 = (size_t)c.B * c.N;
+    SatScope sat(e->prec == F5_PREC_F16 && e->opt.sat_check, c.p<int>(c.w.status));
+    std::vector<float> tnfe(1, t_rows_host[0]), dts(1, 0.0f);
+    RC(stage_inputs(c, &a2, x, tnfe, dts));
+    std::vector<uint32_t> words(c.w.rscal_words, 0u);       // [tgrid B | dt 2 B | cfg B]: only the times are read by a forward
+    memcpy(words.data(), t_rows_host, (size_t)c.B * 4);
+    RC(f5_launch_stage_words(words.data(), words.size(), c.p<uint32_t>(c.w.rscal), s));
     const Ops& K = c.ops;
     RC(run_prep(c, 1));
     RC(K.pack_x(c.p<float>(c.w.traj), c.pb(c.w.xin, 0), c.pb(c.w.xin, 1), (int)M1, mel, s));
@@ -1731,6 +1896,39 @@ extern "C" int f5_op_ode_stage(const float* pred, const float* null_pred, float 
     F5_REQUIRE(pred != nullptr && base != nullptr && dt_dev != nullptr && out != nullptr, "ode_stage: null pred / base / dt / out");
     F5_REQUIRE(mode == 0 || (mode == 1 && k1 != nullptr && k2 != nullptr && k3 != nullptr), "ode_stage: mode 1 needs k1, k2 and k3");
     return g_ops.ode_stage(o, (hipStream_t)stream);
+}
+// the stage kernel with guidance strength and step size per row (rowops.hpp f5_launch_ode_stage_rows)
+extern "C" int f5_op_ode_stage_rows(const float* pred, const float* null_pred, const float* cfg_rows, const float* base, const float* dt_rows,
+                                    int rows_per_vec, int nvec, float coef, float divisor, int mode, float* kstore, const float* k1,
+                                    const float* k2, const float* k3, float* out, void* xin_hi, void* xin_lo, int rows, int mel_dim,
+                                    void* stream) {
+    F5OdeArgs o;
+    memset(&o, 0, sizeof(o));
+    o.pred = pred;
+    o.null_pred = null_pred;
+    o.base = base;
+    o.coef = coef;
+    o.divisor = divisor;
+    o.mode = mode;
+    o.kstore = kstore;
+    o.k1 = k1;
+    o.k2 = k2;
+    o.k3 = k3;
+    o.out = out;
+    o.xin_hi = (op16_t*)xin_hi;
+    o.xin_lo = (op16_t*)xin_lo;
+    o.rows = rows;
+    o.mel_dim = mel_dim;
+    F5_REQUIRE(pred != nullptr && base != nullptr && out != nullptr, "ode_stage_rows: null pred / base / out");
+    F5_REQUIRE(mode == 0 || (mode == 1 && k1 != nullptr && k2 != nullptr && k3 != nullptr), "ode_stage_rows: mode 1 needs k1, k2 and k3");
+    return g_ops.ode_stage_rows(o, cfg_rows, dt_rows, rows_per_vec, nvec, (hipStream_t)stream);
+}
+// residual update + LN-modulate with per-row vectors (rowops.hpp f5_launch_resid_gate_ln_rows), eps 1e-6
+extern "C" int f5_op_resid_gate_ln_rows(const float* y, float* x, const float* gate, const uint8_t* rowkeep, const float* ln_scale,
+                                        const float* ln_shift, void* out_hi, void* out_lo, int rows, int dim, int rows_per_vec, int nvec,
+                                        size_t vec_stride, void* stream) {
+    return g_ops.resid_gate_ln_rows(y, x, gate, rowkeep, ln_scale, ln_shift, (op16_t*)out_hi, (op16_t*)out_lo, rows, dim, rows_per_vec, nvec,
+                                    vec_stride, 1e-6f, (hipStream_t)stream);
 }
 extern "C" int f5_op_pack_cond_text(const float* cond, const int32_t* lens, const float* text_emb, void* out_hi, void* out_lo, int B,
                                     int seq_len, int mel_dim, int dt, int null_keeps_cond, void* stream) {

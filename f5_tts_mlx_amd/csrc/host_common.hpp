@@ -101,6 +101,18 @@ struct Ops {
     int ode_stage(const F5OdeArgs& a, hipStream_t s) const {
         return h ? f5hf::f5_launch_ode_stage(reinterpret_cast<const f5hf::F5OdeArgs&>(a), s) : f5bf::f5_launch_ode_stage(a, s);
     }
+    int ode_stage_rows(const F5OdeArgs& a, const float* cfg_rows, const float* dt_rows, int rows_per_vec, int nvec, hipStream_t s) const {
+        return h ? f5hf::f5_launch_ode_stage_rows(reinterpret_cast<const f5hf::F5OdeArgs&>(a), cfg_rows, dt_rows, rows_per_vec, nvec, s)
+                 : f5bf::f5_launch_ode_stage_rows(a, cfg_rows, dt_rows, rows_per_vec, nvec, s);
+    }
+    int resid_gate_ln_rows(const float* y, float* x, const float* gate, const uint8_t* rowkeep, const float* ln_scale, const float* ln_shift,
+                           op16_t* hi, op16_t* lo, int rows, int dim, int rows_per_vec, int nvec, size_t vec_stride, float eps,
+                           hipStream_t s) const {
+        return h ? f5hf::f5_launch_resid_gate_ln_rows(y, x, gate, rowkeep, ln_scale, ln_shift, H(hi), H(lo), rows, dim, rows_per_vec, nvec,
+                                                      vec_stride, eps, s)
+                 : f5bf::f5_launch_resid_gate_ln_rows(y, x, gate, rowkeep, ln_scale, ln_shift, hi, lo, rows, dim, rows_per_vec, nvec,
+                                                      vec_stride, eps, s);
+    }
     int ln_modulate(const float* x, const float* scale, const float* shift, op16_t* hi, op16_t* lo, int rows, int dim, float eps,
                     hipStream_t s, float* mean_out = nullptr) const {
         return h ? f5hf::f5_launch_ln_modulate(x, scale, shift, H(hi), H(lo), rows, dim, eps, s, mean_out)

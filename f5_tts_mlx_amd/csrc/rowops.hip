@@ -63,6 +63,84 @@ int f5_launch_ln_modulate(const float* x, const float* scale, const float* shift
     return 0;
 }
 
+// =================================================================================================
+// Residual update + the LN-modulate that follows it, modulation vectors chosen PER ROW (per-request sampling controls: every batch
+// row has its own time, hence its own adaLN vectors).  Row r reads vector v = (r / rows_per_vec) % nvec of gate / ln_scale / ln_shift
+// (vec_stride floats apart): in the engine rows_per_vec = N and nvec = B, so the stacked cond and null branches share their rows' vectors.
+//   WITH_Y:  x = fmaf(gate[v], rowkeep[r] ? y : 0, x)   (a selection: a dropped row's y is not even loaded), written back
+//   WITH_LN: h = LN(x) (1 + ln_scale[v]) + ln_shift[v] through f5_ln_modulate_row, from the registers that hold the row
+// One wave per row like ln_modulate_kernel; no atomics except the saturation report of the packers.
+// =================================================================================================
+template <int NV, bool WITH_Y, bool WITH_LN>
+__global__ __launch_bounds__(256) void resid_gate_ln_rows_kernel(const float* __restrict__ y, float* __restrict__ x,
+                                                                 const float* __restrict__ gate, const uint8_t* __restrict__ rowkeep,
+                                                                 const float* __restrict__ ln_scale, const float* __restrict__ ln_shift,
+                                                                 op16_t* __restrict__ out_hi, op16_t* __restrict__ out_lo, int rows,
+                                                                 int rows_per_vec, int nvec, size_t vec_stride, float eps, int* sat_flag) {
+    constexpr int DIM = NV * 256;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const size_t voff = (size_t)((row / rows_per_vec) % nvec) * vec_stride;
+    float* xr = x + (size_t)row * DIM;
+    f32x4 v[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = *reinterpret_cast<const f32x4*>(xr + i * 256 + lane * 4);
+    if (WITH_Y) {
+        const bool keep = rowkeep == nullptr || rowkeep[row] != 0;
+        const float* yr = y + (size_t)row * DIM;
+        f32x4 g[NV], t[NV];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            g[i] = *reinterpret_cast<const f32x4*>(gate + voff + i * 256 + lane * 4);
+            t[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            if (keep) t[i] = *reinterpret_cast<const f32x4*>(yr + i * 256 + lane * 4);
+        }
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[i][e] = fmaf(g[i][e], t[i][e], v[i][e]);
+            *reinterpret_cast<f32x4*>(xr + i * 256 + lane * 4) = v[i];
+        }
+    }
+    if (WITH_LN) f5_ln_modulate_row<NV>(v, ln_scale + voff, ln_shift + voff, out_hi, out_lo, (size_t)row, lane, eps, sat_flag);
+}
+
+int f5_launch_resid_gate_ln_rows(const float* y, float* x, const float* gate, const uint8_t* rowkeep, const float* ln_scale,
+                                 const float* ln_shift, op16_t* out_hi, op16_t* out_lo, int rows, int dim, int rows_per_vec, int nvec,
+                                 size_t vec_stride, float eps, hipStream_t s) {
+    F5_REQUIRE(x != nullptr, "resid_gate_ln_rows: x is null");
+    F5_REQUIRE(y != nullptr || ln_scale != nullptr, "resid_gate_ln_rows: nothing to do (y and ln_scale are both null)");
+    F5_REQUIRE(rows_per_vec >= 1, "resid_gate_ln_rows: rows_per_vec must be >= 1 (got %d)", rows_per_vec);
+    F5_REQUIRE(nvec >= 1, "resid_gate_ln_rows: nvec must be >= 1 (got %d)", nvec);
+    F5_REQUIRE(dim % 256 == 0 && dim >= 256 && dim <= 1024, "resid_gate_ln_rows: dim must be 256/512/768/1024 (got %d)", dim);
+    F5_REQUIRE(vec_stride >= (size_t)dim, "resid_gate_ln_rows: vec_stride %zu is smaller than dim %d", vec_stride, dim);
+    F5_REQUIRE(vec_stride % 4 == 0, "resid_gate_ln_rows: vec_stride %zu must be a multiple of 4 floats (16-byte loads)", vec_stride);
+    F5_REQUIRE(y == nullptr || gate != nullptr, "resid_gate_ln_rows: y without a gate");
+    F5_REQUIRE(ln_scale == nullptr || (ln_shift != nullptr && out_hi != nullptr), "resid_gate_ln_rows: ln_scale without ln_shift / out_hi");
+    F5_REQUIRE(rows >= 1, "resid_gate_ln_rows: no rows (got %d)", rows);
+    const dim3 grid(f5_cdiv(rows, 4)), block(256);
+#define RGL_LAUNCH(NV_)                                                                                                                  \
+    if (y != nullptr && ln_scale != nullptr)                                                                                             \
+        hipLaunchKernelGGL((resid_gate_ln_rows_kernel<NV_, true, true>), grid, block, 0, s, y, x, gate, rowkeep, ln_scale, ln_shift, out_hi, \
+                           out_lo, rows, rows_per_vec, nvec, vec_stride, eps, f5_sat_flag_host);                                         \
+    else if (y != nullptr)                                                                                                               \
+        hipLaunchKernelGGL((resid_gate_ln_rows_kernel<NV_, true, false>), grid, block, 0, s, y, x, gate, rowkeep, ln_scale, ln_shift, out_hi, \
+                           out_lo, rows, rows_per_vec, nvec, vec_stride, eps, f5_sat_flag_host);                                         \
+    else                                                                                                                                 \
+        hipLaunchKernelGGL((resid_gate_ln_rows_kernel<NV_, false, true>), grid, block, 0, s, y, x, gate, rowkeep, ln_scale, ln_shift, out_hi, \
+                           out_lo, rows, rows_per_vec, nvec, vec_stride, eps, f5_sat_flag_host);
+    switch (dim / 256) {
+        case 1: RGL_LAUNCH(1); break;
+        case 2: RGL_LAUNCH(2); break;
+        case 3: RGL_LAUNCH(3); break;
+        default: RGL_LAUNCH(4); break;
+    }
+#undef RGL_LAUNCH
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+
 // MX-fp8 variant: same math, output as e4m3 + one E8M0 scale per 32 columns (8 lanes x 4 columns = one block)
 template <int NV>
 __global__ __launch_bounds__(256) void ln_modulate_f8_kernel(const float* __restrict__ x, const float* __restrict__ scale,
@@ -666,7 +744,12 @@ int f5_launch_pack_x(const float* y, op16_t* out_hi, op16_t* out_lo, int rows, i
     return 0;
 }
 
-__global__ __launch_bounds__(256) void ode_stage_kernel(F5OdeArgs p) {
+// One element of a stage: shared by the kernel with one (cfg, dt) for the call and the one that reads them per row, so that both do
+// the same arithmetic.  ROWS: row r uses cfg_rows[v] / dt_rows[v], v = (r / rows_per_vec) % nvec, and a row whose cfg is below 1e-5 takes
+// k = pred by selection (cfm.py:352): its null_pred is not loaded.
+template <bool ROWS>
+__device__ __forceinline__ void f5_ode_stage_elem(const F5OdeArgs& p, const float* __restrict__ cfg_rows, const float* __restrict__ dt_rows,
+                                                  int rows_per_vec, int nvec) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;   // over rows * 128 (padded columns)
     if (i >= (size_t)p.rows * 128) return;
     const size_t row = i >> 7;
@@ -676,9 +759,18 @@ __global__ __launch_bounds__(256) void ode_stage_kernel(F5OdeArgs p) {
         const size_t idx = row * p.mel_dim + c;
         const float pr = p.pred[idx];
         float k = pr;
-        if (p.null_pred) k = pr + (pr - p.null_pred[idx]) * (p.cfg_ptr ? p.cfg_ptr[0] : p.cfg);     // cfm.py:364
+        float dt;
+        if (ROWS) {
+            const int v = (int)((row / (size_t)rows_per_vec) % (size_t)nvec);
+            const float cfg = cfg_rows[v];
+            dt = dt_rows[v];
+            if (p.null_pred && !(cfg < 1e-5f)) k = pr + (pr - p.null_pred[idx]) * cfg;
+        } else {
+            if (p.null_pred) k = pr + (pr - p.null_pred[idx]) * (p.cfg_ptr ? p.cfg_ptr[0] : p.cfg);     // cfm.py:364
+            dt = p.dt_ptr[0];
+        }
         if (p.kstore) p.kstore[idx] = k;
-        const float a = (p.coef * p.dt_ptr[0]) / p.divisor;
+        const float a = (p.coef * dt) / p.divisor;
         float upd = k;
         if (p.mode == 1) upd = ((p.k1[idx] + 2.0f * p.k2[idx]) + 2.0f * p.k3[idx]) + k;  // cfm.py:117
         o = p.base[idx] + a * upd;
@@ -693,11 +785,28 @@ __global__ __launch_bounds__(256) void ode_stage_kernel(F5OdeArgs p) {
         f5_sat_commit(trk, p.sat_flag);
     }
 }
+__global__ __launch_bounds__(256) void ode_stage_kernel(F5OdeArgs p) { f5_ode_stage_elem<false>(p, nullptr, nullptr, 1, 1); }
+__global__ __launch_bounds__(256) void ode_stage_rows_kernel(F5OdeArgs p, const float* __restrict__ cfg_rows,
+                                                             const float* __restrict__ dt_rows, int rows_per_vec, int nvec) {
+    f5_ode_stage_elem<true>(p, cfg_rows, dt_rows, rows_per_vec, nvec);
+}
 int f5_launch_ode_stage(const F5OdeArgs& a, hipStream_t s) {
     F5_REQUIRE(a.mel_dim <= 128, "ode_stage: mel_dim must be <= 128");
     F5OdeArgs ab = a;
     if (ab.sat_flag == nullptr) ab.sat_flag = f5_sat_flag_host;
     hipLaunchKernelGGL(ode_stage_kernel, dim3(f5_cdiv((long)a.rows * 128, 256)), dim3(256), 0, s, ab);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+int f5_launch_ode_stage_rows(const F5OdeArgs& a, const float* cfg_rows, const float* dt_rows, int rows_per_vec, int nvec, hipStream_t s) {
+    F5_REQUIRE(a.mel_dim <= 128, "ode_stage_rows: mel_dim must be <= 128");
+    F5_REQUIRE(cfg_rows != nullptr && dt_rows != nullptr, "ode_stage_rows: null cfg_rows / dt_rows");
+    F5_REQUIRE(rows_per_vec >= 1 && nvec >= 1, "ode_stage_rows: rows_per_vec and nvec must be >= 1 (got %d, %d)", rows_per_vec, nvec);
+    F5_REQUIRE(a.rows >= 1, "ode_stage_rows: no rows (got %d)", a.rows);
+    F5OdeArgs ab = a;
+    if (ab.sat_flag == nullptr) ab.sat_flag = f5_sat_flag_host;
+    hipLaunchKernelGGL(ode_stage_rows_kernel, dim3(f5_cdiv((long)a.rows * 128, 256)), dim3(256), 0, s, ab, cfg_rows, dt_rows, rows_per_vec,
+                       nvec);
     F5_LAUNCH_CHECK();
     return 0;
 }

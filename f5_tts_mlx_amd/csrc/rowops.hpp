@@ -24,6 +24,14 @@ extern thread_local int* f5_sat_flag_host;   // rowops.hip (per host thread): wh
 int f5_launch_ln_modulate(const float* x, const float* scale, const float* shift, op16_t* out_hi, op16_t* out_lo,
                           int rows, int dim, float eps, hipStream_t s, float* mean_out = nullptr);
 
+// Residual update and the LN-modulate behind it with the modulation vectors chosen per row: row r of the [rows][dim] buffers reads vector
+// v = (r / rows_per_vec) % nvec of gate / ln_scale / ln_shift (vec_stride floats apart).  With y (fp32, may be null):
+// x = fmaf(gate[v], rowkeep[r] ? y : 0, x) in place (rowkeep may be null); with ln_scale (may be null, then ln_shift too): (out_hi, out_lo) =
+// LN(x)(1 + ln_scale[v]) + ln_shift[v], the bits of f5_launch_ln_modulate on that row.  y null = f5_launch_ln_modulate with per-row vectors.
+int f5_launch_resid_gate_ln_rows(const float* y, float* x, const float* gate, const uint8_t* rowkeep, const float* ln_scale,
+                                 const float* ln_shift, op16_t* out_hi, op16_t* out_lo, int rows, int dim, int rows_per_vec, int nvec,
+                                 size_t vec_stride, float eps, hipStream_t s);
+
 // ConvNeXtV2 front half (convnext_v2.py:46-48): depthwise Conv1d(k=7,pad=3)+bias -> LayerNorm(affine).
 int f5_launch_dwconv_ln(const float* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,
                         op16_t* out_hi, op16_t* out_lo, int nbatch, int seq_len, int dim, float eps, hipStream_t s);
@@ -88,6 +96,9 @@ struct F5OdeArgs {
     int* sat_flag;           // null = f5_sat_flag_host (op16.hpp f5_sat_commit)
 };
 int f5_launch_ode_stage(const F5OdeArgs& a, hipStream_t s);
+// the same with guidance scale and step size PER ROW: row r uses cfg_rows[v] and dt_rows[v] (dev fp32 [nvec] each), v = (r / rows_per_vec)
+// % nvec, in place of cfg / cfg_ptr / dt_ptr; a row with cfg_rows[v] < 1e-5 takes k = pred by selection even when null_pred is given
+int f5_launch_ode_stage_rows(const F5OdeArgs& a, const float* cfg_rows, const float* dt_rows, int rows_per_vec, int nvec, hipStream_t s);
 
 // out = where(n < lens[b], cond, y)  (cfm.py:395-397)
 int f5_launch_splice(const float* cond, const float* y, const int* lens, float* out, int B, int seq_len, int mel_dim,

@@ -19,7 +19,7 @@ from .weights import DiTConfig
 class DiT:
     def __init__(self, *, dim, depth=8, heads=8, dim_head=64, dropout=0.0, ff_mult=4, mel_dim=100, text_num_embeds=256,
                  text_dim=None, text_mask_padding=True, conv_layers=0, precision: str = "f16",
-                 device: str | torch.device = "cuda:0"):
+                 device: str | torch.device = "cuda:0", row_times: bool = False):
         if text_dim is None:
             text_dim = mel_dim
         if dropout != 0.0:
@@ -34,6 +34,9 @@ class DiT:
         self.precision = precision
         self.device = torch.device(device)
         self._engine: Optional[Engine] = None
+        # True: a (b,) `time` is ONE batched forward (f5_dit_forward_rows) where differing entries otherwise mean b batch-1 forwards; the
+        # default keeps the loop (its results are the scalar route's bits)
+        self.row_times = bool(row_times)
 
     @classmethod
     def from_config(cls, cfg: DiTConfig, precision="f16", device="cuda:0") -> "DiT":
@@ -61,7 +64,7 @@ class DiT:
         drop_audio_cond, cfm.py:225) but its `DiT` accepts it — is the second branch with the engine option `null_keeps_cond`.
         `time` may be a scalar or a (b,) tensor; rows with different times run as separate batch-1 forwards at the SAME padded
         length with their own row of `mask`, which is exact (no cross-utterance arithmetic in the DiT; GRN / conv-pos see the
-        same padding)."""
+        same padding).  With the attribute `row_times = True` such a batch is one forward on the engine's per-row route instead."""
         drop_audio_cond, drop_text = _flag(drop_audio_cond), _flag(drop_text)
         if drop_text and not drop_audio_cond:
             self.engine.set_option("null_keeps_cond", 1)
@@ -84,6 +87,11 @@ class DiT:
                 raise ValueError(f"time has {len(times)} entries for a batch of {B}")
         else:
             times = [float(time if not torch.is_tensor(time) else time.reshape(-1)[0])] * B
+        row_t = None
+        if self.row_times and torch.is_tensor(time) and time.numel() > 1:
+            # one batched forward: every row's adaLN vectors from its own time (Engine.dit_forward); a (b,) time takes this route whether or
+            # not its entries differ, so that a batch does not change kernels with its values
+            row_t, times = times, times[:1]
         if len(set(times)) > 1:
             outs = [self._forward(x[i:i + 1], cond[i:i + 1], text[i:i + 1], times[i], drop_audio_cond, drop_text,
                                   None if mask is None else mask[i:i + 1]) for i in range(B)]
@@ -93,7 +101,7 @@ class DiT:
         else:
             durations = [N] * B
         # `cond` arrives already masked (step_cond), so the conditioning length is the full sequence
-        pred, null = self.engine.dit_forward(x, text, cond, [N] * B, durations, times[0],
+        pred, null = self.engine.dit_forward(x, text, cond, [N] * B, durations, times[0] if row_t is None else row_t,
                                              cfg_strength=2.0 if drop_text else 0.0, use_mask=mask is not None)
         return null if drop_text else pred
 

@@ -73,6 +73,37 @@ class F5SampleArgs(C.Structure):
     ]
 
 
+class F5RowControls(C.Structure):
+    _fields_ = [("t_rows", C.c_void_p), ("cfg_rows", C.c_void_p), ("cond_keep_dev", C.c_void_p)]
+
+
+def row_controls(t, cfg_strength, B: int):
+    """Per-row sampling controls of a sample() call (f5_sample_rows): `t` may be a (steps,) grid or one grid per row (B, steps),
+    `cfg_strength` a float or a length-B sequence.  Either one being per-row selects the rows route and the other is broadcast.
+    -> (steps, None) for an all-scalar call, else (steps, (t_rows (B, steps) fp32, cfg_rows (B,) fp32)), both C-contiguous."""
+    t = np.asarray(t, dtype=np.float32)
+    cfg_seq = np.ndim(cfg_strength) != 0
+    if t.ndim not in (1, 2):
+        raise ValueError(f"t must be (steps,) or (B, steps), got shape {t.shape}")
+    if t.ndim == 1 and not cfg_seq:
+        return int(t.shape[0]), None
+    if t.ndim == 2 and t.shape[0] != B:
+        raise ValueError(f"per-row time grid: expected {B} rows, got {t.shape[0]}")
+    cfg = np.asarray(cfg_strength, dtype=np.float32)
+    if cfg_seq and cfg.shape != (B,):
+        raise ValueError(f"per-row cfg_strength: expected {B} values, got shape {cfg.shape}")
+    steps = int(t.shape[-1])
+    t_rows = np.ascontiguousarray(np.broadcast_to(t, (B, steps)), dtype=np.float32)
+    cfg_rows = np.ascontiguousarray(np.broadcast_to(cfg, (B,)), dtype=np.float32)
+    return steps, (t_rows, cfg_rows)
+
+
+def _rows_slice(t, cfg_strength, b0: int, b1: int):
+    """The controls of batch rows [b0, b1) of a sample() call: per-row forms are sliced, shared ones pass through."""
+    t = np.asarray(t, dtype=np.float32)
+    return (t[b0:b1] if t.ndim == 2 else t), (cfg_strength if np.ndim(cfg_strength) == 0 else list(cfg_strength)[b0:b1])
+
+
 def library_path() -> Path:
     return _LIB_PATH
 
@@ -100,6 +131,15 @@ def load_library() -> C.CDLL:
     lib.f5_debug_last_convpos_kernel.argtypes = [C.c_char_p, C.c_int]
     lib.f5_op_noise_from_bits.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.f5_sample_edit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    # the per-row route (docs/row_controls.md).  An older build named by F5TTS_HIP_LIB (A/B runs) lacks these symbols: it still loads, and
+    # a call of the route on it raises AttributeError -- never a fall-back
+    for name, types in (("f5_sample_rows", [C.c_void_p] * 4), ("f5_dit_forward_rows", [C.c_void_p] * 7),
+                        ("f5_workspace_bytes_rows", [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+                        ("f5_op_resid_gate_ln_rows", [C.c_void_p] * 8 + [C.c_int] * 4 + [C.c_size_t, C.c_void_p]),
+                        ("f5_op_ode_stage_rows", [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 7
+                         + [C.c_int, C.c_int, C.c_void_p])):
+        if hasattr(lib, name):
+            getattr(lib, name).argtypes = types
     lib.f5_op_wave_patch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int,
                                      C.c_int, C.c_void_p]
     lib.f5_wave_block_energy.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -355,11 +395,15 @@ class Engine:
         self.finalize()
 
     # ---- workspace -------------------------------------------------------------------------
-    def workspace(self, B: int, N: int, nt: int, steps: int, method: str) -> torch.Tensor:
+    def workspace(self, B: int, N: int, nt: int, steps: int, method: str, rows: bool = False) -> torch.Tensor:
+        """The engine's workspace, grown on demand; rows: the larger plan of the per-row route (f5_workspace_bytes_rows)."""
         if method not in METHODS:
             raise ValueError(f"Unknown method: {method}")
         nbytes = C.c_size_t()
-        check(self.lib.f5_workspace_bytes(self._h, B, N, nt, steps, METHODS[method], C.byref(nbytes)), "f5_workspace_bytes")
+        if rows:
+            check(self.lib.f5_workspace_bytes_rows(self._h, B, N, nt, steps, METHODS[method], C.byref(nbytes)), "f5_workspace_bytes_rows")
+        else:
+            check(self.lib.f5_workspace_bytes(self._h, B, N, nt, steps, METHODS[method], C.byref(nbytes)), "f5_workspace_bytes")
         if self._workspace is None or self._workspace.numel() < nbytes.value:
             self._workspace = None
             self._workspace = _aligned_bytes(nbytes.value, self.device)
@@ -406,9 +450,13 @@ class Engine:
         cond_keep = cond_keep.contiguous()
         return cond_keep.view(torch.uint8) if cond_keep.dtype == torch.bool else cond_keep
 
-    def _call_sample(self, a, cond_keep, st) -> None:
-        """f5_sample, or f5_sample_edit when the call carries a conditioning mask."""
-        if cond_keep is None:
+    def _call_sample(self, a, cond_keep, st, rows=None) -> None:
+        """f5_sample, f5_sample_edit when the call carries a conditioning mask, f5_sample_rows when it carries per-row controls
+        (rows = (t_rows, cfg_rows) of row_controls; the mask rides in the controls)."""
+        if rows is not None:
+            rc = F5RowControls(rows[0].ctypes.data, rows[1].ctypes.data, 0 if cond_keep is None else cond_keep.data_ptr())
+            check(self.lib.f5_sample_rows(self._h, C.byref(a), C.byref(rc), st), "f5_sample_rows")
+        elif cond_keep is None:
             check(self.lib.f5_sample(self._h, C.byref(a), st), "f5_sample")
         else:
             check(self.lib.f5_sample_edit(self._h, C.byref(a), ptr(cond_keep), st), "f5_sample_edit")
@@ -419,7 +467,9 @@ class Engine:
                trajectory: Optional[torch.Tensor] = None, cond_keep: Optional[torch.Tensor] = None):
         """ODE solve on the GPU. cond (B,N,mel) fp32 zero-padded to N=max(durations); text (B,nt) int32
         (-1 padded); y0 (B,N,mel).  use_graph: True / False / "auto" (eager on the first sighting of a shape
-        signature, captured hipGraph from the second on).  cond_keep (speech editing, f5_sample_edit): bool / uint8 CUDA tensor (B, N),
+        signature, captured hipGraph from the second on).  Per-request controls: `t` may also be (B, steps), one grid per row, and
+        `cfg_strength` a length-B sequence; either selects f5_sample_rows (the other is broadcast), and the controls follow the call through
+        the re-runs, the bf16x3 fall-back and the split halves.  cond_keep (speech editing, f5_sample_edit): bool / uint8 CUDA tensor (B, N),
         non-zero = frame n of row b is conditioning -- it replaces the prefix rule n < lens[b]; it follows the call through the re-runs,
         the cross-check, the bf16x3 fall-back and the split halves.  Returns (out (B,N,mel), trajectory (steps,B,N,mel) or None)."""
         if method not in METHODS:
@@ -432,7 +482,7 @@ class Engine:
                                          use_graph=use_graph, return_trajectory=return_trajectory, out=out, trajectory=trajectory,
                                          cond_keep=cond_keep)
         B, N, mel = cond.shape
-        steps = int(len(t))
+        steps, rows = row_controls(t, cfg_strength, B)
         assert y0.shape == cond.shape and y0.dtype == torch.float32 and y0.is_contiguous() and y0.is_cuda
         if use_mask is None:
             use_mask = B > 1                       # cfm.py:333-336
@@ -441,14 +491,16 @@ class Engine:
                                       return_trajectory, out, trajectory, cond_keep)
             if done is not None:
                 return done                        # (None: a half reported its status word -- the whole call is repeated below, unsplit)
-        ws = self.workspace(B, N, text.shape[1], steps, method)
+        ws = self.workspace(B, N, text.shape[1], steps, method, rows=rows is not None)
         if out is None:
             out = torch.empty_like(cond)
         if return_trajectory and trajectory is None:
             trajectory = torch.empty((steps, B, N, mel), dtype=torch.float32, device=self.device)
-        a, keep = self._args(text, cond, lens, durations, y0, t, steps, method, cfg_strength, use_mask, use_graph, out,
+        # (per-row route: the scalar slots of the arguments are not read; they carry row 0's grid and the largest strength)
+        a, keep = self._args(text, cond, lens, durations, y0, t if rows is None else rows[0][0], steps, method,
+                             cfg_strength if rows is None else float(rows[1].max()), use_mask, use_graph, out,
                              trajectory if return_trajectory else None, ws)
-        launch = lambda: self._run_on_side_stream(lambda st: self._call_sample(a, cond_keep, st))  # noqa: E731
+        launch = lambda: self._run_on_side_stream(lambda st: self._call_sample(a, cond_keep, st, rows))  # noqa: E731
         launch()
         saturated = self._after_call(a, launch, f"sample(B={B}, N={N}, {method}, {steps} points)", (B, N, steps, method))
         del keep
@@ -496,29 +548,32 @@ class Engine:
         calls = []
         for eng, (b0, b1) in ((self, (0, h)), (sib, (h, B))):
             tr = torch.empty((steps, b1 - b0, N, mel), dtype=torch.float32, device=self.device) if return_trajectory else None
-            ws = eng.workspace(b1 - b0, N, nt, steps, method)
-            a, keep = eng._args(text[b0:b1], cond[b0:b1], lens[b0:b1], durations[b0:b1], y0[b0:b1], t, steps, method, cfg_strength,
-                                use_mask, use_graph, out[b0:b1], tr, ws)
-            calls.append((eng, a, keep, tr, None if cond_keep is None else cond_keep[b0:b1]))     # (each half gets its rows of the mask)
+            th, ch = _rows_slice(t, cfg_strength, b0, b1)                  # (each half gets its rows of the controls ...)
+            _, rows = row_controls(th, ch, b1 - b0)
+            ws = eng.workspace(b1 - b0, N, nt, steps, method, rows=rows is not None)
+            a, keep = eng._args(text[b0:b1], cond[b0:b1], lens[b0:b1], durations[b0:b1], y0[b0:b1], th if rows is None else rows[0][0], steps,
+                                method, ch if rows is None else float(rows[1].max()), use_mask, use_graph, out[b0:b1], tr, ws)
+            calls.append((eng, a, keep, tr, None if cond_keep is None else cond_keep[b0:b1], rows))     # (... and of the mask)
 
-        def run(eng, a, ck):
+        def run(eng, a, ck, rows):
             torch.cuda.set_device(self.device)         # (the worker thread's current device)
-            eng._run_on_side_stream(lambda st: eng._call_sample(a, ck, st), cur)
+            eng._run_on_side_stream(lambda st: eng._call_sample(a, ck, st, rows), cur)
 
-        key = (B, N, nt, steps, method, use_graph, bool(use_mask), return_trajectory, cfg_strength >= 1e-5, cond_keep is not None)
+        guided = tuple(bool(np.any(np.asarray(c[5][1] if c[5] is not None else cfg_strength) >= 1e-5)) for c in calls)
+        key = (B, N, nt, steps, method, use_graph, bool(use_mask), return_trajectory, guided, cond_keep is not None, calls[0][5] is not None)
         if key in self._split_seen:
-            fut = self._pool.submit(run, calls[1][0], calls[1][1], calls[1][4])
+            fut = self._pool.submit(run, calls[1][0], calls[1][1], calls[1][4], calls[1][5])
             try:
-                run(calls[0][0], calls[0][1], calls[0][4])
+                run(calls[0][0], calls[0][1], calls[0][4], calls[0][5])
             finally:
                 fut.result()
         else:
-            for eng, a, _, _, ck in calls:
-                run(eng, a, ck)
+            for eng, a, _, _, ck, rows in calls:
+                run(eng, a, ck, rows)
             self._split_seen.add(key)
         flags = 0
         if self._status_host is not None and self.range_check != "off":
-            for eng, a, _, _, _ in calls:
+            for eng, a, _, _, _, _ in calls:
                 flags |= eng._status_word_blocking(a, cur)
         if flags & (STATUS_FOLD_OVERFLOW | STATUS_SATURATED):
             return None
@@ -655,7 +710,8 @@ class Engine:
 
     def dit_forward(self, x: torch.Tensor, text: torch.Tensor, cond: torch.Tensor, lens, durations, t: float,
                     cfg_strength: float = 2.0, use_mask: Optional[bool] = None):
-        """One DiT evaluation (cond branch and, when cfg_strength >= 1e-5, null branch)."""
+        """One DiT evaluation (cond branch and, when cfg_strength >= 1e-5, null branch).  t: a float, or one time per batch row (length-B
+        sequence: one batched f5_dit_forward_rows call)."""
         self._check_inputs(text, cond, lens, durations)
         self.check_status(block=False)
         if self._use_fallback:
@@ -663,13 +719,23 @@ class Engine:
         B, N, mel = cond.shape
         if use_mask is None:
             use_mask = B > 1
-        ws = self.workspace(B, N, text.shape[1], 2, "euler")
+        t_rows = None
+        if np.ndim(t) != 0:
+            t_rows = np.ascontiguousarray(t, dtype=np.float32)
+            if t_rows.shape != (B,):
+                raise ValueError(f"per-row time: expected {B} values, got shape {t_rows.shape}")
+        ws = self.workspace(B, N, text.shape[1], 2, "euler", rows=t_rows is not None)
         pred = torch.empty_like(cond)
         null = torch.empty_like(cond) if cfg_strength >= 1e-5 else None
         a, keep = self._args(text, cond, lens, durations, None, np.zeros(2, np.float32), 2, "euler", cfg_strength, use_mask,
                              False, None, None, ws)
-        launch = lambda: self._run_on_side_stream(lambda st: check(   # noqa: E731
-            self.lib.f5_dit_forward(self._h, C.byref(a), ptr(x), C.c_float(t), ptr(pred), ptr(null), st), "f5_dit_forward"))
+        if t_rows is None:
+            launch = lambda: self._run_on_side_stream(lambda st: check(   # noqa: E731
+                self.lib.f5_dit_forward(self._h, C.byref(a), ptr(x), C.c_float(t), ptr(pred), ptr(null), st), "f5_dit_forward"))
+        else:
+            launch = lambda: self._run_on_side_stream(lambda st: check(   # noqa: E731
+                self.lib.f5_dit_forward_rows(self._h, C.byref(a), ptr(x), C.c_void_p(t_rows.ctypes.data), ptr(pred), ptr(null), st),
+                "f5_dit_forward_rows"))
         launch()
         saturated = self._after_call(a, launch, f"dit_forward(B={B}, N={N})", (B, N, 2, "forward"))
         del keep

@@ -231,6 +231,35 @@ def _load_reference(ref_audio_path, ref_audio_text, which: str):
     return torch.from_numpy(np.asarray(audio)).to(torch.float32), int(sr), ref_audio_text
 
 
+CONTROL_KEYS = ("cfg_strength", "sway_sampling_coef", "seed", "speed")
+
+
+def request_controls(controls, n_requests: int, row_req, defaults: dict) -> dict:
+    """Per-request sampling controls -> the keyword arguments of F5TTS.sample.  controls: None, or a list with one entry per request, each
+    None or a dict with any of CONTROL_KEYS; an entry overrides the call-level value (`defaults`) for all rows of its request.  row_req:
+    the request of every batch row.  A control no request overrides stays the call-level scalar, so a call without overrides is the call
+    it was before; an overridden one becomes a list with one value per row.  ValueError naming the request: a list of the wrong length,
+    an entry that is neither None nor a dict, an unknown key."""
+    out = dict(defaults)
+    if controls is None:
+        return out
+    controls = list(controls)
+    if len(controls) != n_requests:
+        raise ValueError(f"controls: expected one entry per request ({n_requests}), got {len(controls)}")
+    for i, c in enumerate(controls):
+        if c is None:
+            continue
+        if not isinstance(c, dict):
+            raise ValueError(f"request {i}: controls entry must be None or a dict, got {type(c).__name__}")
+        unknown = sorted(set(c) - set(CONTROL_KEYS))
+        if unknown:
+            raise ValueError(f"request {i}: unknown control(s) {unknown}; expected any of {list(CONTROL_KEYS)}")
+    for key in CONTROL_KEYS:
+        if any(c is not None and key in c for c in controls):
+            out[key] = [controls[i][key] if controls[i] is not None and key in controls[i] else defaults[key] for i in row_req]
+    return out
+
+
 def generate_many(
     requests,
     *,
@@ -246,6 +275,7 @@ def generate_many(
     quantization_bits: Optional[int] = None,
     trim_silence_db: Optional[float] = None,
     output_sample_rate: Optional[int] = None,
+    controls=None,
 ):
     """Many voices in one call (no reference counterpart; docs/multi_voice.md).  requests: a list of (generation_text, ref_audio_path or
     None, ref_audio_text); None = the bundled sample and its text.  -> a list of waves, one per request, in order.
@@ -259,14 +289,20 @@ def generate_many(
     takes `lens`, else one call per row --, each row is trimmed by its own reference's kept sample count and the rows of a request
     are concatenated.  Every row gets the same `seed` (the reference re-seeds per element).
 
+    controls (docs/row_controls.md): None, or a list with one entry per request, each None or a dict with any of "cfg_strength",
+    "sway_sampling_coef", "seed", "speed"; an entry overrides the call-level value for all rows of that request, and requests with
+    different settings still share the one batch (the engine indexes time grid and guidance strength by batch row).
+
     It equals prepare_references -> sample(mel, text, durations, lens=frames) -> the decode -> the same slices, bit for bit; it does
     NOT equal a loop of generate() calls bit for bit (the batch has a key-padding mask, GRN and the conv position embedding see the
     padding, and the gain is fp64 arithmetic on fp32 block sums instead of torch's fp32 mean).
     ValueError before any launch, naming the request: an empty list, a request without text, a reference recording without a
-    transcript, a reference at a rate the resampler refuses."""
+    transcript, a reference at a rate the resampler refuses, a `controls` list of the wrong length or with an unknown key."""
     requests = list(requests)
     if not requests:
         raise ValueError("generate_many needs at least one request")
+    call_level = dict(cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed, speed=speed)
+    request_controls(controls, len(requests), [], call_level)          # validation only: the rows are not known yet
     if output_sample_rate is not None:
         output_sample_rate = _audio._rate(output_sample_rate, "output_sample_rate")
         _audio.check_resample_ratio(SAMPLE_RATE, output_sample_rate)
@@ -304,17 +340,19 @@ def generate_many(
     texts = convert_char_to_pinyin([ref_texts[i] + " " + s for i, ss in enumerate(sentences) for s in ss])
     cond = refs.mel[torch.tensor(row_req, device=refs.mel.device)]
     lens = torch.tensor([refs.frames[i] for i in row_req], dtype=torch.int64)
+    ctl = request_controls(controls, len(requests), row_req, call_level)
+    req_speed = [speed if controls is None or controls[i] is None else controls[i].get("speed", speed) for i in range(len(requests))]
     durs = None                                                       # duration predictor, per row, with lens (cfm.py:307-308)
     if estimate_duration:
-        per_req = [int(estimated_duration(np.broadcast_to(np.float32(0), (refs.samples[i],)), ref_texts[i], requests[i][0], speed)
+        per_req = [int(estimated_duration(np.broadcast_to(np.float32(0), (refs.samples[i],)), ref_texts[i], requests[i][0], req_speed[i])
                        * FRAMES_PER_SEC) for i in range(len(requests))]
         durs = torch.tensor([per_req[i] for i in row_req], dtype=torch.int64)
 
     start_date = datetime.datetime.now()
     try:                                                              # mel frames out of sample(): each row is vocoded on its own frames
         f5tts._vocoder = None
-        mel, _ = f5tts.sample(cond, text=texts, duration=durs, lens=lens, steps=steps, method=method, speed=speed,
-                              cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
+        mel, _ = f5tts.sample(cond, text=texts, duration=durs, lens=lens, steps=steps, method=method, speed=ctl["speed"],
+                              cfg_strength=ctl["cfg_strength"], sway_sampling_coef=ctl["sway_sampling_coef"], seed=ctl["seed"])
     finally:
         f5tts._vocoder = voc
     frames = f5tts.last_durations                                     # per-row frame counts after the clamps of cfm.py:317-318
@@ -351,11 +389,42 @@ def read_requests(path):
                 raise ValueError(f"{path}:{no}: not a JSON object ({exc.msg})") from None
             if not isinstance(obj, dict) or not isinstance(obj.get("text"), str):
                 raise ValueError(f'{path}:{no}: expected an object with a "text" string')
-            unknown = set(obj) - {"text", "ref_audio", "ref_text", "output"}
+            unknown = set(obj) - {"text", "ref_audio", "ref_text", "output"} - {"cfg", "sway_coef", "seed", "speed"}
             if unknown:
                 raise ValueError(f"{path}:{no}: unknown key(s) {sorted(unknown)}")
             reqs.append({k: obj.get(k) for k in ("text", "ref_audio", "ref_text", "output")})
     return reqs
+
+
+def read_request_controls(path):
+    """The optional per-request sampling controls of a --requests file: the keys "cfg", "sway_coef", "seed" and "speed" of every line
+    (same lines as read_requests, which ignores them) -> a list with one entry per request for generate_many(controls=...): a dict with
+    the controls the line sets ("cfg_strength", "sway_sampling_coef", "seed", "speed"), or None when it sets none."""
+    import json
+    names = {"cfg": "cfg_strength", "sway_coef": "sway_sampling_coef", "seed": "seed", "speed": "speed"}
+    out = []
+    with open(path, encoding="utf-8") as f:
+        for no, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            try:
+                obj = json.loads(line)
+            except json.JSONDecodeError as exc:
+                raise ValueError(f"{path}:{no}: not a JSON object ({exc.msg})") from None
+            if not isinstance(obj, dict):
+                raise ValueError(f"{path}:{no}: expected an object")
+            c = {}
+            for key, name in names.items():
+                if key not in obj:
+                    continue
+                v = obj[key]
+                ok = (isinstance(v, int) and not isinstance(v, bool)) if key == "seed" else (
+                    (isinstance(v, (int, float)) and not isinstance(v, bool)) or (key == "sway_coef" and v is None))
+                if not ok:
+                    raise ValueError(f'{path}:{no}: "{key}" must be {"an integer" if key == "seed" else "a number"}, got {v!r}')
+                c[name] = v
+            out.append(c or None)
+    return out
 
 
 # command line: the reference's flags and defaults (generate.py:248-362), table driven
@@ -410,10 +479,12 @@ def main(argv=None):
     ns = parse_args(argv)
     if ns.requests is not None:
         reqs = read_requests(ns.requests)
+        controls = read_request_controls(ns.requests)
         waves = generate_many([(r["text"], r["ref_audio"], r["ref_text"]) for r in reqs], steps=ns.steps, method=ns.method,
                               cfg_strength=ns.cfg, sway_sampling_coef=ns.sway_coef, speed=ns.speed, seed=ns.seed,
                               estimate_duration=ns.estimate_duration, model_name=ns.model, quantization_bits=ns.q,
-                              trim_silence_db=ns.trim_silence, output_sample_rate=ns.output_rate)
+                              trim_silence_db=ns.trim_silence, output_sample_rate=ns.output_rate,
+                              controls=controls if any(c is not None for c in controls) else None)
         for r, wave in zip(reqs, waves):
             if r["output"] is not None:
                 write_wav(r["output"], wave.detach().cpu().numpy(), ns.output_rate or SAMPLE_RATE)

@@ -140,6 +140,25 @@ int f5_sample(f5_engine* e, const f5_sample_args* args, void* stream);
  * everything f5_sample refuses. */
 int f5_sample_edit(f5_engine* e, const f5_sample_args* args, const uint8_t* cond_keep_dev /* [B][N] */, void* stream);
 
+/* Per-request sampling controls: f5_sample with the time grid and the guidance strength chosen PER BATCH ROW, so that requests with
+ * different sway coefficients / cfg strengths share one call.  args->t and args->cfg_strength are not read.  The adaLN table is built for
+ * every (evaluation, row) pair, [nfe][B][(6 depth + 2) dim] floats (about 545 MB for 32 rows x 31 evaluations at the 335M shape): only
+ * f5_workspace_bytes_rows asks for that space, f5_workspace_bytes is unchanged.  The two gated projections of a block write their fp32
+ * result into a dead buffer and one row kernel applies the row's gate and produces the LayerNorm-modulate that follows; the LN fold and
+ * the fused LN tail do not run (ln_fold = 1 fails with a message), precision mxfp8 is refused.  A row with cfg_rows[b] < 1e-5 takes the
+ * conditional prediction alone (cfm.py:352); the null branch runs when any row is guided.  Controls (and the optional keep mask, as in
+ * f5_sample_edit) are staged into the workspace outside the captured part: one hipGraph per shape signature serves every set of
+ * values, and the rows flag is part of the cache key.  Status word, f5_sample_status*, trajectory and the final splice are f5_sample's.
+ * Refused before any launch: null controls / t_rows / cfg_rows, a non-finite control value, a workspace smaller than
+ * f5_workspace_bytes_rows, and everything f5_sample refuses. */
+typedef struct f5_row_controls {
+    const float* t_rows;          /* host [B][steps]: each row's own time grid (cfm.py:379-381 evaluated per row) */
+    const float* cfg_rows;        /* host [B] */
+    const uint8_t* cond_keep_dev; /* dev [B][N] or NULL: as f5_sample_edit */
+} f5_row_controls;
+int f5_workspace_bytes_rows(f5_engine* e, int B, int N, int nt, int steps, int method, size_t* bytes);
+int f5_sample_rows(f5_engine* e, const f5_sample_args* args, const f5_row_controls* controls, void* stream);
+
 /* Status word of the last f5_sample / f5_dit_forward on the workspace of `args`.  It is the FIRST 32-bit word of the workspace for every
  * shape and solver (a caller may copy it itself).  bit 1 (F5_STATUS_FOLD_RAN) = the LN fold (engine option "ln_fold") ran in that call;
  * bit 0 (F5_STATUS_FOLD_OVERFLOW) = a value of the folded LayerNorm operand (x - m)(1 + scale) did not fit fp16 (precision f16): the
@@ -167,6 +186,10 @@ int f5_engine_ln_fold_active(f5_engine* e, const f5_sample_args* args, int* acti
  * cfg_strength >= 1e-5) as dev [B][N][mel] each. */
 int f5_dit_forward(f5_engine* e, const f5_sample_args* args, const float* x, float t, float* pred, float* null_pred,
                    void* stream);
+/* The same with one time per batch row (host [B]), as the reference's DiT takes it: one batched forward for rows at different times.
+ * Workspace: f5_workspace_bytes_rows(B, N, nt, 2, F5_EULER). */
+int f5_dit_forward_rows(f5_engine* e, const f5_sample_args* args, const float* x, const float* t_rows_host /* [B] */, float* pred,
+                        float* null_pred, void* stream);
 
 /* ---- per-op entry points (exported for the parity tests; all pointers are dev) ------------------
  * 16-bit operand buffers (a_hi, w_hi, qk_hi, out_hi ...) hold bf16 by default; f5_op_set_operand_type(1) switches every
@@ -247,6 +270,21 @@ int f5_op_cfg_axpy(const float* pred, const float* null_pred, float cfg, const f
 int f5_op_ode_stage(const float* pred, const float* null_pred, float cfg, const float* cfg_ptr, const float* base, const float* dt_dev,
                     float coef, float divisor, int mode, float* kstore, const float* k1, const float* k2, const float* k3, float* out,
                     void* xin_hi, void* xin_lo, int rows, int mel_dim, void* stream);
+/* f5_op_ode_stage with the guidance strength and the step size per row: row r uses cfg_rows[v] and dt_rows[v] (dev fp32 [nvec] each),
+ * v = (r / rows_per_vec) % nvec.  Same arithmetic per element; a row with cfg_rows[v] < 1e-5 takes k = pred by selection (cfm.py:352),
+ * even when null_pred is given (a NaN there reaches nothing). */
+int f5_op_ode_stage_rows(const float* pred, const float* null_pred, const float* cfg_rows, const float* base, const float* dt_rows,
+                         int rows_per_vec, int nvec, float coef, float divisor, int mode, float* kstore, const float* k1, const float* k2,
+                         const float* k3, float* out, void* xin_hi, void* xin_lo, int rows, int mel_dim, void* stream);
+/* Residual update and the LayerNorm-modulate behind it with per-row vectors: row r of the [rows][dim] buffers reads vector
+ * v = (r / rows_per_vec) % nvec of gate / ln_scale / ln_shift (vec_stride >= dim floats apart, a multiple of 4).
+ * With y (fp32 [rows][dim], the GEMM result including bias; may be NULL): x = fmaf(gate[v][c], rowkeep[r] ? y : 0, x) in place (rowkeep
+ * uint8 [rows] or NULL; a selection: NaN in a dropped row's y reaches nothing).  With ln_scale (NULL together with ln_shift = no LN
+ * output): (out_hi, out_lo) = LN(x)(1 + ln_scale[v]) + ln_shift[v], eps 1e-6, the bits of f5_op_ln_modulate on that row (out_lo may
+ * be NULL).  y == NULL is f5_op_ln_modulate with per-row vectors.  dim 256 / 512 / 768 / 1024. */
+int f5_op_resid_gate_ln_rows(const float* y, float* x, const float* gate, const uint8_t* rowkeep, const float* ln_scale,
+                             const float* ln_shift, void* out_hi, void* out_lo, int rows, int dim, int rows_per_vec, int nvec,
+                             size_t vec_stride, void* stream);
 /* dit.py:250 (A operand of the hoisted input projection): [2][B][seq_len][128 + dt] 16-bit operands = [cond, zero padded to 128 | text_emb];
  * branch 0: cond where n < lens[b] (step_cond, cfm.py:331), branch 1: cond dropped (dit.py:249) unless null_keeps_cond;
  * cond [B][seq_len][mel_dim <= 128], text_emb [2][B][seq_len][dt] */
