@@ -1636,7 +1636,8 @@ extern "C" int f5_op_gemm(const void* a_hi, const void* a_lo, const void* w_hi, 
 }
 
 // MX-fp8 GEMM: A8/W8 e4m3 [rows][ld] + E8M0 scales [rows][K/32].  epi 0: out_f32 = acc + bias; 1: out_bf = bf16(acc + bias);
-// 2: (out8, out8s) = MX-fp8(gelu_tanh(acc + bias)); 4: out_f32 += gate * ((acc + bias) * keep[row])
+// 2: (out8, out8s) = MX-fp8(gelu_tanh(acc + bias)); 4: out_f32 += gate * ((acc + bias) * keep[row]).  Always the bf16 build of the
+// kernel (the mode has no fp16 form): epi 1 writes bf16 whatever f5_op_set_operand_type says.  ldo serves the output of the epilogue.
 extern "C" int f5_op_gemm_f8(const void* a8, const void* a_scales, const void* w8, const void* w_scales, const float* bias,
                              const float* gate, const uint8_t* rowkeep, float* out_f32, void* out_bf, void* out8, void* out8_scales,
                              int M, int N, int K, int lda8, int ldw8, int ldo, int epi, void* stream) {
@@ -1668,6 +1669,47 @@ extern "C" int f5_op_gemm_f8(const void* a8, const void* a_scales, const void* w
 }
 extern "C" int f5_op_quantize_mx(const float* x, int ldx, void* q, int ldq, void* scales, int rows, int cols, void* stream) {
     return f5_launch_quantize_mx(x, ldx, (uint8_t*)q, ldq, (uint8_t*)scales, rows, cols, (hipStream_t)stream);
+}
+// the weights' quantiser (f5_engine_finalize, precision mxfp8): 16-bit rows of the current operand type -> e4m3 + E8M0
+extern "C" int f5_op_quantize_mx_bf16(const void* x16, int ldx, void* q, int ldq, void* scales, int rows, int cols, void* stream) {
+    return g_ops.h ? f5hf::f5_launch_quantize_mx_bf16((const f5hf::op16_t*)x16, ldx, (uint8_t*)q, ldq, (uint8_t*)scales, rows, cols,
+                                                      (hipStream_t)stream)
+                   : f5bf::f5_launch_quantize_mx_bf16((const op16_t*)x16, ldx, (uint8_t*)q, ldq, (uint8_t*)scales, rows, cols,
+                                                      (hipStream_t)stream);
+}
+// LN-modulate straight into an MX-fp8 A operand (the first launch of both halves of an mxfp8 block)
+extern "C" int f5_op_ln_modulate_f8(const float* x, const float* scale, const float* shift, void* q, void* q_scales, int rows, int dim,
+                                    float eps, void* stream) {
+    return f5_launch_ln_modulate_f8(x, scale, shift, (uint8_t*)q, (uint8_t*)q_scales, rows, dim, eps, (hipStream_t)stream);
+}
+// the QKV projection of an mxfp8 block: F5GemmArgs filled as run_dit fills them
+extern "C" int f5_op_qkv_rope_f8(const void* a8, const void* a_scales, const void* w8, const void* w_scales, const float* bias,
+                                 const float* rope_cos, const float* rope_sin, void* qk, void* vt, int B, int seq_len, int npad, int heads,
+                                 int dmodel, int lda8, int ldw8, float q_premul, void* stream) {
+    F5GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A8 = (const uint8_t*)a8;
+    g.As = (const uint8_t*)a_scales;
+    g.W8 = (const uint8_t*)w8;
+    g.Ws = (const uint8_t*)w_scales;
+    g.lda8 = lda8;
+    g.ldw8 = ldw8;
+    g.M = B * seq_len;
+    g.N = 3 * dmodel;
+    g.K = dmodel;
+    g.nseg = 1;
+    g.bias = bias;
+    g.out_bf[0] = (op16_t*)qk;
+    g.ldob = 2 * dmodel;
+    g.rope_cos = rope_cos;
+    g.rope_sin = rope_sin;
+    g.seq_len = seq_len;
+    g.npad = npad;
+    g.heads = heads;
+    g.dmodel = dmodel;
+    g.vt[0] = (op16_t*)vt;
+    g.q_premul = q_premul;
+    return f5_launch_gemm_f8(g, EPI_QKV_ROPE, (hipStream_t)stream);
 }
 
 // group-major twins of the rotation tables ([dim_head/4][seq_len][4] = (cos, cos, sin, sin) of two neighbouring pairs; the q table

@@ -272,15 +272,36 @@ int f5_launch_gemm_f8(const F5GemmArgs& a_in, int epi, hipStream_t stream) {
     F5_REQUIRE(a.A8 && a.W8 && a.As && a.Ws, "gemm_f8: null operand");
     F5_REQUIRE(a.lda8 % 16 == 0 && a.ldw8 % 16 == 0 && a.lda8 >= a.K && a.ldw8 >= a.K, "gemm_f8: leading dims must be multiples of 16 and >= K");
     F5_REQUIRE((size_t)a.M * a.lda8 < (1ull << 32) && (size_t)(a.N + 256) * a.ldw8 < (1ull << 32), "gemm_f8: operands must be < 4 GiB");
+    // the operand rows are staged with 16-byte global_load_lds, the scales of a K tile with one 4-byte one per row (K / 32 % 4 == 0)
+    const auto al = [](const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; };
+    F5_REQUIRE(al(a.A8, 16) && al(a.W8, 16) && al(a.As, 4) && al(a.Ws, 4),
+               "gemm_f8: A8 / W8 must be 16-byte aligned, the scales 4-byte aligned");
+    // the staged epilogues store whole 16-byte (fp32 / 16-bit rows) or 8-byte (e4m3 rows) chunks of an output row
     switch (epi) {
-        case EPI_F32: return launch_f8<EPI_F32>(a, stream);
-        case EPI_BF16: return launch_f8<EPI_BF16>(a, stream);
+        case EPI_F32:
+            F5_REQUIRE(a.out_f32 && a.ldo >= a.N, "gemm_f8(f32): out_f32 missing or ldo < N");
+            return launch_f8<EPI_F32>(a, stream);
+        case EPI_BF16:
+            F5_REQUIRE(a.out_bf[0] && a.ldob >= a.N, "gemm_f8(bf16): out_bf missing or ldob < N");
+            F5_REQUIRE(a.ldob % 8 == 0 && al(a.out_bf[0], 16) && (a.out_bf[1] == nullptr || al(a.out_bf[1], 16)),
+                       "gemm_f8(bf16): ldob must be a multiple of 8 and out_bf 16-byte aligned (16-byte row stores)");
+            return launch_f8<EPI_BF16>(a, stream);
         case EPI_GELU_TANH:
             F5_REQUIRE(a.out8 && a.out8s && a.ldo8 >= a.N, "gemm_f8(gelu): fp8 output buffers missing");
+            F5_REQUIRE(a.ldo8 % 8 == 0 && al(a.out8, 8), "gemm_f8(gelu): ldo8 must be a multiple of 8 and out8 8-byte aligned (8-byte row stores)");
             return launch_f8<EPI_GELU_TANH>(a, stream);
-        case EPI_RESID_GATE: return launch_f8<EPI_RESID_GATE>(a, stream);
+        case EPI_RESID_GATE:
+            F5_REQUIRE(a.out_f32 && a.gate && a.ldo >= a.N, "gemm_f8(resid): out_f32 / gate missing or ldo < N");
+            F5_REQUIRE(a.ldo % 4 == 0 && al(a.out_f32, 16) && al(a.gate, 16),
+                       "gemm_f8(resid): ldo must be a multiple of 4, out_f32 and gate 16-byte aligned (16-byte row accesses)");
+            return launch_f8<EPI_RESID_GATE>(a, stream);
         case EPI_QKV_ROPE:
             F5_REQUIRE(a.dmodel % 128 == 0 && a.N == 3 * a.dmodel, "gemm_f8(qkv): N must be 3*dmodel, dmodel %% 128 == 0");
+            F5_REQUIRE(a.out_bf[0] && a.vt[0] && a.rope_cos && a.rope_sin, "gemm_f8(qkv): qk / vt / rotation tables missing");
+            F5_REQUIRE(a.seq_len > 0 && a.M % a.seq_len == 0 && a.npad >= a.seq_len && a.heads * 64 == a.dmodel,
+                       "gemm_f8(qkv): M must be a multiple of seq_len, npad >= seq_len, heads * 64 == dmodel");
+            F5_REQUIRE(a.ldob >= 2 * a.dmodel && a.ldob % 8 == 0 && al(a.out_bf[0], 16) && (a.out_bf[1] == nullptr || al(a.out_bf[1], 16)),
+                       "gemm_f8(qkv): ldob must be a multiple of 8 and >= 2*dmodel, qk 16-byte aligned (16-byte row stores)");
             return launch_f8<EPI_QKV_ROPE>(a, stream);
         default: f5_set_error("gemm_f8: unsupported epilogue %d", epi); return 2;
     }
@@ -306,6 +327,8 @@ __global__ __launch_bounds__(256) void quantize_mx_kernel(const float* __restric
 }
 int f5_launch_quantize_mx(const float* x, int ldx, uint8_t* q, int ldq, uint8_t* sc, int rows, int cols, hipStream_t stream) {
     F5_REQUIRE(rows > 0 && cols > 0 && cols % 32 == 0 && ldx % 4 == 0 && ldq % 4 == 0, "quantize_mx: cols must be a multiple of 32");
+    F5_REQUIRE(x && q && sc && ldx >= cols && ldq >= cols && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(q) & 3) == 0,
+               "quantize_mx: ldx / ldq below cols, or x not 16-byte / q not 4-byte aligned");
     hipLaunchKernelGGL(quantize_mx_kernel, dim3(f5_cdiv(rows, 4)), dim3(256), 0, stream, x, ldx, q, ldq, sc, rows, cols);
     F5_LAUNCH_CHECK();
     return 0;

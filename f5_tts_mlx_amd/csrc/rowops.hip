@@ -190,6 +190,10 @@ __global__ __launch_bounds__(256) void ln_modulate_f8_kernel(const float* __rest
 int f5_launch_ln_modulate_f8(const float* x, const float* scale, const float* shift, uint8_t* q, uint8_t* qs, int rows, int dim,
                              float eps, hipStream_t s) {
     F5_REQUIRE(dim % 256 == 0 && dim >= 256 && dim <= 1024, "ln_modulate_f8: dim must be 256/512/768/1024 (got %d)", dim);
+    F5_REQUIRE(rows > 0 && x && scale && shift && q && qs, "ln_modulate_f8: no rows or a null pointer");
+    F5_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift)) & 15) == 0 &&
+                   (reinterpret_cast<uintptr_t>(q) & 3) == 0,
+               "ln_modulate_f8: x / scale / shift must be 16-byte aligned, q 4-byte aligned");
     const dim3 grid(f5_cdiv(rows, 4)), block(256);
     switch (dim / 256) {
         case 1: hipLaunchKernelGGL((ln_modulate_f8_kernel<1>), grid, block, 0, s, x, scale, shift, q, qs, rows, eps); break;
@@ -221,6 +225,8 @@ __global__ __launch_bounds__(256) void quantize_mx_bf16_kernel(const op16_t* __r
 }
 int f5_launch_quantize_mx_bf16(const op16_t* x, int ldx, uint8_t* q, int ldq, uint8_t* sc, int rows, int cols, hipStream_t stream) {
     F5_REQUIRE(rows > 0 && cols > 0 && cols % 32 == 0 && ldx % 4 == 0 && ldq % 4 == 0, "quantize_mx_bf16: cols must be a multiple of 32");
+    F5_REQUIRE(x && q && sc && ldx >= cols && ldq >= cols && (reinterpret_cast<uintptr_t>(x) & 7) == 0 && (reinterpret_cast<uintptr_t>(q) & 3) == 0,
+               "quantize_mx_bf16: ldx / ldq below cols, or x not 8-byte / q not 4-byte aligned");
     hipLaunchKernelGGL(quantize_mx_bf16_kernel, dim3(f5_cdiv(rows, 4)), dim3(256), 0, stream, x, ldx, q, ldq, sc, rows, cols);
     F5_LAUNCH_CHECK();
     return 0;

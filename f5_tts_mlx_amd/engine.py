@@ -137,7 +137,11 @@ def load_library() -> C.CDLL:
                         ("f5_workspace_bytes_rows", [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
                         ("f5_op_resid_gate_ln_rows", [C.c_void_p] * 8 + [C.c_int] * 4 + [C.c_size_t, C.c_void_p]),
                         ("f5_op_ode_stage_rows", [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 7
-                         + [C.c_int, C.c_int, C.c_void_p])):
+                         + [C.c_int, C.c_int, C.c_void_p]),
+                        # MX-fp8 producers and the QKV projection of the mode (float arguments: eps, q_premul)
+                        ("f5_op_ln_modulate_f8", [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
+                        ("f5_op_quantize_mx_bf16", [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+                        ("f5_op_qkv_rope_f8", [C.c_void_p] * 9 + [C.c_int] * 7 + [C.c_float, C.c_void_p])):
         if hasattr(lib, name):
             getattr(lib, name).argtypes = types
     lib.f5_op_wave_patch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int,

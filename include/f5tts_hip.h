@@ -457,13 +457,40 @@ int f5_debug_set_op_q_premul(float factor); /* f5_op_qkv_rope scales q by factor
 /* ---- MX-fp8 path (BASELINE configs[4]; gfx950 v_mfma_scale_f32_32x32x64_f8f6f4): OCP e4m3 elements, one E8M0 scale per 32
  * consecutive K elements (scale = 2^ceil(log2(amax/448))).  No reference counterpart (the reference's reduced-precision mode
  * is MLX int4/int8 weight quantisation, cfm.py:510-515). ---------------------------------------------------------------- */
-/* rows of fp32 [rows][ldx] -> e4m3 [rows][ldq] + E8M0 [rows][cols/32]; cols % 32 == 0 */
+/* rows of fp32 [rows][ldx] -> e4m3 [rows][ldq] + E8M0 [rows][cols/32] (dense); cols % 32 == 0, ldx % 4 == 0, ldq % 4 == 0, both
+ * >= cols; x 16-byte aligned, q 4-byte aligned.  Finite inputs. */
 int f5_op_quantize_mx(const float* x, int ldx, void* q, int ldq, void* scales, int rows, int cols, void* stream);
-/* C = A W^T on MX-fp8 operands (N % 256 == 0, K % 128 == 0).  epi 0: out_f32 = acc + bias; 1: out_bf = bf16(acc + bias);
- * 2: (out8, out8_scales) = MX-fp8(gelu_tanh(acc + bias)); 4: out_f32 += gate * ((acc + bias) * keep[row]) */
+/* the same from 16-bit rows of the operand type of f5_op_set_operand_type (bf16 or fp16; what quantises the weights of the mode from
+ * their 16-bit copies); x16 8-byte aligned */
+int f5_op_quantize_mx_bf16(const void* x16, int ldx, void* q, int ldq, void* scales, int rows, int cols, void* stream);
+/* (q, q_scales) = MX-fp8(LN(x) (1 + scale) + shift): x fp32 [rows][dim] dense, q e4m3 [rows][dim], q_scales E8M0 [rows][dim/32];
+ * dim 256 / 512 / 768 / 1024; x / scale / shift 16-byte aligned, q 4-byte aligned.  The A operand of the QKV and FF1 GEMMs of an
+ * mxfp8 block (dit.py:270 with the MX rounding of oracle/mx_oracle.py behind it). */
+int f5_op_ln_modulate_f8(const float* x, const float* scale, const float* shift, void* q, void* q_scales, int rows, int dim, float eps,
+                         void* stream);
+/* C = A W^T on MX-fp8 operands.  epi 0: out_f32 = acc + bias; 1: out_bf = bf16(acc + bias);
+ * 2: (out8, out8_scales) = MX-fp8(gelu_tanh(acc + bias)); 4: out_f32 += gate * ((acc + bias) * keep[row]) (rowkeep NULL = all 1).
+ * Shapes: N % 256 == 0, K % 128 == 0, any M >= 1.  a8 [M][lda8] and w8 [N][ldw8] (exactly N rows are read, in whole 256-row tiles):
+ * lda8 / ldw8 multiples of 16 and >= K, both pointers 16-byte aligned (the rows are staged with 16-byte LDS-direct loads); a_scales
+ * [M][K/32] and w_scales [N][K/32] dense, 4-byte aligned.
+ * `ldo` is the leading dimension of whichever output the epilogue writes, >= N, and the launcher refuses what the row stores of the
+ * epilogue cannot take:
+ *   epi 0  out_f32, element stores: no further rule;
+ *   epi 1  out_bf, 16-byte stores: ldo % 8 == 0, out_bf 16-byte aligned;
+ *   epi 2  out8, 8-byte stores: ldo % 8 == 0, out8 8-byte aligned; out8_scales is dense [M][N/32] -- it has NO leading dimension;
+ *   epi 4  out_f32 and gate, 16-byte accesses: ldo % 4 == 0, out_f32 and gate 16-byte aligned.
+ * Operand type: the MX-fp8 mode exists in the bf16 build of the kernels only.  epi 1 writes bf16 (one round-to-nearest-even of the fp32
+ * value) whatever f5_op_set_operand_type says, and so does f5_op_qkv_rope_f8. */
 int f5_op_gemm_f8(const void* a8, const void* a_scales, const void* w8, const void* w_scales, const float* bias,
                   const float* gate, const uint8_t* rowkeep, float* out_f32, void* out_bf, void* out8, void* out8_scales,
                   int M, int N, int K, int lda8, int ldw8, int ldo, int epi, void* stream);
+/* the QKV projection of an mxfp8 block (what f5_op_qkv_rope is to the 16-bit modes): M = B seq_len rows, N = 3 dmodel, K = dmodel,
+ * heads * 64 == dmodel, dmodel % 128 == 0 (and % 256 through N); qk bf16 [M][2 dmodel] dense, 16-byte aligned (rotated q | k, q times
+ * q_premul when that is non-zero); vt bf16 [B heads 64][npad], V transposed, columns seq_len ... npad - 1 are not written;
+ * rope_cos / rope_sin [seq_len][32] (f5_op_rope_table, dim_head 64); B > 1 needs seq_len >= 4.  Operands as for f5_op_gemm_f8. */
+int f5_op_qkv_rope_f8(const void* a8, const void* a_scales, const void* w8, const void* w_scales, const float* bias, const float* rope_cos,
+                      const float* rope_sin, void* qk, void* vt, int B, int seq_len, int npad, int heads, int dmodel, int lda8, int ldw8,
+                      float q_premul, void* stream);
 
 /* ---- audio front-end (audio.py:115-230) ---------------------------------------------------------- */
 /* log-mel spectrogram (audio.py:162-210: zero centre padding, periodic Hann, |rfft|, HTK filterbank, log(max(., 1e-5))) of a
