@@ -1030,9 +1030,10 @@ __global__ __launch_bounds__(256, 1) void f5_attn2p_kernel(F5AttnArgs p) {
 // v2s: v2 with the KV range split across KS wave groups INSIDE the workgroup (small batches: B*H*ceil(N/128)
 // workgroups of 4 waves leave the 256 CUs with one wave per SIMD and the whole kernel is one workgroup's latency
 // chain over all KV tiles).  Group g (4 waves, the same 128 queries as the other groups) walks tiles g, g+KS, ...
-// with its own LDS ring; barriers are shared, so every group runs ceil(ntile/KS) iterations.  At the end groups
-// 1..KS-1 park (m, l, O^T) in LDS (the rings are dead by then) and group 0 merges them flash-decoding style:
+// with its own LDS ring; barriers are shared, so every group runs ceil(ntile/KS) iterations.  At the end the groups
+// park (m, l, O^T) in LDS (the rings are dead by then) and merge them flash-decoding style:
 // m = max m_g, l = sum l_g 2^((m_g-m)c), O = sum O_g 2^((m_g-m)c) — the same numbers as one pass up to fp32 rounding.
+// Every group merges and stores its 1 / KS of the head dimension (the fp8 output: group 0 merges all of it).
 // =================================================================================================
 template <bool HP, int KS, int NST, bool FAST = false>
 __global__ __launch_bounds__(256 * KS, 1) void f5_attn2s_kernel(F5AttnArgs p) {
@@ -1240,6 +1241,109 @@ __global__ __launch_bounds__(256 * KS, 1) void f5_attn2s_kernel(F5AttnArgs p) {
     // ---- merge the KS partial states (same lane of the same wave index in every group holds the same elements)
     __syncthreads();                                     // every ring is dead
     float* mrg = reinterpret_cast<float*>(smem_all);     // [KS-1][4 waves][34][64 lanes]
+    if (HP || !p.out8) {
+        // Every group finishes its share of O^T: group g owns the Q = 32 / KS accumulator elements [g Q, (g + 1) Q) of (db, e) -- head-dim
+        // block db == g for two groups, a quarter each for four.  It parks (m, l) and the elements it does not own, reads its partners'
+        // parts of the ones it does, and merges them with the expressions and in the group order of the one-group merge below: per wave
+        // 1 / KS of the exponent-weighted sums and of the output.  The one-pass kernels then hand the packed 16-bit rows over through
+        // LDS, so that a head's row (128 bytes, one line) leaves as eight 16-byte stores instead of one 8-byte store per lane and line.
+        constexpr int Q = 32 / KS, NPK = 2 + 32 - Q;     // floats a lane parks: m, l, the elements of the other groups
+        constexpr int SLD = 64 + 8;                      // staging row (16-bit elements): 128 queries x 64, padded
+        static_assert(KS * 4 * NPK * 64 * 4 + (HP ? 0 : 128 * SLD * 2) <= KS * RING * 2, "merge area + output staging fit in the rings");
+        float* mine = mrg + (size_t)((grp * 4 + wave) * NPK) * 64 + lane;
+        mine[0] = m_run;
+        mine[64] = l_run;
+#pragma unroll
+        for (int g = 0; g < KS; ++g)                     // (unrolled, grp is wave-uniform: one scalar branch, constant register indices)
+            if (grp == g) {
+#pragma unroll
+                for (int i = 0; i < 32; ++i)
+                    if (i / Q != g) mine[(2 + (i < g * Q ? i : i - Q)) * 64] = o[i >> 4][i & 15];
+            }
+        __syncthreads();
+        const float* src[KS];
+        float mg[KS];
+#pragma unroll
+        for (int g = 0; g < KS; ++g) {
+            src[g] = mrg + (size_t)((g * 4 + wave) * NPK) * 64 + lane;
+            mg[g] = src[g][0];
+        }
+        float m_all = mg[0];
+#pragma unroll
+        for (int g = 1; g < KS; ++g) m_all = fmaxf(m_all, mg[g]);
+        float ag[KS];
+#pragma unroll
+        for (int g = 0; g < KS; ++g) ag[g] = __builtin_amdgcn_exp2f((mg[g] - m_all) * c2);    // empty group: m = -inf -> 0
+        // The roundings are spelled out (explicit fma, nothing left to contract): of "l_0 a_0 + l_1 a_1" the compiler may fuse either product
+        // into the addition, and for l it rounds l_1 a_1 and fuses l_0 a_0 in the one-group merge below (all six instantiations).  The
+        // bits are pinned by tests/test_split_tail_gpu.py.
+        float l_all = __builtin_fmaf(src[0][64], ag[0], src[1][64] * ag[1]);
+#pragma unroll
+        for (int g = 2; g < KS; ++g) l_all = __builtin_fmaf(src[g][64], ag[g], l_all);
+        float own[Q];
+#pragma unroll
+        for (int g = 0; g < KS; ++g)
+            if (grp == g) {
+#pragma unroll
+                for (int j = 0; j < Q; ++j) {
+                    const int i = g * Q + j;
+                    // every element gets its own copy of the weights: the SLP vectoriser pairs the elements up, and a weight it knows to be
+                    // common to a pair may be broadcast out of the HI half of a register pair -- the packed-f32 form that must not run
+                    // next to MFMAs (build.sh, tests/test_isa.py)
+                    float w[KS];
+#pragma unroll
+                    for (int k = 0; k < KS; ++k) {
+                        w[k] = ag[k];
+                        asm volatile("" : "+v"(w[k]));
+                    }
+                    float x[KS];                         // the element's partial sums in group order (group 0 parks i >= Q at slot i - Q)
+#pragma unroll
+                    for (int k = 0; k < KS; ++k) x[k] = k == g ? o[i >> 4][i & 15] : src[k][(2 + (i < k * Q ? i : i - Q)) * 64];
+                    // (which product is rounded and which is fused, as the one-group merge is compiled -- see l_all: with two groups the
+                    // compiler rounds o_1 a_1 and fuses o_0 a_0, with four it rounds o_0 a_0 and fuses the others one after the other)
+                    float acc;
+                    if (KS == 2) {
+                        acc = __builtin_fmaf(x[0], w[0], x[1] * w[1]);
+                    } else {
+                        acc = x[0] * w[0];
+#pragma unroll
+                        for (int k = 1; k < KS; ++k) acc = __builtin_fmaf(x[k], w[k], acc);
+                    }
+                    own[j] = acc;
+                }
+            }
+        const float l_tot = l_all + __shfl_xor(l_all, 32, 64);
+        const float inv = 1.0f / l_tot;
+        const int qr = q0 + lq;
+        op16_t* stg = reinterpret_cast<op16_t*>(mrg + KS * 4 * NPK * 64);
+#pragma unroll
+        for (int j = 0; j < Q; j += 4) {
+            const int i = grp * Q + j;                   // (db, rg) of these four elements
+            const int d = (i >> 4) * 32 + 8 * ((i & 15) >> 2) + 4 * hi;
+            const float v0 = own[j] * inv, v1 = own[j + 1] * inv, v2 = own[j + 2] * inv, v3 = own[j + 3] * inv;
+            const u32x2 pk = {f5_pack2_bounded(v0, v1), f5_pack2_bounded(v2, v3)};
+            if (HP) {
+                if (qr < p.seq_len) {
+                    const size_t off = (rowbase + qr) * p.ldo + h * 64 + d;
+                    *reinterpret_cast<u32x2*>(p.out[0] + off) = pk;
+                    if (p.out[1]) *reinterpret_cast<u32x2*>(p.out[1] + off) = u32x2{f5_pack2_lo(v0, v1), f5_pack2_lo(v2, v3)};
+                }
+            } else {
+                *reinterpret_cast<u32x2*>(&stg[(wave * 32 + lq) * SLD + d]) = pk;
+            }
+        }
+        if (HP) return;
+        __syncthreads();                                 // the last barrier; a row's blocks come from different groups
+#pragma unroll
+        for (int c = tid; c < 128 * 8; c += 256 * KS) {
+            const int row = c >> 3, ch = c & 7;
+            const int qrow = qblk * 128 + row;
+            if (qrow < p.seq_len)
+                *reinterpret_cast<u32x4*>(p.out[0] + (rowbase + qrow) * p.ldo + h * 64 + ch * 8) = *reinterpret_cast<const u32x4*>(&stg[row * SLD + ch * 8]);
+        }
+        return;
+    }
+    // fp8 output (attn_store_f8 wants whole rows in one wave): groups 1.. park everything, group 0 merges and stores
     if (grp > 0) {
         float* dst = mrg + (size_t)((grp - 1) * 4 + wave) * 34 * 64 + lane;
         dst[0] = m_run;

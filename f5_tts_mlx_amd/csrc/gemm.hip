@@ -334,7 +334,8 @@ template <int EPI, int MB, int NB, int NST, int WM = 2, int WN = 2, int KS = 1, 
 __global__ __launch_bounds__(64 * WM * WN * KS) void f5_gemm_ring_kernel(F5GemmArgs p, int tiles_n, int ntiles) {
     // WM x WN waves per K group, wave tile 32*MB x 32*NB; KS groups split the K tiles round-robin (group g owns tiles
     // g, g+KS, ...; its own ring) and are summed in group order through LDS at the end: small-M problems are one round
-    // of workgroups whose run time is a single workgroup's chain of K steps, which KS cuts by KS.
+    // of workgroups whose run time is a single workgroup's chain of K steps, which KS cuts by KS.  Where the wave tile has one
+    // column block per group, every group sums and finishes one of them (SHARE below); otherwise group 0 does all of it.
     constexpr int NTG = 64 * WM * WN;                   // threads per K group
     constexpr int BMt = 32 * MB * WM, BNt = 32 * NB * WN;
     constexpr int NA = BMt * 8 / NTG, NW = BNt * 8 / NTG;
@@ -444,7 +445,18 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void f5_gemm_ring_kernel(F5GemmA
     constexpr bool PRE_RESID = EPI == EPI_RESID_GATE && MB * NB <= 3;   // 64 more live VGPRs would spill the 2x2 wave tile
     ResidPre<PRE_RESID ? MB : 1, PRE_RESID ? NB : 1> rpre;
     const bool use_pre = PRE_RESID && p.ln_counter == nullptr && (p.debug_flags & (8 | 256)) == 0;
-    if (PRE_RESID && use_pre && grp == 0 && FOLD != 1)
+    // K-split launches whose wave tile has one column block per group: BOTH groups finish the tile (see the tail).  Group g owns column
+    // block nb == g, so it is also the group that requests that block's residual operands: half as many per wave, in front of each
+    // group's first tile.  ln_counter, the fold producer, the q | k | v epilogue (its staged form needs whole heads per wave) and the
+    // debug flags 8 / 256 keep the one-group tail.
+    constexpr bool SHARE = KS > 1 && NB == KS && FOLD == 0 && EPI != EPI_QKV_ROPE;
+    const bool share = SHARE && p.ln_counter == nullptr && (p.debug_flags & (8 | 256)) == 0;
+    constexpr bool SHARE_PRE = SHARE && PRE_RESID;      // (use_pre implies share there)
+    ResidPre<SHARE_PRE ? MB : 1, 1> rown;
+    if constexpr (SHARE_PRE) {
+        if (use_pre) resid_preload<MB, 1>(p, rown, m0 + wm * (32 * MB), n0 + wn * (32 * NB) + grp * 32, lane);
+    }
+    if (PRE_RESID && !SHARE_PRE && use_pre && grp == 0 && FOLD != 1)
         resid_preload<PRE_RESID ? MB : 1, PRE_RESID ? NB : 1>(p, rpre, m0 + wm * (32 * MB), n0 + wn * (32 * NB), lane);
     static_assert(FOLD == 0 || (FOLD == 1 && PRE_RESID && NB == 2) || (FOLD == 2 && EPI == EPI_GELU_TANH && NB == 2 && KS == 1 && WM * WN == 8),
                   "fold producer = the preloaded residual epilogue on 64-column wave tiles; fold consumer = the 8-wave GELU launch");
@@ -567,6 +579,64 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void f5_gemm_ring_kernel(F5GemmA
     }
 #undef RING_STEP
 #undef RING_ISSUE
+    if constexpr (SHARE) {
+        if (share) {
+            // Both groups finish the tile: group g parks the column blocks it does not own, reads its partners' parts of block nb == g,
+            // adds them in GROUP order (acc_0 + acc_1 + ..., whichever group does the adding) and runs the epilogue of that block as a
+            // one-block wave tile.  Half the LDS traffic, half the epilogue arithmetic and half the stores per wave of a launch whose
+            // run time is one workgroup's chain.  Layout: [staging, one region per wave of every group][parts: wave, block, partner].
+            constexpr int RED1 = MB * 16 * 64;              // floats of one wave's part of one column block
+            constexpr int STG1 = small_tile_staged<EPI, 1>() ? small_tile_stage_elems<1>() : 0;
+            constexpr int STGS = KS * WM * WN * STG1;       // 16-bit elements
+            static_assert(STGS * 2 + WM * WN * NB * (KS - 1) * RED1 * 4 <= KS * RING * 2, "staging + parked parts fit in the rings");
+            float* red = reinterpret_cast<float*>(smem_all + STGS) + (size_t)wave * (NB * (KS - 1) * RED1) + lane;
+            __syncthreads();                                // every ring is dead
+            // (the loops over g are unrolled and grp is wave-uniform: one scalar branch, constant register indices)
+#pragma unroll
+            for (int g = 0; g < KS; ++g)
+                if (grp == g) {
+#pragma unroll
+                    for (int nb = 0; nb < NB; ++nb)
+                        if (nb != g) {                      // slot of group g among block nb's parts: the partners in group order
+                            float* dst = red + (nb * (KS - 1) + (g < nb ? g : g - 1)) * RED1;
+#pragma unroll
+                            for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                                for (int e = 0; e < 16; ++e) dst[(mb * 16 + e) * 64] = acc[mb][nb][e];
+                        }
+                }
+            __syncthreads();                                // the last barrier: from here on every wave is on its own
+            f32x16 own[MB][1];
+#pragma unroll
+            for (int g = 0; g < KS; ++g)
+                if (grp == g) {
+                    const float* src = red + g * (KS - 1) * RED1;
+#pragma unroll
+                    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) {
+                            const float mine = acc[mb][g][e];
+                            float s = g == 0 ? mine : src[(mb * 16 + e) * 64];           // group 0's term first
+#pragma unroll
+                            for (int h = 1; h < KS; ++h) s += h == g ? mine : src[(h < g ? h : h - 1) * RED1 + (mb * 16 + e) * 64];
+                            own[mb][0][e] = s;
+                        }
+                }
+            const int row0 = m0 + wm * (32 * MB), col0 = n0 + wn * (32 * NB) + grp * 32;
+            if (small_tile_staged<EPI, NB>() && n0 + BNt <= p.N && (p.debug_flags & 2) == 0) {
+                staged_epilogue_bf16<EPI, MB, 1>(p, own, smem_all + wave_all * STG1, row0, col0, lane);
+                return;
+            }
+            if constexpr (SHARE_PRE) {
+                if (use_pre) {
+                    resid_epilogue_preloaded<MB, 1>(p, own, rown, row0, col0, lane);
+                    return;
+                }
+            }
+            gemm_epilogue<EPI, MB, 1>(p, own, m0, col0, wm, 0, lane);
+            return;
+        }
+    }
     constexpr int STG = small_tile_staged<EPI, NB>() ? WM * WN * small_tile_stage_elems<NB>() : 0;   // staging area (bf16 elements)
     if (KS > 1) {
         // partial sums of groups 1.. -> LDS (behind the epilogue staging area), added by group 0 in group order
