@@ -66,6 +66,7 @@ enum F5ConvPosKernel {
     F5CP_4,          // f5_convpos_kernel<false,4>
     F5CP_HP1,        // f5_convpos_kernel<true,1>
     F5CP_HP2,        // f5_convpos_kernel<true,2>
+    F5CP_RING,       // f5_convpos_ring_kernel
     F5CP_XCD = 16
 };
 namespace f5dbg {

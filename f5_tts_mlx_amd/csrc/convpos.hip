@@ -4,6 +4,8 @@
 // The A operand is a sliding window over ONE LDS-resident halo tile of x ((128 + taps - 1) rows x 64 ci),
 // so x is read from HBM once per block; the per-tap weight slab [64 co][64 ci] is double-buffered.
 // Sequence edges are zero padded per batch element (Conv1d padding); no mask (dit.py:251 passes none).
+// Two kernels: f5_convpos_kernel (register-staged slabs, small LDS footprint: several workgroups per CU hide each other's round
+// trips) and, for single-segment grids of one round, f5_convpos_ring_kernel further down (same arithmetic, slabs by LDS-DMA into a ring).
 #include "convpos.hpp"
 #include "rowops.hpp"     // f5_sat_flag_host
 
@@ -12,6 +14,12 @@ namespace F5_NS {
 #define XLD 72  // LDS row stride (elements) for both tiles: 144 B rows => conflict-free ds_read_b128
 #define CP_ROWS 128
 #define CP_MAXTAPS 31
+// Ablation switches for tools/convpos_bench.py's probe builds (-DCP_ABL=bits); 0 in the library, where every test below is a constant
+// that compiles away.  1: no tap loop; 2: tap loop without fragment reads and MFMAs; 4: tap loop without the slab loads and stores;
+// 8: epilogue without its stores.  Applies to f5_convpos_kernel and to f5_convpos_ring_kernel alike.
+#ifndef CP_ABL
+#define CP_ABL 0
+#endif
 
 // TPS = taps per pipeline step: the weight slabs of TPS taps are fetched, stored and synchronised together (fewer, fatter
 // steps).  Measured no better than TPS = 1 at batch 1 and worse at batch 32, where the 18 KB weight ring of TPS = 1 lets 3-4
@@ -99,8 +107,10 @@ __global__ __launch_bounds__(256) void f5_convpos_kernel(F5ConvPosArgs p) {
         acc[1][e] = 0.0f;
     }
 
-    CP_LOADW(0);
-    CP_STOREW(0);
+    if (!(CP_ABL & 4)) {
+        CP_LOADW(0);
+        CP_STOREW(0);
+    }
     __syncthreads();
 
     // mode 1 accumulates into x.  `out[off] += v` element by element in the epilogue made the compiler keep every
@@ -119,13 +129,13 @@ __global__ __launch_bounds__(256) void f5_convpos_kernel(F5ConvPosArgs p) {
             }
     }
 
-    for (int t0 = 0, step = 0; t0 < taps; t0 += TPS, ++step) {
+    for (int t0 = 0, step = 0; t0 < ((CP_ABL & 1) ? 0 : taps); t0 += TPS, ++step) {
         const int cur = step & 1;
-        if (t0 + TPS < taps) CP_LOADW(t0 + TPS);
+        if (!(CP_ABL & 4) && t0 + TPS < taps) CP_LOADW(t0 + TPS);
 #pragma unroll
         for (int tt = 0; tt < TPS; ++tt) {
             const int t = t0 + tt;
-            if (t < taps) {
+            if (!(CP_ABL & 2) && t < taps) {
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) {
                     const int aoff = (wave * 32 + lr + t) * XLD + ks * 16 + hi * 8;
@@ -146,7 +156,7 @@ __global__ __launch_bounds__(256) void f5_convpos_kernel(F5ConvPosArgs p) {
                 }
             }
         }
-        if (t0 + TPS < taps) CP_STOREW(cur ^ 1);
+        if (!(CP_ABL & 4) && t0 + TPS < taps) CP_STOREW(cur ^ 1);
         __syncthreads();
     }
 
@@ -167,7 +177,9 @@ __global__ __launch_bounds__(256) void f5_convpos_kernel(F5ConvPosArgs p) {
             if (n < p.seq_len) {
                 const float v = f5_mish(acc[nb][r] + bias);
                 const size_t off = (rowbase + n) * p.ldo + co;
-                if (p.mode == 0) {
+                if ((CP_ABL & 8) && p.taps > 0) {
+                    asm volatile("" ::"v"(v), "v"(old[nb][r]));           // the arithmetic stays, the stores go
+                } else if (p.mode == 0) {
                     op16_t h, l;
                     f5_split(v, h, l, trk);
                     p.out_bf[0][off] = h;
@@ -181,8 +193,269 @@ __global__ __launch_bounds__(256) void f5_convpos_kernel(F5ConvPosArgs p) {
     f5_sat_commit(trk, p.sat_flag);
 }
 
-int f5_convpos_tps = 0;   // taps per pipeline step: 0 auto, 1 / 2 / 4 forced (f5_debug_set_convpos_tps)
+// ================================================================================================================================
+// f5_convpos_ring_kernel: the single-segment conv for grids of one round (one workgroup per CU, one wave per SIMD), where nothing
+// but the kernel's own pipeline hides a round trip.  Same workgroup -> (token tile, group, element) mapping, same 128-token tile and
+// 4 waves, same arithmetic in the same order as f5_convpos_kernel<false, .> (per accumulator: taps ascending, ks = 0..3), so the same
+// bits.  What differs is how the operands travel:
+//   - the weight slabs go HBM -> LDS by global_load_lds (16 B per lane, no staging VGPRs) into a ring of NST slots of 8 KB; the first
+//     NST - 1 slabs are requested in the prologue, and behind every tap's barrier the next one goes into the slot of the tap before.
+//     One barrier per tap; the counted `s_waitcnt vmcnt` in front of it leaves NST - 3 slabs in flight;
+//   - the halo tile goes the same way, in front of slab 0 (rows outside [0, seq_len) are zeros written by ds_write), so the prologue
+//     is one burst of requests and not a chain of load -> store -> load;
+//   - the fragments of tap t + 1 are read from LDS into a second register set BEFORE the MFMAs of tap t (tools/convpos_bench.py's probe
+//     builds: with a read -> wait -> MFMA sequence per K step the tap loop without any slab traffic took 7.7 us against 3.4 us of
+//     MFMA time).  The barrier of tap t therefore waits for slab t + 1.
+// LDS images.  An LDS-DMA instruction writes lane-linear (wave base + 16 lane), so rows are 128 B without padding and the 16-byte
+// chunk c of row r sits at chunk c ^ ((r >> 1) & 7): applied to the SOURCE address when staging and again on every read.
+// ds_read_b128 is served in groups of 16 lanes, 256 B over the 64 banks; the lanes of a group read one logical chunk c of 16
+// consecutive rows r0 .. r0 + 15 (r0 = wave * 32 + t (+ 16) for the sliding A window, any tap offset t).  Byte address mod 256 =
+// 128 (r & 1) + 16 (c ^ ((r >> 1) & 7)): among the 8 rows of either parity r >> 1 runs over 8 consecutive numbers, all residues
+// mod 8, so the 16 lanes hit 16 different 16-byte bank groups whatever r0 is: no conflict for any t.
+// vmcnt is counted per wave in issue order.  Order of issue: halo, slab 0, the 2 bias loads and mode 1's 32 `old` loads, slabs
+// 1 .. NST-2, then one slab per tap.  A wait for "slabs below u" may leave 2 (issued - u) instructions out when the slabs issued so
+// far are all the ring can hold ("steady": the counts are then compile-time constants), plus bias and `old` while u == 1; otherwise
+// the wave drains (short tap counts, the tail).
+// Ordering.  A slab is read one barrier after the wait that retired it; a slot is refilled behind the barrier of tap t with the slab of
+// tap t + NST - 1, and was last read (tap t - 1's fragments) before the barrier of tap t - 1, where lgkmcnt(0) retired the reads.
+// Measured at (C 1024, N 937, 2 elements), op level: ring depth 4 / 8 / 12 and 1 / 2 / 4 taps per barrier within each other's scatter,
+// mode 0's rows staged through LDS into 16-byte stores no faster than the 2-byte stores (profiles/r08): 8 slots, 1 tap, direct stores.
+// ================================================================================================================================
+#ifndef CP_RING_NST
+#define CP_RING_NST 8
+#endif
+#define CPR_XROWS 160                     // halo rows staged (158 used at 31 taps): 5 LDS-DMA pieces of 8 rows per wave
+#define CPR_SLAB (64 * 64)                // elements per weight slab image
+
+__device__ __forceinline__ void cp_glds16(const op16_t* gptr, op16_t* lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),
+                                     (__attribute__((address_space(3))) void*)(lds_wave_base), 16, 0, 0);
+}
+__device__ __forceinline__ int cp_swz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 1) & 7)) << 3); }
+// workgroup barrier the compiler moves no memory access across; this wave's LDS accesses are complete when it arrives
+__device__ __forceinline__ void cp_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+template <int N>
+__device__ __forceinline__ void cp_vmcnt() {
+    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+constexpr size_t cp_ring_lds_bytes(int nst) { return (size_t)(CPR_XROWS * 64 + nst * CPR_SLAB) * sizeof(op16_t); }
+
+template <int NST>
+__global__ __launch_bounds__(256) void f5_convpos_ring_kernel(F5ConvPosArgs p) {
+    static_assert(NST >= 3 && 2 * (NST - 2) + 34 < 64, "ring depth: two slabs in use, vmcnt range");
+    extern __shared__ __attribute__((aligned(16))) op16_t cp_smem[];
+    op16_t* const sX = cp_smem;
+    op16_t* const sW = cp_smem + CPR_XROWS * 64;
+
+    asm volatile("" ::"s"(p.in[0]), "s"(p.W[0]), "s"(p.bias), "s"(p.B), "s"(p.seq_len), "s"(p.groups), "s"(p.taps), "s"(p.ld), "s"(p.mode),
+                 "s"(p.out_bf[0]), "s"(p.out_f32), "s"(p.ldo));              // the argument block in one scalar-load clause
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int hi = lane >> 5, lr = lane & 31;
+    int n0, g, b;                          // f5_convpos_kernel's mapping, 1-D group-per-XCD numbering included
+    if (gridDim.y == 1 && (p.groups & 7) == 0) {
+        const int nx = (p.seq_len + CP_ROWS - 1) / CP_ROWS;
+        const int per_group = nx * p.B;
+        const int s_ = blockIdx.x >> 3;
+        const int gl = s_ / per_group, rem = s_ - gl * per_group;
+        g = gl * 8 + (blockIdx.x & 7);
+        b = rem / nx;
+        n0 = (rem - b * nx) * CP_ROWS;
+    } else {
+        n0 = blockIdx.x * CP_ROWS;
+        g = blockIdx.y;
+        b = blockIdx.z;
+    }
+    const int taps = p.taps;
+    const int pad = taps >> 1;
+    const int halo = CP_ROWS + taps - 1;
+    const size_t rowbase = (size_t)b * p.seq_len;
+    const int kdim = taps * 64;
+
+    // ---- halo tile: in-range rows by LDS-DMA (the lanes of the other rows are masked off and write zeros themselves) ----------
+#pragma unroll
+    for (int j = 0; j < CPR_XROWS * 8 / 256; ++j) {
+        const int qd = j * 256 + tid;
+        const int r = qd >> 3, c = qd & 7;
+        const int n = n0 - pad + r;
+        if (r < halo && n >= 0 && n < p.seq_len)
+            cp_glds16(p.in[0] + (rowbase + n) * p.ld + g * 64 + ((c ^ ((r >> 1) & 7)) << 3), sX + (j * 256 + wave * 64) * 8);
+        else
+            *reinterpret_cast<u32x4*>(&sX[qd * 8]) = u32x4{0u, 0u, 0u, 0u};
+    }
+
+    // ---- weight slabs: 2 pieces per wave per tap, source chunk swizzled, advanced by one tap per issue ------------------------
+    const op16_t* wptr[2];
+    int wlds[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int qd = i * 256 + tid;
+        const int r = qd >> 3, c = qd & 7;
+        wptr[i] = p.W[0] + (size_t)(g * 64 + r) * kdim + ((c ^ ((r >> 1) & 7)) << 3);
+        wlds[i] = (i * 256 + wave * 64) * 8;
+    }
+    int issued = 0, islot = 0;
+#define CPR_ISSUE()                                                   \
+    if (!(CP_ABL & 4) && issued < taps) {                             \
+        op16_t* st_ = sW + islot * CPR_SLAB;                          \
+        cp_glds16(wptr[0], st_ + wlds[0]);                            \
+        cp_glds16(wptr[1], st_ + wlds[1]);                            \
+        wptr[0] += 64;                                                \
+        wptr[1] += 64;                                                \
+        islot = islot + 1 == NST ? 0 : islot + 1;                     \
+        ++issued;                                                     \
+    }
+    CPR_ISSUE();
+    asm volatile("" ::: "memory");
+
+    // bias, and for mode 1 the old values, requested before the tap loop as in f5_convpos_kernel (clamped rows, straight-line loads)
+    float bias2[2] = {p.bias[g * 64 + lr], p.bias[g * 64 + 32 + lr]};
+    float old[2][16];
+    if (p.mode != 0) {
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                int n = n0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                if (n > p.seq_len - 1) n = p.seq_len - 1;
+                old[nb][r] = p.out_f32[(rowbase + n) * p.ldo + g * 64 + nb * 32 + lr];
+            }
+    }
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int i = 1; i < NST - 1; ++i) CPR_ISSUE();
+
+    f32x16 acc[2];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        acc[0][e] = 0.0f;
+        acc[1][e] = 0.0f;
+    }
+
+    // halo and slab 0 have landed (this wave's pieces); the barrier makes every wave's visible
+    if (issued == NST - 1) {
+        if (p.mode != 0) cp_vmcnt<2 * (NST - 2) + 34>();
+        else cp_vmcnt<2 * (NST - 2) + 2>();
+    } else {
+        cp_vmcnt<0>();
+    }
+    cp_barrier();
+
+    op16x8 fa[2][4], fw[2][8];             // fragments of two taps: [set][ks] and [set][ks * 2 + nb]
+#define CPR_READ(set_, t_)                                                                                             \
+    {                                                                                                                  \
+        const op16_t* sw_ = sW + ((t_) % NST) * CPR_SLAB;                                                              \
+        _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                             \
+            fa[set_][ks] = *reinterpret_cast<const op16x8*>(&sX[cp_swz(wave * 32 + lr + (t_), ks * 2 + hi)]);          \
+            _Pragma("unroll") for (int nb = 0; nb < 2; ++nb)                                                           \
+                fw[set_][ks * 2 + nb] = *reinterpret_cast<const op16x8*>(&sw_[cp_swz(nb * 32 + lr, ks * 2 + hi)]);     \
+        }                                                                                                              \
+    }
+    // tap t_: slab t_ + 1 has landed and is made visible, the slot of tap t_ - 1 takes the next slab, tap t_ + 1's fragments are
+    // requested (NEXT_), then the MFMAs of tap t_ run on the set read one tap earlier.  No condition around the reads or the MFMAs:
+    // with `if (t + 1 < taps)` around either the compiler waited lgkmcnt(0) in front of the MFMAs and carried the accumulators
+    // through VGPRs from one iteration to the next
+#define CPR_TAP(cur_, t_, NEXT_)                                                                                       \
+    {                                                                                                                  \
+        if (issued - ((t_) + 2) == NST - 3) cp_vmcnt<2 * (NST - 3)>();                                                 \
+        else cp_vmcnt<0>();                                                                                            \
+        cp_barrier();                                                                                                  \
+        CPR_ISSUE();                                                                                                   \
+        if (!(CP_ABL & 2)) {                                                                                           \
+            if (NEXT_) CPR_READ((cur_) ^ 1, (t_) + 1);                                                                 \
+            _Pragma("unroll") for (int ks = 0; ks < 4; ++ks)                                                           \
+                _Pragma("unroll") for (int nb = 0; nb < 2; ++nb)                                                       \
+                    acc[nb] = F5_MFMA32(fa[cur_][ks], fw[cur_][ks * 2 + nb], acc[nb], 0, 0, 0);                        \
+        }                                                                                                              \
+    }
+    // the tap count is odd: pairs of taps, then the last one on set 0
+    if (!(CP_ABL & 1)) {
+        if (!(CP_ABL & 2)) CPR_READ(0, 0);
+        int t = 0;
+        for (; t + 1 < taps; t += 2) {
+            CPR_TAP(0, t, true);
+            CPR_TAP(1, t + 1, true);
+        }
+        CPR_TAP(0, t, false);
+    }
+
+    // ---- epilogue: + bias, Mish, store (f5_convpos_kernel's, value for value) ------------------------------------------------
+    asm volatile("" : "+v"(bias2[0]), "+v"(bias2[1]));
+    f5_sat_t trk;
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb) {
+        const int co = g * 64 + nb * 32 + lr;
+        const float bias = bias2[nb];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int n = n0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            if (n < p.seq_len) {
+                const float v = f5_mish(acc[nb][r] + bias);
+                const size_t off = (rowbase + n) * p.ldo + co;
+                if ((CP_ABL & 8) && p.taps > 0) {
+                    asm volatile("" ::"v"(v), "v"(old[nb][r]));
+                } else if (p.mode == 0) {
+                    op16_t h, l;
+                    f5_split(v, h, l, trk);
+                    p.out_bf[0][off] = h;
+                    if (p.out_bf[1]) p.out_bf[1][off] = l;
+                } else {
+                    p.out_f32[off] = old[nb][r] + v;
+                }
+            }
+        }
+    }
+    f5_sat_commit(trk, p.sat_flag);
+}
+
+// the ring kernel's LDS (84 KB at 8 slots) is beyond the 64 KB a kernel gets without asking: asked once per device
+static int cp_launch_ring(const F5ConvPosArgs& ab, dim3 grid, hipStream_t stream) {
+    constexpr size_t lds = cp_ring_lds_bytes(CP_RING_NST);
+    static bool asked[64] = {};
+    int dev = 0;
+    F5_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "convpos: no current device");
+    if (!asked[dev]) {
+        F5_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&f5_convpos_ring_kernel<CP_RING_NST>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
+                   "convpos: %zu bytes of LDS refused", lds);
+        asked[dev] = true;
+    }
+    hipLaunchKernelGGL((f5_convpos_ring_kernel<CP_RING_NST>), grid, dim3(256), lds, stream, ab);
+    return 0;
+}
+
+int f5_convpos_tps = 0;   // taps per pipeline step: 0 auto, 1 / 2 / 4 forced, 8: the ring kernel (f5_debug_set_convpos_tps)
 int f5_convpos_xcd_map = 1;   // 0: plain 3-D block numbering (A/B)
+// grids up to this many workgroups count as "one round" for the automatic route to the ring kernel (256 CUs, one workgroup each)
+#ifndef CP_RING_MAX_WG
+#define CP_RING_MAX_WG 256
+#endif
+
+// The kernel a launch of this shape runs under the current selectors (F5ConvPosKernel, F5CP_XCD included): the one place that
+// decides, used by the launcher and by the f5_debug_convpos_route hook.
+//   ring kernel, automatic: single segment, groups dealt to XCDs (a multiple of 8 of them, numbering on), seq_len >= 512 and a grid
+//   of one round.  Below 512 tokens or beyond one round several workgroups share a CU, and f5_convpos_kernel<false,1>'s 36 KB of LDS
+//   lets 3-4 of them hide each other's round trips (batch 32: 304 us), which the ring kernel's 84 KB does not.
+//   selector 8 forces it for every single-segment launch; with three segments 8 acts like 2 and 4: f5_convpos_kernel<true,2>.
+int f5_convpos_route(int B, int seq_len, int groups, int nseg) {
+    const long nwg = (long)f5_cdiv(seq_len, CP_ROWS) * groups * B;
+    const bool xcd = groups % 8 == 0 && f5_convpos_xcd_map;
+    const int tps = f5_convpos_tps;
+    int k;
+    if (nseg == 3) k = tps > 1 ? F5CP_HP2 : F5CP_HP1;
+    else if (tps == 8 || (tps == 0 && xcd && seq_len >= 512 && nwg <= CP_RING_MAX_WG)) k = F5CP_RING;
+    else if (tps >= 4) k = F5CP_4;
+    else if (tps >= 2) k = F5CP_2;
+    else k = F5CP_1;       // measured (tools/convpos_bench.py): 1 tap per step beats 2 and 4 at every size (batch 32: 304 / 355 / 629 us)
+    return k | (xcd ? F5CP_XCD : 0);
+}
+
 int f5_launch_convpos(const F5ConvPosArgs& a, hipStream_t stream) {
     f5dbg::last_convpos_kernel = F5CP_NONE;                // a launch that is refused, or fails, reports no kernel
     F5_REQUIRE(a.B > 0 && a.seq_len > 0 && a.groups > 0, "convpos: bad shape");
@@ -191,33 +464,27 @@ int f5_launch_convpos(const F5ConvPosArgs& a, hipStream_t stream) {
     F5_REQUIRE(a.ld % 8 == 0, "convpos: ld must be a multiple of 8");
     dim3 grid(f5_cdiv(a.seq_len, CP_ROWS), a.groups, a.B);
     const long nwg = (long)grid.x * grid.y * grid.z;
-    const bool xcd = a.groups % 8 == 0 && f5_convpos_xcd_map;
-    if (xcd) grid = dim3((unsigned)nwg, 1, 1);             // group-per-XCD numbering (see the kernel)
-    // taps per pipeline step: measured (tools/convpos_bench.py) 1 is best at every size once the groups are dealt to XCDs
-    // (batch 1: 19.8 / 21.1 / 21.3 us for 1 / 2 / 4; batch 32: 304 / 355 / 629 us); 2 and 4 stay selectable for experiments
-    int tps = f5_convpos_tps;
-    if (tps == 0) tps = 1;
+    const int reached = f5_convpos_route(a.B, a.seq_len, a.groups, a.nseg);
+    if (reached & F5CP_XCD) grid = dim3((unsigned)nwg, 1, 1);   // group-per-XCD numbering (see the kernel)
     F5ConvPosArgs ab = a;
     if (ab.sat_flag == nullptr) ab.sat_flag = f5_sat_flag_host;
-    int reached;
-    if (a.nseg == 3) {
+    switch (reached & (F5CP_XCD - 1)) {
+    case F5CP_HP1:
+    case F5CP_HP2:
         F5_REQUIRE(a.in[1] && a.W[1], "convpos: bf16x3 needs lo operands");
-        // the three-pass kernel is built for 1 and 2 taps per step only: a selector of 4 runs <true, 2>
-        if (tps > 1) hipLaunchKernelGGL((f5_convpos_kernel<true, 2>), grid, dim3(256), 0, stream, ab);
+        // the three-pass kernel is built for 1 and 2 taps per step only: a selector of 4 or 8 runs <true, 2>
+        if ((reached & (F5CP_XCD - 1)) == F5CP_HP2) hipLaunchKernelGGL((f5_convpos_kernel<true, 2>), grid, dim3(256), 0, stream, ab);
         else hipLaunchKernelGGL((f5_convpos_kernel<true, 1>), grid, dim3(256), 0, stream, ab);
-        reached = tps > 1 ? F5CP_HP2 : F5CP_HP1;
-    } else if (tps >= 4) {
-        hipLaunchKernelGGL((f5_convpos_kernel<false, 4>), grid, dim3(256), 0, stream, ab);
-        reached = F5CP_4;
-    } else if (tps >= 2) {
-        hipLaunchKernelGGL((f5_convpos_kernel<false, 2>), grid, dim3(256), 0, stream, ab);
-        reached = F5CP_2;
-    } else {
-        hipLaunchKernelGGL((f5_convpos_kernel<false, 1>), grid, dim3(256), 0, stream, ab);
-        reached = F5CP_1;
+        break;
+    case F5CP_RING:
+        if (const int rc = cp_launch_ring(ab, grid, stream)) return rc;
+        break;
+    case F5CP_4: hipLaunchKernelGGL((f5_convpos_kernel<false, 4>), grid, dim3(256), 0, stream, ab); break;
+    case F5CP_2: hipLaunchKernelGGL((f5_convpos_kernel<false, 2>), grid, dim3(256), 0, stream, ab); break;
+    default: hipLaunchKernelGGL((f5_convpos_kernel<false, 1>), grid, dim3(256), 0, stream, ab); break;
     }
     F5_LAUNCH_CHECK();
-    f5dbg::last_convpos_kernel = reached | (xcd ? F5CP_XCD : 0);
+    f5dbg::last_convpos_kernel = reached;
     return 0;
 }
 }  // namespace F5_NS

@@ -30,5 +30,7 @@ struct F5ConvPosArgs {
 };
 
 int f5_launch_convpos(const F5ConvPosArgs& a, hipStream_t stream);
+// the kernel f5_launch_convpos runs for this shape under the current selectors: an F5ConvPosKernel, plus F5CP_XCD (host only)
+int f5_convpos_route(int B, int seq_len, int groups, int nseg);
 }  // namespace F5_NS
 #endif

@@ -1425,7 +1425,7 @@ extern "C" uint16_t f5_debug_f2h_bits(float f) { return f5_f2h_bits(f); }
 extern "C" float f5_debug_h_bits2f(uint16_t h) { return f5_h_bits2f(h); }
 extern "C" uint16_t f5_debug_f2bf_bits(float f) { return f5_f2bf_bits(f); }
 extern "C" int f5_debug_set_convpos_tps(int v) {
-    F5_REQUIRE(v == 0 || v == 1 || v == 2 || v == 4, "conv-pos taps per pipeline step must be 0 (auto), 1, 2 or 4");
+    F5_REQUIRE(v == 0 || v == 1 || v == 2 || v == 4 || v == 8, "conv-pos taps per pipeline step must be 0 (auto), 1, 2, 4 or 8 (the ring kernel)");
     F5_SET_BOTH(f5_convpos_tps, v);
     return 0;
 }
@@ -1521,15 +1521,24 @@ extern "C" int f5_debug_last_attn_kernel(char* buf, int n) {
     if (k != F5A_NONE && (f5dbg::last_attn_kernel & F5A_OUT8)) s += "+f8";
     return copy_name(s, buf, n);
 }
+// name of an F5ConvPosKernel word, "+xcd" appended when it carries F5CP_XCD
+static std::string convpos_kernel_name(int word) {
+    static const char* const names[] = {"", "f5_convpos_kernel<false,1>", "f5_convpos_kernel<false,2>", "f5_convpos_kernel<false,4>",
+                                        "f5_convpos_kernel<true,1>", "f5_convpos_kernel<true,2>", "f5_convpos_ring_kernel"};
+    const int k = word & (F5CP_XCD - 1);
+    std::string s = k <= F5CP_RING ? names[k] : "";
+    if (k != F5CP_NONE && (word & F5CP_XCD)) s += "+xcd";
+    return s;
+}
 // name of the instantiation the most recent f5_launch_convpos of the process launched, "+xcd" appended when the 1-D block numbering
 // ran ("" = it refused the launch); returns its length
-extern "C" int f5_debug_last_convpos_kernel(char* buf, int n) {
-    static const char* const names[] = {"", "f5_convpos_kernel<false,1>", "f5_convpos_kernel<false,2>", "f5_convpos_kernel<false,4>",
-                                        "f5_convpos_kernel<true,1>", "f5_convpos_kernel<true,2>"};
-    const int k = f5dbg::last_convpos_kernel & (F5CP_XCD - 1);
-    std::string s = k <= F5CP_HP2 ? names[k] : "";
-    if (k != F5CP_NONE && (f5dbg::last_convpos_kernel & F5CP_XCD)) s += "+xcd";
-    return copy_name(s, buf, n);
+extern "C" int f5_debug_last_convpos_kernel(char* buf, int n) { return copy_name(convpos_kernel_name(f5dbg::last_convpos_kernel), buf, n); }
+// The name a conv-pos launch of this shape would report under the current selectors, without launching anything or touching a device
+// (f5_convpos_route is the launcher's own decision; the selectors are the same in both operand builds)
+extern "C" int f5_debug_convpos_route(int B, int seq_len, int groups, int nseg, char* buf, int n) {
+    F5_REQUIRE(B > 0 && seq_len > 0 && groups > 0 && (nseg == 1 || nseg == 3), "convpos route: bad shape");
+    copy_name(convpos_kernel_name(f5bf::f5_convpos_route(B, seq_len, groups, nseg)), buf, n);
+    return 0;
 }
 // The route (gemm_route.hpp) a GEMM launch of this shape would take under the current knobs and process-wide flags, without launching
 // anything or touching a device.  variant_bits: 1 = group-major rotation tables, 2 = fused LN tail, 4 = LN-fold producer, 8 = consumer in

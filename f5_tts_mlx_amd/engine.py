@@ -129,6 +129,8 @@ def load_library() -> C.CDLL:
     lib.f5_debug_h_bits2f.restype = C.c_float
     lib.f5_debug_h_bits2f.argtypes = [C.c_uint16]
     lib.f5_debug_last_convpos_kernel.argtypes = [C.c_char_p, C.c_int]
+    if hasattr(lib, "f5_debug_convpos_route"):            # absent from an older build named by F5TTS_HIP_LIB
+        lib.f5_debug_convpos_route.argtypes = [C.c_int] * 4 + [C.c_char_p, C.c_int]
     lib.f5_op_noise_from_bits.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.f5_sample_edit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     # the per-row route (docs/row_controls.md).  An older build named by F5TTS_HIP_LIB (A/B runs) lacks these symbols: it still loads, and

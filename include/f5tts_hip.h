@@ -383,6 +383,9 @@ int f5_debug_last_attn_kernel(char* buf, int n);
  * block numbering ran; "" after a launch that was refused.  Host side only: nothing reaches a kernel.  The operand type is
  * f5_op_get_operand_type's. */
 int f5_debug_last_convpos_kernel(char* buf, int n);
+/* which conv-pos kernel WOULD a launch of this shape run under the current selectors?  The launcher's own decision, in the names of
+ * f5_debug_last_convpos_kernel (f5_convpos_ring_kernel among them); nothing is launched and no device is touched. */
+int f5_debug_convpos_route(int B, int seq_len, int groups, int nseg, char* buf, int n);
 /* which kernel WOULD it run?  The same routing function the launcher switches over (csrc/gemm_route.hpp), asked for a launch of this
  * epilogue and shape under the current selectors (f5_debug_set_gemm_tile / _ring / _qkv_tile) and process-wide flags; nothing is
  * launched and no device is touched.  variant_bits: 1 = group-major rotation tables set (transposed q / k tiles), 2 = fused LN tail,
@@ -410,8 +413,10 @@ int f5_debug_set_gemm_order(int v);
 int f5_debug_set_gemm_ring(int v);
 int f5_debug_set_gemm_qkv_tile(int sel);    /* small-M QKV projection with pair-major tables: 0 = auto (role-split 128x256 tiles when one round of >= 176), 1 = small tiles, 12 / 13 = lock-step 8-wave 128x256 ring, 14 = role-split whenever one round */
 int f5_debug_set_gemm_nband(int n);         /* 256x256 GEMM: tiles numbered in bands of n column tiles (0 = n fastest) */
-/* conv-pos kernel: weight slabs per pipeline step, 0 = auto (1 at every size), 1 / 2 / 4.  The one-pass kernel (nseg 1) is built for
- * all three; the three-pass kernel (nseg 3) for 1 and 2 only: with nseg == 3 a selector of 2 or 4 runs f5_convpos_kernel<true,2>
+/* conv-pos kernel: weight slabs per pipeline step, 0 = auto, 1 / 2 / 4, or 8 = the ring kernel f5_convpos_ring_kernel, weight slabs by LDS-DMA
+ * into a deep ring, for every one-pass launch.  Auto is 1 slab per step, except that one-pass launches of one round (at most 256 workgroups)
+ * with seq_len >= 512 and the groups dealt to XCDs run the ring kernel.  The one-pass kernel (nseg 1) is built for 1 / 2 / 4; the
+ * three-pass kernel (nseg 3) for 1 and 2 only: with nseg == 3 a selector of 2, 4 or 8 runs f5_convpos_kernel<true,2>
  * (f5_debug_last_convpos_kernel says which instantiation a launch ran) */
 int f5_debug_set_convpos_tps(int taps);
 int f5_debug_set_convpos_xcd_map(int on);   /* conv-pos kernel: 1 (default) = groups dealt to XCDs, 0 = plain 3-D block numbering */
