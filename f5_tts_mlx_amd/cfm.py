@@ -229,6 +229,9 @@ class F5TTS:
                                                  # F5-TTS sampler, so an all-True mask is the call without it (docs/edit.md)
         wave_lens=None,                          # extension: sample counts (b,) of a padded raw-wave batch `cond` (b, nw): each row's mel
                                                  # is taken on its own samples (no gain, no trim), `lens` defaults to the rows' frame counts
+        audio_cfg_strength=None,                 # extension (dual guidance, docs/dual_guidance.md): a scalar or one value per row; with
+                                                 # it `cfg_strength` is the TEXT strength (text-only against unconditional) and this the
+                                                 # SPEAKER strength (full against text-only); None = the single-knob call, untouched
     ) -> tuple[torch.Tensor, torch.Tensor]:
         self.eval()
         device = self.transformer.device
@@ -253,6 +256,10 @@ class F5TTS:
         sway_seq, sway_rows = per_row(sway_sampling_coef, batch, "sway_sampling_coef")
         seed_seq, seed_rows = per_row(seed, batch, "seed")
         speed_seq, speed_rows = per_row(speed, batch, "speed")
+        dual_kw = {}
+        if audio_cfg_strength is not None:
+            audio_seq, audio_rows = per_row(audio_cfg_strength, batch, "audio_cfg_strength")
+            dual_kw["audio_cfg_strength"] = [float(v) for v in audio_rows] if audio_seq else float(audio_cfg_strength)
         if speed_seq:
             speed = [float(v) for v in speed_rows]
         if isinstance(text, list):
@@ -314,7 +321,7 @@ class F5TTS:
         out, trajectory = self.transformer.engine.sample(
             text.to(device).contiguous(), cond_p, lens.tolist(), duration.tolist(), y0, t, method=method,
             cfg_strength=[float(v) for v in cfg_rows] if cfg_seq else float(cfg_strength), use_mask=(batch > 1 or pad_to is not None), use_graph=use_graph, return_trajectory=True,
-            cond_keep=cond_keep)
+            cond_keep=cond_keep, **dual_kw)
 
         if exists(self._vocoder):
             out = self._vocoder(out)

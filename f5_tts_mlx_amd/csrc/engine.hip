@@ -5,7 +5,8 @@
 //   * time MLP + all 22 adaLN linears + final adaLN for every function evaluation time (t only),
 //   * the text path (TextEmbedding + ConvNeXtV2 blocks) for the cond and null branches (text only),
 //   * the cond/text part of the input projection  W_c*cond + W_t*text + b  (dit.py:250).
-// Per function evaluation the cond and null branches run as one batch of 2*B*N rows.
+// Per function evaluation the cond and null branches run as one batch of 2*B*N rows; dual guidance (f5_sample_dual) adds a third
+// branch (audio dropped, text kept) behind them: 3*B*N rows in the order F, N, T (docs/dual_guidance.md).
 #include <stdarg.h>
 
 #include <cmath>
@@ -76,9 +77,11 @@ struct Workspace {
     // f5_sample_rows / f5_dit_forward_rows only (plan_workspace_rows; behind `total`: no offset of the plan above moves)
     size_t rscal = 0, rscal_words = 0;          // per-row controls, staged per call: [tgrid nfe x B | dt steps x B | cfg B] floats
     size_t rtgrid = 0, rdt = 0, rcfg = 0;
+    size_t racfg = 0;                           // dual guidance: the rows' audio strengths, B floats behind rcfg (0 words in the rows plan)
     size_t rsinus = 0, rth = 0, rtemb = 0;      // time MLP of every (evaluation, row): [nfe x B] rows each
     size_t rmod = 0;                            // adaLN table [nfe][B][(6L+2) D]
     size_t total_rows = 0;                      // bytes of the plan including the rows part
+    int nbr = 2;                                // branches the plan lays out: 2 (cond + null), 3 = dual guidance (F, N, T)
 };
 
 // Per-engine launch options: everything that reaches a kernel as a by-value argument or changes the launch sequence of sample()
@@ -431,30 +434,33 @@ constexpr long LN_FOLD_AUTO_ROWS = 22000;
 constexpr long LN_FOLD_SMALL_ROWS = 2048;
 constexpr bool LN_FOLD_SMALL_AUTO = false;     // measured -1.5 ... +0.7 % at batch 1 (profiles/r06): below the 4 % bar, so opt-in (ln_fold = 1)
 
-static Workspace plan_workspace(const f5_engine* e, int B, int N, int nt, int steps, int method) {
+// nbr = branches of a function evaluation the plan has room for.  The text path always runs for two (the third branch of dual guidance
+// reuses branch 0's text embedding), so only the buffers of the DiT itself -- MB rows -- and the per-branch durations grow with it.
+static Workspace plan_workspace(const f5_engine* e, int B, int N, int nt, int steps, int method, int nbr = 2) {
     const f5_config& c = e->cfg;
     const int D = c.dim, Dt = c.text_dim, FF = c.ff_dim, TF = c.text_ff_dim, L = c.depth, np = e->np, mel = c.mel_dim;
-    const size_t M1 = (size_t)B * N, M2 = 2 * M1;
+    const size_t M1 = (size_t)B * N, M2 = 2 * M1, MB = (size_t)nbr * M1;
     const int nfe = (steps - 1) * nfe_per_step(method);
     const int npad = (N + 63) / 64 * 64;
     Bump b;
     Workspace w;
+    w.nbr = nbr;
     const size_t nfe1 = (size_t)(nfe > 0 ? nfe : 1);
     // one counter per 64 rows of the residual stream; only small-M launches fuse (gemm.hpp ln_counter), large ones get none
     w.lncnt_words = (M2 + 63) / 64 <= 512 ? (M2 + 63) / 64 : 0;
-    w.scal_words = (size_t)1 + 3 * B + nfe1 + steps + 1 + w.lncnt_words;
+    w.scal_words = (size_t)1 + (size_t)(1 + nbr) * B + nfe1 + steps + 1 + w.lncnt_words;
     w.scal = b.take(w.scal_words * 4);
     w.status = w.scal;                      // offset 0, whatever the sizes
     w.lens = w.scal + 4;
     w.dur2 = w.lens + (size_t)B * 4;
-    w.tgrid = w.dur2 + (size_t)2 * B * 4;
+    w.tgrid = w.dur2 + (size_t)nbr * B * 4;
     w.dt = w.tgrid + nfe1 * 4;
     w.cfgv = w.dt + (size_t)steps * 4;
     w.lncnt = w.cfgv + 4;
     w.text = b.take((size_t)B * (nt > 0 ? nt : 1) * 4);
     w.ids = b.take(M2 * 4);
     w.keep = b.take(M2);
-    w.rowkeep = b.take(M2);
+    w.rowkeep = b.take(MB);
     w.sinus = b.take((size_t)(nfe + 1) * c.freq_embed_dim * 4);
     w.th = b.take((size_t)(nfe + 1) * D * 4);
     w.temb = b.take((size_t)(nfe + 1) * D * 4);
@@ -466,7 +472,7 @@ static Workspace plan_workspace(const f5_engine* e, int B, int N, int nt, int st
     w.traj = b.take((size_t)steps * M1 * mel * 4);
     w.ytmp = b.take(M1 * mel * 4);
     w.kst = b.take(3 * M1 * mel * 4);
-    w.vel = b.take(M2 * mel * 4);
+    w.vel = b.take(MB * mel * 4);
     for (int p = 0; p < 2; ++p) w.xin[p] = p < np ? b.take(M1 * 128 * 2) : 0;
     w.te[0] = b.take(M2 * Dt * 4);
     w.te[1] = b.take(M2 * Dt * 4);
@@ -476,19 +482,19 @@ static Workspace plan_workspace(const f5_engine* e, int B, int N, int nt, int st
     for (int p = 0; p < 2; ++p) {
         w.tln[p] = p < np ? b.take(M2 * Dt * 2) : 0;
         w.tg2[p] = p < np ? b.take(M2 * TF * 2) : 0;
-        w.ct[p] = p < np ? b.take(M2 * (128 + Dt) * 2) : 0;
+        w.ct[p] = p < np ? b.take(MB * (128 + Dt) * 2) : 0;
     }
-    w.hc = b.take(M2 * D * 4);
-    w.x = b.take(M2 * D * 4);
-    w.vt_bytes = (size_t)2 * B * c.heads * 64 * npad * 2;
+    w.hc = b.take(MB * D * 4);
+    w.x = b.take(MB * D * 4);
+    w.vt_bytes = (size_t)nbr * B * c.heads * 64 * npad * 2;
     for (int p = 0; p < 2; ++p) {
-        w.xb[p] = p < np ? b.take(M2 * D * 2) : 0;
-        w.c1[p] = p < np ? b.take(M2 * D * 2) : 0;
-        w.h[p] = p < np ? b.take(M2 * D * 2) : 0;
-        w.qk[p] = p < np ? b.take(M2 * 2 * D * 2) : 0;
+        w.xb[p] = p < np ? b.take(MB * D * 2) : 0;
+        w.c1[p] = p < np ? b.take(MB * D * 2) : 0;
+        w.h[p] = p < np ? b.take(MB * D * 2) : 0;
+        w.qk[p] = p < np ? b.take(MB * 2 * D * 2) : 0;
         w.vt[p] = p < np ? b.take(w.vt_bytes) : 0;
-        w.ao[p] = p < np ? b.take(M2 * D * 2) : 0;
-        w.ffh[p] = p < np ? b.take(M2 * FF * 2) : 0;
+        w.ao[p] = p < np ? b.take(MB * D * 2) : 0;
+        w.ffh[p] = p < np ? b.take(MB * FF * 2) : 0;
     }
     // LN fold buffers only where the fold can run (a superset of ln_fold_state(): that one also knows the branch count of the call):
     // one-pass 16-bit operand modes, the option not 0, and -- in the automatic mode -- enough rows for it to be chosen with both branches
@@ -525,18 +531,19 @@ extern "C" int f5_workspace_bytes(f5_engine* e, int B, int N, int nt, int steps,
 // The plan of f5_sample with the per-row part appended: the staged controls and the time / adaLN tables of every (evaluation, row) pair.
 // The fp32 scratch of the two gated projections needs no space of its own: w.qk[0] (2 M D 16-bit values = M D floats) is dead from the end
 // of a block's attention to the next block's QKV projection, which is where both projections run.
-static Workspace plan_workspace_rows(const f5_engine* e, int B, int N, int nt, int steps, int method) {
-    Workspace w = plan_workspace(e, B, N, nt, steps, method);
+static Workspace plan_workspace_rows(const f5_engine* e, int B, int N, int nt, int steps, int method, int nbr = 2) {
+    Workspace w = plan_workspace(e, B, N, nt, steps, method, nbr);
     const f5_config& c = e->cfg;
     const int nfe = (steps - 1) * nfe_per_step(method);
     const size_t nfe1 = (size_t)(nfe > 0 ? nfe : 1), rows = nfe1 * B;
     Bump b;
     b.off = w.total;
-    w.rscal_words = rows + (size_t)steps * B + B;
+    w.rscal_words = rows + (size_t)steps * B + B + (nbr == 3 ? (size_t)B : 0);
     w.rscal = b.take(w.rscal_words * 4);
     w.rtgrid = w.rscal;
     w.rdt = w.rtgrid + rows * 4;
     w.rcfg = w.rdt + (size_t)steps * B * 4;
+    w.racfg = w.rcfg + (size_t)B * 4;
     w.rsinus = b.take(rows * c.freq_embed_dim * 4);
     w.rth = b.take(rows * c.dim * 4);
     w.rtemb = b.take(rows * c.dim * 4);
@@ -553,6 +560,15 @@ extern "C" int f5_workspace_bytes_rows(f5_engine* e, int B, int N, int nt, int s
     return 0;
 }
 
+// The rows plan with room for the third branch of dual guidance (f5_sample_dual / f5_dit_forward_dual).
+extern "C" int f5_workspace_bytes_dual(f5_engine* e, int B, int N, int nt, int steps, int method, size_t* bytes) {
+    F5_REQUIRE(e && bytes, "null argument");
+    F5_REQUIRE(B >= 1 && N >= 1 && steps >= 1, "bad sizes B=%d N=%d steps=%d", B, N, steps);
+    F5_REQUIRE(method >= F5_EULER && method <= F5_RK4, "Unknown method: %d", method);
+    *bytes = plan_workspace_rows(e, B, N, nt, steps, method, 3).total_rows;
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // launch context
 // ------------------------------------------------------------------------------------------------
@@ -560,10 +576,11 @@ struct Ctx : LaunchView {
     f5_engine* e;
     Workspace w;
     hipStream_t s;
-    int B, N, nt, nb;   // nb = branches evaluated per function evaluation (1 or 2)
+    int B, N, nt, nb;   // nb = branches evaluated per function evaluation (1 or 2; 1 or 3 with dual guidance)
     int npad;
     bool edit = false;  // f5_sample_edit: conditioning frames are chosen by the mask at w.cond_keep instead of n < lens[b]
     bool rows = false;  // f5_sample_rows / f5_dit_forward_rows: time and guidance strength per batch row (w.r*: plan_workspace_rows)
+    bool dual = false;  // f5_sample_dual / f5_dit_forward_dual: the rows route with three branches F, N, T (w.nbr == 3)
     bool use_mask;
 };
 
@@ -685,8 +702,8 @@ static int run_prep(const Ctx& c, int nfe) {
         const float qf = q_premul_factor(e);
         RC(f5_launch_rope_table_g4(t, t + 2 * tn, c.N, cf.dim_head, qf != 0.0f ? qf : 1.0f, s));      // q table | k table, 64 N floats each
     }
-    RC(f5_launch_rowkeep(c.p<int>(w.dur2), c.p<uint8_t>(w.rowkeep), 2 * c.B, c.N, s));
-    for (int p = 0; p < e->np; ++p) RC(K.zero_vt_pad(c.pb(w.vt, p), (size_t)2 * c.B * cf.heads * 64, c.N, c.npad, s));
+    RC(f5_launch_rowkeep(c.p<int>(w.dur2), c.p<uint8_t>(w.rowkeep), w.nbr * c.B, c.N, s));
+    for (int p = 0; p < e->np; ++p) RC(K.zero_vt_pad(c.pb(w.vt, p), (size_t)w.nbr * c.B * cf.heads * 64, c.N, c.npad, s));
 
     // --- text path for both branches (dit.py:196-229, convnext_v2.py:46-54)
     // conv_layers == 0 (dit.py:193-194): the plain embedding, no positional table and no masking; text_mask_padding == 0: no masking
@@ -714,13 +731,16 @@ static int run_prep(const Ctx& c, int nfe) {
         cur ^= 1;
     }
     // --- hoisted part of the input projection: Hc = [cond | text] * Wct^T + b   (dit.py:249-250)
-    if (c.edit)
+    if (c.dual)         // three branches F, N, T; the text path above stays at two
+        RC(K.pack_cond_text_dual(c.p<float>(w.cond), c.p<int>(w.lens), c.edit ? c.p<uint8_t>(w.cond_keep) : nullptr, c.p<float>(w.te[cur]),
+                                 c.pb(w.ct, 0), c.pb(w.ct, 1), c.B, c.N, cf.mel_dim, Dt, s));
+    else if (c.edit)
         RC(K.pack_cond_text_keep(c.p<float>(w.cond), c.p<uint8_t>(w.cond_keep), c.p<float>(w.te[cur]), c.pb(w.ct, 0), c.pb(w.ct, 1),
                                  c.B, c.N, cf.mel_dim, Dt, e->opt.null_keeps_cond, s));
     else
         RC(K.pack_cond_text(c.p<float>(w.cond), c.p<int>(w.lens), c.p<float>(w.te[cur]), c.pb(w.ct, 0), c.pb(w.ct, 1), c.B,
                                 c.N, cf.mel_dim, Dt, e->opt.null_keeps_cond, s));
-    F5GemmArgs gh = gemm_base(c, c.pb(w.ct, 0), c.pb(w.ct, 1), 128 + Dt, e->wct, M2, D, 128 + Dt, c.a<float>(e->bproj));
+    F5GemmArgs gh = gemm_base(c, c.pb(w.ct, 0), c.pb(w.ct, 1), 128 + Dt, e->wct, w.nbr * M1, D, 128 + Dt, c.a<float>(e->bproj));
     gh.out_f32 = c.p<float>(w.hc);
     gh.ldo = D;
     RC(K.gemm(gh, EPI_F32, s));
@@ -1042,12 +1062,14 @@ static int run_sample_body(const Ctx& c, const f5_sample_args* a, int i0 = 0, in
         RC(K.pack_x(traj, c.pb(w.xin, 0), c.pb(w.xin, 1), (int)M1, mel, s));
     }
     const float* pred = c.p<float>(w.vel);
-    const float* nullp = c.nb == 2 ? pred + M1 * mel : nullptr;
+    const float* nullp = c.nb >= 2 ? pred + M1 * mel : nullptr;
+    const float* textp = c.nb == 3 ? pred + 2 * M1 * mel : nullptr;       // dual guidance: the branches are F, N, T
     float* kst = c.p<float>(w.kst);
     float* ytmp = c.p<float>(w.ytmp);
     // per-row controls: every stage reads its row's guidance strength and the step's [B] step sizes
     const float* dt_rows = nullptr;
     auto stage = [&](const F5OdeArgs& o) {
+        if (c.dual) return K.ode_stage_dual(o, textp, c.p<float>(w.racfg), c.p<float>(w.rcfg), dt_rows, c.N, c.B, s);
         return c.rows ? K.ode_stage_rows(o, c.p<float>(w.rcfg), dt_rows, c.N, c.B, s) : K.ode_stage(o, s);
     };
     for (int i = i0; i + 1 < a->steps && i < i1; ++i) {
@@ -1135,17 +1157,19 @@ static int stage_inputs(Ctx& c, const f5_sample_args* a, const float* x_override
     // host scalars -> workspace as kernel arguments (no host buffer outlives this call, no host synchronisation)
     const size_t nfe1 = tnfe.empty() ? 1 : tnfe.size();
     std::vector<uint32_t> words(w.scal_words, 0u);
-    F5_REQUIRE(w.scal_words == (size_t)1 + 3 * c.B + nfe1 + a->steps + 1 + w.lncnt_words && dts.size() <= (size_t)a->steps,
+    const size_t nd = (size_t)(1 + w.nbr) * c.B;     // lens and the durations of every branch
+    F5_REQUIRE(w.scal_words == (size_t)1 + nd + nfe1 + a->steps + 1 + w.lncnt_words && dts.size() <= (size_t)a->steps,
                "internal: scalar staging layout");
     const int fold_state = ln_fold_state(c);
     if (fold_state < 0) return 2;
     words[0] = fold_state >= 1 ? 2u : 0u;            // status word: bit 1 = the LN fold runs in this call, bit 0 is the kernels'
     uint32_t* wd = words.data() + 1;
     memcpy(wd, a->lens, (size_t)c.B * 4);
-    for (int b = 0; b < c.B; ++b) wd[c.B + b] = wd[2 * c.B + b] = (uint32_t)a->durations[b];
-    if (!tnfe.empty()) memcpy(wd + 3 * c.B, tnfe.data(), tnfe.size() * 4);
-    if (!dts.empty()) memcpy(wd + 3 * c.B + nfe1, dts.data(), dts.size() * 4);
-    memcpy(wd + 3 * c.B + nfe1 + a->steps, &a->cfg_strength, 4);
+    for (int br = 1; br <= w.nbr; ++br)
+        for (int b = 0; b < c.B; ++b) wd[br * c.B + b] = (uint32_t)a->durations[b];
+    if (!tnfe.empty()) memcpy(wd + nd, tnfe.data(), tnfe.size() * 4);
+    if (!dts.empty()) memcpy(wd + nd + nfe1, dts.data(), dts.size() * 4);
+    memcpy(wd + nd + nfe1 + a->steps, &a->cfg_strength, 4);
     RC(f5_launch_stage_words(words.data(), words.size(), c.p<uint32_t>(w.scal), s));
     // caller-owned device inputs -> workspace (the captured graph only references the workspace and the arena)
     RC(f5_launch_copy_words(a->text, c.ws + w.text, (size_t)c.B * c.nt, s));
@@ -1209,10 +1233,32 @@ static void ctx_to_rows(Ctx& c, const f5_sample_args* a, const float* cfg_rows, 
         if (!(cfg_rows[b] < 1e-5f)) c.nb = 2;
 }
 
+// ... and to dual guidance: the rows route on the three-branch plan; all three branches as soon as ANY row has either strength
+static void ctx_to_dual(Ctx& c, const f5_sample_args* a, const float* text_rows, const float* audio_rows, int n) {
+    c.rows = c.dual = true;
+    c.w = plan_workspace_rows(c.e, a->B, a->N, a->nt, a->steps, a->method, 3);
+    c.nb = 1;
+    for (int b = 0; b < n; ++b)
+        if (!(text_rows[b] < 1e-5f) || !(audio_rows[b] < 1e-5f)) c.nb = 3;
+}
+// what dual guidance refuses on top of the per-row route, before any launch
+static int check_dual_route(const f5_engine* e, const char* what) {
+    RC(check_rows_route(e, what));
+    F5_REQUIRE(!e->opt.null_keeps_cond, "%s: engine option null_keeps_cond = 1 gives the second branch the meaning (audio kept, text dropped); "
+               "dual guidance needs it to be (both dropped)", what);
+    return 0;
+}
+
 // f5_sample (edit = false), f5_sample_edit (the mask replaces n < lens[b] in the hoisted input packing and the final splice) and
-// f5_sample_rows (rc != null: time grid and guidance strength per batch row)
+// f5_sample_rows (rc != null: time grid and guidance strength per batch row) and f5_sample_dual (rc->audio_rows != null as well)
+struct RowCtl {
+    const float* t_rows;
+    const float* cfg_rows;      // the text strength of dual guidance
+    const float* audio_rows;    // null = f5_sample_rows
+    const char* what;           // the entry point, for messages
+};
 static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* cond_keep, bool edit, void* stream,
-                       const f5_row_controls* rc = nullptr) {
+                       const RowCtl* rc = nullptr) {
     F5_REQUIRE(!edit || cond_keep, "f5_sample_edit: cond_keep is null");
     RC(check_args(e, a));
     F5_REQUIRE(a->y0 && (a->t || rc) && a->out, "null pointer in f5_sample_args (y0/t/out)");
@@ -1220,13 +1266,18 @@ static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* con
     Ctx c = make_ctx(e, a, s);
     c.edit = edit;
     if (rc) {
-        RC(check_rows_route(e, "f5_sample_rows"));
+        const bool dual = rc->audio_rows != nullptr;
+        RC(dual ? check_dual_route(e, rc->what) : check_rows_route(e, rc->what));
         for (size_t i = 0; i < (size_t)a->B * a->steps; ++i)
-            F5_REQUIRE(std::isfinite(rc->t_rows[i]), "f5_sample_rows: t_rows[%zu][%zu] is not finite", i / a->steps, i % a->steps);
-        for (int b = 0; b < a->B; ++b) F5_REQUIRE(std::isfinite(rc->cfg_rows[b]), "f5_sample_rows: cfg_rows[%d] is not finite", b);
-        ctx_to_rows(c, a, rc->cfg_rows, a->B);
-        F5_REQUIRE(a->workspace_bytes >= c.w.total_rows, "f5_sample_rows: workspace too small: %zu < %zu (f5_workspace_bytes_rows)",
-                   a->workspace_bytes, c.w.total_rows);
+            F5_REQUIRE(std::isfinite(rc->t_rows[i]), "%s: t_rows[%zu][%zu] is not finite", rc->what, i / a->steps, i % a->steps);
+        for (int b = 0; b < a->B; ++b)
+            F5_REQUIRE(std::isfinite(rc->cfg_rows[b]), "%s: %s[%d] is not finite", rc->what, dual ? "text_cfg_rows" : "cfg_rows", b);
+        for (int b = 0; b < a->B && dual; ++b)
+            F5_REQUIRE(std::isfinite(rc->audio_rows[b]), "%s: audio_cfg_rows[%d] is not finite", rc->what, b);
+        if (dual) ctx_to_dual(c, a, rc->cfg_rows, rc->audio_rows, a->B);
+        else ctx_to_rows(c, a, rc->cfg_rows, a->B);
+        F5_REQUIRE(a->workspace_bytes >= c.w.total_rows, "%s: workspace too small: %zu < %zu (%s)", rc->what, a->workspace_bytes,
+                   c.w.total_rows, dual ? "f5_workspace_bytes_dual" : "f5_workspace_bytes_rows");
         if (ln_fold_state(c) < 0) return 2;
     }
     F5_REQUIRE(a->workspace_bytes >= c.w.total, "workspace too small: %zu < %zu", a->workspace_bytes, c.w.total);
@@ -1252,6 +1303,7 @@ static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* con
             }
         }
         memcpy(rd + (size_t)a->steps * c.B, rc->cfg_rows, (size_t)c.B * 4);
+        if (c.dual) memcpy(rd + (size_t)a->steps * c.B + c.B, rc->audio_rows, (size_t)c.B * 4);
         RC(stage_inputs(c, a, nullptr, tnfe, dts));
         RC(f5_launch_stage_words(words.data(), words.size(), c.p<uint32_t>(c.w.rscal), s));
     } else {
@@ -1264,8 +1316,8 @@ static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* con
     // hipGraph cache.  The key is everything a captured node depends on BY VALUE: shapes, solver, branch count, masking and the
     // workspace address.  Per-call scalars (cfg strength, time grid, dt) are read from workspace memory staged above.
     char shape_key[192];
-    snprintf(shape_key, sizeof(shape_key), "B%d N%d nt%d st%d m%d nb%d mask%d edit%d rows%d ke%d ws%p opt", c.B, c.N, c.nt, a->steps,
-             a->method, c.nb, (int)c.use_mask, (int)c.edit, (int)c.rows, g_knob_epoch, a->workspace);
+    snprintf(shape_key, sizeof(shape_key), "B%d N%d nt%d st%d m%d nb%d mask%d edit%d rows%d dual%d ke%d ws%p opt", c.B, c.N, c.nt, a->steps,
+             a->method, c.nb, (int)c.use_mask, (int)c.edit, (int)c.rows, (int)c.dual, g_knob_epoch, a->workspace);
     std::string key(shape_key);
     for (const OptDesc& o : k_options) key += " " + std::to_string(e->opt.*o.member);
     const bool graph_on = a->use_graph == F5_GRAPH_ON, graph_auto = a->use_graph == F5_GRAPH_AUTO;
@@ -1307,7 +1359,16 @@ extern "C" int f5_sample_rows(f5_engine* e, const f5_sample_args* a, const f5_ro
     F5_REQUIRE(rc != nullptr, "f5_sample_rows: controls is null");
     F5_REQUIRE(rc->t_rows != nullptr, "f5_sample_rows: controls.t_rows is null");
     F5_REQUIRE(rc->cfg_rows != nullptr, "f5_sample_rows: controls.cfg_rows is null");
-    return sample_impl(e, a, rc->cond_keep_dev, rc->cond_keep_dev != nullptr, stream, rc);
+    const RowCtl ctl = {rc->t_rows, rc->cfg_rows, nullptr, "f5_sample_rows"};
+    return sample_impl(e, a, rc->cond_keep_dev, rc->cond_keep_dev != nullptr, stream, &ctl);
+}
+extern "C" int f5_sample_dual(f5_engine* e, const f5_sample_args* a, const f5_dual_controls* dc, void* stream) {
+    F5_REQUIRE(dc != nullptr, "f5_sample_dual: controls is null");
+    F5_REQUIRE(dc->t_rows != nullptr, "f5_sample_dual: controls.t_rows is null");
+    F5_REQUIRE(dc->text_cfg_rows != nullptr, "f5_sample_dual: controls.text_cfg_rows is null");
+    F5_REQUIRE(dc->audio_cfg_rows != nullptr, "f5_sample_dual: controls.audio_cfg_rows is null");
+    const RowCtl ctl = {dc->t_rows, dc->text_cfg_rows, dc->audio_cfg_rows, "f5_sample_dual"};
+    return sample_impl(e, a, dc->cond_keep_dev, dc->cond_keep_dev != nullptr, stream, &ctl);
 }
 
 // Status word of the last f5_sample / f5_dit_forward that used this workspace (its FIRST 32-bit word, for every shape and solver):
@@ -1393,6 +1454,44 @@ extern "C" int f5_dit_forward_rows(f5_engine* e, const f5_sample_args* a, const 
     RC(run_dit(c, 0));
     RC(f5_launch_copy_words(c.ws + c.w.vel, pred, M1 * mel, s));
     if (null_pred && c.nb == 2) RC(f5_launch_copy_words(c.ws + c.w.vel + M1 * mel * 4, null_pred, M1 * mel, s));
+    return 0;
+}
+
+// One evaluation of the three branches of dual guidance, one time per batch row: pred = F (audio and text kept), null_pred = N (both
+// dropped), text_pred = T (audio dropped, text kept).  All three always run (args->cfg_strength is not read).  Workspace:
+// f5_workspace_bytes_dual with steps = 2, method = F5_EULER.
+extern "C" int f5_dit_forward_dual(f5_engine* e, const f5_sample_args* a, const float* x, const float* t_rows_host, float* pred,
+                                   float* null_pred, float* text_pred, void* stream) {
+    RC(check_args(e, a));
+    F5_REQUIRE(x && pred, "null pointer");
+    F5_REQUIRE(t_rows_host != nullptr, "f5_dit_forward_dual: t_rows is null");
+    RC(check_dual_route(e, "f5_dit_forward_dual"));
+    for (int b = 0; b < a->B; ++b) F5_REQUIRE(std::isfinite(t_rows_host[b]), "f5_dit_forward_dual: t_rows[%d] is not finite", b);
+    hipStream_t s = (hipStream_t)stream;
+    f5_sample_args a2 = *a;
+    a2.steps = 2;
+    a2.method = F5_EULER;
+    Ctx c = make_ctx(e, &a2, s);
+    const float on = 1.0f;
+    ctx_to_dual(c, &a2, &on, &on, 1);
+    F5_REQUIRE(a->workspace_bytes >= c.w.total_rows, "f5_dit_forward_dual: workspace too small: %zu < %zu (f5_workspace_bytes_dual)",
+               a->workspace_bytes, c.w.total_rows);
+    if (ln_fold_state(c) < 0) return 2;
+    const int mel = e->cfg.mel_dim;
+    const size_t M1 = (size_t)c.B * c.N;
+    SatScope sat(e->prec == F5_PREC_F16 && e->opt.sat_check, c.p<int>(c.w.status));
+    std::vector<float> tnfe(1, t_rows_host[0]), dts(1, 0.0f);
+    RC(stage_inputs(c, &a2, x, tnfe, dts));
+    std::vector<uint32_t> words(c.w.rscal_words, 0u);       // [tgrid B | dt 2 B | cfg B | audio B]: only the times are read by a forward
+    memcpy(words.data(), t_rows_host, (size_t)c.B * 4);
+    RC(f5_launch_stage_words(words.data(), words.size(), c.p<uint32_t>(c.w.rscal), s));
+    const Ops& K = c.ops;
+    RC(run_prep(c, 1));
+    RC(K.pack_x(c.p<float>(c.w.traj), c.pb(c.w.xin, 0), c.pb(c.w.xin, 1), (int)M1, mel, s));
+    RC(run_dit(c, 0));
+    float* outs[3] = {pred, null_pred, text_pred};          // the branch order of the engine: F, N, T
+    for (int br = 0; br < 3; ++br)
+        if (outs[br]) RC(f5_launch_copy_words(c.ws + c.w.vel + (size_t)br * M1 * mel * 4, outs[br], M1 * mel, s));
     return 0;
 }
 
@@ -1973,6 +2072,42 @@ extern "C" int f5_op_ode_stage_rows(const float* pred, const float* null_pred, c
     F5_REQUIRE(pred != nullptr && base != nullptr && out != nullptr, "ode_stage_rows: null pred / base / out");
     F5_REQUIRE(mode == 0 || (mode == 1 && k1 != nullptr && k2 != nullptr && k3 != nullptr), "ode_stage_rows: mode 1 needs k1, k2 and k3");
     return g_ops.ode_stage_rows(o, cfg_rows, dt_rows, rows_per_vec, nvec, (hipStream_t)stream);
+}
+// the stage kernel of dual guidance (rowops.hpp f5_launch_ode_stage_dual, which refuses what it refuses)
+extern "C" int f5_op_ode_stage_dual(const float* pred, const float* text_pred, const float* null_pred, const float* audio_cfg_rows,
+                                    const float* text_cfg_rows, const float* base, const float* dt_rows, int rows_per_vec, int nvec, float coef,
+                                    float divisor, int mode, float* kstore, const float* k1, const float* k2, const float* k3, float* out,
+                                    void* xin_hi, void* xin_lo, int rows, int mel_dim, void* stream) {
+    F5OdeArgs o;
+    memset(&o, 0, sizeof(o));
+    o.pred = pred;
+    o.null_pred = null_pred;
+    o.base = base;
+    o.coef = coef;
+    o.divisor = divisor;
+    o.mode = mode;
+    o.kstore = kstore;
+    o.k1 = k1;
+    o.k2 = k2;
+    o.k3 = k3;
+    o.out = out;
+    o.xin_hi = (op16_t*)xin_hi;
+    o.xin_lo = (op16_t*)xin_lo;
+    o.rows = rows;
+    o.mel_dim = mel_dim;
+    return g_ops.ode_stage_dual(o, text_pred, audio_cfg_rows, text_cfg_rows, dt_rows, rows_per_vec, nvec, (hipStream_t)stream);
+}
+extern "C" int f5_op_pack_cond_text_dual(const float* cond, const int32_t* lens, const float* text_emb, void* out_hi, void* out_lo, int B,
+                                         int seq_len, int mel_dim, int dt, void* stream) {
+    F5_REQUIRE(lens != nullptr, "pack_cond_text_dual: lens is null");
+    return g_ops.pack_cond_text_dual(cond, lens, nullptr, text_emb, (op16_t*)out_hi, (op16_t*)out_lo, B, seq_len, mel_dim, dt,
+                                     (hipStream_t)stream);
+}
+extern "C" int f5_op_pack_cond_text_dual_keep(const float* cond, const uint8_t* keep, const float* text_emb, void* out_hi, void* out_lo, int B,
+                                              int seq_len, int mel_dim, int dt, void* stream) {
+    F5_REQUIRE(keep != nullptr, "pack_cond_text_dual_keep: keep is null");
+    return g_ops.pack_cond_text_dual(cond, nullptr, keep, text_emb, (op16_t*)out_hi, (op16_t*)out_lo, B, seq_len, mel_dim, dt,
+                                     (hipStream_t)stream);
 }
 // residual update + LN-modulate with per-row vectors (rowops.hpp f5_launch_resid_gate_ln_rows), eps 1e-6
 extern "C" int f5_op_resid_gate_ln_rows(const float* y, float* x, const float* gate, const uint8_t* rowkeep, const float* ln_scale,

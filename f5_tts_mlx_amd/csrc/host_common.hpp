@@ -105,6 +105,12 @@ struct Ops {
         return h ? f5hf::f5_launch_ode_stage_rows(reinterpret_cast<const f5hf::F5OdeArgs&>(a), cfg_rows, dt_rows, rows_per_vec, nvec, s)
                  : f5bf::f5_launch_ode_stage_rows(a, cfg_rows, dt_rows, rows_per_vec, nvec, s);
     }
+    int ode_stage_dual(const F5OdeArgs& a, const float* text_pred, const float* audio_rows, const float* text_rows, const float* dt_rows,
+                       int rows_per_vec, int nvec, hipStream_t s) const {
+        return h ? f5hf::f5_launch_ode_stage_dual(reinterpret_cast<const f5hf::F5OdeArgs&>(a), text_pred, audio_rows, text_rows, dt_rows,
+                                                  rows_per_vec, nvec, s)
+                 : f5bf::f5_launch_ode_stage_dual(a, text_pred, audio_rows, text_rows, dt_rows, rows_per_vec, nvec, s);
+    }
     int resid_gate_ln_rows(const float* y, float* x, const float* gate, const uint8_t* rowkeep, const float* ln_scale, const float* ln_shift,
                            op16_t* hi, op16_t* lo, int rows, int dim, int rows_per_vec, int nvec, size_t vec_stride, float eps,
                            hipStream_t s) const {
@@ -142,6 +148,11 @@ struct Ops {
                             int mel_dim, int dt, int null_keeps_cond, hipStream_t s) const {
         return h ? f5hf::f5_launch_pack_cond_text_keep(cond, keep, text_emb, H(hi), H(lo), B, seq_len, mel_dim, dt, null_keeps_cond, s)
                  : f5bf::f5_launch_pack_cond_text_keep(cond, keep, text_emb, hi, lo, B, seq_len, mel_dim, dt, null_keeps_cond, s);
+    }
+    int pack_cond_text_dual(const float* cond, const int* lens, const uint8_t* keep, const float* text_emb, op16_t* hi, op16_t* lo, int B,
+                            int seq_len, int mel_dim, int dt, hipStream_t s) const {
+        return h ? f5hf::f5_launch_pack_cond_text_dual(cond, lens, keep, text_emb, H(hi), H(lo), B, seq_len, mel_dim, dt, s)
+                 : f5bf::f5_launch_pack_cond_text_dual(cond, lens, keep, text_emb, hi, lo, B, seq_len, mel_dim, dt, s);
     }
     int pack_x(const float* y, op16_t* hi, op16_t* lo, int rows, int mel_dim, hipStream_t s) const {
         return h ? f5hf::f5_launch_pack_x(y, H(hi), H(lo), rows, mel_dim, s) : f5bf::f5_launch_pack_x(y, hi, lo, rows, mel_dim, s);

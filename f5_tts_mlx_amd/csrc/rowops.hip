@@ -525,8 +525,10 @@ int f5_launch_text_embed(const int* text, int nt, const float* table, const floa
 // branch 0: cond masked by n < lens[b] (step_cond, cfm.py:331); branch 1: cond dropped (dit.py:249) unless null_keeps_cond
 // KEEP: the prefix test is replaced by a per-frame mask, keep[b][n] != 0 (speech editing: the infilling mask of cfm.py:198-224 at
 // sampling time).  The value is SELECTED by the test: a frame that is not kept is never loaded.
+// NB = 3 (dual guidance): a third branch (audio dropped, text kept) behind the two above, so that [F | N | T] starts with exactly what
+// NB = 2 writes: zero cond columns and BRANCH 0's text columns (the text path does not depend on the audio; text_emb stays [2][B][N][dt]).
 // =================================================================================================
-template <bool KEEP>
+template <bool KEEP, int NB>
 __global__ __launch_bounds__(256) void pack_cond_text_kernel(const float* __restrict__ cond, const int* __restrict__ lens,
                                                              const uint8_t* __restrict__ keep,
                                                              const float* __restrict__ text_emb, op16_t* __restrict__ out_hi,
@@ -536,14 +538,15 @@ __global__ __launch_bounds__(256) void pack_cond_text_kernel(const float* __rest
     const int ld = 128 + dt;
     const size_t orow = (((size_t)br * B + b) * seq_len + n) * ld;
     // null_keeps_cond: the second branch is (drop_audio_cond = False, drop_text = True) instead of (True, True), dit.py:245-247 / 209-210
-    const bool use_cond = (br == 0 || null_keeps_cond) && (KEEP ? keep[(size_t)b * seq_len + n] != 0 : n < lens[b]);
+    const bool use_cond = (br == 0 || (br == 1 && null_keeps_cond)) && (KEEP ? keep[(size_t)b * seq_len + n] != 0 : n < lens[b]);
+    const int tbr = (NB == 3 && br == 2) ? 0 : br;      // the text branch this operand branch reads
     f5_sat_t trk;
     for (int c = threadIdx.x; c < ld; c += 256) {
         float v = 0.0f;
         if (c < 128) {
             if (use_cond && c < mel_dim) v = cond[((size_t)b * seq_len + n) * mel_dim + c];
         } else {
-            v = text_emb[(((size_t)br * B + b) * seq_len + n) * dt + (c - 128)];
+            v = text_emb[(((size_t)tbr * B + b) * seq_len + n) * dt + (c - 128)];
         }
         op16_t h, l;
         f5_split(v, h, l, trk);
@@ -556,7 +559,7 @@ __global__ __launch_bounds__(256) void pack_cond_text_kernel(const float* __rest
 int f5_launch_pack_cond_text(const float* cond, const int* lens, const float* text_emb, op16_t* out_hi, op16_t* out_lo,
                              int B, int seq_len, int mel_dim, int dt, int null_keeps_cond, hipStream_t s) {
     F5_REQUIRE(mel_dim <= 128, "pack_cond_text: mel_dim must be <= 128");
-    hipLaunchKernelGGL(pack_cond_text_kernel<false>, dim3(seq_len, B, 2), dim3(256), 0, s, cond, lens, (const uint8_t*)nullptr, text_emb,
+    hipLaunchKernelGGL((pack_cond_text_kernel<false, 2>), dim3(seq_len, B, 2), dim3(256), 0, s, cond, lens, (const uint8_t*)nullptr, text_emb,
                        out_hi, out_lo, B, seq_len, mel_dim, dt, null_keeps_cond, f5_sat_flag_host);
     F5_LAUNCH_CHECK();
     return 0;
@@ -565,8 +568,24 @@ int f5_launch_pack_cond_text_keep(const float* cond, const uint8_t* keep, const 
                                   int B, int seq_len, int mel_dim, int dt, int null_keeps_cond, hipStream_t s) {
     F5_REQUIRE(mel_dim <= 128, "pack_cond_text_keep: mel_dim must be <= 128");
     F5_REQUIRE(keep, "pack_cond_text_keep: keep is null");
-    hipLaunchKernelGGL(pack_cond_text_kernel<true>, dim3(seq_len, B, 2), dim3(256), 0, s, cond, (const int*)nullptr, keep, text_emb,
+    hipLaunchKernelGGL((pack_cond_text_kernel<true, 2>), dim3(seq_len, B, 2), dim3(256), 0, s, cond, (const int*)nullptr, keep, text_emb,
                        out_hi, out_lo, B, seq_len, mel_dim, dt, null_keeps_cond, f5_sat_flag_host);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+// the three-branch operand of dual guidance, [3][B][seq_len][128 + dt] in the order F, N, T; keep == null: the prefix test n < lens[b]
+int f5_launch_pack_cond_text_dual(const float* cond, const int* lens, const uint8_t* keep, const float* text_emb, op16_t* out_hi,
+                                  op16_t* out_lo, int B, int seq_len, int mel_dim, int dt, hipStream_t s) {
+    F5_REQUIRE(mel_dim <= 128, "pack_cond_text_dual: mel_dim must be <= 128");
+    F5_REQUIRE(cond && (lens || keep) && text_emb && out_hi, "pack_cond_text_dual: null pointer");
+    F5_REQUIRE(B >= 1 && seq_len >= 1 && mel_dim >= 1 && dt >= 0, "pack_cond_text_dual: bad sizes B=%d seq_len=%d mel_dim=%d dt=%d", B, seq_len,
+               mel_dim, dt);
+    if (keep)
+        hipLaunchKernelGGL((pack_cond_text_kernel<true, 3>), dim3(seq_len, B, 3), dim3(256), 0, s, cond, (const int*)nullptr, keep, text_emb,
+                           out_hi, out_lo, B, seq_len, mel_dim, dt, 0, f5_sat_flag_host);
+    else
+        hipLaunchKernelGGL((pack_cond_text_kernel<false, 3>), dim3(seq_len, B, 3), dim3(256), 0, s, cond, lens, (const uint8_t*)nullptr,
+                           text_emb, out_hi, out_lo, B, seq_len, mel_dim, dt, 0, f5_sat_flag_host);
     F5_LAUNCH_CHECK();
     return 0;
 }
@@ -753,9 +772,15 @@ int f5_launch_pack_x(const float* y, op16_t* out_hi, op16_t* out_lo, int rows, i
 // One element of a stage: shared by the kernel with one (cfg, dt) for the call and the one that reads them per row, so that both do
 // the same arithmetic.  ROWS: row r uses cfg_rows[v] / dt_rows[v], v = (r / rows_per_vec) % nvec, and a row whose cfg is below 1e-5 takes
 // k = pred by selection (cfm.py:352): its null_pred is not loaded.
-template <bool ROWS>
+// ROUTE 2 (dual guidance): three predictions F = pred (audio and text kept), T = text_pred (audio dropped), N = null_pred (both dropped)
+// and two strengths per row, a = audio_rows[v] (F against T) and c = cfg_rows[v] (T against N):
+//     k = (F + (F - T) a) + (T - N) c
+// T is loaded when either strength is >= 1e-5, N only when c >= 1e-5; a row with both below takes k = F.  All by selection.
+enum { ODE_SCALAR = 0, ODE_ROWS = 1, ODE_DUAL = 2 };
+template <int ROUTE>
 __device__ __forceinline__ void f5_ode_stage_elem(const F5OdeArgs& p, const float* __restrict__ cfg_rows, const float* __restrict__ dt_rows,
-                                                  int rows_per_vec, int nvec) {
+                                                  int rows_per_vec, int nvec, const float* __restrict__ text_pred = nullptr,
+                                                  const float* __restrict__ audio_rows = nullptr) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;   // over rows * 128 (padded columns)
     if (i >= (size_t)p.rows * 128) return;
     const size_t row = i >> 7;
@@ -766,7 +791,17 @@ __device__ __forceinline__ void f5_ode_stage_elem(const F5OdeArgs& p, const floa
         const float pr = p.pred[idx];
         float k = pr;
         float dt;
-        if (ROWS) {
+        if (ROUTE == ODE_DUAL) {
+            const int v = (int)((row / (size_t)rows_per_vec) % (size_t)nvec);
+            const float ca = audio_rows[v], ct = cfg_rows[v];
+            dt = dt_rows[v];
+            const bool text_on = !(ct < 1e-5f);
+            if (text_pred && (text_on || !(ca < 1e-5f))) {
+                const float tp = text_pred[idx];
+                k = pr + (pr - tp) * ca;
+                if (p.null_pred && text_on) k = k + (tp - p.null_pred[idx]) * ct;
+            }
+        } else if (ROUTE == ODE_ROWS) {
             const int v = (int)((row / (size_t)rows_per_vec) % (size_t)nvec);
             const float cfg = cfg_rows[v];
             dt = dt_rows[v];
@@ -791,16 +826,40 @@ __device__ __forceinline__ void f5_ode_stage_elem(const F5OdeArgs& p, const floa
         f5_sat_commit(trk, p.sat_flag);
     }
 }
-__global__ __launch_bounds__(256) void ode_stage_kernel(F5OdeArgs p) { f5_ode_stage_elem<false>(p, nullptr, nullptr, 1, 1); }
+__global__ __launch_bounds__(256) void ode_stage_kernel(F5OdeArgs p) { f5_ode_stage_elem<ODE_SCALAR>(p, nullptr, nullptr, 1, 1); }
 __global__ __launch_bounds__(256) void ode_stage_rows_kernel(F5OdeArgs p, const float* __restrict__ cfg_rows,
                                                              const float* __restrict__ dt_rows, int rows_per_vec, int nvec) {
-    f5_ode_stage_elem<true>(p, cfg_rows, dt_rows, rows_per_vec, nvec);
+    f5_ode_stage_elem<ODE_ROWS>(p, cfg_rows, dt_rows, rows_per_vec, nvec);
+}
+__global__ __launch_bounds__(256) void ode_stage_dual_kernel(F5OdeArgs p, const float* __restrict__ text_pred,
+                                                             const float* __restrict__ audio_rows, const float* __restrict__ text_rows,
+                                                             const float* __restrict__ dt_rows, int rows_per_vec, int nvec) {
+    f5_ode_stage_elem<ODE_DUAL>(p, text_rows, dt_rows, rows_per_vec, nvec, text_pred, audio_rows);
 }
 int f5_launch_ode_stage(const F5OdeArgs& a, hipStream_t s) {
     F5_REQUIRE(a.mel_dim <= 128, "ode_stage: mel_dim must be <= 128");
     F5OdeArgs ab = a;
     if (ab.sat_flag == nullptr) ab.sat_flag = f5_sat_flag_host;
     hipLaunchKernelGGL(ode_stage_kernel, dim3(f5_cdiv((long)a.rows * 128, 256)), dim3(256), 0, s, ab);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+int f5_launch_ode_stage_dual(const F5OdeArgs& a, const float* text_pred, const float* audio_cfg_rows, const float* text_cfg_rows,
+                             const float* dt_rows, int rows_per_vec, int nvec, hipStream_t s) {
+    F5_REQUIRE(a.pred != nullptr, "ode_stage_dual: pred is null");
+    F5_REQUIRE(a.base != nullptr, "ode_stage_dual: base is null");
+    F5_REQUIRE(a.out != nullptr, "ode_stage_dual: out is null");
+    F5_REQUIRE(audio_cfg_rows != nullptr && text_cfg_rows != nullptr, "ode_stage_dual: null audio_cfg_rows / text_cfg_rows");
+    F5_REQUIRE(dt_rows != nullptr, "ode_stage_dual: dt_rows is null");
+    F5_REQUIRE(rows_per_vec >= 1, "ode_stage_dual: rows_per_vec must be >= 1 (got %d)", rows_per_vec);
+    F5_REQUIRE(nvec >= 1, "ode_stage_dual: nvec must be >= 1 (got %d)", nvec);
+    F5_REQUIRE(a.mel_dim <= 128, "ode_stage_dual: mel_dim must be <= 128");
+    F5_REQUIRE(a.rows >= 1 && a.mel_dim >= 1, "ode_stage_dual: no rows / columns (got %d, %d)", a.rows, a.mel_dim);
+    F5_REQUIRE(a.mode == 0 || (a.mode == 1 && a.k1 != nullptr && a.k2 != nullptr && a.k3 != nullptr), "ode_stage_dual: mode 1 needs k1, k2 and k3");
+    F5OdeArgs ab = a;
+    if (ab.sat_flag == nullptr) ab.sat_flag = f5_sat_flag_host;
+    hipLaunchKernelGGL(ode_stage_dual_kernel, dim3(f5_cdiv((long)a.rows * 128, 256)), dim3(256), 0, s, ab, text_pred, audio_cfg_rows,
+                       text_cfg_rows, dt_rows, rows_per_vec, nvec);
     F5_LAUNCH_CHECK();
     return 0;
 }

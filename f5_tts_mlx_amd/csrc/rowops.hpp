@@ -55,6 +55,10 @@ int f5_launch_pack_cond_text(const float* cond, const int* lens, const float* te
 // the same with the prefix test n < lens[b] replaced by a per-frame mask keep (dev uint8 [B][seq_len], non-zero = conditioning frame)
 int f5_launch_pack_cond_text_keep(const float* cond, const uint8_t* keep, const float* text_emb, op16_t* out_hi, op16_t* out_lo,
                                   int B, int seq_len, int mel_dim, int dt, int null_keeps_cond, hipStream_t s);
+// dual guidance: three branches [3][B][seq_len][128 + dt] in the order F (cond, text), N (neither), T (text alone: zero cond columns and
+// branch 0's text columns; text_emb stays [2][B][seq_len][dt]); keep == null: the prefix test n < lens[b], else the per-frame mask
+int f5_launch_pack_cond_text_dual(const float* cond, const int* lens, const uint8_t* keep, const float* text_emb, op16_t* out_hi,
+                                  op16_t* out_lo, int B, int seq_len, int mel_dim, int dt, hipStream_t s);
 
 // sinusoidal time embedding (dit.py:61-67)
 int f5_launch_time_sinus(const float* t, float* out, int n, int dim, hipStream_t s);
@@ -99,6 +103,11 @@ int f5_launch_ode_stage(const F5OdeArgs& a, hipStream_t s);
 // the same with guidance scale and step size PER ROW: row r uses cfg_rows[v] and dt_rows[v] (dev fp32 [nvec] each), v = (r / rows_per_vec)
 // % nvec, in place of cfg / cfg_ptr / dt_ptr; a row with cfg_rows[v] < 1e-5 takes k = pred by selection even when null_pred is given
 int f5_launch_ode_stage_rows(const F5OdeArgs& a, const float* cfg_rows, const float* dt_rows, int rows_per_vec, int nvec, hipStream_t s);
+// dual guidance: F = a.pred, T = text_pred, N = a.null_pred (either of the last two may be null) and two strengths per row,
+// k = (F + (F - T) audio[v]) + (T - N) text[v]; T is loaded when either strength is >= 1e-5, N only when text[v] >= 1e-5, a row with both
+// below takes k = F.  Everything behind k is f5_launch_ode_stage_rows.
+int f5_launch_ode_stage_dual(const F5OdeArgs& a, const float* text_pred, const float* audio_cfg_rows, const float* text_cfg_rows,
+                             const float* dt_rows, int rows_per_vec, int nvec, hipStream_t s);
 
 // out = where(n < lens[b], cond, y)  (cfm.py:395-397)
 int f5_launch_splice(const float* cond, const float* y, const int* lens, float* out, int B, int seq_len, int mel_dim,

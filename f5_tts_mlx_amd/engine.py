@@ -77,14 +77,26 @@ class F5RowControls(C.Structure):
     _fields_ = [("t_rows", C.c_void_p), ("cfg_rows", C.c_void_p), ("cond_keep_dev", C.c_void_p)]
 
 
-def row_controls(t, cfg_strength, B: int):
+class F5DualControls(C.Structure):
+    _fields_ = [("t_rows", C.c_void_p), ("text_cfg_rows", C.c_void_p), ("audio_cfg_rows", C.c_void_p), ("cond_keep_dev", C.c_void_p)]
+
+
+def row_controls(t, cfg_strength, B: int, audio_cfg_strength=None):
     """Per-row sampling controls of a sample() call (f5_sample_rows): `t` may be a (steps,) grid or one grid per row (B, steps),
     `cfg_strength` a float or a length-B sequence.  Either one being per-row selects the rows route and the other is broadcast.
-    -> (steps, None) for an all-scalar call, else (steps, (t_rows (B, steps) fp32, cfg_rows (B,) fp32)), both C-contiguous."""
+    -> (steps, None) for an all-scalar call, else (steps, (t_rows (B, steps) fp32, cfg_rows (B,) fp32)), both C-contiguous.
+    audio_cfg_strength (a float or a length-B sequence; docs/dual_guidance.md): dual guidance, f5_sample_dual -- always the per-row form,
+    whatever the values are, with a third entry audio_rows (B,) fp32; `cfg_strength` is then the text strength."""
     t = np.asarray(t, dtype=np.float32)
     cfg_seq = np.ndim(cfg_strength) != 0
     if t.ndim not in (1, 2):
         raise ValueError(f"t must be (steps,) or (B, steps), got shape {t.shape}")
+    if audio_cfg_strength is not None:
+        audio = np.asarray(audio_cfg_strength, dtype=np.float32)
+        if audio.ndim != 0 and audio.shape != (B,):
+            raise ValueError(f"per-row audio_cfg_strength: expected {B} values, got shape {audio.shape}")
+        steps, rows = row_controls(t if t.ndim == 2 else np.broadcast_to(t, (B, t.shape[0])), cfg_strength, B)
+        return steps, rows + (np.ascontiguousarray(np.broadcast_to(audio, (B,)), dtype=np.float32),)
     if t.ndim == 1 and not cfg_seq:
         return int(t.shape[0]), None
     if t.ndim == 2 and t.shape[0] != B:
@@ -102,6 +114,18 @@ def _rows_slice(t, cfg_strength, b0: int, b1: int):
     """The controls of batch rows [b0, b1) of a sample() call: per-row forms are sliced, shared ones pass through."""
     t = np.asarray(t, dtype=np.float32)
     return (t[b0:b1] if t.ndim == 2 else t), (cfg_strength if np.ndim(cfg_strength) == 0 else list(cfg_strength)[b0:b1])
+
+
+def _audio_slice(audio_cfg_strength, b0: int, b1: int):
+    """The audio strengths of batch rows [b0, b1): None and a scalar pass through."""
+    if audio_cfg_strength is None or np.ndim(audio_cfg_strength) == 0:
+        return audio_cfg_strength
+    return list(np.asarray(audio_cfg_strength, dtype=np.float32)[b0:b1])
+
+
+def _plan_of(rows):
+    """The workspace plan a call's controls need (Engine.workspace `rows`): False, True (per-row) or "dual"."""
+    return False if rows is None else ("dual" if len(rows) == 3 else True)
 
 
 def library_path() -> Path:
@@ -137,6 +161,13 @@ def load_library() -> C.CDLL:
     # a call of the route on it raises AttributeError -- never a fall-back
     for name, types in (("f5_sample_rows", [C.c_void_p] * 4), ("f5_dit_forward_rows", [C.c_void_p] * 7),
                         ("f5_workspace_bytes_rows", [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+                        # dual guidance (docs/dual_guidance.md)
+                        ("f5_sample_dual", [C.c_void_p] * 4), ("f5_dit_forward_dual", [C.c_void_p] * 8),
+                        ("f5_workspace_bytes_dual", [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+                        ("f5_op_ode_stage_dual", [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 7
+                         + [C.c_int, C.c_int, C.c_void_p]),
+                        ("f5_op_pack_cond_text_dual", [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
+                        ("f5_op_pack_cond_text_dual_keep", [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
                         ("f5_op_resid_gate_ln_rows", [C.c_void_p] * 8 + [C.c_int] * 4 + [C.c_size_t, C.c_void_p]),
                         ("f5_op_ode_stage_rows", [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 7
                          + [C.c_int, C.c_int, C.c_void_p]),
@@ -401,12 +432,17 @@ class Engine:
         self.finalize()
 
     # ---- workspace -------------------------------------------------------------------------
-    def workspace(self, B: int, N: int, nt: int, steps: int, method: str, rows: bool = False) -> torch.Tensor:
-        """The engine's workspace, grown on demand; rows: the larger plan of the per-row route (f5_workspace_bytes_rows)."""
+    def workspace(self, B: int, N: int, nt: int, steps: int, method: str, rows=False) -> torch.Tensor:
+        """The engine's workspace, grown on demand; rows: the larger plan of the per-row route (f5_workspace_bytes_rows), "dual": the
+        three-branch plan of dual guidance (f5_workspace_bytes_dual)."""
         if method not in METHODS:
             raise ValueError(f"Unknown method: {method}")
         nbytes = C.c_size_t()
-        if rows:
+        if isinstance(rows, str):
+            if rows != "dual":
+                raise ValueError(f"rows must be False, True or 'dual', got {rows!r}")
+            check(self.lib.f5_workspace_bytes_dual(self._h, B, N, nt, steps, METHODS[method], C.byref(nbytes)), "f5_workspace_bytes_dual")
+        elif rows:
             check(self.lib.f5_workspace_bytes_rows(self._h, B, N, nt, steps, METHODS[method], C.byref(nbytes)), "f5_workspace_bytes_rows")
         else:
             check(self.lib.f5_workspace_bytes(self._h, B, N, nt, steps, METHODS[method], C.byref(nbytes)), "f5_workspace_bytes")
@@ -458,8 +494,11 @@ class Engine:
 
     def _call_sample(self, a, cond_keep, st, rows=None) -> None:
         """f5_sample, f5_sample_edit when the call carries a conditioning mask, f5_sample_rows when it carries per-row controls
-        (rows = (t_rows, cfg_rows) of row_controls; the mask rides in the controls)."""
-        if rows is not None:
+        (rows = (t_rows, cfg_rows) of row_controls; the mask rides in the controls), f5_sample_dual when they carry audio strengths too."""
+        if rows is not None and len(rows) == 3:
+            dc = F5DualControls(rows[0].ctypes.data, rows[1].ctypes.data, rows[2].ctypes.data, 0 if cond_keep is None else cond_keep.data_ptr())
+            check(self.lib.f5_sample_dual(self._h, C.byref(a), C.byref(dc), st), "f5_sample_dual")
+        elif rows is not None:
             rc = F5RowControls(rows[0].ctypes.data, rows[1].ctypes.data, 0 if cond_keep is None else cond_keep.data_ptr())
             check(self.lib.f5_sample_rows(self._h, C.byref(a), C.byref(rc), st), "f5_sample_rows")
         elif cond_keep is None:
@@ -470,14 +509,17 @@ class Engine:
     def sample(self, text: torch.Tensor, cond: torch.Tensor, lens: Sequence[int], durations: Sequence[int], y0: torch.Tensor,
                t: np.ndarray, method: str = "euler", cfg_strength: float = 2.0, use_mask: Optional[bool] = None,
                use_graph=True, return_trajectory: bool = True, out: Optional[torch.Tensor] = None,
-               trajectory: Optional[torch.Tensor] = None, cond_keep: Optional[torch.Tensor] = None):
+               trajectory: Optional[torch.Tensor] = None, cond_keep: Optional[torch.Tensor] = None, audio_cfg_strength=None):
         """ODE solve on the GPU. cond (B,N,mel) fp32 zero-padded to N=max(durations); text (B,nt) int32
         (-1 padded); y0 (B,N,mel).  use_graph: True / False / "auto" (eager on the first sighting of a shape
         signature, captured hipGraph from the second on).  Per-request controls: `t` may also be (B, steps), one grid per row, and
         `cfg_strength` a length-B sequence; either selects f5_sample_rows (the other is broadcast), and the controls follow the call through
         the re-runs, the bf16x3 fall-back and the split halves.  cond_keep (speech editing, f5_sample_edit): bool / uint8 CUDA tensor (B, N),
         non-zero = frame n of row b is conditioning -- it replaces the prefix rule n < lens[b]; it follows the call through the re-runs,
-        the cross-check, the bf16x3 fall-back and the split halves.  Returns (out (B,N,mel), trajectory (steps,B,N,mel) or None)."""
+        the cross-check, the bf16x3 fall-back and the split halves.  audio_cfg_strength (a float or a length-B sequence; None = today's
+        call): dual guidance, f5_sample_dual -- `cfg_strength` is then the TEXT strength (text-only against unconditional) and this the
+        SPEAKER strength (full against text-only), k = (F + (F - T) a) + (T - N) c (docs/dual_guidance.md); the call takes that route
+        whatever the values are.  Returns (out (B,N,mel), trajectory (steps,B,N,mel) or None)."""
         if method not in METHODS:
             raise ValueError(f"Unknown method: {method}")
         self._check_inputs(text, cond, lens, durations)
@@ -486,18 +528,18 @@ class Engine:
         if self._use_fallback:                         # an earlier call saturated fp16 / failed its cross-check: bf16x3 from now on
             return self._fallback.sample(text, cond, lens, durations, y0, t, method=method, cfg_strength=cfg_strength, use_mask=use_mask,
                                          use_graph=use_graph, return_trajectory=return_trajectory, out=out, trajectory=trajectory,
-                                         cond_keep=cond_keep)
+                                         cond_keep=cond_keep, audio_cfg_strength=audio_cfg_strength)
         B, N, mel = cond.shape
-        steps, rows = row_controls(t, cfg_strength, B)
+        steps, rows = row_controls(t, cfg_strength, B, audio_cfg_strength)
         assert y0.shape == cond.shape and y0.dtype == torch.float32 and y0.is_contiguous() and y0.is_cuda
         if use_mask is None:
             use_mask = B > 1                       # cfm.py:333-336
         if 0 < self.split_batch <= B and self.verify_calls == 0:
             done = self._sample_split(text, cond, lens, durations, y0, t, steps, method, cfg_strength, use_mask, use_graph,
-                                      return_trajectory, out, trajectory, cond_keep)
+                                      return_trajectory, out, trajectory, cond_keep, audio_cfg_strength)
             if done is not None:
                 return done                        # (None: a half reported its status word -- the whole call is repeated below, unsplit)
-        ws = self.workspace(B, N, text.shape[1], steps, method, rows=rows is not None)
+        ws = self.workspace(B, N, text.shape[1], steps, method, rows=_plan_of(rows))
         if out is None:
             out = torch.empty_like(cond)
         if return_trajectory and trajectory is None:
@@ -513,12 +555,12 @@ class Engine:
         if saturated and self._use_fallback:           # ("sync": re-run THIS call in bf16x3, into the same output buffers)
             return self._fallback.sample(text, cond, lens, durations, y0, t, method=method, cfg_strength=cfg_strength, use_mask=use_mask,
                                          use_graph=use_graph, return_trajectory=return_trajectory, out=out, trajectory=trajectory,
-                                         cond_keep=cond_keep)
+                                         cond_keep=cond_keep, audio_cfg_strength=audio_cfg_strength)
         if self.verify_calls > 0 and self.precision == "f16" and self._ensure_fallback() is not None:
             self.verify_calls -= 1
             ref, ref_traj = self._fallback.sample(text, cond, lens, durations, y0, t, method=method, cfg_strength=cfg_strength,
                                                   use_mask=use_mask, use_graph=False, return_trajectory=return_trajectory,
-                                                  cond_keep=cond_keep)
+                                                  cond_keep=cond_keep, audio_cfg_strength=audio_cfg_strength)
             self.last_verify_l1 = l1 = float((out - ref).abs().mean())
             if not (l1 <= self.verify_tol):
                 self.verify_events += 1
@@ -535,7 +577,7 @@ class Engine:
 
     # ---- two half batches on two streams ---------------------------------------------------------
     def _sample_split(self, text, cond, lens, durations, y0, t, steps, method, cfg_strength, use_mask, use_graph, return_trajectory,
-                      out, trajectory, cond_keep=None):
+                      out, trajectory, cond_keep=None, audio_cfg_strength=None):
         """sample() of a large batch as two independent half batches: this engine runs utterances [0, h) on its stream, a sibling handle
         on the same weights arena runs [h, B) on its own, each enqueued by its own host thread (the HIP runtime lets a thread run only a
         few dozen launches ahead of the GPU, so one thread cannot keep two streams fed).  Utterances do not interact (both halves keep
@@ -555,8 +597,8 @@ class Engine:
         for eng, (b0, b1) in ((self, (0, h)), (sib, (h, B))):
             tr = torch.empty((steps, b1 - b0, N, mel), dtype=torch.float32, device=self.device) if return_trajectory else None
             th, ch = _rows_slice(t, cfg_strength, b0, b1)                  # (each half gets its rows of the controls ...)
-            _, rows = row_controls(th, ch, b1 - b0)
-            ws = eng.workspace(b1 - b0, N, nt, steps, method, rows=rows is not None)
+            _, rows = row_controls(th, ch, b1 - b0, _audio_slice(audio_cfg_strength, b0, b1))
+            ws = eng.workspace(b1 - b0, N, nt, steps, method, rows=_plan_of(rows))
             a, keep = eng._args(text[b0:b1], cond[b0:b1], lens[b0:b1], durations[b0:b1], y0[b0:b1], th if rows is None else rows[0][0], steps,
                                 method, ch if rows is None else float(rows[1].max()), use_mask, use_graph, out[b0:b1], tr, ws)
             calls.append((eng, a, keep, tr, None if cond_keep is None else cond_keep[b0:b1], rows))     # (... and of the mask)
@@ -565,8 +607,9 @@ class Engine:
             torch.cuda.set_device(self.device)         # (the worker thread's current device)
             eng._run_on_side_stream(lambda st: eng._call_sample(a, ck, st, rows), cur)
 
-        guided = tuple(bool(np.any(np.asarray(c[5][1] if c[5] is not None else cfg_strength) >= 1e-5)) for c in calls)
-        key = (B, N, nt, steps, method, use_graph, bool(use_mask), return_trajectory, guided, cond_keep is not None, calls[0][5] is not None)
+        guided = tuple(bool(np.any(np.asarray(c[5][1] if c[5] is not None else cfg_strength) >= 1e-5)
+                            or (c[5] is not None and len(c[5]) == 3 and np.any(c[5][2] >= 1e-5))) for c in calls)
+        key = (B, N, nt, steps, method, use_graph, bool(use_mask), return_trajectory, guided, cond_keep is not None, _plan_of(calls[0][5]))
         if key in self._split_seen:
             fut = self._pool.submit(run, calls[1][0], calls[1][1], calls[1][4], calls[1][5])
             try:
@@ -715,27 +758,37 @@ class Engine:
         return self._resolve(flags, what, shape, rerun=True)
 
     def dit_forward(self, x: torch.Tensor, text: torch.Tensor, cond: torch.Tensor, lens, durations, t: float,
-                    cfg_strength: float = 2.0, use_mask: Optional[bool] = None):
+                    cfg_strength: float = 2.0, use_mask: Optional[bool] = None, audio_cfg_strength=None):
         """One DiT evaluation (cond branch and, when cfg_strength >= 1e-5, null branch).  t: a float, or one time per batch row (length-B
-        sequence: one batched f5_dit_forward_rows call)."""
+        sequence: one batched f5_dit_forward_rows call).  audio_cfg_strength not None (its values are not read): the three branches of
+        dual guidance in one f5_dit_forward_dual call -> (pred, null_pred, text_pred)."""
         self._check_inputs(text, cond, lens, durations)
         self.check_status(block=False)
         if self._use_fallback:
-            return self._fallback.dit_forward(x, text, cond, lens, durations, t, cfg_strength=cfg_strength, use_mask=use_mask)
+            return self._fallback.dit_forward(x, text, cond, lens, durations, t, cfg_strength=cfg_strength, use_mask=use_mask,
+                                              audio_cfg_strength=audio_cfg_strength)
         B, N, mel = cond.shape
         if use_mask is None:
             use_mask = B > 1
+        dual = audio_cfg_strength is not None
         t_rows = None
-        if np.ndim(t) != 0:
+        if dual:
+            t_rows = np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.float32), (B,)), dtype=np.float32)
+        elif np.ndim(t) != 0:
             t_rows = np.ascontiguousarray(t, dtype=np.float32)
             if t_rows.shape != (B,):
                 raise ValueError(f"per-row time: expected {B} values, got shape {t_rows.shape}")
-        ws = self.workspace(B, N, text.shape[1], 2, "euler", rows=t_rows is not None)
+        ws = self.workspace(B, N, text.shape[1], 2, "euler", rows="dual" if dual else t_rows is not None)
         pred = torch.empty_like(cond)
-        null = torch.empty_like(cond) if cfg_strength >= 1e-5 else None
+        null = torch.empty_like(cond) if (dual or cfg_strength >= 1e-5) else None
+        text_pred = torch.empty_like(cond) if dual else None
         a, keep = self._args(text, cond, lens, durations, None, np.zeros(2, np.float32), 2, "euler", cfg_strength, use_mask,
                              False, None, None, ws)
-        if t_rows is None:
+        if dual:
+            launch = lambda: self._run_on_side_stream(lambda st: check(   # noqa: E731
+                self.lib.f5_dit_forward_dual(self._h, C.byref(a), ptr(x), C.c_void_p(t_rows.ctypes.data), ptr(pred), ptr(null), ptr(text_pred),
+                                             st), "f5_dit_forward_dual"))
+        elif t_rows is None:
             launch = lambda: self._run_on_side_stream(lambda st: check(   # noqa: E731
                 self.lib.f5_dit_forward(self._h, C.byref(a), ptr(x), C.c_float(t), ptr(pred), ptr(null), st), "f5_dit_forward"))
         else:
@@ -746,5 +799,6 @@ class Engine:
         saturated = self._after_call(a, launch, f"dit_forward(B={B}, N={N})", (B, N, 2, "forward"))
         del keep
         if saturated and self._use_fallback:
-            return self._fallback.dit_forward(x, text, cond, lens, durations, t, cfg_strength=cfg_strength, use_mask=use_mask)
-        return pred, null
+            return self._fallback.dit_forward(x, text, cond, lens, durations, t, cfg_strength=cfg_strength, use_mask=use_mask,
+                                              audio_cfg_strength=audio_cfg_strength)
+        return (pred, null, text_pred) if dual else (pred, null)

@@ -103,6 +103,8 @@ def generate(
     resample_ref: bool = False,             # extension: accept a reference recording at any sample rate
     output_sample_rate: Optional[int] = None,   # extension: hand back (and write) the wave at this rate instead of 24 kHz
     vocode_batched: bool = False,           # extension: with batch_sentences, ONE ragged vocoder call instead of one per sentence
+    audio_cfg_strength: Optional[float] = None,   # extension (dual guidance, docs/dual_guidance.md): speaker strength; `cfg_strength` is
+                                            # then the text strength.  None = the single-knob call: sample() gets no new keyword
 ):
     """generate.py:113-245.  `batch_sentences=True` (opt-in, no reference counterpart; SURVEY.md section 8(f)2 names it as the point of
     owning the app loop): the sentences of a multi-sentence text are sampled as one ragged batch -- one `sample()` call, one set of
@@ -153,10 +155,11 @@ def generate(
 
     sentences = split_sentences(generation_text)
     is_single_generation = len(sentences) <= 1 or duration is not None
+    dual_kw = {} if audio_cfg_strength is None else dict(audio_cfg_strength=_strength(audio_cfg_strength, "audio_cfg_strength"))
 
     def run(text_for_model, dur):
         wave, _ = f5tts.sample(audio[None], text=text_for_model, duration=dur, steps=steps, method=method, speed=speed,
-                               cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
+                               cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed, **dual_kw)
         wave = wave.reshape(-1) if wave.ndim > 1 and wave.shape[0] == 1 else wave
         return wave[audio.shape[0]:]                                  # trim the reference by SAMPLES (generate.py:183)
 
@@ -185,7 +188,7 @@ def generate(
         try:
             f5tts._vocoder = None
             mel, _ = f5tts.sample(cond, text=texts, duration=durs, steps=steps, method=method, speed=speed, cfg_strength=cfg_strength,
-                                  sway_sampling_coef=sway_sampling_coef, seed=seed)
+                                  sway_sampling_coef=sway_sampling_coef, seed=seed, **dual_kw)
         finally:
             f5tts._vocoder = voc
         frames = f5tts.last_durations                                 # per-element frame counts after the clamps of cfm.py:317-318
@@ -232,6 +235,15 @@ def _load_reference(ref_audio_path, ref_audio_text, which: str):
 
 
 CONTROL_KEYS = ("cfg_strength", "sway_sampling_coef", "seed", "speed")
+# dual guidance (docs/dual_guidance.md): accepted beside CONTROL_KEYS; it reaches sample() only when the call or a request sets it
+AUDIO_CFG_KEY = "audio_cfg_strength"
+
+
+def _strength(v, what: str) -> float:
+    """a guidance strength as a finite float, or ValueError naming `what`"""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+        raise ValueError(f"{what} must be a finite number, got {v!r}")
+    return float(v)
 
 
 def request_controls(controls, n_requests: int, row_req, defaults: dict) -> dict:
@@ -239,9 +251,14 @@ def request_controls(controls, n_requests: int, row_req, defaults: dict) -> dict
     None or a dict with any of CONTROL_KEYS; an entry overrides the call-level value (`defaults`) for all rows of its request.  row_req:
     the request of every batch row.  A control no request overrides stays the call-level scalar, so a call without overrides is the call
     it was before; an overridden one becomes a list with one value per row.  ValueError naming the request: a list of the wrong length,
-    an entry that is neither None nor a dict, an unknown key."""
+    an entry that is neither None nor a dict, an unknown key.
+    "audio_cfg_strength" (dual guidance) is accepted beside CONTROL_KEYS.  The key appears in the result only when `defaults` carries it
+    (the call-level value) or a request sets it, and then always as one value per row: a row whose request does not set it gets the
+    call-level value, or -- where there is none -- its own cfg_strength, which is algebraically the single-knob rule for that row."""
     out = dict(defaults)
     if controls is None:
+        if AUDIO_CFG_KEY in out:
+            out[AUDIO_CFG_KEY] = [_strength(out[AUDIO_CFG_KEY], AUDIO_CFG_KEY)] * len(row_req)
         return out
     controls = list(controls)
     if len(controls) != n_requests:
@@ -251,12 +268,25 @@ def request_controls(controls, n_requests: int, row_req, defaults: dict) -> dict
             continue
         if not isinstance(c, dict):
             raise ValueError(f"request {i}: controls entry must be None or a dict, got {type(c).__name__}")
-        unknown = sorted(set(c) - set(CONTROL_KEYS))
+        unknown = sorted(set(c) - set(CONTROL_KEYS) - {AUDIO_CFG_KEY})
         if unknown:
-            raise ValueError(f"request {i}: unknown control(s) {unknown}; expected any of {list(CONTROL_KEYS)}")
+            raise ValueError(f"request {i}: unknown control(s) {unknown}; expected any of {list(CONTROL_KEYS) + [AUDIO_CFG_KEY]}")
+        if AUDIO_CFG_KEY in c:
+            _strength(c[AUDIO_CFG_KEY], f"request {i}: {AUDIO_CFG_KEY}")
     for key in CONTROL_KEYS:
         if any(c is not None and key in c for c in controls):
             out[key] = [controls[i][key] if controls[i] is not None and key in controls[i] else defaults[key] for i in row_req]
+    if AUDIO_CFG_KEY in defaults or any(c is not None and AUDIO_CFG_KEY in c for c in controls):
+        cfg = out["cfg_strength"]
+        rows = []
+        for r, i in enumerate(row_req):
+            if controls[i] is not None and AUDIO_CFG_KEY in controls[i]:
+                rows.append(float(controls[i][AUDIO_CFG_KEY]))
+            elif AUDIO_CFG_KEY in defaults:
+                rows.append(_strength(defaults[AUDIO_CFG_KEY], AUDIO_CFG_KEY))
+            else:
+                rows.append(float(cfg[r] if isinstance(cfg, list) else cfg))
+        out[AUDIO_CFG_KEY] = rows
     return out
 
 
@@ -276,6 +306,7 @@ def generate_many(
     trim_silence_db: Optional[float] = None,
     output_sample_rate: Optional[int] = None,
     controls=None,
+    audio_cfg_strength: Optional[float] = None,
 ):
     """Many voices in one call (no reference counterpart; docs/multi_voice.md).  requests: a list of (generation_text, ref_audio_path or
     None, ref_audio_text); None = the bundled sample and its text.  -> a list of waves, one per request, in order.
@@ -292,6 +323,9 @@ def generate_many(
     controls (docs/row_controls.md): None, or a list with one entry per request, each None or a dict with any of "cfg_strength",
     "sway_sampling_coef", "seed", "speed"; an entry overrides the call-level value for all rows of that request, and requests with
     different settings still share the one batch (the engine indexes time grid and guidance strength by batch row).
+    audio_cfg_strength (docs/dual_guidance.md), as an argument or as a key of a controls entry: dual guidance -- the speaker strength,
+    with cfg_strength as the text strength.  sample() gets the keyword (one value per row) only when the call or some request sets it; a
+    row whose request does not set it, in a call that does not either, gets its own cfg_strength (the single-knob rule for that row).
 
     It equals prepare_references -> sample(mel, text, durations, lens=frames) -> the decode -> the same slices, bit for bit; it does
     NOT equal a loop of generate() calls bit for bit (the batch has a key-padding mask, GRN and the conv position embedding see the
@@ -302,6 +336,8 @@ def generate_many(
     if not requests:
         raise ValueError("generate_many needs at least one request")
     call_level = dict(cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed, speed=speed)
+    if audio_cfg_strength is not None:
+        call_level[AUDIO_CFG_KEY] = _strength(audio_cfg_strength, AUDIO_CFG_KEY)
     request_controls(controls, len(requests), [], call_level)          # validation only: the rows are not known yet
     if output_sample_rate is not None:
         output_sample_rate = _audio._rate(output_sample_rate, "output_sample_rate")
@@ -352,7 +388,8 @@ def generate_many(
     try:                                                              # mel frames out of sample(): each row is vocoded on its own frames
         f5tts._vocoder = None
         mel, _ = f5tts.sample(cond, text=texts, duration=durs, lens=lens, steps=steps, method=method, speed=ctl["speed"],
-                              cfg_strength=ctl["cfg_strength"], sway_sampling_coef=ctl["sway_sampling_coef"], seed=ctl["seed"])
+                              cfg_strength=ctl["cfg_strength"], sway_sampling_coef=ctl["sway_sampling_coef"], seed=ctl["seed"],
+                              **({AUDIO_CFG_KEY: ctl[AUDIO_CFG_KEY]} if AUDIO_CFG_KEY in ctl else {}))
     finally:
         f5tts._vocoder = voc
     frames = f5tts.last_durations                                     # per-row frame counts after the clamps of cfm.py:317-318
@@ -389,7 +426,7 @@ def read_requests(path):
                 raise ValueError(f"{path}:{no}: not a JSON object ({exc.msg})") from None
             if not isinstance(obj, dict) or not isinstance(obj.get("text"), str):
                 raise ValueError(f'{path}:{no}: expected an object with a "text" string')
-            unknown = set(obj) - {"text", "ref_audio", "ref_text", "output"} - {"cfg", "sway_coef", "seed", "speed"}
+            unknown = set(obj) - {"text", "ref_audio", "ref_text", "output"} - {"cfg", "sway_coef", "seed", "speed", "audio_cfg"}
             if unknown:
                 raise ValueError(f"{path}:{no}: unknown key(s) {sorted(unknown)}")
             reqs.append({k: obj.get(k) for k in ("text", "ref_audio", "ref_text", "output")})
@@ -397,11 +434,12 @@ def read_requests(path):
 
 
 def read_request_controls(path):
-    """The optional per-request sampling controls of a --requests file: the keys "cfg", "sway_coef", "seed" and "speed" of every line
-    (same lines as read_requests, which ignores them) -> a list with one entry per request for generate_many(controls=...): a dict with
-    the controls the line sets ("cfg_strength", "sway_sampling_coef", "seed", "speed"), or None when it sets none."""
+    """The optional per-request sampling controls of a --requests file: the keys "cfg", "sway_coef", "seed", "speed" and "audio_cfg" of
+    every line (same lines as read_requests, which ignores them) -> a list with one entry per request for generate_many(controls=...):
+    a dict with the controls the line sets ("cfg_strength", "sway_sampling_coef", "seed", "speed", "audio_cfg_strength"), or None when
+    it sets none."""
     import json
-    names = {"cfg": "cfg_strength", "sway_coef": "sway_sampling_coef", "seed": "seed", "speed": "speed"}
+    names = {"cfg": "cfg_strength", "sway_coef": "sway_sampling_coef", "seed": "seed", "speed": "speed", "audio_cfg": AUDIO_CFG_KEY}
     out = []
     with open(path, encoding="utf-8") as f:
         for no, line in enumerate(f, 1):
@@ -437,7 +475,8 @@ _CLI = (
     ("--ref-text", str, None, "transcript of --ref-audio"),
     ("--output", str, None, "WAV file to write"),
     ("--steps", int, 8, "ODE grid points (steps - 1 solver updates)"),
-    ("--cfg", float, 2.0, "classifier-free guidance strength"),
+    ("--cfg", float, 2.0, "classifier-free guidance strength (with --audio-cfg: the text strength)"),
+    ("--audio-cfg", float, None, "dual guidance: speaker strength (full against text-only prediction); --cfg is then the text strength"),
     ("--sway-coef", float, -1.0, "sway-sampling coefficient of the time grid"),
     ("--speed", float, 1.0, "speaking-rate factor used by the duration heuristics"),
     ("--seed", int, None, "noise seed"),
@@ -484,7 +523,8 @@ def main(argv=None):
                               cfg_strength=ns.cfg, sway_sampling_coef=ns.sway_coef, speed=ns.speed, seed=ns.seed,
                               estimate_duration=ns.estimate_duration, model_name=ns.model, quantization_bits=ns.q,
                               trim_silence_db=ns.trim_silence, output_sample_rate=ns.output_rate,
-                              controls=controls if any(c is not None for c in controls) else None)
+                              controls=controls if any(c is not None for c in controls) else None,
+                              **({} if ns.audio_cfg is None else dict(audio_cfg_strength=ns.audio_cfg)))
         for r, wave in zip(reqs, waves):
             if r["output"] is not None:
                 write_wav(r["output"], wave.detach().cpu().numpy(), ns.output_rate or SAMPLE_RATE)
@@ -501,7 +541,8 @@ def main(argv=None):
     generate(text, duration=ns.duration, estimate_duration=ns.estimate_duration, model_name=ns.model, ref_audio_path=ns.ref_audio,
              ref_audio_text=ns.ref_text, steps=ns.steps, method=ns.method, cfg_strength=ns.cfg, sway_sampling_coef=ns.sway_coef,
              speed=ns.speed, seed=ns.seed, quantization_bits=ns.q, output_path=ns.output, resample_ref=ns.resample_ref,
-             output_sample_rate=ns.output_rate, batch_sentences=ns.batch_sentences, vocode_batched=ns.vocode_batched)
+             output_sample_rate=ns.output_rate, batch_sentences=ns.batch_sentences, vocode_batched=ns.vocode_batched,
+             **({} if ns.audio_cfg is None else dict(audio_cfg_strength=ns.audio_cfg)))
 
 
 if __name__ == "__main__":

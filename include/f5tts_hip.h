@@ -159,6 +159,28 @@ typedef struct f5_row_controls {
 int f5_workspace_bytes_rows(f5_engine* e, int B, int N, int nt, int steps, int method, size_t* bytes);
 int f5_sample_rows(f5_engine* e, const f5_sample_args* args, const f5_row_controls* controls, void* stream);
 
+/* Dual guidance: f5_sample_rows with TWO guidance strengths per batch row.  The reference trains three conditioning states (its loss
+ * forward drops the audio alone, and the text only together with the audio, cfm.py:230-232): F = audio and text kept, T = audio dropped,
+ * N = both dropped.  Per element, in fp32, with a = audio_cfg_rows[b] and c = text_cfg_rows[b]:
+ *     k = (F + (F - T) a) + (T - N) c
+ * (a == c is algebraically F + (F - N) c, the rule of f5_sample -- within rounding, not bit for bit).  A row with both strengths below
+ * 1e-5 takes k = F; T is loaded when either is >= 1e-5, N only when c >= 1e-5; selections, so a NaN on a side that is not taken
+ * reaches nothing.  All three branches run as one batch of 3 B N rows (in the order F, N, T) as soon as any row has either strength,
+ * else F alone.  The route is the per-row one (adaLN table per (evaluation, row), no LN fold); the text path still runs for two
+ * branches, T reuses F's text embedding.  f5_workspace_bytes_dual is the plan of f5_workspace_bytes_rows with every buffer of the DiT
+ * itself at 3 B N rows; f5_workspace_bytes and f5_workspace_bytes_rows are unchanged.  Graphs: controls are staged outside the captured
+ * part and a dual flag is part of the cache key.  args->t and args->cfg_strength are not read.
+ * Refused before any launch: everything f5_sample_rows refuses (mxfp8 included), a non-finite strength, a workspace below
+ * f5_workspace_bytes_dual, and engine option null_keeps_cond = 1 (the meanings of the branches would collide). */
+typedef struct f5_dual_controls {
+    const float* t_rows;          /* host [B][steps] */
+    const float* text_cfg_rows;   /* host [B]: T against N */
+    const float* audio_cfg_rows;  /* host [B]: F against T */
+    const uint8_t* cond_keep_dev; /* dev [B][N] or NULL: as f5_sample_edit */
+} f5_dual_controls;
+int f5_workspace_bytes_dual(f5_engine* e, int B, int N, int nt, int steps, int method, size_t* bytes);
+int f5_sample_dual(f5_engine* e, const f5_sample_args* args, const f5_dual_controls* controls, void* stream);
+
 /* Status word of the last f5_sample / f5_dit_forward on the workspace of `args`.  It is the FIRST 32-bit word of the workspace for every
  * shape and solver (a caller may copy it itself).  bit 1 (F5_STATUS_FOLD_RAN) = the LN fold (engine option "ln_fold") ran in that call;
  * bit 0 (F5_STATUS_FOLD_OVERFLOW) = a value of the folded LayerNorm operand (x - m)(1 + scale) did not fit fp16 (precision f16): the
@@ -190,6 +212,11 @@ int f5_dit_forward(f5_engine* e, const f5_sample_args* args, const float* x, flo
  * Workspace: f5_workspace_bytes_rows(B, N, nt, 2, F5_EULER). */
 int f5_dit_forward_rows(f5_engine* e, const f5_sample_args* args, const float* x, const float* t_rows_host /* [B] */, float* pred,
                         float* null_pred, void* stream);
+/* One evaluation of the three branches of dual guidance (f5_sample_dual): pred = F, null_pred = N, text_pred = T, dev [B][N][mel] each
+ * (null_pred and text_pred may be NULL); all three always run, args->cfg_strength is not read.
+ * Workspace: f5_workspace_bytes_dual(B, N, nt, 2, F5_EULER). */
+int f5_dit_forward_dual(f5_engine* e, const f5_sample_args* args, const float* x, const float* t_rows_host /* [B] */, float* pred,
+                        float* null_pred, float* text_pred, void* stream);
 
 /* ---- per-op entry points (exported for the parity tests; all pointers are dev) ------------------
  * 16-bit operand buffers (a_hi, w_hi, qk_hi, out_hi ...) hold bf16 by default; f5_op_set_operand_type(1) switches every
@@ -276,6 +303,16 @@ int f5_op_ode_stage(const float* pred, const float* null_pred, float cfg, const 
 int f5_op_ode_stage_rows(const float* pred, const float* null_pred, const float* cfg_rows, const float* base, const float* dt_rows,
                          int rows_per_vec, int nvec, float coef, float divisor, int mode, float* kstore, const float* k1, const float* k2,
                          const float* k3, float* out, void* xin_hi, void* xin_lo, int rows, int mel_dim, void* stream);
+/* f5_op_ode_stage_rows for dual guidance: F = pred, T = text_pred, N = null_pred and two strengths per row,
+ * k = (F + (F - T) audio_cfg_rows[v]) + (T - N) text_cfg_rows[v] in fp32.  T is loaded when either strength is >= 1e-5, N only when
+ * text_cfg_rows[v] >= 1e-5, a row with both below takes k = F: selections, a NaN on a side that is not taken reaches nothing.  A NULL
+ * text_pred is k = F; a NULL null_pred leaves the (T - N) term out.  Everything behind k (step, kstore, rk4 combine, xin packing) has the
+ * bits of f5_op_ode_stage.  Refused before a launch, each with its own message: null pred, base, out, strengths or dt_rows;
+ * rows_per_vec < 1; nvec < 1; mel_dim > 128. */
+int f5_op_ode_stage_dual(const float* pred, const float* text_pred, const float* null_pred, const float* audio_cfg_rows,
+                         const float* text_cfg_rows, const float* base, const float* dt_rows, int rows_per_vec, int nvec, float coef,
+                         float divisor, int mode, float* kstore, const float* k1, const float* k2, const float* k3, float* out,
+                         void* xin_hi, void* xin_lo, int rows, int mel_dim, void* stream);
 /* Residual update and the LayerNorm-modulate behind it with per-row vectors: row r of the [rows][dim] buffers reads vector
  * v = (r / rows_per_vec) % nvec of gate / ln_scale / ln_shift (vec_stride >= dim floats apart, a multiple of 4).
  * With y (fp32 [rows][dim], the GEMM result including bias; may be NULL): x = fmaf(gate[v][c], rowkeep[r] ? y : 0, x) in place (rowkeep
@@ -303,6 +340,13 @@ int f5_op_splice(const float* cond, const float* y, const int32_t* lens, float* 
 int f5_op_pack_cond_text_keep(const float* cond, const uint8_t* keep, const float* text_emb, void* out_hi, void* out_lo, int B,
                               int seq_len, int mel_dim, int dt, int null_keeps_cond, void* stream);
 int f5_op_splice_keep(const float* cond, const float* y, const uint8_t* keep, float* out, int B, int seq_len, int mel_dim, void* stream);
+/* The three-branch operand of dual guidance: [3][B][seq_len][128 + dt] in the order F, N, T.  Branches 0 and 1 are what
+ * f5_op_pack_cond_text (or its keep twin) writes with null_keeps_cond = 0; branch 2 has zero cond columns and BRANCH 0's text columns
+ * (text_emb stays [2][B][seq_len][dt]).  Split, saturation report, operand types and selection as there. */
+int f5_op_pack_cond_text_dual(const float* cond, const int32_t* lens, const float* text_emb, void* out_hi, void* out_lo, int B, int seq_len,
+                              int mel_dim, int dt, void* stream);
+int f5_op_pack_cond_text_dual_keep(const float* cond, const uint8_t* keep, const float* text_emb, void* out_hi, void* out_lo, int B,
+                                   int seq_len, int mel_dim, int dt, void* stream);
 /* Frame gather (no reference counterpart; the layout step of speech editing): src dev [B][n_src][mel_dim] fp32, src_idx dev int32
  * [B][seq_len] -> cond_out dev [B][seq_len][mel_dim], keep_out dev uint8 [B][seq_len].  An index in [0, n_src) copies that frame of the
  * same row and sets keep to 1; any other index (-1 is the documented "regenerate here") writes zeros and keep 0 and reads nothing.
