@@ -6,6 +6,10 @@
 
 `resample` changes the sample rate (no reference counterpart: the reference refuses anything but 24 kHz): the polyphase table is
 built on the host in fp64 (`resample_table`), the filter runs in one HIP kernel (`f5_resample_batch`, csrc/audio.hip).
+
+`join_rows` is the back half of a ragged batch (no reference counterpart; docs/sentence_joins.md): the decoded sentences of every
+request are laid out with an optional edge trim, pauses and linear cross-fades by host integer arithmetic (`join_layout`,
+`sentence_windows`) and ONE HIP launch (`f5_wave_join`, csrc/audio.hip).
 """
 from __future__ import annotations
 
@@ -390,6 +394,173 @@ def prepare_references(waves, sample_rates=24_000, *, trim_silence_db: Optional[
     gain = reference_gain(energy, begin, length, ENERGY_BLOCK, target_rms)
     mel = log_mel_spectrogram_ragged(buf, length, begin, gain, sample_rate=SR, hop_length=hop_length)
     return References(mel, [n // hop_length for n in length], length, begin, gain)
+
+
+# ---- sentence joins (no reference counterpart; docs/sentence_joins.md): the back half of generate() / generate_many() ---------------
+JOIN_SEG_MAX = 64                    # f5_wave_join: segments per output row
+JOIN_SAMPLE_RATE = 24_000            # the model's rate: what the millisecond arguments of join_rows are counted in
+
+
+def _per_request(value, Q: int, name: str) -> list:
+    """one value for every request, or one per request -> a list of Q"""
+    if isinstance(value, (list, tuple, np.ndarray)):
+        if len(value) != Q:
+            raise ValueError(f"{name} must be one value or one per request ({Q}), got {len(value)}")
+        return list(value)
+    return [value] * Q
+
+
+def join_layout(begin, length, row_req, *, fade, gap):
+    """Where the sentences of every request go: pure integer arithmetic, no GPU.  Row r of the decoded batch holds a sentence at samples
+    [begin[r], begin[r] + length[r]) and belongs to request row_req[r]; `fade` and `gap` are sample counts, one for all requests or one
+    per request.  Per request, in row order, the first segment sits at 0.  For consecutive sentences a and b:
+    F = min(fade, len_a // 2, len_b // 2) -- a very short sentence shortens its own fades and does not raise --, fade_out[a] =
+    fade_in[b] = F; with gap == 0 they overlap by F, dst_begin[b] = dst_end[a] - F (a cross-fade), with gap > 0 they do not,
+    dst_begin[b] = dst_end[a] + gap (a fade to silence, the pause, a fade from silence).  The first sentence's head and the last one's
+    tail are not faded.  -> (table int32 [Q][S][6] for f5_wave_join, out_lens: samples per request, Lout = the longest); Q = the largest
+    request number + 1, S = the most sentences of a request, shorter requests pad with empty entries."""
+    R = len(row_req)
+    begin, length = _host_ints(begin, R, "begin"), _host_ints(length, R, "length")
+    row_req = [int(q) for q in row_req]
+    if R == 0 or min(row_req) < 0:
+        raise ValueError("join_layout needs at least one row, and request numbers from 0")
+    Q = max(row_req) + 1
+    fade = [int(f) for f in _per_request(fade, Q, "fade")]
+    gap = [int(g) for g in _per_request(gap, Q, "gap")]
+    for r in range(R):
+        if begin[r] < 0 or length[r] < 0:
+            raise ValueError(f"row {r}: begin = {begin[r]} and length = {length[r]} must not be negative")
+    if min(fade) < 0 or min(gap) < 0:
+        raise ValueError(f"fade and gap must not be negative (got {fade}, {gap})")
+    rows = [[r for r in range(R) if row_req[r] == q] for q in range(Q)]
+    S = max(len(rs) for rs in rows)
+    if S > JOIN_SEG_MAX:
+        raise ValueError(f"a request of {S} sentences exceeds the {JOIN_SEG_MAX} segments of a row of f5_wave_join")
+    table = np.zeros((Q, S, 6), dtype=np.int64)
+    out_lens = []
+    for q, rs in enumerate(rows):
+        at = 0                                                         # where the previous sentence ended
+        for k, r in enumerate(rs):
+            F = 0
+            if k > 0:
+                F = min(fade[q], length[rs[k - 1]] // 2, length[r] // 2)
+                table[q, k - 1, 5] = F
+                at = at - F if gap[q] == 0 else at + gap[q]
+            table[q, k] = (at, r, begin[r], length[r], F, 0)
+            at += length[r]
+        out_lens.append(at)
+    if table.max(initial=0) > 2 ** 31 - 1:
+        raise ValueError("the joined waves exceed 2^31 - 1 samples")
+    return table.astype(np.int32), out_lens, max(out_lens)
+
+
+def sentence_windows(energy, begin, length, block: int, threshold_db: float, keep_blocks: int):
+    """Edge trim of generated sentences: silence_window's rule on the part of each decoded row that follows its reference.  energy
+    (r, nblk): the block energies of the rows with lens = begin + length, blocks aligned at sample 0.  Only whole blocks that start at
+    or after begin[r] are candidates -- the reference part never is, and neither is the block begin[r] falls into.  The kept window is
+    [max(begin, (first_loud - keep_blocks) block), min(begin + length, (last_loud + 1 + keep_blocks) block)).  A row with no loud
+    block keeps its whole range: a silent sentence must not abort a finished batch.  Host fp64, no GPU -> (begin, length)."""
+    e = np.asarray(energy.cpu() if isinstance(energy, torch.Tensor) else energy, dtype=np.float64)
+    if e.ndim == 1:
+        e = e[None]
+    R = e.shape[0]
+    begin, length = _host_ints(begin, R, "begin"), _host_ints(length, R, "length")
+    block, keep_blocks = int(block), int(keep_blocks)
+    if block < 1 or keep_blocks < 0:
+        raise ValueError(f"block must be >= 1 and keep_blocks >= 0 (got {block}, {keep_blocks})")
+    out_b, out_n = [], []
+    for r in range(R):
+        end = begin[r] + length[r]
+        k0, nb = -(-begin[r] // block), -(-end // block)
+        if nb > e.shape[1]:
+            raise ValueError(f"row {r}: {end} samples need {nb} blocks of {block}, the table has {e.shape[1]}")
+        k = np.arange(k0, max(nb, k0))
+        n_k = np.minimum((k + 1) * block, end) - k * block
+        with np.errstate(divide="ignore", invalid="ignore"):
+            level = 10.0 * np.log10(e[r, k0:max(nb, k0)] / n_k)
+        loud = k[np.nonzero(level > threshold_db)[0]]
+        lo, hi = begin[r], end
+        if loud.size:
+            lo = max(lo, (int(loud[0]) - keep_blocks) * block)
+            hi = min(hi, (int(loud[-1]) + 1 + keep_blocks) * block)
+        out_b.append(lo)
+        out_n.append(hi - lo)
+    return out_b, out_n
+
+
+def _ms_to_samples(ms) -> int:
+    return int(round(float(ms) * JOIN_SAMPLE_RATE / 1000.0))
+
+
+def wave_join(src: torch.Tensor, table, Lout: int) -> torch.Tensor:
+    """src [R, Ls] fp32 on the GPU, table int32 (Q, S, 6) on the host (join_layout) -> (Q, Lout): f5_wave_join, one call, no
+    synchronisation.  The library refuses a bad table (ValueError here)."""
+    lib = _eng.load_library()
+    src = _padded_batch(src, None)
+    table = np.ascontiguousarray(np.asarray(table, dtype=np.int32))
+    if table.ndim != 3 or table.shape[2] != 6:
+        raise ValueError(f"a join table is (Q, S, 6), got {table.shape}")
+    Q, S = table.shape[:2]
+    R, Ls = src.shape
+    out = torch.empty((Q, int(Lout)), dtype=torch.float32, device=src.device)
+    with torch.cuda.device(src.device):
+        rc = lib.f5_wave_join(_eng.ptr(src), R, C.c_int64(Ls), table.ctypes.data_as(C.c_void_p), Q, S, _eng.ptr(out), C.c_int64(int(Lout)),
+                              _eng.stream_ptr(src.device))
+    if rc != 0 and lib.f5_last_error().startswith(b"wave_join:"):
+        raise ValueError(lib.f5_last_error().decode("utf-8", "replace"))
+    _eng.check(rc, "f5_wave_join")
+    return out
+
+
+def join_rows(decoded, begin, length, row_req, *, cross_fade_ms=0, pause_ms=0, trim_db=None, keep_ms: float = 50):
+    """The decoded rows of a ragged batch -> one wave per request.  decoded [R, Ls] on the GPU; row r holds a sentence of request
+    row_req[r] at samples [begin[r], begin[r] + length[r]) (begin = its reference's samples).  cross_fade_ms, pause_ms and trim_db are
+    one value for all requests or one per request (None = 0 / no trim for that request).
+    With a trim_db: ONE block_energy launch on the decoded rows (blocks of 240 samples aligned at 0, lens = begin + length) and ONE
+    copy of its table to the host -- the only synchronisation --, then sentence_windows cuts leading and trailing near-silence below
+    trim_db off every sentence of the requests that ask for it, keeping keep_ms of margin.  Without one: no energy launch and no
+    synchronisation.  Then join_layout (host integers) and ONE f5_wave_join launch.
+    -> (waves (Q, Lout) fp32, exactly 0.0 past each request's length; out_lens).  With cross_fade_ms = 0, no pause and no trim row q
+    is torch.cat of its sentences' slices, bit for bit."""
+    decoded = _padded_batch(decoded, None)
+    R = decoded.shape[0]
+    begin, length = _host_ints(begin, R, "begin"), _host_ints(length, R, "length")
+    row_req = [int(q) for q in row_req]
+    if len(row_req) != R:
+        raise ValueError(f"row_req must have one entry per row ({R}), got {len(row_req)}")
+    for r in range(R):
+        if begin[r] < 0 or length[r] < 0 or begin[r] + length[r] > decoded.shape[1]:
+            raise ValueError(f"row {r}: samples [{begin[r]}, {begin[r] + length[r]}) lie outside the row of {decoded.shape[1]}")
+    Q = max(row_req) + 1
+    fade = [_ms_to_samples(v or 0) for v in _per_request(cross_fade_ms, Q, "cross_fade_ms")]
+    gap = [_ms_to_samples(v or 0) for v in _per_request(pause_ms, Q, "pause_ms")]
+    trim = _per_request(trim_db, Q, "trim_db")
+    if any(t is not None for t in trim):
+        lens = [b + n for b, n in zip(begin, length)]
+        energy = block_energy(decoded, lens, ENERGY_BLOCK).cpu().numpy()   # the one synchronisation
+        keep = int(round(keep_ms * JOIN_SAMPLE_RATE / 1000.0 / ENERGY_BLOCK))
+        for q in range(Q):
+            if trim[q] is None:
+                continue
+            rs = [r for r in range(R) if row_req[r] == q]
+            b, n = sentence_windows(energy[rs], [begin[r] for r in rs], [length[r] for r in rs], ENERGY_BLOCK, float(trim[q]), keep)
+            for i, r in enumerate(rs):
+                begin[r], length[r] = b[i], n[i]
+    table, out_lens, Lout = join_layout(begin, length, row_req, fade=fade, gap=gap)
+    return wave_join(decoded, table, Lout), out_lens
+
+
+def resample_rows(waves: torch.Tensor, lens, orig_sr: int, new_sr: int) -> list:
+    """waves (Q, L) padded with EXACT zeros past lens[q] -> a list of Q waves at new_sr, from ONE f5_resample_batch call on the padded
+    batch, each sliced to ceil(n lens[q] / o).  The bits of resample() on each waves[q, :lens[q]] by itself: the filter treats
+    everything outside [0, L) as zero, the padding is zero, and an output sample's taps and their order depend on its index alone."""
+    orig_sr, new_sr = _rate(orig_sr, "orig_sr"), _rate(new_sr, "new_sr")
+    lens = _host_ints(lens, waves.shape[0], "lens")
+    if orig_sr == new_sr:
+        return [waves[q, :lens[q]] for q in range(len(lens))]
+    _, _, o, n, _, _ = resample_table(orig_sr, new_sr)
+    out = resample(waves, orig_sr, new_sr)
+    return [out[q, :-((-n * lens[q]) // o)] for q in range(len(lens))]
 
 
 def check_resample_ratio(orig_sr: int, new_sr: int) -> None:

@@ -502,3 +502,108 @@ extern "C" int f5_op_wave_patch(const float* gen, const float* src, const int32_
     F5_LAUNCH_CHECK();
     return 0;
 }
+
+// =================================================================================================
+// Sentence join (no reference counterpart; the back half of generate() / generate_many(): docs/sentence_joins.md).  Q output waves are
+// laid out from R decoded rows by a table of segments (dst_begin, src_row, src_begin, len, fade_in, fade_out), in samples; the rules
+// per output sample are in include/f5tts_hip.h.  One thread per output sample, one workgroup per 256 consecutive samples of one output
+// row: the segment table is a kernel argument (uniform reads), the stores are one coalesced dword per lane (rows are Lout floats apart,
+// so they share no alignment wider than that), and each source sample is loaded by the one or two lanes whose output it reaches --
+// selected by the index tests, so nothing outside the ranges the table names is loaded.  Of the S entries of a row at most two cover
+// a sample (checked on the host): the first hit is the earlier segment, the second the one that fades in over it.
+// The fade weight w(i, F) = (2 i + 1) / (2 F) is one correctly rounded fp32 division of two integers below 2^24 (hence F <= 2^22).
+// =================================================================================================
+#define WJ_SEG_MAX 64
+#define WJ_FADE_MAX (1 << 22)
+#define WJ_WORDS 960                 // int32 words of table per launch (a kernel argument of 3 840 bytes): 160 segments
+struct F5WaveJoinTable {
+    int w[WJ_WORDS];                 // [rows][S][6]
+};
+__device__ __forceinline__ float wave_join_weight(int i, int F) { return __fdiv_rn((float)(2 * i + 1), (float)(2 * F)); }
+
+__global__ __launch_bounds__(256) void wave_join_kernel(const float* __restrict__ src, int R, long Ls, F5WaveJoinTable t, int S,
+                                                        float* __restrict__ out, long Lout) {
+    const long s = (long)blockIdx.x * 256 + threadIdx.x;
+    if (s >= Lout) return;
+    const int* seg = t.w + (size_t)blockIdx.y * S * 6;
+    out += (long)blockIdx.y * Lout;                                 // the launcher offsets out to the first row of the launch
+    int ka = -1, kb = -1;
+    for (int k = 0; k < S; ++k) {
+        const long i = s - seg[6 * k];
+        if (i >= 0 && i < seg[6 * k + 3]) {
+            if (ka < 0) ka = k;
+            else kb = k;
+        }
+    }
+    float v = 0.0f;                                                 // covered by no segment
+    if (ka >= 0) {
+        const int* a = seg + 6 * ka;
+        const long ia = s - a[0], sa = (long)a[2] + ia;
+        // (checked on the host: a table that lies cannot take the loads out of src)
+        const float xa = (a[1] < R && sa < Ls) ? src[(long)a[1] * Ls + sa] : 0.0f;
+        if (kb < 0) {
+            const long ja = (long)a[3] - 1 - ia;
+            v = xa;                                                 // selected: the source's own bits
+            if (ia < a[4]) v = __fmul_rn(wave_join_weight((int)ia, a[4]), xa);
+            else if (ja < a[5]) v = __fmul_rn(wave_join_weight((int)ja, a[5]), xa);
+        } else {
+            const int* b = seg + 6 * kb;
+            const long ib = s - b[0], sb = (long)b[2] + ib;
+            const float xb = (b[1] < R && sb < Ls) ? src[(long)b[1] * Ls + sb] : 0.0f;
+            v = fmaf(wave_join_weight((int)ib, b[4]), xb - xa, xa);
+        }
+    }
+    out[s] = v;
+}
+
+extern "C" int f5_wave_join(const float* src, int R, int64_t Ls, const int32_t* segs_host, int Q, int S, float* out, int64_t Lout,
+                            void* stream) {
+    F5_REQUIRE(src && segs_host && out, "wave_join: null pointer");
+    F5_REQUIRE(R >= 1 && R <= 65535, "wave_join: R = %d source rows outside 1..65535", R);
+    F5_REQUIRE(Q >= 1 && Q <= 65535, "wave_join: Q = %d output rows outside 1..65535", Q);
+    F5_REQUIRE(S >= 1 && S <= WJ_SEG_MAX, "wave_join: S = %d segments per row outside 1..%d", S, WJ_SEG_MAX);
+    F5_REQUIRE(Ls >= 0 && Ls <= 0x7fffffffLL, "wave_join: Ls = %lld outside 0..2^31 - 1", (long long)Ls);
+    F5_REQUIRE(Lout >= 0 && Lout <= 0x7fffffffLL, "wave_join: Lout = %lld outside 0..2^31 - 1", (long long)Lout);
+    for (int q = 0; q < Q; ++q) {
+        const int32_t* t = segs_host + (size_t)q * S * 6;
+        int prev = -1;                                              // the last segment that was not empty
+        for (int k = 0; k < S; ++k) {
+            const int64_t d0 = t[6 * k], row = t[6 * k + 1], s0 = t[6 * k + 2], len = t[6 * k + 3], fi = t[6 * k + 4], fo = t[6 * k + 5];
+            F5_REQUIRE(d0 >= 0 && row >= 0 && s0 >= 0 && len >= 0 && fi >= 0 && fo >= 0,
+                       "wave_join: row %d segment %d has a negative field (%lld, %lld, %lld, %lld, %lld, %lld)", q, k, (long long)d0,
+                       (long long)row, (long long)s0, (long long)len, (long long)fi, (long long)fo);
+            F5_REQUIRE(row < R, "wave_join: row %d segment %d names source row %lld, but R = %d", q, k, (long long)row, R);
+            F5_REQUIRE(s0 + len <= Ls, "wave_join: row %d segment %d reads source samples [%lld, %lld), outside [0, %lld]", q, k,
+                       (long long)s0, (long long)(s0 + len), (long long)Ls);
+            F5_REQUIRE(fi <= WJ_FADE_MAX && fo <= WJ_FADE_MAX, "wave_join: row %d segment %d has a fade longer than 2^22 samples (%lld, %lld)",
+                       q, k, (long long)fi, (long long)fo);
+            F5_REQUIRE(fi + fo <= len, "wave_join: row %d segment %d is %lld samples long, shorter than its fades of %lld + %lld", q, k,
+                       (long long)len, (long long)fi, (long long)fo);
+            if (len == 0) continue;                                 // an empty entry covers nothing and takes no part in the order
+            F5_REQUIRE(d0 + len <= Lout, "wave_join: row %d segment %d ends at %lld, beyond the row length Lout = %lld", q, k,
+                       (long long)(d0 + len), (long long)Lout);
+            if (prev >= 0) {
+                const int64_t p0 = t[6 * prev], p1 = p0 + t[6 * prev + 3], pfo = t[6 * prev + 5];
+                F5_REQUIRE(d0 >= p0, "wave_join: row %d segment %d begins at %lld, before segment %d at %lld: the table must be sorted by dst_begin",
+                           q, k, (long long)d0, prev, (long long)p0);
+                // a pure cross-fade: the last F samples of one segment are the first F of the next, F = its fade-out = the other's
+                // fade-in.  With fade_in + fade_out <= len on both sides no third segment can reach such a sample.
+                F5_REQUIRE(d0 >= p1 || (p1 - d0 == pfo && p1 - d0 == fi),
+                           "wave_join: row %d segments %d and %d overlap by %lld samples, which is not a pure cross-fade (fade_out %lld, fade_in %lld)",
+                           q, prev, k, (long long)(p1 - d0), (long long)pfo, (long long)fi);
+            }
+            prev = k;
+        }
+    }
+    if (Lout == 0) return 0;
+    const int rows_max = WJ_WORDS / (6 * S);
+    for (int q0 = 0; q0 < Q; q0 += rows_max) {
+        const int rows = Q - q0 < rows_max ? Q - q0 : rows_max;
+        F5WaveJoinTable t;
+        memcpy(t.w, segs_host + (size_t)q0 * S * 6, (size_t)rows * S * 6 * sizeof(int));
+        hipLaunchKernelGGL(wave_join_kernel, dim3((unsigned)((Lout + 255) / 256), (unsigned)rows), dim3(256), 0, (hipStream_t)stream, src,
+                           R, (long)Ls, t, S, out + (size_t)q0 * Lout, (long)Lout);
+    }
+    F5_LAUNCH_CHECK();
+    return 0;
+}

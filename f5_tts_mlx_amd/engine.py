@@ -179,6 +179,8 @@ def load_library() -> C.CDLL:
             getattr(lib, name).argtypes = types
     lib.f5_op_wave_patch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int,
                                      C.c_int, C.c_void_p]
+    if hasattr(lib, "f5_wave_join"):                      # absent from an older build named by F5TTS_HIP_LIB: a call on it raises
+        lib.f5_wave_join.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
     lib.f5_wave_block_energy.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.f5_mel_spectrogram_ragged.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]

@@ -83,6 +83,52 @@ def _takes_lens(vocoder) -> bool:
         return False
 
 
+JOIN_KEYS = ("cross_fade_ms", "sentence_pause_ms", "trim_sentence_db")
+
+
+def _join_value(v, name: str, what: str = ""):
+    """one sentence-join setting: None, or a finite number that is not negative (the two durations) or is below 0 (the trim level);
+    ValueError naming the argument (and, through `what`, the request)"""
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+        raise ValueError(f"{what}{name} must be a finite number, got {v!r}")
+    if name == "trim_sentence_db":
+        if not v < 0:
+            raise ValueError(f"{what}{name} must be below 0 dB, got {v!r}")
+    elif v < 0:
+        raise ValueError(f"{what}{name} must not be negative, got {v!r}")
+    return float(v)
+
+
+def join_options(cross_fade_ms, sentence_pause_ms, trim_sentence_db, n_requests: Optional[int] = None):
+    """The three sentence-join arguments of generate() / generate_many() (docs/sentence_joins.md) -> None when none of them is set: the
+    call is then the call it was, and nothing of the join is reached.  Otherwise the keyword arguments of audio.join_rows.  With
+    n_requests (generate_many) each argument may also be a list with one value per request (None = not set for that request)."""
+    given = dict(zip(JOIN_KEYS, (cross_fade_ms, sentence_pause_ms, trim_sentence_db)))
+    out = {}
+    for name, v in given.items():
+        if n_requests is not None and isinstance(v, (list, tuple)):
+            if len(v) != n_requests:
+                raise ValueError(f"{name}: expected one value or one per request ({n_requests}), got {len(v)}")
+            out[name] = [_join_value(x, name, f"request {i}: ") for i, x in enumerate(v)]
+            if all(x is None for x in out[name]):
+                out[name] = None
+        else:
+            out[name] = _join_value(v, name)
+    if all(v is None for v in out.values()):
+        return None
+    return dict(cross_fade_ms=out["cross_fade_ms"] or 0, pause_ms=out["sentence_pause_ms"] or 0, trim_db=out["trim_sentence_db"])
+
+
+def _padded_rows(rows):
+    """1-D waves of different lengths -> one zero-padded [R, longest] buffer"""
+    buf = torch.zeros((len(rows), max(max(int(r.shape[0]) for r in rows), 1)), dtype=torch.float32, device=rows[0].device)
+    for i, r in enumerate(rows):
+        buf[i, :r.shape[0]] = r
+    return buf
+
+
 def generate(
     generation_text: str,
     duration: Optional[float] = None,
@@ -105,6 +151,9 @@ def generate(
     vocode_batched: bool = False,           # extension: with batch_sentences, ONE ragged vocoder call instead of one per sentence
     audio_cfg_strength: Optional[float] = None,   # extension (dual guidance, docs/dual_guidance.md): speaker strength; `cfg_strength` is
                                             # then the text strength.  None = the single-knob call: sample() gets no new keyword
+    cross_fade_ms: Optional[float] = None,  # extension (sentence joins, docs/sentence_joins.md): linear cross-fade between sentences
+    sentence_pause_ms: Optional[float] = None,   # extension: silence between sentences; the sentences then fade to and from it
+    trim_sentence_db: Optional[float] = None,    # extension: cut leading / trailing near-silence below this level off every sentence
 ):
     """generate.py:113-245.  `batch_sentences=True` (opt-in, no reference counterpart; SURVEY.md section 8(f)2 names it as the point of
     owning the app loop): the sentences of a multi-sentence text are sampled as one ragged batch -- one `sample()` call, one set of
@@ -124,7 +173,16 @@ def generate(
     and that wave is what is returned and written.  The converter (audio.resample) is a Hann-windowed sinc polyphase filter with
     6 zero crossings and a roll-off of 0.99: the design of torchaudio's default `resample`, which the PyTorch F5-TTS front end
     applies to its reference audio.  It is a short filter and its stop band is modest: docs/resample.md records the figures (a
-    14 kHz tone at 48 kHz comes through the conversion to 24 kHz about 22 dB down, a 10 kHz tone at 24 kHz -> 16 kHz about 45 dB)."""
+    14 kHz tone at 48 kHz comes through the conversion to 24 kHz about 22 dB down, a 10 kHz tone at 24 kHz -> 16 kHz about 45 dB).
+
+    Sentence joins (opt-in, docs/sentence_joins.md): `cross_fade_ms`, `sentence_pause_ms` and `trim_sentence_db` (all None: the code
+    above, unchanged, and nothing of the join is called).  With any of them set the decoded sentences, reference part included, go as
+    rows of one padded buffer to audio.join_rows: an optional edge trim per sentence (-42 is the customary level), then one
+    f5_wave_join launch that lays them out with linear cross-fades (no pause) or fades to and from a pause.  A single-sentence text
+    goes through it only for the trim.  ValueError before any launch for a negative or non-finite value and a trim level not below 0."""
+    join = None                                                       # all three unset: nothing of the join is called
+    if cross_fade_ms is not None or sentence_pause_ms is not None or trim_sentence_db is not None:
+        join = join_options(cross_fade_ms, sentence_pause_ms, trim_sentence_db)
     if output_sample_rate is not None:
         output_sample_rate = _audio._rate(output_sample_rate, "output_sample_rate")
     if f5tts is None:
@@ -157,11 +215,17 @@ def generate(
     is_single_generation = len(sentences) <= 1 or duration is not None
     dual_kw = {} if audio_cfg_strength is None else dict(audio_cfg_strength=_strength(audio_cfg_strength, "audio_cfg_strength"))
 
-    def run(text_for_model, dur):
+    def run(text_for_model, dur, whole=False):
         wave, _ = f5tts.sample(audio[None], text=text_for_model, duration=dur, steps=steps, method=method, speed=speed,
                                cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed, **dual_kw)
         wave = wave.reshape(-1) if wave.ndim > 1 and wave.shape[0] == 1 else wave
-        return wave[audio.shape[0]:]                                  # trim the reference by SAMPLES (generate.py:183)
+        return wave if whole else wave[audio.shape[0]:]               # trim the reference by SAMPLES (generate.py:183)
+
+    def joined(rows, ends):
+        """decoded rows [R, L] (reference part included; row r ends at ends[r]) -> the one wave of this call"""
+        n_ref = audio.shape[0]
+        waves, out_lens = _audio.join_rows(rows, [min(n_ref, e) for e in ends], [max(e - n_ref, 0) for e in ends], [0] * len(ends), **join)
+        return waves[0, :out_lens[0]]
 
     start_date = datetime.datetime.now()
     if is_single_generation:
@@ -170,7 +234,11 @@ def generate(
         elif estimate_duration:
             duration = int(estimated_duration(audio, ref_audio_text, generation_text, speed) * FRAMES_PER_SEC)
         text = convert_char_to_pinyin([ref_audio_text + " " + generation_text])
-        wave = run(text, duration)
+        if join is not None and join["trim_db"] is not None:          # one sentence: a one-segment layout, for the trim alone
+            wave = run(text, duration, whole=True)
+            wave = joined(wave[None], [wave.shape[0]])
+        else:
+            wave = run(text, duration)
     elif batch_sentences:
         # every sentence gets the reference mel as conditioning and its own duration; sample() pads to the longest (cfm.py:319-321)
         texts = convert_char_to_pinyin([ref_audio_text + " " + t for t in sentences])
@@ -194,7 +262,13 @@ def generate(
         frames = f5tts.last_durations                                 # per-element frame counts after the clamps of cfm.py:317-318
         if vocode_batched and _takes_lens(voc):
             waves = voc(mel, lens=frames)                             # (sentences, 256 * (N - 1)), row i zero past its own frames
-            wave = torch.cat([waves[i, audio.shape[0]:HOP_LENGTH * (int(frames[i]) - 1)] for i in range(len(sentences))], dim=0)
+            if join is not None:
+                wave = joined(waves, [HOP_LENGTH * (int(f) - 1) for f in frames])
+            else:
+                wave = torch.cat([waves[i, audio.shape[0]:HOP_LENGTH * (int(frames[i]) - 1)] for i in range(len(sentences))], dim=0)
+        elif join is not None:
+            rows = [voc(mel[i:i + 1, :int(frames[i])]).reshape(-1) for i in range(len(sentences))]
+            wave = joined(_padded_rows(rows), [int(r.shape[0]) for r in rows])
         else:
             wave = torch.cat([voc(mel[i:i + 1, :int(frames[i])]).reshape(-1)[audio.shape[0]:] for i in range(len(sentences))], dim=0)
     else:
@@ -205,8 +279,11 @@ def generate(
             elif estimate_duration:                                   # quirk kept: uses the WHOLE text (generate.py:208)
                 duration = int(estimated_duration(audio, ref_audio_text, generation_text, speed) * FRAMES_PER_SEC)
             text = convert_char_to_pinyin([ref_audio_text + " " + sentence_text])
-            output.append(run(text, duration))
-        wave = torch.cat(output, dim=0)
+            output.append(run(text, duration, whole=join is not None))
+        if join is not None:
+            wave = joined(_padded_rows(output), [int(r.shape[0]) for r in output])
+        else:
+            wave = torch.cat(output, dim=0)
 
     if wave.is_cuda:
         torch.cuda.synchronize()
@@ -307,6 +384,9 @@ def generate_many(
     output_sample_rate: Optional[int] = None,
     controls=None,
     audio_cfg_strength: Optional[float] = None,
+    cross_fade_ms=None,
+    sentence_pause_ms=None,
+    trim_sentence_db=None,
 ):
     """Many voices in one call (no reference counterpart; docs/multi_voice.md).  requests: a list of (generation_text, ref_audio_path or
     None, ref_audio_text); None = the bundled sample and its text.  -> a list of waves, one per request, in order.
@@ -327,14 +407,25 @@ def generate_many(
     with cfg_strength as the text strength.  sample() gets the keyword (one value per row) only when the call or some request sets it; a
     row whose request does not set it, in a call that does not either, gets its own cfg_strength (the single-knob rule for that row).
 
+    cross_fade_ms, sentence_pause_ms, trim_sentence_db (docs/sentence_joins.md; all None: the assembly above, unchanged): each one value
+    for the call or a list with one per request (None = not set for that request).  With any of them set the decoded rows go to
+    audio.join_rows -- an optional edge trim per sentence, then ONE f5_wave_join launch for all requests: linear cross-fades between
+    the sentences of a request, or fades to and from a pause -- and `output_sample_rate` becomes ONE resample call on the padded
+    result, each request sliced to its own length: the bits of resampling each request by itself, since the filter treats everything
+    outside a wave as zero and the padding is exactly zero.
+
     It equals prepare_references -> sample(mel, text, durations, lens=frames) -> the decode -> the same slices, bit for bit; it does
     NOT equal a loop of generate() calls bit for bit (the batch has a key-padding mask, GRN and the conv position embedding see the
     padding, and the gain is fp64 arithmetic on fp32 block sums instead of torch's fp32 mean).
     ValueError before any launch, naming the request: an empty list, a request without text, a reference recording without a
-    transcript, a reference at a rate the resampler refuses, a `controls` list of the wrong length or with an unknown key."""
+    transcript, a reference at a rate the resampler refuses, a `controls` list of the wrong length or with an unknown key, a join
+    setting that is negative or not finite, a trim level not below 0."""
     requests = list(requests)
     if not requests:
         raise ValueError("generate_many needs at least one request")
+    join = None                                                       # all three unset: nothing of the join is called
+    if cross_fade_ms is not None or sentence_pause_ms is not None or trim_sentence_db is not None:
+        join = join_options(cross_fade_ms, sentence_pause_ms, trim_sentence_db, len(requests))
     call_level = dict(cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed, speed=speed)
     if audio_cfg_strength is not None:
         call_level[AUDIO_CFG_KEY] = _strength(audio_cfg_strength, AUDIO_CFG_KEY)
@@ -393,17 +484,29 @@ def generate_many(
     finally:
         f5tts._vocoder = voc
     frames = f5tts.last_durations                                     # per-row frame counts after the clamps of cfm.py:317-318
-    if _takes_lens(voc):
-        decoded = voc(mel, lens=frames)                               # (rows, 256 * (N - 1)), row r zero past its own frames
-        rows = [decoded[r, refs.samples[i]:HOP_LENGTH * (int(frames[r]) - 1)] for r, i in enumerate(row_req)]
+    if join is not None:
+        if _takes_lens(voc):
+            decoded = voc(mel, lens=frames)
+            ends = [HOP_LENGTH * (int(f) - 1) for f in frames]
+        else:
+            rows = [voc(mel[r:r + 1, :int(frames[r])]).reshape(-1) for r in range(len(row_req))]
+            decoded, ends = _padded_rows(rows), [int(r.shape[0]) for r in rows]
+        n_ref = [refs.samples[i] for i in row_req]
+        joined, out_lens = _audio.join_rows(decoded, [min(b, e) for b, e in zip(n_ref, ends)], [max(e - b, 0) for b, e in zip(n_ref, ends)],
+                                            row_req, **join)
+        out = _audio.resample_rows(joined, out_lens, SAMPLE_RATE, output_sample_rate or SAMPLE_RATE)
     else:
-        rows = [voc(mel[r:r + 1, :int(frames[r])]).reshape(-1)[refs.samples[i]:] for r, i in enumerate(row_req)]
-    out = []
-    for i in range(len(requests)):
-        wave = torch.cat([rows[r] for r, q in enumerate(row_req) if q == i], dim=0)
-        if output_sample_rate is not None and output_sample_rate != SAMPLE_RATE:
-            wave = _audio.resample(wave, SAMPLE_RATE, output_sample_rate)[0]
-        out.append(wave)
+        if _takes_lens(voc):
+            decoded = voc(mel, lens=frames)                           # (rows, 256 * (N - 1)), row r zero past its own frames
+            rows = [decoded[r, refs.samples[i]:HOP_LENGTH * (int(frames[r]) - 1)] for r, i in enumerate(row_req)]
+        else:
+            rows = [voc(mel[r:r + 1, :int(frames[r])]).reshape(-1)[refs.samples[i]:] for r, i in enumerate(row_req)]
+        out = []
+        for i in range(len(requests)):
+            wave = torch.cat([rows[r] for r, q in enumerate(row_req) if q == i], dim=0)
+            if output_sample_rate is not None and output_sample_rate != SAMPLE_RATE:
+                wave = _audio.resample(wave, SAMPLE_RATE, output_sample_rate)[0]
+            out.append(wave)
     if out[0].is_cuda:
         torch.cuda.synchronize()
     total = sum(w.shape[0] for w in out) / (output_sample_rate or SAMPLE_RATE)
@@ -426,11 +529,39 @@ def read_requests(path):
                 raise ValueError(f"{path}:{no}: not a JSON object ({exc.msg})") from None
             if not isinstance(obj, dict) or not isinstance(obj.get("text"), str):
                 raise ValueError(f'{path}:{no}: expected an object with a "text" string')
-            unknown = set(obj) - {"text", "ref_audio", "ref_text", "output"} - {"cfg", "sway_coef", "seed", "speed", "audio_cfg"}
+            unknown = set(obj) - {"text", "ref_audio", "ref_text", "output"} - {"cfg", "sway_coef", "seed", "speed", "audio_cfg"} - set(JOIN_FILE_KEYS)
             if unknown:
                 raise ValueError(f"{path}:{no}: unknown key(s) {sorted(unknown)}")
             reqs.append({k: obj.get(k) for k in ("text", "ref_audio", "ref_text", "output")})
     return reqs
+
+
+JOIN_FILE_KEYS = {"cross_fade_ms": "cross_fade_ms", "pause_ms": "sentence_pause_ms", "trim_db": "trim_sentence_db"}
+
+
+def read_request_joins(path):
+    """The optional per-request sentence-join settings of a --requests file: the keys "cross_fade_ms", "pause_ms" and "trim_db" of every
+    line (same lines as read_requests, which ignores them) -> a dict for generate_many(**...) with, for every setting some line sets, a
+    list with one value per request (None where a line leaves it out); empty when no line sets any.  ValueError naming file and line for
+    a value join_options would refuse."""
+    import json
+    cols = {name: [] for name in JOIN_FILE_KEYS.values()}
+    with open(path, encoding="utf-8") as f:
+        for no, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            try:
+                obj = json.loads(line)
+            except json.JSONDecodeError as exc:
+                raise ValueError(f"{path}:{no}: not a JSON object ({exc.msg})") from None
+            if not isinstance(obj, dict):
+                raise ValueError(f"{path}:{no}: expected an object")
+            for key, name in JOIN_FILE_KEYS.items():
+                try:
+                    cols[name].append(_join_value(obj.get(key), name))
+                except ValueError as exc:
+                    raise ValueError(f'{path}:{no}: "{key}": {exc}') from None
+    return {name: v for name, v in cols.items() if any(x is not None for x in v)}
 
 
 def read_request_controls(path):
@@ -503,6 +634,12 @@ def parse_args(argv=None):
                          "left out: the bundled sample); excludes --text and --output")
     ap.add_argument("--trim-silence", type=float, default=None, metavar="DB",
                     help="with --requests: cut leading and trailing silence below DB dB off every reference (-42 is customary; default: cut nothing)")
+    ap.add_argument("--cross-fade-ms", type=float, default=None, metavar="MS",
+                    help="linear cross-fade of MS milliseconds between the sentences of a text (default: plain concatenation)")
+    ap.add_argument("--sentence-pause-ms", type=float, default=None, metavar="MS",
+                    help="MS milliseconds of silence between sentences; with --cross-fade-ms the sentences fade to and from it")
+    ap.add_argument("--trim-sentence-db", type=float, default=None, metavar="DB",
+                    help="cut leading and trailing near-silence below DB dB off every generated sentence (-42 is customary)")
     ns = ap.parse_args(argv)
     if ns.requests is not None:
         for flag, value in (("--text", ns.text), ("--output", ns.output), ("--ref-audio", ns.ref_audio), ("--ref-text", ns.ref_text),
@@ -519,12 +656,16 @@ def main(argv=None):
     if ns.requests is not None:
         reqs = read_requests(ns.requests)
         controls = read_request_controls(ns.requests)
+        joins = dict(cross_fade_ms=ns.cross_fade_ms, sentence_pause_ms=ns.sentence_pause_ms, trim_sentence_db=ns.trim_sentence_db)
+        for name, per_req in read_request_joins(ns.requests).items():  # a line's own value goes before the flag's
+            joins[name] = [joins[name] if v is None else v for v in per_req]
+        joins = {k: v for k, v in joins.items() if v is not None}
         waves = generate_many([(r["text"], r["ref_audio"], r["ref_text"]) for r in reqs], steps=ns.steps, method=ns.method,
                               cfg_strength=ns.cfg, sway_sampling_coef=ns.sway_coef, speed=ns.speed, seed=ns.seed,
                               estimate_duration=ns.estimate_duration, model_name=ns.model, quantization_bits=ns.q,
                               trim_silence_db=ns.trim_silence, output_sample_rate=ns.output_rate,
                               controls=controls if any(c is not None for c in controls) else None,
-                              **({} if ns.audio_cfg is None else dict(audio_cfg_strength=ns.audio_cfg)))
+                              **({} if ns.audio_cfg is None else dict(audio_cfg_strength=ns.audio_cfg)), **joins)
         for r, wave in zip(reqs, waves):
             if r["output"] is not None:
                 write_wav(r["output"], wave.detach().cpu().numpy(), ns.output_rate or SAMPLE_RATE)
@@ -542,7 +683,9 @@ def main(argv=None):
              ref_audio_text=ns.ref_text, steps=ns.steps, method=ns.method, cfg_strength=ns.cfg, sway_sampling_coef=ns.sway_coef,
              speed=ns.speed, seed=ns.seed, quantization_bits=ns.q, output_path=ns.output, resample_ref=ns.resample_ref,
              output_sample_rate=ns.output_rate, batch_sentences=ns.batch_sentences, vocode_batched=ns.vocode_batched,
-             **({} if ns.audio_cfg is None else dict(audio_cfg_strength=ns.audio_cfg)))
+             **({} if ns.audio_cfg is None else dict(audio_cfg_strength=ns.audio_cfg)),
+             **{k: v for k, v in (("cross_fade_ms", ns.cross_fade_ms), ("sentence_pause_ms", ns.sentence_pause_ms),
+                                  ("trim_sentence_db", ns.trim_sentence_db)) if v is not None})
 
 
 if __name__ == "__main__":

@@ -616,6 +616,31 @@ int f5_resample_batch(const float* wave, int B, int64_t L, const float* taps, co
 int f5_op_wave_patch(const float* gen, const float* src, const int32_t* segs_host, const float* fade, float* out, int B, int64_t L,
                      int64_t Ls, int S, int F, void* stream);
 
+/* Sentence join (no reference counterpart; the last step of generate() / generate_many() when edge trim, pauses or cross-fades between
+ * sentences are asked for): ONE call lays Q output waves out from R decoded rows.  src dev [R][Ls] (the decoded rows), out dev [Q][Lout];
+ * segs_host host int32 [Q][S][6] = (dst_begin, src_row, src_begin, len, fade_in, fade_out) in samples -- staged to the device through
+ * kernel arguments like f5_op_wave_patch's table, in chunks of output rows when it does not fit one launch (160 segments per launch;
+ * no host buffer outlives the call, no synchronisation).  A row with fewer than S segments pads with len = 0 entries; an empty entry
+ * covers nothing and takes no part in the order.  Segment k of row q covers out[q][dst_begin .. dst_begin + len) =: [d0, d1).
+ * Fade weight: w(i, F) = (float)(2 i + 1) / (float)(2 F), ONE correctly rounded fp32 division of two exactly representable integers
+ * (a linear fade, as in the PyTorch F5-TTS infer_process; no table is handed over, so every join has its own length).  out[q][s]:
+ *   - covered by no segment (between segments, or past the last one): exactly +0.0f;
+ *   - covered by one segment, outside its fades: src[src_row][src_begin + s - d0] by selection: the source's own bits, not 1.0f * x;
+ *   - in the first fade_in samples of a segment, not overlapped: w(i, fade_in) * x, i = s - d0, one fp32 multiplication;
+ *   - in the last fade_out samples of a segment, not overlapped: w(j, fade_out) * x, j = d1 - 1 - s, one fp32 multiplication;
+ *   - covered by segment k (value a) and the next non-empty segment k' (value b): fmaf(w(i, F), b - a, a), i = s - d0[k'] -- ONE fused
+ *     multiply-add on the fp32 difference, the form of f5_op_wave_patch.  Allowed only as a pure cross-fade: fade_out[k] ==
+ *     fade_in[k'] == F and the overlap is exactly those F samples.  w(F - 1 - i, F) = 1 - w(i, F) in the reals: a constant-gain
+ *     cross-fade, each output a convex combination of two samples.
+ * A source sample outside the ranges the table names is never loaded (selected by the index tests, never multiplied by a mask): NaN in
+ * the padding of src stays out of out.
+ * Refused on the host before any launch, each with its own message: null pointers; R or Q outside 1 .. 65 535; S outside 1 .. 64; Ls or
+ * Lout outside 0 .. 2^31 - 1; a negative field; src_row >= R; a source range that leaves [0, Ls]; a fade longer than 2^22 (beyond it
+ * 2 i + 1 and 2 F are no longer exact in fp32); fade_in + fade_out > len; non-empty segments of a row not sorted by dst_begin; a
+ * segment that ends beyond Lout; an overlap that is not the pure cross-fade above (with fade_in + fade_out <= len this also rules out
+ * three segments covering one sample).  Lout = 0 is a successful call without a launch. */
+int f5_wave_join(const float* src, int R, int64_t Ls, const int32_t* segs_host, int Q, int S, float* out, int64_t Lout, void* stream);
+
 /* ---- vocoder: Vocos mel-24khz behind one call (replaces `self._vocoder(out)`, cfm.py:399-400; wiring cfm.py:446,471) ---------
  * The reference delegates to the third-party `vocos_mlx` package (not in its repository); this is the published Vocos
  * architecture (ConvNeXt backbone + ISTFT head) on the same kernels as the DiT.  Same ownership rules as the engine: the caller
