@@ -232,6 +232,8 @@ class F5TTS:
         audio_cfg_strength=None,                 # extension (dual guidance, docs/dual_guidance.md): a scalar or one value per row; with
                                                  # it `cfg_strength` is the TEXT strength (text-only against unconditional) and this the
                                                  # SPEAKER strength (full against text-only); None = the single-knob call, untouched
+        cfg_interval=None,                       # extension (guidance window, docs/guidance_window.md): (lo, hi) or one pair per row; a
+                                                 # row is guided only at evaluations whose time lies in [lo, hi]; None = guided throughout
     ) -> tuple[torch.Tensor, torch.Tensor]:
         self.eval()
         device = self.transformer.device
@@ -260,6 +262,11 @@ class F5TTS:
         if audio_cfg_strength is not None:
             audio_seq, audio_rows = per_row(audio_cfg_strength, batch, "audio_cfg_strength")
             dual_kw["audio_cfg_strength"] = [float(v) for v in audio_rows] if audio_seq else float(audio_cfg_strength)
+        if cfg_interval is not None:
+            window = np.asarray(cfg_interval, dtype=np.float32)
+            if window.shape not in ((2,), (batch, 2)):
+                raise ValueError(f"cfg_interval: expected (lo, hi) or {batch} pairs of shape ({batch}, 2), got shape {window.shape}")
+            dual_kw["cfg_interval"] = window
         if speed_seq:
             speed = [float(v) for v in speed_rows]
         if isinstance(text, list):

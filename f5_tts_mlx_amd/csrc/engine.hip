@@ -82,6 +82,10 @@ struct Workspace {
     size_t rmod = 0;                            // adaLN table [nfe][B][(6L+2) D]
     size_t total_rows = 0;                      // bytes of the plan including the rows part
     int nbr = 2;                                // branches the plan lays out: 2 (cond + null), 3 = dual guidance (F, N, T)
+    // f5_sample_window only (plan_workspace_window; behind `total_rows`): the rows' EFFECTIVE strengths of every evaluation, [nfe][B] floats
+    // each, staged per call; stage j reads row j where the rows / dual calls read the one [B] vector at rcfg / racfg
+    size_t wcfg = 0, wacfg = 0, wtab_words = 0;
+    size_t total_window = 0;                    // bytes of the plan including the tables (0 = not a window plan)
 };
 
 // Per-engine launch options: everything that reaches a kernel as a by-value argument or changes the launch sequence of sample()
@@ -129,6 +133,7 @@ struct f5_engine : WeightStore {
     F5Options opt = g_default_options;
     GraphCache graphs;                // cached hipGraphExecs, at most f5_engine_set_graph_cache (default 8)
     std::vector<std::string> seen;    // signatures sampled once in "auto" graph mode (captured on the second sighting)
+    std::vector<uint8_t> last_pattern; // f5_sample_window: wide (1) / narrow (0) per evaluation of the most recent call (f5_debug_last_sample_pattern)
 };
 
 static int nfe_per_step(int method) { return method == F5_EULER ? 1 : (method == F5_MIDPOINT ? 2 : 4); }
@@ -569,6 +574,28 @@ extern "C" int f5_workspace_bytes_dual(f5_engine* e, int B, int N, int nt, int s
     return 0;
 }
 
+// The rows / dual plan with the effective-strength tables of a guidance window appended (f5_sample_window).
+static Workspace plan_workspace_window(const f5_engine* e, int B, int N, int nt, int steps, int method, bool dual) {
+    Workspace w = plan_workspace_rows(e, B, N, nt, steps, method, dual ? 3 : 2);
+    const int nfe = (steps - 1) * nfe_per_step(method);
+    const size_t rows = (size_t)(nfe > 0 ? nfe : 1) * B;
+    Bump b;
+    b.off = w.total_rows;
+    w.wtab_words = (dual ? 2 : 1) * rows;
+    w.wcfg = b.take(w.wtab_words * 4);
+    w.wacfg = dual ? w.wcfg + rows * 4 : 0;
+    w.total_window = b.off;
+    return w;
+}
+
+extern "C" int f5_workspace_bytes_window(f5_engine* e, int B, int N, int nt, int steps, int method, int dual, size_t* bytes) {
+    F5_REQUIRE(e && bytes, "null argument");
+    F5_REQUIRE(B >= 1 && N >= 1 && steps >= 1, "bad sizes B=%d N=%d steps=%d", B, N, steps);
+    F5_REQUIRE(method >= F5_EULER && method <= F5_RK4, "Unknown method: %d", method);
+    *bytes = plan_workspace_window(e, B, N, nt, steps, method, dual != 0).total_window;
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // launch context
 // ------------------------------------------------------------------------------------------------
@@ -582,6 +609,9 @@ struct Ctx : LaunchView {
     bool rows = false;  // f5_sample_rows / f5_dit_forward_rows: time and guidance strength per batch row (w.r*: plan_workspace_rows)
     bool dual = false;  // f5_sample_dual / f5_dit_forward_dual: the rows route with three branches F, N, T (w.nbr == 3)
     bool use_mask;
+    // f5_sample_window: wide (1) / narrow (0) per evaluation, null = every evaluation runs `nb` branches.  A narrow one runs the
+    // conditional branch alone and its stage takes k = F for every row (the effective strengths at w.wcfg / w.wacfg are 0 there).
+    const uint8_t* pattern = nullptr;
 };
 
 // factor folded into q by the QKV epilogue (0 = none): single-segment operand modes only, see run_dit
@@ -1068,9 +1098,20 @@ static int run_sample_body(const Ctx& c, const f5_sample_args* a, int i0 = 0, in
     float* ytmp = c.p<float>(w.ytmp);
     // per-row controls: every stage reads its row's guidance strength and the step's [B] step sizes
     const float* dt_rows = nullptr;
+    // guidance window: evaluation j reads row j of the effective-strength tables, and a narrow one runs the DiT on a one-branch context
+    const bool win = c.pattern != nullptr;
+    Ctx narrow = c;
+    narrow.nb = 1;
+    int jcur = 0;
+    auto dit = [&](int j) {
+        jcur = j;
+        return run_dit(win && !c.pattern[j] ? narrow : c, j);
+    };
     auto stage = [&](const F5OdeArgs& o) {
-        if (c.dual) return K.ode_stage_dual(o, textp, c.p<float>(w.racfg), c.p<float>(w.rcfg), dt_rows, c.N, c.B, s);
-        return c.rows ? K.ode_stage_rows(o, c.p<float>(w.rcfg), dt_rows, c.N, c.B, s) : K.ode_stage(o, s);
+        const float* cfg_rows = win ? c.p<float>(w.wcfg) + (size_t)jcur * c.B : c.p<float>(w.rcfg);
+        const float* acfg_rows = win ? c.p<float>(w.wacfg) + (size_t)jcur * c.B : c.p<float>(w.racfg);
+        if (c.dual) return K.ode_stage_dual(o, textp, acfg_rows, cfg_rows, dt_rows, c.N, c.B, s);
+        return c.rows ? K.ode_stage_rows(o, cfg_rows, dt_rows, c.N, c.B, s) : K.ode_stage(o, s);
     };
     for (int i = i0; i + 1 < a->steps && i < i1; ++i) {
         if (c.rows) dt_rows = c.p<float>(w.rdt) + (size_t)i * c.B;
@@ -1089,33 +1130,33 @@ static int run_sample_body(const Ctx& c, const f5_sample_args* a, int i0 = 0, in
         o.xin_hi = c.pb(w.xin, 0);
         o.xin_lo = c.pb(w.xin, 1);
         if (a->method == F5_EULER) {
-            RC(run_dit(c, i));
+            RC(dit(i));
             o.coef = 1.0f;
             o.out = ynext;
             RC(stage(o));
         } else if (a->method == F5_MIDPOINT) {
-            RC(run_dit(c, 2 * i));
+            RC(dit(2 * i));
             o.coef = 0.5f;
             o.out = ytmp;
             RC(stage(o));
-            RC(run_dit(c, 2 * i + 1));
+            RC(dit(2 * i + 1));
             o.coef = 1.0f;
             o.out = ynext;
             RC(stage(o));
         } else {
-            RC(run_dit(c, 4 * i));
+            RC(dit(4 * i));
             o.coef = 0.5f;
             o.out = ytmp;
             o.kstore = kst;
             RC(stage(o));
-            RC(run_dit(c, 4 * i + 1));
+            RC(dit(4 * i + 1));
             o.kstore = kst + M1 * mel;
             RC(stage(o));
-            RC(run_dit(c, 4 * i + 2));
+            RC(dit(4 * i + 2));
             o.coef = 1.0f;
             o.kstore = kst + 2 * M1 * mel;
             RC(stage(o));
-            RC(run_dit(c, 4 * i + 3));
+            RC(dit(4 * i + 3));
             o.kstore = nullptr;
             o.mode = 1;
             o.divisor = 6.0f;
@@ -1250,12 +1291,15 @@ static int check_dual_route(const f5_engine* e, const char* what) {
 }
 
 // f5_sample (edit = false), f5_sample_edit (the mask replaces n < lens[b] in the hoisted input packing and the final splice) and
-// f5_sample_rows (rc != null: time grid and guidance strength per batch row) and f5_sample_dual (rc->audio_rows != null as well)
+// f5_sample_rows (rc != null: time grid and guidance strength per batch row) and f5_sample_dual (rc->audio_rows != null as well) and
+// f5_sample_window (rc->lo_rows != null: either of the two with the strengths gated per evaluation by each row's time window)
 struct RowCtl {
     const float* t_rows;
     const float* cfg_rows;      // the text strength of dual guidance
     const float* audio_rows;    // null = f5_sample_rows
     const char* what;           // the entry point, for messages
+    const float* lo_rows = nullptr;   // f5_sample_window: each row's guidance window [lo, hi] on its own evaluation times (null = no window)
+    const float* hi_rows = nullptr;
 };
 static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* cond_keep, bool edit, void* stream,
                        const RowCtl* rc = nullptr) {
@@ -1271,11 +1315,26 @@ static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* con
         for (size_t i = 0; i < (size_t)a->B * a->steps; ++i)
             F5_REQUIRE(std::isfinite(rc->t_rows[i]), "%s: t_rows[%zu][%zu] is not finite", rc->what, i / a->steps, i % a->steps);
         for (int b = 0; b < a->B; ++b)
-            F5_REQUIRE(std::isfinite(rc->cfg_rows[b]), "%s: %s[%d] is not finite", rc->what, dual ? "text_cfg_rows" : "cfg_rows", b);
+            F5_REQUIRE(std::isfinite(rc->cfg_rows[b]), "%s: %s[%d] is not finite", rc->what, (dual || rc->lo_rows) ? "text_cfg_rows" : "cfg_rows", b);
         for (int b = 0; b < a->B && dual; ++b)
             F5_REQUIRE(std::isfinite(rc->audio_rows[b]), "%s: audio_cfg_rows[%d] is not finite", rc->what, b);
+        const bool window = rc->lo_rows != nullptr;
+        for (int b = 0; b < a->B && window; ++b) {
+            F5_REQUIRE(std::isfinite(rc->lo_rows[b]), "%s: lo_rows[%d] is not finite", rc->what, b);
+            F5_REQUIRE(std::isfinite(rc->hi_rows[b]), "%s: hi_rows[%d] is not finite", rc->what, b);
+            F5_REQUIRE(rc->lo_rows[b] <= rc->hi_rows[b], "%s: lo_rows[%d] = %g is above hi_rows[%d] = %g", rc->what, b, rc->lo_rows[b], b,
+                       rc->hi_rows[b]);
+        }
         if (dual) ctx_to_dual(c, a, rc->cfg_rows, rc->audio_rows, a->B);
         else ctx_to_rows(c, a, rc->cfg_rows, a->B);
+        if (window) {
+            F5_REQUIRE(e->opt.ln_fold != 1, "%s: ln_fold = 1: the folded LN cannot run with per-row sampling controls (its constants are per "
+                       "evaluation); use ln_fold = -1 or 0", rc->what);
+            // the branch count of the call is settled below, once the evaluation times say which evaluations are wide
+            c.w = plan_workspace_window(e, a->B, a->N, a->nt, a->steps, a->method, dual);
+            F5_REQUIRE(a->workspace_bytes >= c.w.total_window, "%s: workspace too small: %zu < %zu (f5_workspace_bytes_window)", rc->what,
+                       a->workspace_bytes, c.w.total_window);
+        }
         F5_REQUIRE(a->workspace_bytes >= c.w.total_rows, "%s: workspace too small: %zu < %zu (%s)", rc->what, a->workspace_bytes,
                    c.w.total_rows, dual ? "f5_workspace_bytes_dual" : "f5_workspace_bytes_rows");
         if (ln_fold_state(c) < 0) return 2;
@@ -1286,6 +1345,8 @@ static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* con
     SatScope sat(e->prec == F5_PREC_F16 && e->opt.sat_check, c.p<int>(c.w.status));
 
     std::vector<float> tnfe, dts;
+    std::vector<uint8_t> pattern;       // f5_sample_window: wide / narrow per evaluation
+    std::vector<uint32_t> wtab;         // ... and the effective strengths, [nfe][B] text (| [nfe][B] audio)
     if (rc) {
         // every row's own grid through the same fp32 arithmetic, laid out [nfe][B] / [steps - 1][B]; the scalar slots get row 0's
         const int nfe = (a->steps - 1) * nfe_per_step(a->method);
@@ -1304,8 +1365,32 @@ static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* con
         }
         memcpy(rd + (size_t)a->steps * c.B, rc->cfg_rows, (size_t)c.B * 4);
         if (c.dual) memcpy(rd + (size_t)a->steps * c.B + c.B, rc->audio_rows, (size_t)c.B * 4);
+        if (rc->lo_rows) {
+            // a row's strengths count at evaluation j when lo <= t_eval[j][b] <= hi on the fp32 time staged above (both ends inclusive), else
+            // they are 0; an evaluation is wide when any row is left with a strength >= 1e-5 (the test of ctx_to_rows / ctx_to_dual)
+            const size_t rows = (size_t)(nfe > 0 ? nfe : 1) * c.B;
+            wtab.assign(c.w.wtab_words, 0u);
+            float* wt = reinterpret_cast<float*>(wtab.data());
+            float* wa = c.dual ? wt + rows : nullptr;
+            pattern.assign((size_t)nfe, 0);
+            bool any_wide = false;
+            for (int j = 0; j < nfe; ++j)
+                for (int b = 0; b < c.B; ++b) {
+                    const float tj = rt[(size_t)j * c.B + b];
+                    const bool in = rc->lo_rows[b] <= tj && tj <= rc->hi_rows[b];
+                    const float ct = in ? rc->cfg_rows[b] : 0.0f, ca = (in && c.dual) ? rc->audio_rows[b] : 0.0f;
+                    wt[(size_t)j * c.B + b] = ct;
+                    if (wa) wa[(size_t)j * c.B + b] = ca;
+                    if (!(ct < 1e-5f) || (c.dual && !(ca < 1e-5f))) pattern[j] = 1;
+                    any_wide = any_wide || pattern[j];
+                }
+            c.nb = any_wide ? (c.dual ? 3 : 2) : 1;
+            c.pattern = pattern.data();
+            e->last_pattern = pattern;
+        }
         RC(stage_inputs(c, a, nullptr, tnfe, dts));
         RC(f5_launch_stage_words(words.data(), words.size(), c.p<uint32_t>(c.w.rscal), s));
+        if (rc->lo_rows) RC(f5_launch_stage_words(wtab.data(), wtab.size(), c.p<uint32_t>(c.w.wcfg), s));
     } else {
         eval_times(a->t, a->steps, a->method, tnfe, dts);
         RC(stage_inputs(c, a, nullptr, tnfe, dts));
@@ -1320,6 +1405,17 @@ static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* con
              a->method, c.nb, (int)c.use_mask, (int)c.edit, (int)c.rows, (int)c.dual, g_knob_epoch, a->workspace);
     std::string key(shape_key);
     for (const OptDesc& o : k_options) key += " " + std::to_string(e->opt.*o.member);
+    if (c.pattern) {
+        // the wide / narrow pattern decides which evaluations run one branch: structural, so part of the key (nfe bits as hex); the
+        // strengths and bounds behind it are staged values and are not
+        key += " win";
+        static const char hex[] = "0123456789abcdef";
+        for (size_t j = 0; j < pattern.size(); j += 4) {
+            int v = 0;
+            for (size_t k = j; k < j + 4 && k < pattern.size(); ++k) v |= pattern[k] << (k - j);
+            key += hex[v];
+        }
+    }
     const bool graph_on = a->use_graph == F5_GRAPH_ON, graph_auto = a->use_graph == F5_GRAPH_AUTO;
     GraphCache::Entry* entry = (graph_on || graph_auto) ? e->graphs.find(key, a->workspace) : nullptr;
     bool graph = graph_on || entry != nullptr;
@@ -1369,6 +1465,23 @@ extern "C" int f5_sample_dual(f5_engine* e, const f5_sample_args* a, const f5_du
     F5_REQUIRE(dc->audio_cfg_rows != nullptr, "f5_sample_dual: controls.audio_cfg_rows is null");
     const RowCtl ctl = {dc->t_rows, dc->text_cfg_rows, dc->audio_cfg_rows, "f5_sample_dual"};
     return sample_impl(e, a, dc->cond_keep_dev, dc->cond_keep_dev != nullptr, stream, &ctl);
+}
+
+extern "C" int f5_sample_window(f5_engine* e, const f5_sample_args* a, const f5_window_controls* wc, void* stream) {
+    F5_REQUIRE(wc != nullptr, "f5_sample_window: controls is null");
+    F5_REQUIRE(wc->t_rows != nullptr, "f5_sample_window: controls.t_rows is null");
+    F5_REQUIRE(wc->text_cfg_rows != nullptr, "f5_sample_window: controls.text_cfg_rows is null");
+    F5_REQUIRE(wc->lo_rows != nullptr, "f5_sample_window: controls.lo_rows is null");
+    F5_REQUIRE(wc->hi_rows != nullptr, "f5_sample_window: controls.hi_rows is null");
+    const RowCtl ctl = {wc->t_rows, wc->text_cfg_rows, wc->audio_cfg_rows, "f5_sample_window", wc->lo_rows, wc->hi_rows};
+    return sample_impl(e, a, wc->cond_keep_dev, wc->cond_keep_dev != nullptr, stream, &ctl);
+}
+extern "C" int f5_debug_last_sample_pattern(f5_engine* e, int* nfe, uint8_t* wide, int cap) {
+    F5_REQUIRE(e && nfe, "null argument");
+    F5_REQUIRE(cap == 0 || wide, "f5_debug_last_sample_pattern: wide is null with cap = %d", cap);
+    *nfe = (int)e->last_pattern.size();
+    for (int j = 0; j < cap && j < *nfe; ++j) wide[j] = e->last_pattern[j];
+    return 0;
 }
 
 // Status word of the last f5_sample / f5_dit_forward that used this workspace (its FIRST 32-bit word, for every shape and solver):

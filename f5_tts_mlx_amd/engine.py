@@ -81,13 +81,44 @@ class F5DualControls(C.Structure):
     _fields_ = [("t_rows", C.c_void_p), ("text_cfg_rows", C.c_void_p), ("audio_cfg_rows", C.c_void_p), ("cond_keep_dev", C.c_void_p)]
 
 
-def row_controls(t, cfg_strength, B: int, audio_cfg_strength=None):
+class F5WindowControls(C.Structure):
+    _fields_ = [("t_rows", C.c_void_p), ("text_cfg_rows", C.c_void_p), ("audio_cfg_rows", C.c_void_p), ("lo_rows", C.c_void_p),
+                ("hi_rows", C.c_void_p), ("cond_keep_dev", C.c_void_p)]
+
+
+class WindowRows(tuple):
+    """The per-row controls of a call with a guidance window: the (t_rows, cfg_rows[, audio_rows]) tuple of row_controls with the rows'
+    window bounds beside it, `window` = (lo_rows (B,) fp32, hi_rows (B,) fp32).  Its length still says single (2) or dual (3) guidance."""
+    window = None
+
+
+def window_rows(cfg_interval, B: int):
+    """`cfg_interval` of a sample() call -- one (lo, hi) pair or a (B, 2) array, one pair per row -- as (lo_rows, hi_rows), (B,) fp32 each.
+    Shape only: the values (finite, lo <= hi) are checked by the C call and, with a request's name, by generate.py."""
+    w = np.asarray(cfg_interval, dtype=np.float32)
+    if w.shape not in ((2,), (B, 2)):
+        raise ValueError(f"cfg_interval: expected (lo, hi) or {B} pairs of shape ({B}, 2), got shape {w.shape}")
+    w = np.broadcast_to(w, (B, 2))
+    return np.ascontiguousarray(w[:, 0]), np.ascontiguousarray(w[:, 1])
+
+
+def row_controls(t, cfg_strength, B: int, audio_cfg_strength=None, cfg_interval=None):
     """Per-row sampling controls of a sample() call (f5_sample_rows): `t` may be a (steps,) grid or one grid per row (B, steps),
     `cfg_strength` a float or a length-B sequence.  Either one being per-row selects the rows route and the other is broadcast.
     -> (steps, None) for an all-scalar call, else (steps, (t_rows (B, steps) fp32, cfg_rows (B,) fp32)), both C-contiguous.
     audio_cfg_strength (a float or a length-B sequence; docs/dual_guidance.md): dual guidance, f5_sample_dual -- always the per-row form,
-    whatever the values are, with a third entry audio_rows (B,) fp32; `cfg_strength` is then the text strength."""
+    whatever the values are, with a third entry audio_rows (B,) fp32; `cfg_strength` is then the text strength.
+    cfg_interval ((lo, hi) or (B, 2); docs/guidance_window.md): guidance window, f5_sample_window -- always the per-row form too, returned
+    as a WindowRows whose `window` holds (lo_rows, hi_rows)."""
     t = np.asarray(t, dtype=np.float32)
+    if cfg_interval is not None:
+        window = window_rows(cfg_interval, B)
+        if t.ndim == 1:
+            t = np.broadcast_to(t, (B, t.shape[0]))
+        steps, rows = row_controls(t, cfg_strength, B, audio_cfg_strength)
+        rows = WindowRows(rows)
+        rows.window = window
+        return steps, rows
     cfg_seq = np.ndim(cfg_strength) != 0
     if t.ndim not in (1, 2):
         raise ValueError(f"t must be (steps,) or (B, steps), got shape {t.shape}")
@@ -123,9 +154,21 @@ def _audio_slice(audio_cfg_strength, b0: int, b1: int):
     return list(np.asarray(audio_cfg_strength, dtype=np.float32)[b0:b1])
 
 
+def _window_slice(cfg_interval, b0: int, b1: int):
+    """The guidance windows of batch rows [b0, b1): None and a single pair pass through."""
+    if cfg_interval is None or np.ndim(cfg_interval) == 1:
+        return cfg_interval
+    return np.asarray(cfg_interval, dtype=np.float32)[b0:b1]
+
+
 def _plan_of(rows):
-    """The workspace plan a call's controls need (Engine.workspace `rows`): False, True (per-row) or "dual"."""
-    return False if rows is None else ("dual" if len(rows) == 3 else True)
+    """The workspace plan a call's controls need (Engine.workspace `rows`): False, True (per-row), "dual", or with a guidance window
+    "window" / "window_dual"."""
+    if rows is None:
+        return False
+    if getattr(rows, "window", None) is not None:
+        return "window_dual" if len(rows) == 3 else "window"
+    return "dual" if len(rows) == 3 else True
 
 
 def library_path() -> Path:
@@ -164,6 +207,10 @@ def load_library() -> C.CDLL:
                         # dual guidance (docs/dual_guidance.md)
                         ("f5_sample_dual", [C.c_void_p] * 4), ("f5_dit_forward_dual", [C.c_void_p] * 8),
                         ("f5_workspace_bytes_dual", [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+                        # guidance window (docs/guidance_window.md)
+                        ("f5_sample_window", [C.c_void_p] * 4),
+                        ("f5_workspace_bytes_window", [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+                        ("f5_debug_last_sample_pattern", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
                         ("f5_op_ode_stage_dual", [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 7
                          + [C.c_int, C.c_int, C.c_void_p]),
                         ("f5_op_pack_cond_text_dual", [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
@@ -401,6 +448,14 @@ class Engine:
         if self._sibling is not None:
             self._sibling.set_option(name, value)
 
+    def last_sample_pattern(self) -> np.ndarray:
+        """Wide (1) / narrow (0) per function evaluation of this handle's most recent f5_sample_window call (test hook, host bookkeeping)."""
+        nfe = C.c_int(0)
+        check(self.lib.f5_debug_last_sample_pattern(self._h, C.byref(nfe), None, 0), "f5_debug_last_sample_pattern")
+        wide = np.zeros(max(nfe.value, 1), dtype=np.uint8)
+        check(self.lib.f5_debug_last_sample_pattern(self._h, C.byref(nfe), C.c_void_p(wide.ctypes.data), nfe.value), "f5_debug_last_sample_pattern")
+        return wide[:nfe.value]
+
     def _ensure_sibling(self) -> "Engine":
         """A second handle on THIS engine's weights arena (own workspace, own hipGraphs, own status word) and the host thread that drives
         it: the second half batch of a split sample()."""
@@ -436,13 +491,17 @@ class Engine:
     # ---- workspace -------------------------------------------------------------------------
     def workspace(self, B: int, N: int, nt: int, steps: int, method: str, rows=False) -> torch.Tensor:
         """The engine's workspace, grown on demand; rows: the larger plan of the per-row route (f5_workspace_bytes_rows), "dual": the
-        three-branch plan of dual guidance (f5_workspace_bytes_dual)."""
+        three-branch plan of dual guidance (f5_workspace_bytes_dual), "window" / "window_dual": either with the effective-strength tables
+        of a guidance window behind it (f5_workspace_bytes_window)."""
         if method not in METHODS:
             raise ValueError(f"Unknown method: {method}")
         nbytes = C.c_size_t()
-        if isinstance(rows, str):
+        if rows in ("window", "window_dual"):
+            check(self.lib.f5_workspace_bytes_window(self._h, B, N, nt, steps, METHODS[method], int(rows == "window_dual"), C.byref(nbytes)),
+                  "f5_workspace_bytes_window")
+        elif isinstance(rows, str):
             if rows != "dual":
-                raise ValueError(f"rows must be False, True or 'dual', got {rows!r}")
+                raise ValueError(f"rows must be False, True, 'dual', 'window' or 'window_dual', got {rows!r}")
             check(self.lib.f5_workspace_bytes_dual(self._h, B, N, nt, steps, METHODS[method], C.byref(nbytes)), "f5_workspace_bytes_dual")
         elif rows:
             check(self.lib.f5_workspace_bytes_rows(self._h, B, N, nt, steps, METHODS[method], C.byref(nbytes)), "f5_workspace_bytes_rows")
@@ -496,8 +555,14 @@ class Engine:
 
     def _call_sample(self, a, cond_keep, st, rows=None) -> None:
         """f5_sample, f5_sample_edit when the call carries a conditioning mask, f5_sample_rows when it carries per-row controls
-        (rows = (t_rows, cfg_rows) of row_controls; the mask rides in the controls), f5_sample_dual when they carry audio strengths too."""
-        if rows is not None and len(rows) == 3:
+        (rows = (t_rows, cfg_rows) of row_controls; the mask rides in the controls), f5_sample_dual when they carry audio strengths too,
+        f5_sample_window when they carry a guidance window (WindowRows)."""
+        if getattr(rows, "window", None) is not None:
+            lo, hi = rows.window
+            wc = F5WindowControls(rows[0].ctypes.data, rows[1].ctypes.data, rows[2].ctypes.data if len(rows) == 3 else 0, lo.ctypes.data,
+                                  hi.ctypes.data, 0 if cond_keep is None else cond_keep.data_ptr())
+            check(self.lib.f5_sample_window(self._h, C.byref(a), C.byref(wc), st), "f5_sample_window")
+        elif rows is not None and len(rows) == 3:
             dc = F5DualControls(rows[0].ctypes.data, rows[1].ctypes.data, rows[2].ctypes.data, 0 if cond_keep is None else cond_keep.data_ptr())
             check(self.lib.f5_sample_dual(self._h, C.byref(a), C.byref(dc), st), "f5_sample_dual")
         elif rows is not None:
@@ -511,7 +576,8 @@ class Engine:
     def sample(self, text: torch.Tensor, cond: torch.Tensor, lens: Sequence[int], durations: Sequence[int], y0: torch.Tensor,
                t: np.ndarray, method: str = "euler", cfg_strength: float = 2.0, use_mask: Optional[bool] = None,
                use_graph=True, return_trajectory: bool = True, out: Optional[torch.Tensor] = None,
-               trajectory: Optional[torch.Tensor] = None, cond_keep: Optional[torch.Tensor] = None, audio_cfg_strength=None):
+               trajectory: Optional[torch.Tensor] = None, cond_keep: Optional[torch.Tensor] = None, audio_cfg_strength=None,
+               cfg_interval=None):
         """ODE solve on the GPU. cond (B,N,mel) fp32 zero-padded to N=max(durations); text (B,nt) int32
         (-1 padded); y0 (B,N,mel).  use_graph: True / False / "auto" (eager on the first sighting of a shape
         signature, captured hipGraph from the second on).  Per-request controls: `t` may also be (B, steps), one grid per row, and
@@ -521,7 +587,10 @@ class Engine:
         the cross-check, the bf16x3 fall-back and the split halves.  audio_cfg_strength (a float or a length-B sequence; None = today's
         call): dual guidance, f5_sample_dual -- `cfg_strength` is then the TEXT strength (text-only against unconditional) and this the
         SPEAKER strength (full against text-only), k = (F + (F - T) a) + (T - N) c (docs/dual_guidance.md); the call takes that route
-        whatever the values are.  Returns (out (B,N,mel), trajectory (steps,B,N,mel) or None)."""
+        whatever the values are.  cfg_interval ((lo, hi) or a (B, 2) array; None = today's call): guidance window, f5_sample_window -- a
+        row is guided only at evaluations whose time lies in its [lo, hi] (both ends inclusive), and an evaluation in which no row is
+        guided runs the conditional branch alone (docs/guidance_window.md); it follows the call like the dual strengths do.
+        Returns (out (B,N,mel), trajectory (steps,B,N,mel) or None)."""
         if method not in METHODS:
             raise ValueError(f"Unknown method: {method}")
         self._check_inputs(text, cond, lens, durations)
@@ -530,15 +599,15 @@ class Engine:
         if self._use_fallback:                         # an earlier call saturated fp16 / failed its cross-check: bf16x3 from now on
             return self._fallback.sample(text, cond, lens, durations, y0, t, method=method, cfg_strength=cfg_strength, use_mask=use_mask,
                                          use_graph=use_graph, return_trajectory=return_trajectory, out=out, trajectory=trajectory,
-                                         cond_keep=cond_keep, audio_cfg_strength=audio_cfg_strength)
+                                         cond_keep=cond_keep, audio_cfg_strength=audio_cfg_strength, cfg_interval=cfg_interval)
         B, N, mel = cond.shape
-        steps, rows = row_controls(t, cfg_strength, B, audio_cfg_strength)
+        steps, rows = row_controls(t, cfg_strength, B, audio_cfg_strength, cfg_interval)
         assert y0.shape == cond.shape and y0.dtype == torch.float32 and y0.is_contiguous() and y0.is_cuda
         if use_mask is None:
             use_mask = B > 1                       # cfm.py:333-336
         if 0 < self.split_batch <= B and self.verify_calls == 0:
             done = self._sample_split(text, cond, lens, durations, y0, t, steps, method, cfg_strength, use_mask, use_graph,
-                                      return_trajectory, out, trajectory, cond_keep, audio_cfg_strength)
+                                      return_trajectory, out, trajectory, cond_keep, audio_cfg_strength, cfg_interval)
             if done is not None:
                 return done                        # (None: a half reported its status word -- the whole call is repeated below, unsplit)
         ws = self.workspace(B, N, text.shape[1], steps, method, rows=_plan_of(rows))
@@ -557,12 +626,12 @@ class Engine:
         if saturated and self._use_fallback:           # ("sync": re-run THIS call in bf16x3, into the same output buffers)
             return self._fallback.sample(text, cond, lens, durations, y0, t, method=method, cfg_strength=cfg_strength, use_mask=use_mask,
                                          use_graph=use_graph, return_trajectory=return_trajectory, out=out, trajectory=trajectory,
-                                         cond_keep=cond_keep, audio_cfg_strength=audio_cfg_strength)
+                                         cond_keep=cond_keep, audio_cfg_strength=audio_cfg_strength, cfg_interval=cfg_interval)
         if self.verify_calls > 0 and self.precision == "f16" and self._ensure_fallback() is not None:
             self.verify_calls -= 1
             ref, ref_traj = self._fallback.sample(text, cond, lens, durations, y0, t, method=method, cfg_strength=cfg_strength,
                                                   use_mask=use_mask, use_graph=False, return_trajectory=return_trajectory,
-                                                  cond_keep=cond_keep, audio_cfg_strength=audio_cfg_strength)
+                                                  cond_keep=cond_keep, audio_cfg_strength=audio_cfg_strength, cfg_interval=cfg_interval)
             self.last_verify_l1 = l1 = float((out - ref).abs().mean())
             if not (l1 <= self.verify_tol):
                 self.verify_events += 1
@@ -579,7 +648,7 @@ class Engine:
 
     # ---- two half batches on two streams ---------------------------------------------------------
     def _sample_split(self, text, cond, lens, durations, y0, t, steps, method, cfg_strength, use_mask, use_graph, return_trajectory,
-                      out, trajectory, cond_keep=None, audio_cfg_strength=None):
+                      out, trajectory, cond_keep=None, audio_cfg_strength=None, cfg_interval=None):
         """sample() of a large batch as two independent half batches: this engine runs utterances [0, h) on its stream, a sibling handle
         on the same weights arena runs [h, B) on its own, each enqueued by its own host thread (the HIP runtime lets a thread run only a
         few dozen launches ahead of the GPU, so one thread cannot keep two streams fed).  Utterances do not interact (both halves keep
@@ -599,7 +668,7 @@ class Engine:
         for eng, (b0, b1) in ((self, (0, h)), (sib, (h, B))):
             tr = torch.empty((steps, b1 - b0, N, mel), dtype=torch.float32, device=self.device) if return_trajectory else None
             th, ch = _rows_slice(t, cfg_strength, b0, b1)                  # (each half gets its rows of the controls ...)
-            _, rows = row_controls(th, ch, b1 - b0, _audio_slice(audio_cfg_strength, b0, b1))
+            _, rows = row_controls(th, ch, b1 - b0, _audio_slice(audio_cfg_strength, b0, b1), _window_slice(cfg_interval, b0, b1))
             ws = eng.workspace(b1 - b0, N, nt, steps, method, rows=_plan_of(rows))
             a, keep = eng._args(text[b0:b1], cond[b0:b1], lens[b0:b1], durations[b0:b1], y0[b0:b1], th if rows is None else rows[0][0], steps,
                                 method, ch if rows is None else float(rows[1].max()), use_mask, use_graph, out[b0:b1], tr, ws)
@@ -612,6 +681,10 @@ class Engine:
         guided = tuple(bool(np.any(np.asarray(c[5][1] if c[5] is not None else cfg_strength) >= 1e-5)
                             or (c[5] is not None and len(c[5]) == 3 and np.any(c[5][2] >= 1e-5))) for c in calls)
         key = (B, N, nt, steps, method, use_graph, bool(use_mask), return_trajectory, guided, cond_keep is not None, _plan_of(calls[0][5]))
+        if cfg_interval is not None:
+            # which evaluations run one branch follows from the times, strengths and bounds (the C call works it out): a new set of them
+            # may mean a new graph, and a capture runs the halves one after the other
+            key += tuple(x.tobytes() for c in calls for x in tuple(c[5]) + tuple(c[5].window))
         if key in self._split_seen:
             fut = self._pool.submit(run, calls[1][0], calls[1][1], calls[1][4], calls[1][5])
             try:

@@ -151,6 +151,8 @@ def generate(
     vocode_batched: bool = False,           # extension: with batch_sentences, ONE ragged vocoder call instead of one per sentence
     audio_cfg_strength: Optional[float] = None,   # extension (dual guidance, docs/dual_guidance.md): speaker strength; `cfg_strength` is
                                             # then the text strength.  None = the single-knob call: sample() gets no new keyword
+    cfg_interval=None,                      # extension (guidance window, docs/guidance_window.md): (lo, hi) -- guidance only at function
+                                            # evaluations whose time lies in [lo, hi]; None = guided throughout, no new keyword to sample()
     cross_fade_ms: Optional[float] = None,  # extension (sentence joins, docs/sentence_joins.md): linear cross-fade between sentences
     sentence_pause_ms: Optional[float] = None,   # extension: silence between sentences; the sentences then fade to and from it
     trim_sentence_db: Optional[float] = None,    # extension: cut leading / trailing near-silence below this level off every sentence
@@ -183,6 +185,7 @@ def generate(
     join = None                                                       # all three unset: nothing of the join is called
     if cross_fade_ms is not None or sentence_pause_ms is not None or trim_sentence_db is not None:
         join = join_options(cross_fade_ms, sentence_pause_ms, trim_sentence_db)
+    window_kw = {} if cfg_interval is None else dict(cfg_interval=_interval(cfg_interval, "request 0: cfg_interval"))
     if output_sample_rate is not None:
         output_sample_rate = _audio._rate(output_sample_rate, "output_sample_rate")
     if f5tts is None:
@@ -214,6 +217,7 @@ def generate(
     sentences = split_sentences(generation_text)
     is_single_generation = len(sentences) <= 1 or duration is not None
     dual_kw = {} if audio_cfg_strength is None else dict(audio_cfg_strength=_strength(audio_cfg_strength, "audio_cfg_strength"))
+    dual_kw.update(window_kw)
 
     def run(text_for_model, dur, whole=False):
         wave, _ = f5tts.sample(audio[None], text=text_for_model, duration=dur, steps=steps, method=method, speed=speed,
@@ -316,6 +320,24 @@ CONTROL_KEYS = ("cfg_strength", "sway_sampling_coef", "seed", "speed")
 AUDIO_CFG_KEY = "audio_cfg_strength"
 
 
+# guidance window (docs/guidance_window.md): accepted beside CONTROL_KEYS like AUDIO_CFG_KEY; a (lo, hi) pair
+CFG_INTERVAL_KEY = "cfg_interval"
+# the window of a row whose request sets none in a call where another request does: every finite time, i.e. guided throughout
+WHOLE_INTERVAL = (-float(np.finfo(np.float32).max), float(np.finfo(np.float32).max))
+
+
+def _interval(v, what: str):
+    """a guidance window as a (lo, hi) tuple of finite floats with lo <= hi, or ValueError naming `what`"""
+    if isinstance(v, (str, bytes)) or not isinstance(v, (list, tuple, np.ndarray)) or len(v) != 2:
+        raise ValueError(f"{what} must be a pair (lo, hi), got {v!r}")
+    lo, hi = (_strength(x, what) for x in v)
+    if max(abs(lo), abs(hi)) > WHOLE_INTERVAL[1]:                      # (the C call compares in fp32)
+        raise ValueError(f"{what} must be a pair of finite fp32 numbers, got {v!r}")
+    if lo > hi:
+        raise ValueError(f"{what} must have lo <= hi, got {v!r}")
+    return (lo, hi)
+
+
 def _strength(v, what: str) -> float:
     """a guidance strength as a finite float, or ValueError naming `what`"""
     if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
@@ -331,11 +353,17 @@ def request_controls(controls, n_requests: int, row_req, defaults: dict) -> dict
     an entry that is neither None nor a dict, an unknown key.
     "audio_cfg_strength" (dual guidance) is accepted beside CONTROL_KEYS.  The key appears in the result only when `defaults` carries it
     (the call-level value) or a request sets it, and then always as one value per row: a row whose request does not set it gets the
-    call-level value, or -- where there is none -- its own cfg_strength, which is algebraically the single-knob rule for that row."""
+    call-level value, or -- where there is none -- its own cfg_strength, which is algebraically the single-knob rule for that row.
+    "cfg_interval" (guidance window) likewise: a (lo, hi) pair of finite numbers with lo <= hi, in the result only when `defaults` or a
+    request carries it, then one pair per row; a row without one gets the call-level pair or, where there is none, WHOLE_INTERVAL."""
     out = dict(defaults)
+    if CFG_INTERVAL_KEY in out:
+        out[CFG_INTERVAL_KEY] = _interval(out[CFG_INTERVAL_KEY], CFG_INTERVAL_KEY)
     if controls is None:
         if AUDIO_CFG_KEY in out:
             out[AUDIO_CFG_KEY] = [_strength(out[AUDIO_CFG_KEY], AUDIO_CFG_KEY)] * len(row_req)
+        if CFG_INTERVAL_KEY in out:
+            out[CFG_INTERVAL_KEY] = [out[CFG_INTERVAL_KEY]] * len(row_req)
         return out
     controls = list(controls)
     if len(controls) != n_requests:
@@ -345,11 +373,13 @@ def request_controls(controls, n_requests: int, row_req, defaults: dict) -> dict
             continue
         if not isinstance(c, dict):
             raise ValueError(f"request {i}: controls entry must be None or a dict, got {type(c).__name__}")
-        unknown = sorted(set(c) - set(CONTROL_KEYS) - {AUDIO_CFG_KEY})
+        unknown = sorted(set(c) - set(CONTROL_KEYS) - {AUDIO_CFG_KEY, CFG_INTERVAL_KEY})
         if unknown:
-            raise ValueError(f"request {i}: unknown control(s) {unknown}; expected any of {list(CONTROL_KEYS) + [AUDIO_CFG_KEY]}")
+            raise ValueError(f"request {i}: unknown control(s) {unknown}; expected any of {list(CONTROL_KEYS) + [AUDIO_CFG_KEY, CFG_INTERVAL_KEY]}")
         if AUDIO_CFG_KEY in c:
             _strength(c[AUDIO_CFG_KEY], f"request {i}: {AUDIO_CFG_KEY}")
+        if CFG_INTERVAL_KEY in c:
+            _interval(c[CFG_INTERVAL_KEY], f"request {i}: {CFG_INTERVAL_KEY}")
     for key in CONTROL_KEYS:
         if any(c is not None and key in c for c in controls):
             out[key] = [controls[i][key] if controls[i] is not None and key in controls[i] else defaults[key] for i in row_req]
@@ -364,6 +394,10 @@ def request_controls(controls, n_requests: int, row_req, defaults: dict) -> dict
             else:
                 rows.append(float(cfg[r] if isinstance(cfg, list) else cfg))
         out[AUDIO_CFG_KEY] = rows
+    if CFG_INTERVAL_KEY in defaults or any(c is not None and CFG_INTERVAL_KEY in c for c in controls):
+        out[CFG_INTERVAL_KEY] = [_interval(controls[i][CFG_INTERVAL_KEY], f"request {i}: {CFG_INTERVAL_KEY}")
+                                 if controls[i] is not None and CFG_INTERVAL_KEY in controls[i] else out.get(CFG_INTERVAL_KEY, WHOLE_INTERVAL)
+                                 for i in row_req]
     return out
 
 
@@ -384,6 +418,7 @@ def generate_many(
     output_sample_rate: Optional[int] = None,
     controls=None,
     audio_cfg_strength: Optional[float] = None,
+    cfg_interval=None,
     cross_fade_ms=None,
     sentence_pause_ms=None,
     trim_sentence_db=None,
@@ -406,6 +441,10 @@ def generate_many(
     audio_cfg_strength (docs/dual_guidance.md), as an argument or as a key of a controls entry: dual guidance -- the speaker strength,
     with cfg_strength as the text strength.  sample() gets the keyword (one value per row) only when the call or some request sets it; a
     row whose request does not set it, in a call that does not either, gets its own cfg_strength (the single-knob rule for that row).
+    cfg_interval (docs/guidance_window.md), as an argument or as a key of a controls entry: a (lo, hi) pair -- the rows of the request are
+    guided only at function evaluations whose time lies in [lo, hi], and an evaluation in which no row of the batch is guided runs the
+    conditional branch alone.  sample() gets the keyword (one pair per row) only when the call or some request sets it; a row without
+    one is then guided throughout.
 
     cross_fade_ms, sentence_pause_ms, trim_sentence_db (docs/sentence_joins.md; all None: the assembly above, unchanged): each one value
     for the call or a list with one per request (None = not set for that request).  With any of them set the decoded rows go to
@@ -419,7 +458,7 @@ def generate_many(
     padding, and the gain is fp64 arithmetic on fp32 block sums instead of torch's fp32 mean).
     ValueError before any launch, naming the request: an empty list, a request without text, a reference recording without a
     transcript, a reference at a rate the resampler refuses, a `controls` list of the wrong length or with an unknown key, a join
-    setting that is negative or not finite, a trim level not below 0."""
+    setting that is negative or not finite, a trim level not below 0, a cfg_interval that is not two finite numbers with lo <= hi."""
     requests = list(requests)
     if not requests:
         raise ValueError("generate_many needs at least one request")
@@ -429,6 +468,8 @@ def generate_many(
     call_level = dict(cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed, speed=speed)
     if audio_cfg_strength is not None:
         call_level[AUDIO_CFG_KEY] = _strength(audio_cfg_strength, AUDIO_CFG_KEY)
+    if cfg_interval is not None:
+        call_level[CFG_INTERVAL_KEY] = _interval(cfg_interval, CFG_INTERVAL_KEY)
     request_controls(controls, len(requests), [], call_level)          # validation only: the rows are not known yet
     if output_sample_rate is not None:
         output_sample_rate = _audio._rate(output_sample_rate, "output_sample_rate")
@@ -480,7 +521,7 @@ def generate_many(
         f5tts._vocoder = None
         mel, _ = f5tts.sample(cond, text=texts, duration=durs, lens=lens, steps=steps, method=method, speed=ctl["speed"],
                               cfg_strength=ctl["cfg_strength"], sway_sampling_coef=ctl["sway_sampling_coef"], seed=ctl["seed"],
-                              **({AUDIO_CFG_KEY: ctl[AUDIO_CFG_KEY]} if AUDIO_CFG_KEY in ctl else {}))
+                              **{k: ctl[k] for k in (AUDIO_CFG_KEY, CFG_INTERVAL_KEY) if k in ctl})
     finally:
         f5tts._vocoder = voc
     frames = f5tts.last_durations                                     # per-row frame counts after the clamps of cfm.py:317-318
@@ -529,7 +570,7 @@ def read_requests(path):
                 raise ValueError(f"{path}:{no}: not a JSON object ({exc.msg})") from None
             if not isinstance(obj, dict) or not isinstance(obj.get("text"), str):
                 raise ValueError(f'{path}:{no}: expected an object with a "text" string')
-            unknown = set(obj) - {"text", "ref_audio", "ref_text", "output"} - {"cfg", "sway_coef", "seed", "speed", "audio_cfg"} - set(JOIN_FILE_KEYS)
+            unknown = set(obj) - {"text", "ref_audio", "ref_text", "output"} - {"cfg", "sway_coef", "seed", "speed", "audio_cfg", "cfg_interval"} - set(JOIN_FILE_KEYS)
             if unknown:
                 raise ValueError(f"{path}:{no}: unknown key(s) {sorted(unknown)}")
             reqs.append({k: obj.get(k) for k in ("text", "ref_audio", "ref_text", "output")})
@@ -565,8 +606,8 @@ def read_request_joins(path):
 
 
 def read_request_controls(path):
-    """The optional per-request sampling controls of a --requests file: the keys "cfg", "sway_coef", "seed", "speed" and "audio_cfg" of
-    every line (same lines as read_requests, which ignores them) -> a list with one entry per request for generate_many(controls=...):
+    """The optional per-request sampling controls of a --requests file: the keys "cfg", "sway_coef", "seed", "speed", "audio_cfg" and
+    "cfg_interval" ([lo, hi], kept under the same name) of every line (same lines as read_requests, which ignores them) -> a list with one entry per request for generate_many(controls=...):
     a dict with the controls the line sets ("cfg_strength", "sway_sampling_coef", "seed", "speed", "audio_cfg_strength"), or None when
     it sets none."""
     import json
@@ -592,6 +633,11 @@ def read_request_controls(path):
                 if not ok:
                     raise ValueError(f'{path}:{no}: "{key}" must be {"an integer" if key == "seed" else "a number"}, got {v!r}')
                 c[name] = v
+            if CFG_INTERVAL_KEY in obj:
+                try:
+                    c[CFG_INTERVAL_KEY] = _interval(obj[CFG_INTERVAL_KEY], f'"{CFG_INTERVAL_KEY}"')
+                except ValueError as exc:
+                    raise ValueError(f"{path}:{no}: {exc}") from None
             out.append(c or None)
     return out
 
@@ -634,6 +680,8 @@ def parse_args(argv=None):
                          "left out: the bundled sample); excludes --text and --output")
     ap.add_argument("--trim-silence", type=float, default=None, metavar="DB",
                     help="with --requests: cut leading and trailing silence below DB dB off every reference (-42 is customary; default: cut nothing)")
+    ap.add_argument("--cfg-interval", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="guidance window: guide only at function evaluations whose time lies in [LO, HI] (default: throughout)")
     ap.add_argument("--cross-fade-ms", type=float, default=None, metavar="MS",
                     help="linear cross-fade of MS milliseconds between the sentences of a text (default: plain concatenation)")
     ap.add_argument("--sentence-pause-ms", type=float, default=None, metavar="MS",
@@ -665,7 +713,8 @@ def main(argv=None):
                               estimate_duration=ns.estimate_duration, model_name=ns.model, quantization_bits=ns.q,
                               trim_silence_db=ns.trim_silence, output_sample_rate=ns.output_rate,
                               controls=controls if any(c is not None for c in controls) else None,
-                              **({} if ns.audio_cfg is None else dict(audio_cfg_strength=ns.audio_cfg)), **joins)
+                              **({} if ns.audio_cfg is None else dict(audio_cfg_strength=ns.audio_cfg)),
+                              **({} if ns.cfg_interval is None else dict(cfg_interval=tuple(ns.cfg_interval))), **joins)
         for r, wave in zip(reqs, waves):
             if r["output"] is not None:
                 write_wav(r["output"], wave.detach().cpu().numpy(), ns.output_rate or SAMPLE_RATE)
@@ -684,6 +733,7 @@ def main(argv=None):
              speed=ns.speed, seed=ns.seed, quantization_bits=ns.q, output_path=ns.output, resample_ref=ns.resample_ref,
              output_sample_rate=ns.output_rate, batch_sentences=ns.batch_sentences, vocode_batched=ns.vocode_batched,
              **({} if ns.audio_cfg is None else dict(audio_cfg_strength=ns.audio_cfg)),
+             **({} if ns.cfg_interval is None else dict(cfg_interval=tuple(ns.cfg_interval))),
              **{k: v for k, v in (("cross_fade_ms", ns.cross_fade_ms), ("sentence_pause_ms", ns.sentence_pause_ms),
                                   ("trim_sentence_db", ns.trim_sentence_db)) if v is not None})
 

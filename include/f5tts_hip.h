@@ -181,6 +181,35 @@ typedef struct f5_dual_controls {
 int f5_workspace_bytes_dual(f5_engine* e, int B, int N, int nt, int steps, int method, size_t* bytes);
 int f5_sample_dual(f5_engine* e, const f5_sample_args* args, const f5_dual_controls* controls, void* stream);
 
+/* Guidance window: f5_sample_rows / f5_sample_dual with the guidance of row b applied only while lo_rows[b] <= t <= hi_rows[b].  `t` is
+ * the fp32 time of the FUNCTION EVALUATION for that row -- the value the adaLN table is built from; for midpoint and rk4 the stage's
+ * time, not the step's -- and both ends are inclusive, compared in fp32.  Outside its window a row's effective strengths are 0 (with
+ * dual guidance both strengths are gated by the one window).  An evaluation in which some row has an effective strength >= 1e-5 is WIDE:
+ * it runs the call's full branch count (2, or 3 with audio_cfg_rows), and a row outside its window takes k = F by the selection of the
+ * stage kernels.  Every other evaluation is NARROW: the DiT runs on the conditional branch alone (the first B N rows of every buffer)
+ * and every row takes k = F.  With no wide evaluation the whole call runs one branch.  audio_cfg_rows = NULL selects single guidance
+ * (f5_sample_rows' rule and two branches), else dual guidance (f5_sample_dual's rule and three).  f5_workspace_bytes_window is the plan
+ * of f5_workspace_bytes_rows (dual = 0) or f5_workspace_bytes_dual (dual = 1) plus the effective-strength tables, [nfe][B] floats, one
+ * or two of them, behind everything those plans lay out; the other three size calls are unchanged.  Graphs: the tables are staged
+ * outside the captured part with the other row scalars; the wide / narrow pattern is structural and part of the cache key, the
+ * strengths and bounds are not, so one graph serves every set of values with the same pattern.  args->t and args->cfg_strength are not
+ * read.  Refused before any launch, each with its own message: null controls or a null t_rows / text_cfg_rows / lo_rows / hi_rows, a
+ * non-finite strength or bound, lo > hi, a workspace below f5_workspace_bytes_window, and everything f5_sample_rows / f5_sample_dual
+ * refuse (mxfp8 and ln_fold = 1 included). */
+typedef struct f5_window_controls {
+    const float* t_rows;          /* host [B][steps] */
+    const float* text_cfg_rows;   /* host [B]: the strength of single guidance, T against N with dual guidance */
+    const float* audio_cfg_rows;  /* host [B]: F against T, or NULL = single guidance with two branches */
+    const float* lo_rows;         /* host [B] */
+    const float* hi_rows;         /* host [B] */
+    const uint8_t* cond_keep_dev; /* dev [B][N] or NULL: as f5_sample_edit */
+} f5_window_controls;
+int f5_workspace_bytes_window(f5_engine* e, int B, int N, int nt, int steps, int method, int dual, size_t* bytes);
+int f5_sample_window(f5_engine* e, const f5_sample_args* args, const f5_window_controls* controls, void* stream);
+/* Test hook: the wide (1) / narrow (0) flag of every evaluation of the engine's most recent f5_sample_window call that got past its
+ * argument checks.  *nfe gets the number of evaluations, `wide` the first min(*nfe, cap) flags.  Host bookkeeping only. */
+int f5_debug_last_sample_pattern(f5_engine* e, int* nfe, uint8_t* wide, int cap);
+
 /* Status word of the last f5_sample / f5_dit_forward on the workspace of `args`.  It is the FIRST 32-bit word of the workspace for every
  * shape and solver (a caller may copy it itself).  bit 1 (F5_STATUS_FOLD_RAN) = the LN fold (engine option "ln_fold") ran in that call;
  * bit 0 (F5_STATUS_FOLD_OVERFLOW) = a value of the folded LayerNorm operand (x - m)(1 + scale) did not fit fp16 (precision f16): the
