@@ -48,8 +48,9 @@ struct TextBlockW {
 };
 
 struct Workspace {
-    size_t total = 0;
-    size_t scal, scal_words;   // per-call host scalars, contiguous: [status 1 | lens B | dur2 2B | tgrid nfe | dt steps | cfg 1 | lncnt] (32-bit words)
+    size_t total = 0;          // bytes of the whole plan of the call's route (plan_workspace)
+    size_t scal, scal_words;   // per-call host scalars, contiguous: [status 1 | lens B | dur2 nbr B | tgrid nfe | dt steps | cfg 1 | lncnt] (32-bit
+                               // words; lens and dur2 together are (1 + nbr) B)
     size_t status;             // THE FIRST WORD OF THE WORKSPACE for every shape / solver (a C caller may read it without re-planning), staged
                                // with the scalars: bit 1 = the LN fold ran in this call (set by the host), bit 0 = a folded operand left the
                                // fp16 range (set by the producing epilogue); f5_sample_status / f5_sample_status_async
@@ -74,18 +75,16 @@ struct Workspace {
     bool fold_planned;
     size_t vt_bytes;
     size_t cond_keep;              // f5_sample_edit: the per-frame conditioning mask, [B][N] bytes, BEHIND everything above (no other offset moves)
-    // f5_sample_rows / f5_dit_forward_rows only (plan_workspace_rows; behind `total`: no offset of the plan above moves)
+    // per-row routes only (Route::rows; behind everything above: no offset of the base part moves)
     size_t rscal = 0, rscal_words = 0;          // per-row controls, staged per call: [tgrid nfe x B | dt steps x B | cfg B] floats
     size_t rtgrid = 0, rdt = 0, rcfg = 0;
     size_t racfg = 0;                           // dual guidance: the rows' audio strengths, B floats behind rcfg (0 words in the rows plan)
     size_t rsinus = 0, rth = 0, rtemb = 0;      // time MLP of every (evaluation, row): [nfe x B] rows each
     size_t rmod = 0;                            // adaLN table [nfe][B][(6L+2) D]
-    size_t total_rows = 0;                      // bytes of the plan including the rows part
     int nbr = 2;                                // branches the plan lays out: 2 (cond + null), 3 = dual guidance (F, N, T)
-    // f5_sample_window only (plan_workspace_window; behind `total_rows`): the rows' EFFECTIVE strengths of every evaluation, [nfe][B] floats
+    // f5_sample_window only (Route::window; behind the rows part): the rows' EFFECTIVE strengths of every evaluation, [nfe][B] floats
     // each, staged per call; stage j reads row j where the rows / dual calls read the one [B] vector at rcfg / racfg
     size_t wcfg = 0, wacfg = 0, wtab_words = 0;
-    size_t total_window = 0;                    // bytes of the plan including the tables (0 = not a window plan)
 };
 
 // Per-engine launch options: everything that reaches a kernel as a by-value argument or changes the launch sequence of sample()
@@ -439,11 +438,20 @@ constexpr long LN_FOLD_AUTO_ROWS = 22000;
 constexpr long LN_FOLD_SMALL_ROWS = 2048;
 constexpr bool LN_FOLD_SMALL_AUTO = false;     // measured -1.5 ... +0.7 % at batch 1 (profiles/r06): below the 4 % bar, so opt-in (ln_fold = 1)
 
-// nbr = branches of a function evaluation the plan has room for.  The text path always runs for two (the third branch of dual guidance
-// reuses branch 0's text embedding), so only the buffers of the DiT itself -- MB rows -- and the per-branch durations grow with it.
-static Workspace plan_workspace(const f5_engine* e, int B, int N, int nt, int steps, int method, int nbr = 2) {
+// Which of the entry points a call came through, as far as the plan and the launch sequence care: rows = time and guidance strength per
+// batch row (f5_sample_rows, f5_dit_forward_rows and everything below), dual = the rows route with three branches F, N, T
+// (f5_sample_dual, f5_dit_forward_dual), window = the strengths gated per evaluation (f5_sample_window, single or dual).
+struct Route {
+    bool rows = false, dual = false, window = false;
+    int nbr() const { return dual ? 3 : 2; }     // branches of a function evaluation the plan has room for
+};
+
+// The base part, then the per-row part (route.rows), then the window tables (route.window); each part lies behind the one before, so no
+// offset of an earlier part depends on a later one.  The text path always runs for two branches (the third branch of dual guidance reuses
+// branch 0's text embedding), so only the buffers of the DiT itself -- MB rows -- and the per-branch durations grow with nbr.
+static Workspace plan_workspace(const f5_engine* e, int B, int N, int nt, int steps, int method, Route route) {
     const f5_config& c = e->cfg;
-    const int D = c.dim, Dt = c.text_dim, FF = c.ff_dim, TF = c.text_ff_dim, L = c.depth, np = e->np, mel = c.mel_dim;
+    const int D = c.dim, Dt = c.text_dim, FF = c.ff_dim, TF = c.text_ff_dim, L = c.depth, np = e->np, mel = c.mel_dim, nbr = route.nbr();
     const size_t M1 = (size_t)B * N, M2 = 2 * M1, MB = (size_t)nbr * M1;
     const int nfe = (steps - 1) * nfe_per_step(method);
     const int npad = (N + 63) / 64 * 64;
@@ -521,79 +529,51 @@ static Workspace plan_workspace(const f5_engine* e, int B, int N, int nt, int st
         w.ffh8s = b.take(M2 * (FF / 32));
     }
     w.cond_keep = b.take(M1);
+    if (route.rows) {
+        // the staged controls and the time / adaLN tables of every (evaluation, row) pair.  The fp32 scratch of the two gated projections
+        // needs no space of its own: w.qk[0] (2 M D 16-bit values = M D floats) is dead from the end of a block's attention to the next
+        // block's QKV projection, which is where both projections run.
+        const size_t rows = nfe1 * B;
+        w.rscal_words = rows + (size_t)steps * B + B + (route.dual ? (size_t)B : 0);
+        w.rscal = b.take(w.rscal_words * 4);
+        w.rtgrid = w.rscal;
+        w.rdt = w.rtgrid + rows * 4;
+        w.rcfg = w.rdt + (size_t)steps * B * 4;
+        w.racfg = w.rcfg + (size_t)B * 4;
+        w.rsinus = b.take(rows * c.freq_embed_dim * 4);
+        w.rth = b.take(rows * D * 4);
+        w.rtemb = b.take(rows * D * 4);
+        w.rmod = b.take(rows * (size_t)(6 * L + 2) * D * 4);
+        if (route.window) {
+            w.wtab_words = (route.dual ? 2 : 1) * rows;
+            w.wcfg = b.take(w.wtab_words * 4);
+            w.wacfg = route.dual ? w.wcfg + rows * 4 : 0;
+        }
+    }
     w.total = b.off;
     return w;
 }
 
+// the four size queries: f5_workspace_bytes (plain), _rows, _dual (the rows plan with room for the third branch) and _window (either
+// with the effective-strength tables behind it)
+static int workspace_bytes(f5_engine* e, int B, int N, int nt, int steps, int method, Route route, size_t* bytes) {
+    F5_REQUIRE(e && bytes, "null argument");
+    F5_REQUIRE(B >= 1 && N >= 1 && steps >= 1, "bad sizes B=%d N=%d steps=%d", B, N, steps);
+    F5_REQUIRE(method >= F5_EULER && method <= F5_RK4, "Unknown method: %d", method);
+    *bytes = plan_workspace(e, B, N, nt, steps, method, route).total;
+    return 0;
+}
 extern "C" int f5_workspace_bytes(f5_engine* e, int B, int N, int nt, int steps, int method, size_t* bytes) {
-    F5_REQUIRE(e && bytes, "null argument");
-    F5_REQUIRE(B >= 1 && N >= 1 && steps >= 1, "bad sizes B=%d N=%d steps=%d", B, N, steps);
-    F5_REQUIRE(method >= F5_EULER && method <= F5_RK4, "Unknown method: %d", method);
-    *bytes = plan_workspace(e, B, N, nt, steps, method).total;
-    return 0;
+    return workspace_bytes(e, B, N, nt, steps, method, Route{}, bytes);
 }
-
-// The plan of f5_sample with the per-row part appended: the staged controls and the time / adaLN tables of every (evaluation, row) pair.
-// The fp32 scratch of the two gated projections needs no space of its own: w.qk[0] (2 M D 16-bit values = M D floats) is dead from the end
-// of a block's attention to the next block's QKV projection, which is where both projections run.
-static Workspace plan_workspace_rows(const f5_engine* e, int B, int N, int nt, int steps, int method, int nbr = 2) {
-    Workspace w = plan_workspace(e, B, N, nt, steps, method, nbr);
-    const f5_config& c = e->cfg;
-    const int nfe = (steps - 1) * nfe_per_step(method);
-    const size_t nfe1 = (size_t)(nfe > 0 ? nfe : 1), rows = nfe1 * B;
-    Bump b;
-    b.off = w.total;
-    w.rscal_words = rows + (size_t)steps * B + B + (nbr == 3 ? (size_t)B : 0);
-    w.rscal = b.take(w.rscal_words * 4);
-    w.rtgrid = w.rscal;
-    w.rdt = w.rtgrid + rows * 4;
-    w.rcfg = w.rdt + (size_t)steps * B * 4;
-    w.racfg = w.rcfg + (size_t)B * 4;
-    w.rsinus = b.take(rows * c.freq_embed_dim * 4);
-    w.rth = b.take(rows * c.dim * 4);
-    w.rtemb = b.take(rows * c.dim * 4);
-    w.rmod = b.take(rows * (size_t)(6 * c.depth + 2) * c.dim * 4);
-    w.total_rows = b.off;
-    return w;
-}
-
 extern "C" int f5_workspace_bytes_rows(f5_engine* e, int B, int N, int nt, int steps, int method, size_t* bytes) {
-    F5_REQUIRE(e && bytes, "null argument");
-    F5_REQUIRE(B >= 1 && N >= 1 && steps >= 1, "bad sizes B=%d N=%d steps=%d", B, N, steps);
-    F5_REQUIRE(method >= F5_EULER && method <= F5_RK4, "Unknown method: %d", method);
-    *bytes = plan_workspace_rows(e, B, N, nt, steps, method).total_rows;
-    return 0;
+    return workspace_bytes(e, B, N, nt, steps, method, Route{true, false, false}, bytes);
 }
-
-// The rows plan with room for the third branch of dual guidance (f5_sample_dual / f5_dit_forward_dual).
 extern "C" int f5_workspace_bytes_dual(f5_engine* e, int B, int N, int nt, int steps, int method, size_t* bytes) {
-    F5_REQUIRE(e && bytes, "null argument");
-    F5_REQUIRE(B >= 1 && N >= 1 && steps >= 1, "bad sizes B=%d N=%d steps=%d", B, N, steps);
-    F5_REQUIRE(method >= F5_EULER && method <= F5_RK4, "Unknown method: %d", method);
-    *bytes = plan_workspace_rows(e, B, N, nt, steps, method, 3).total_rows;
-    return 0;
+    return workspace_bytes(e, B, N, nt, steps, method, Route{true, true, false}, bytes);
 }
-
-// The rows / dual plan with the effective-strength tables of a guidance window appended (f5_sample_window).
-static Workspace plan_workspace_window(const f5_engine* e, int B, int N, int nt, int steps, int method, bool dual) {
-    Workspace w = plan_workspace_rows(e, B, N, nt, steps, method, dual ? 3 : 2);
-    const int nfe = (steps - 1) * nfe_per_step(method);
-    const size_t rows = (size_t)(nfe > 0 ? nfe : 1) * B;
-    Bump b;
-    b.off = w.total_rows;
-    w.wtab_words = (dual ? 2 : 1) * rows;
-    w.wcfg = b.take(w.wtab_words * 4);
-    w.wacfg = dual ? w.wcfg + rows * 4 : 0;
-    w.total_window = b.off;
-    return w;
-}
-
 extern "C" int f5_workspace_bytes_window(f5_engine* e, int B, int N, int nt, int steps, int method, int dual, size_t* bytes) {
-    F5_REQUIRE(e && bytes, "null argument");
-    F5_REQUIRE(B >= 1 && N >= 1 && steps >= 1, "bad sizes B=%d N=%d steps=%d", B, N, steps);
-    F5_REQUIRE(method >= F5_EULER && method <= F5_RK4, "Unknown method: %d", method);
-    *bytes = plan_workspace_window(e, B, N, nt, steps, method, dual != 0).total_window;
-    return 0;
+    return workspace_bytes(e, B, N, nt, steps, method, Route{true, dual != 0, true}, bytes);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -606,8 +586,7 @@ struct Ctx : LaunchView {
     int B, N, nt, nb;   // nb = branches evaluated per function evaluation (1 or 2; 1 or 3 with dual guidance)
     int npad;
     bool edit = false;  // f5_sample_edit: conditioning frames are chosen by the mask at w.cond_keep instead of n < lens[b]
-    bool rows = false;  // f5_sample_rows / f5_dit_forward_rows: time and guidance strength per batch row (w.r*: plan_workspace_rows)
-    bool dual = false;  // f5_sample_dual / f5_dit_forward_dual: the rows route with three branches F, N, T (w.nbr == 3)
+    Route route;        // rows: time and guidance strength per batch row (w.r*); dual: three branches F, N, T (w.nbr == 3)
     bool use_mask;
     // f5_sample_window: wide (1) / narrow (0) per evaluation, null = every evaluation runs `nb` branches.  A narrow one runs the
     // conditional branch alone and its stage takes k = F for every row (the effective strengths at w.wcfg / w.wacfg are 0 there).
@@ -629,18 +608,20 @@ static F5GemmArgs gemm_base(const Ctx& c, const op16_t* a_hi, const op16_t* a_lo
 // LN fold (gemm.hpp fold_*): 44 of the 46 LN-modulate launches of a forward disappear into the epilogues of the GEMMs around them
 // (the first LN of block 0 follows conv-pos and the final one feeds a small-tile GEMM: both keep the LN kernel).  Only where all
 // four block GEMMs of this shape run on the staged kernels, in the one-pass operand modes, with the transposed q / k tiles.
-// -> 0 = off, 1 = on, -1 = required by the option but impossible here (error set)
-static int ln_fold_state(const Ctx& c) {
+// -> 0 = off, 1 = on, -1 = required by the option but impossible here (error set; `what` names the entry point of a window call)
+static int ln_fold_state(const Ctx& c, const char* what = "") {
     const f5_engine* e = c.e;
     const f5_config& cf = e->cfg;
     if (e->opt.ln_fold == 0) return 0;
-    if (c.rows) {        // the fold's constants c1, c2 are built per evaluation, not per row
-        if (e->opt.ln_fold == 1) {
+    if (c.route.rows) {        // the fold's constants c1, c2 are built per evaluation, not per row
+        if (e->opt.ln_fold != 1) return 0;
+        if (c.route.window)
+            f5_set_error("%s: ln_fold = 1: the folded LN cannot run with per-row sampling controls (its constants are per evaluation); use "
+                         "ln_fold = -1 or 0", what);
+        else
             f5_set_error("ln_fold = 1: the folded LN cannot run with per-row sampling controls (its constants are per evaluation); use ln_fold = "
                          "-1 or 0 for f5_sample_rows / f5_dit_forward_rows");
-            return -1;
-        }
-        return 0;
+        return -1;
     }
     const int D = cf.dim, FF = cf.ff_dim, M = c.nb * c.B * c.N;
     bool ok = e->np == 1 && e->prec != F5_PREC_MXFP8 && e->opt.qkv_tr && !e->opt.fuse_ln && D % 256 == 0 && D <= 2048 && FF % 256 == 0 &&
@@ -684,10 +665,10 @@ static int run_prep(const Ctx& c, int nfe) {
     // --- t-only tables (dit.py:61-82, 267, 286)
     if (nfe > 0) {
         // per-row controls: one table row per (evaluation, batch row), [nfe][B] (f5_launch_skinny_gemm slices any row count by itself)
-        const int nt_rows = c.rows ? nfe * c.B : nfe;
-        const float* tg = c.p<float>(c.rows ? w.rtgrid : w.tgrid);
-        float *sinus = c.p<float>(c.rows ? w.rsinus : w.sinus), *th = c.p<float>(c.rows ? w.rth : w.th);
-        float *temb = c.p<float>(c.rows ? w.rtemb : w.temb), *modt = c.p<float>(c.rows ? w.rmod : w.mod);
+        const int nt_rows = c.route.rows ? nfe * c.B : nfe;
+        const float* tg = c.p<float>(c.route.rows ? w.rtgrid : w.tgrid);
+        float *sinus = c.p<float>(c.route.rows ? w.rsinus : w.sinus), *th = c.p<float>(c.route.rows ? w.rth : w.th);
+        float *temb = c.p<float>(c.route.rows ? w.rtemb : w.temb), *modt = c.p<float>(c.route.rows ? w.rmod : w.mod);
         RC(f5_launch_time_sinus(tg, sinus, nt_rows, cf.freq_embed_dim, s));
         RC(f5_launch_skinny_gemm(sinus, c.a<float>(e->time_w0), c.a<float>(e->time_b0), th, nt_rows, D, cf.freq_embed_dim, 0, 1, s));
         RC(f5_launch_skinny_gemm(th, c.a<float>(e->time_w2), c.a<float>(e->time_b2), temb, nt_rows, D, D, 0, 0, s));
@@ -761,7 +742,7 @@ static int run_prep(const Ctx& c, int nfe) {
         cur ^= 1;
     }
     // --- hoisted part of the input projection: Hc = [cond | text] * Wct^T + b   (dit.py:249-250)
-    if (c.dual)         // three branches F, N, T; the text path above stays at two
+    if (c.route.dual)         // three branches F, N, T; the text path above stays at two
         RC(K.pack_cond_text_dual(c.p<float>(w.cond), c.p<int>(w.lens), c.edit ? c.p<uint8_t>(w.cond_keep) : nullptr, c.p<float>(w.te[cur]),
                                  c.pb(w.ct, 0), c.pb(w.ct, 1), c.B, c.N, cf.mel_dim, Dt, s));
     else if (c.edit)
@@ -792,7 +773,7 @@ static int run_dit(const Ctx& c, int j) {
     const Ops& K = c.ops;
     // per-row controls: `mod` is vector 0 of evaluation j in the [nfe][B][(6L+2) D] table; the row kernels step through the B vectors
     const size_t vstride = (size_t)(6 * L + 2) * D;
-    const float* mod = c.rows ? c.p<float>(w.rmod) + (size_t)j * c.B * vstride : c.p<float>(w.mod) + (size_t)j * vstride;
+    const float* mod = c.route.rows ? c.p<float>(w.rmod) + (size_t)j * c.B * vstride : c.p<float>(w.mod) + (size_t)j * vstride;
     // the gated projections of that route leave their fp32 result (bias included) here: q | k are dead once the attention has run
     float* yscratch = reinterpret_cast<float*>(c.pb(w.qk, 0));
     auto ln_rows = [&](const float* y, const float* gate, const uint8_t* keep, const float* scale, const float* shift) {
@@ -929,7 +910,7 @@ static int run_dit(const Ctx& c, int j) {
     const float* mf = mod + (size_t)L * 6 * D;  // final adaLN: (scale, shift) order, dit.py:287
     bool h_ready = false;
     auto fuse_ln = [&](F5GemmArgs& g, const float* scale, const float* shift) -> bool {
-        if (c.rows || !e->opt.fuse_ln || w.lncnt_words == 0 || !f5_gemm_resid_ln_fusable(f5bf::f5_gemm_query(g, EPI_RESID_GATE), g.ldo)) return false;
+        if (c.route.rows || !e->opt.fuse_ln || w.lncnt_words == 0 || !f5_gemm_resid_ln_fusable(f5bf::f5_gemm_query(g, EPI_RESID_GATE), g.ldo)) return false;
         g.ln_counter = c.p<int>(w.lncnt);
         g.ln_scale = scale;
         g.ln_shift = shift;
@@ -983,7 +964,7 @@ static int run_dit(const Ctx& c, int j) {
     for (int i = 0; i < L && e->prec != F5_PREC_MXFP8; ++i) {
         const BlockW& bw = e->blocks[i];
         const float* m6 = mod + (size_t)i * 6 * D;  // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-        if (!h_ready && c.rows) RC(ln_rows(nullptr, nullptr, nullptr, m6 + D, m6));
+        if (!h_ready && c.route.rows) RC(ln_rows(nullptr, nullptr, nullptr, m6 + D, m6));
         else if (!h_ready) RC(K.ln_modulate(c.p<float>(w.x), m6 + D, m6, c.pb(w.h, 0), c.pb(w.h, 1), M, D, 1e-6f, s, fold ? c.p<float>(w.lnmean) : nullptr));
         F5GemmArgs gq = gemm_base(c, c.pb(w.h, 0), c.pb(w.h, 1), D, bw.qkv, M, 3 * D, D, c.a<float>(bw.bqkv));
         if (h_folded) fold_consumer(gq, i, 0);
@@ -1029,19 +1010,19 @@ static int run_dit(const Ctx& c, int j) {
         RC(K.attention(at, s));
 
         F5GemmArgs go = gemm_base(c, c.pb(w.ao, 0), c.pb(w.ao, 1), D, bw.o, M, D, D, c.a<float>(bw.bo));
-        go.out_f32 = c.rows ? yscratch : c.p<float>(w.x);
+        go.out_f32 = c.route.rows ? yscratch : c.p<float>(w.x);
         go.ldo = D;
-        if (!c.rows) {
+        if (!c.route.rows) {
             go.gate = m6 + 2 * D;
             go.rowkeep = rowkeep;
         }
         const bool fused_mlp_ln = fuse_ln(go, m6 + 4 * D, m6 + 3 * D);     // h = LN(x) (1 + scale_mlp) + shift_mlp in the same launch
         if (fold) fold_producer(go, m6 + 4 * D);
-        RC(K.gemm(go, c.rows ? EPI_F32 : EPI_RESID_GATE, s));
+        RC(K.gemm(go, c.route.rows ? EPI_F32 : EPI_RESID_GATE, s));
         if (fold) RC(fold_rows());
 
         // per-row controls: x += gate_msa[row] * (keep ? y : 0), then the mlp LN-modulate, in one row kernel
-        if (c.rows) RC(ln_rows(yscratch, m6 + 2 * D, rowkeep, m6 + 4 * D, m6 + 3 * D));
+        if (c.route.rows) RC(ln_rows(yscratch, m6 + 2 * D, rowkeep, m6 + 4 * D, m6 + 3 * D));
         else if (!fused_mlp_ln && !fold) RC(K.ln_modulate(c.p<float>(w.x), m6 + 4 * D, m6 + 3 * D, c.pb(w.h, 0), c.pb(w.h, 1), M, D, 1e-6f, s));
         F5GemmArgs g1 = gemm_base(c, c.pb(w.h, 0), c.pb(w.h, 1), D, bw.ff1, M, FF, D, c.a<float>(bw.bff1));
         if (fold) fold_consumer(g1, i, 3 * D);
@@ -1050,9 +1031,9 @@ static int run_dit(const Ctx& c, int j) {
         g1.ldob = FF;
         RC(K.gemm(g1, EPI_GELU_TANH, s));
         F5GemmArgs g2 = gemm_base(c, c.pb(w.ffh, 0), c.pb(w.ffh, 1), FF, bw.ff2, M, D, FF, c.a<float>(bw.bff2));
-        g2.out_f32 = c.rows ? yscratch : c.p<float>(w.x);
+        g2.out_f32 = c.route.rows ? yscratch : c.p<float>(w.x);
         g2.ldo = D;
-        if (!c.rows) g2.gate = m6 + 5 * D;
+        if (!c.route.rows) g2.gate = m6 + 5 * D;
         // the LN that follows FF2: the next block's attention LN (scale_msa, shift_msa), or the final one (dit.py:287: scale, shift)
         const float* m6n = m6 + 6 * D;
         h_ready = (i + 1 < L) ? fuse_ln(g2, m6n + D, m6n) : fuse_ln(g2, mf, mf + D);
@@ -1061,9 +1042,9 @@ static int run_dit(const Ctx& c, int j) {
             fold_producer(g2, m6n + D);
             h_ready = true;
         }
-        RC(K.gemm(g2, c.rows ? EPI_F32 : EPI_RESID_GATE, s));
+        RC(K.gemm(g2, c.route.rows ? EPI_F32 : EPI_RESID_GATE, s));
         if (h_folded) RC(fold_rows());
-        if (c.rows) {        // x += gate_mlp[row] * y, then the LN that follows (no row mask on FF2, as in the gated epilogue above)
+        if (c.route.rows) {        // x += gate_mlp[row] * y, then the LN that follows (no row mask on FF2, as in the gated epilogue above)
             RC(i + 1 < L ? ln_rows(yscratch, m6 + 5 * D, nullptr, m6n + D, m6n) : ln_rows(yscratch, m6 + 5 * D, nullptr, mf, mf + D));
             h_ready = true;
         }
@@ -1110,11 +1091,11 @@ static int run_sample_body(const Ctx& c, const f5_sample_args* a, int i0 = 0, in
     auto stage = [&](const F5OdeArgs& o) {
         const float* cfg_rows = win ? c.p<float>(w.wcfg) + (size_t)jcur * c.B : c.p<float>(w.rcfg);
         const float* acfg_rows = win ? c.p<float>(w.wacfg) + (size_t)jcur * c.B : c.p<float>(w.racfg);
-        if (c.dual) return K.ode_stage_dual(o, textp, acfg_rows, cfg_rows, dt_rows, c.N, c.B, s);
-        return c.rows ? K.ode_stage_rows(o, cfg_rows, dt_rows, c.N, c.B, s) : K.ode_stage(o, s);
+        if (c.route.dual) return K.ode_stage_dual(o, textp, acfg_rows, cfg_rows, dt_rows, c.N, c.B, s);
+        return c.route.rows ? K.ode_stage_rows(o, cfg_rows, dt_rows, c.N, c.B, s) : K.ode_stage(o, s);
     };
     for (int i = i0; i + 1 < a->steps && i < i1; ++i) {
-        if (c.rows) dt_rows = c.p<float>(w.rdt) + (size_t)i * c.B;
+        if (c.route.rows) dt_rows = c.p<float>(w.rdt) + (size_t)i * c.B;
         float* y = traj + (size_t)i * M1 * mel;
         float* ynext = traj + (size_t)(i + 1) * M1 * mel;
         F5OdeArgs o;
@@ -1221,19 +1202,28 @@ static int stage_inputs(Ctx& c, const f5_sample_args* a, const float* x_override
     return 0;
 }
 
-static Ctx make_ctx(f5_engine* e, const f5_sample_args* a, hipStream_t s) {
+// A strength below 1e-5 is "not guided" (written so that a NaN counts as guided: it reaches the finite checks, not a silent one-branch run).
+// -> the branches a call evaluates: 1 when none of the n rows is guided by either strength, else all the route lays out.
+static int branch_count(Route route, const float* cfg, const float* audio, int n) {
+    for (int b = 0; b < n; ++b)
+        if (!(cfg[b] < 1e-5f) || (route.dual && !(audio[b] < 1e-5f))) return route.nbr();
+    return 1;
+}
+
+static Ctx make_ctx(f5_engine* e, const f5_sample_args* a, hipStream_t s, Route route, int nb) {
     Ctx c;
     c.arena = e->arena;
     c.ws = (char*)a->workspace;
     c.np = e->np;
     c.ops = e->ops;
     c.e = e;
-    c.w = plan_workspace(e, a->B, a->N, a->nt, a->steps, a->method);
+    c.route = route;
+    c.w = plan_workspace(e, a->B, a->N, a->nt, a->steps, a->method, route);
     c.s = s;
     c.B = a->B;
     c.N = a->N;
     c.nt = a->nt;
-    c.nb = a->cfg_strength < 1e-5f ? 1 : 2;
+    c.nb = nb;
     c.npad = (a->N + 63) / 64 * 64;
     c.use_mask = a->use_mask != 0;
     return c;
@@ -1259,103 +1249,90 @@ static void eval_times(const float* t, int steps, int method, std::vector<float>
     }
 }
 
-// what the per-row route refuses on top of check_args, before any launch; `what` names the call
-static int check_rows_route(const f5_engine* e, const char* what) {
-    F5_REQUIRE(e->prec != F5_PREC_MXFP8, "%s: precision mxfp8 has no per-row modulation kernels (use f16, bf16 or bf16x3)", what);
+// what a per-row route refuses on top of check_args, before any launch; `what` names the call
+static int check_route(const f5_engine* e, Route route, const char* what) {
+    if (route.rows) F5_REQUIRE(e->prec != F5_PREC_MXFP8, "%s: precision mxfp8 has no per-row modulation kernels (use f16, bf16 or bf16x3)", what);
+    if (route.dual)
+        F5_REQUIRE(!e->opt.null_keeps_cond, "%s: engine option null_keeps_cond = 1 gives the second branch the meaning (audio kept, text dropped); "
+                   "dual guidance needs it to be (both dropped)", what);
     return 0;
 }
 
-// switches a context to the per-row route: the plan with the rows part, and both branches as soon as ANY row is guided
-static void ctx_to_rows(Ctx& c, const f5_sample_args* a, const float* cfg_rows, int ncfg) {
-    c.rows = true;
-    c.w = plan_workspace_rows(c.e, a->B, a->N, a->nt, a->steps, a->method);
-    c.nb = 1;
-    for (int b = 0; b < ncfg; ++b)
-        if (!(cfg_rows[b] < 1e-5f)) c.nb = 2;
+// the size query that matches a route, for the "workspace too small" message
+static const char* workspace_fn(Route route) {
+    if (route.window) return "f5_workspace_bytes_window";
+    return route.dual ? "f5_workspace_bytes_dual" : (route.rows ? "f5_workspace_bytes_rows" : "f5_workspace_bytes");
 }
-
-// ... and to dual guidance: the rows route on the three-branch plan; all three branches as soon as ANY row has either strength
-static void ctx_to_dual(Ctx& c, const f5_sample_args* a, const float* text_rows, const float* audio_rows, int n) {
-    c.rows = c.dual = true;
-    c.w = plan_workspace_rows(c.e, a->B, a->N, a->nt, a->steps, a->method, 3);
-    c.nb = 1;
-    for (int b = 0; b < n; ++b)
-        if (!(text_rows[b] < 1e-5f) || !(audio_rows[b] < 1e-5f)) c.nb = 3;
-}
-// what dual guidance refuses on top of the per-row route, before any launch
-static int check_dual_route(const f5_engine* e, const char* what) {
-    RC(check_rows_route(e, what));
-    F5_REQUIRE(!e->opt.null_keeps_cond, "%s: engine option null_keeps_cond = 1 gives the second branch the meaning (audio kept, text dropped); "
-               "dual guidance needs it to be (both dropped)", what);
+static int check_workspace(const Ctx& c, const f5_sample_args* a, const char* what) {
+    if (c.route.rows)
+        F5_REQUIRE(a->workspace_bytes >= c.w.total, "%s: workspace too small: %zu < %zu (%s)", what, a->workspace_bytes, c.w.total,
+                   workspace_fn(c.route));
+    else
+        F5_REQUIRE(a->workspace_bytes >= c.w.total, "workspace too small: %zu < %zu", a->workspace_bytes, c.w.total);
     return 0;
 }
 
-// f5_sample (edit = false), f5_sample_edit (the mask replaces n < lens[b] in the hoisted input packing and the final splice) and
-// f5_sample_rows (rc != null: time grid and guidance strength per batch row) and f5_sample_dual (rc->audio_rows != null as well) and
-// f5_sample_window (rc->lo_rows != null: either of the two with the strengths gated per evaluation by each row's time window)
+// The controls of one sampling call, whichever entry point it came through: f5_sample (nothing set), f5_sample_edit (cond_keep),
+// f5_sample_rows (route.rows: time grid and guidance strength per batch row), f5_sample_dual (route.dual: audio_rows as well) and
+// f5_sample_window (route.window: either of the two with the strengths gated per evaluation by each row's time window).  With a mask
+// it replaces n < lens[b] in the hoisted input packing and the final splice.
 struct RowCtl {
-    const float* t_rows;
-    const float* cfg_rows;      // the text strength of dual guidance
-    const float* audio_rows;    // null = f5_sample_rows
-    const char* what;           // the entry point, for messages
-    const float* lo_rows = nullptr;   // f5_sample_window: each row's guidance window [lo, hi] on its own evaluation times (null = no window)
+    Route route;
+    const char* what;                     // the entry point, for messages
+    const uint8_t* cond_keep = nullptr;   // device, [B][N]
+    const float* t_rows = nullptr;        // route.rows: [B][steps]
+    const float* cfg_rows = nullptr;      // ... [B]; the text strength of dual guidance
+    const float* audio_rows = nullptr;    // route.dual: [B]
+    const float* lo_rows = nullptr;       // route.window: each row's guidance window [lo, hi] on its own evaluation times
     const float* hi_rows = nullptr;
 };
-static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* cond_keep, bool edit, void* stream,
-                       const RowCtl* rc = nullptr) {
-    F5_REQUIRE(!edit || cond_keep, "f5_sample_edit: cond_keep is null");
-    RC(check_args(e, a));
-    F5_REQUIRE(a->y0 && (a->t || rc) && a->out, "null pointer in f5_sample_args (y0/t/out)");
-    hipStream_t s = (hipStream_t)stream;
-    Ctx c = make_ctx(e, a, s);
-    c.edit = edit;
-    if (rc) {
-        const bool dual = rc->audio_rows != nullptr;
-        RC(dual ? check_dual_route(e, rc->what) : check_rows_route(e, rc->what));
-        for (size_t i = 0; i < (size_t)a->B * a->steps; ++i)
-            F5_REQUIRE(std::isfinite(rc->t_rows[i]), "%s: t_rows[%zu][%zu] is not finite", rc->what, i / a->steps, i % a->steps);
-        for (int b = 0; b < a->B; ++b)
-            F5_REQUIRE(std::isfinite(rc->cfg_rows[b]), "%s: %s[%d] is not finite", rc->what, (dual || rc->lo_rows) ? "text_cfg_rows" : "cfg_rows", b);
-        for (int b = 0; b < a->B && dual; ++b)
-            F5_REQUIRE(std::isfinite(rc->audio_rows[b]), "%s: audio_cfg_rows[%d] is not finite", rc->what, b);
-        const bool window = rc->lo_rows != nullptr;
-        for (int b = 0; b < a->B && window; ++b) {
-            F5_REQUIRE(std::isfinite(rc->lo_rows[b]), "%s: lo_rows[%d] is not finite", rc->what, b);
-            F5_REQUIRE(std::isfinite(rc->hi_rows[b]), "%s: hi_rows[%d] is not finite", rc->what, b);
-            F5_REQUIRE(rc->lo_rows[b] <= rc->hi_rows[b], "%s: lo_rows[%d] = %g is above hi_rows[%d] = %g", rc->what, b, rc->lo_rows[b], b,
-                       rc->hi_rows[b]);
-        }
-        if (dual) ctx_to_dual(c, a, rc->cfg_rows, rc->audio_rows, a->B);
-        else ctx_to_rows(c, a, rc->cfg_rows, a->B);
-        if (window) {
-            F5_REQUIRE(e->opt.ln_fold != 1, "%s: ln_fold = 1: the folded LN cannot run with per-row sampling controls (its constants are per "
-                       "evaluation); use ln_fold = -1 or 0", rc->what);
-            // the branch count of the call is settled below, once the evaluation times say which evaluations are wide
-            c.w = plan_workspace_window(e, a->B, a->N, a->nt, a->steps, a->method, dual);
-            F5_REQUIRE(a->workspace_bytes >= c.w.total_window, "%s: workspace too small: %zu < %zu (f5_workspace_bytes_window)", rc->what,
-                       a->workspace_bytes, c.w.total_window);
-        }
-        F5_REQUIRE(a->workspace_bytes >= c.w.total_rows, "%s: workspace too small: %zu < %zu (%s)", rc->what, a->workspace_bytes,
-                   c.w.total_rows, dual ? "f5_workspace_bytes_dual" : "f5_workspace_bytes_rows");
-        if (ln_fold_state(c) < 0) return 2;
-    }
-    F5_REQUIRE(a->workspace_bytes >= c.w.total, "workspace too small: %zu < %zu", a->workspace_bytes, c.w.total);
-    const int mel = e->cfg.mel_dim;
-    const size_t M1 = (size_t)c.B * c.N;
-    SatScope sat(e->prec == F5_PREC_F16 && e->opt.sat_check, c.p<int>(c.w.status));
 
+// everything a per-row call refuses before any launch, then the workspace size of every call
+static int validate_controls(const Ctx& c, const f5_sample_args* a, const RowCtl& rc) {
+    const Route r = rc.route;
+    if (r.rows) {
+        RC(check_route(c.e, r, rc.what));
+        for (size_t i = 0; i < (size_t)a->B * a->steps; ++i)
+            F5_REQUIRE(std::isfinite(rc.t_rows[i]), "%s: t_rows[%zu][%zu] is not finite", rc.what, i / a->steps, i % a->steps);
+        for (int b = 0; b < a->B; ++b)
+            F5_REQUIRE(std::isfinite(rc.cfg_rows[b]), "%s: %s[%d] is not finite", rc.what, (r.dual || r.window) ? "text_cfg_rows" : "cfg_rows", b);
+        for (int b = 0; b < a->B && r.dual; ++b)
+            F5_REQUIRE(std::isfinite(rc.audio_rows[b]), "%s: audio_cfg_rows[%d] is not finite", rc.what, b);
+        for (int b = 0; b < a->B && r.window; ++b) {
+            F5_REQUIRE(std::isfinite(rc.lo_rows[b]), "%s: lo_rows[%d] is not finite", rc.what, b);
+            F5_REQUIRE(std::isfinite(rc.hi_rows[b]), "%s: hi_rows[%d] is not finite", rc.what, b);
+            F5_REQUIRE(rc.lo_rows[b] <= rc.hi_rows[b], "%s: lo_rows[%d] = %g is above hi_rows[%d] = %g", rc.what, b, rc.lo_rows[b], b,
+                       rc.hi_rows[b]);
+        }
+        // (the window call tries the forced-fold refusal before the size, the other per-row calls after it; a call without per-row
+        // controls meets it in stage_inputs)
+        if (r.window && ln_fold_state(c, rc.what) < 0) return 2;
+    }
+    RC(check_workspace(c, a, rc.what));
+    if (r.rows && ln_fold_state(c, rc.what) < 0) return 2;
+    return 0;
+}
+
+// Stages the call's inputs and controls into the workspace.  Per-row routes: the rows words ([tgrid nfe x B | dt steps x B | cfg B
+// (| audio B)]); with a window also the effective strengths [nfe][B] text (| [nfe][B] audio) and `pattern`, wide (1) / narrow (0) per
+// evaluation, which settles c.nb and becomes c.pattern and the engine's last_pattern.
+static int stage_controls(Ctx& c, const f5_sample_args* a, const RowCtl& rc, std::vector<uint8_t>& pattern) {
+    const Route r = rc.route;
+    hipStream_t s = c.s;
     std::vector<float> tnfe, dts;
-    std::vector<uint8_t> pattern;       // f5_sample_window: wide / narrow per evaluation
-    std::vector<uint32_t> wtab;         // ... and the effective strengths, [nfe][B] text (| [nfe][B] audio)
-    if (rc) {
+    if (!r.rows) {
+        eval_times(a->t, a->steps, a->method, tnfe, dts);
+        RC(stage_inputs(c, a, nullptr, tnfe, dts));
+    } else {
         // every row's own grid through the same fp32 arithmetic, laid out [nfe][B] / [steps - 1][B]; the scalar slots get row 0's
         const int nfe = (a->steps - 1) * nfe_per_step(a->method);
-        std::vector<uint32_t> words(c.w.rscal_words, 0u);
+        const size_t rows = (size_t)(nfe > 0 ? nfe : 1) * c.B;
+        std::vector<uint32_t> words(c.w.rscal_words, 0u), wtab;
         float* rt = reinterpret_cast<float*>(words.data());
-        float* rd = rt + (size_t)(nfe > 0 ? nfe : 1) * c.B;
+        float* rd = rt + rows;
         for (int b = 0; b < c.B; ++b) {
             std::vector<float> tb, db;
-            eval_times(rc->t_rows + (size_t)b * a->steps, a->steps, a->method, tb, db);
+            eval_times(rc.t_rows + (size_t)b * a->steps, a->steps, a->method, tb, db);
             for (size_t j = 0; j < tb.size(); ++j) rt[j * c.B + b] = tb[j];
             for (size_t i = 0; i < db.size(); ++i) rd[i * c.B + b] = db[i];
             if (b == 0) {
@@ -1363,48 +1340,47 @@ static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* con
                 dts = db;
             }
         }
-        memcpy(rd + (size_t)a->steps * c.B, rc->cfg_rows, (size_t)c.B * 4);
-        if (c.dual) memcpy(rd + (size_t)a->steps * c.B + c.B, rc->audio_rows, (size_t)c.B * 4);
-        if (rc->lo_rows) {
+        memcpy(rd + (size_t)a->steps * c.B, rc.cfg_rows, (size_t)c.B * 4);
+        if (r.dual) memcpy(rd + (size_t)a->steps * c.B + c.B, rc.audio_rows, (size_t)c.B * 4);
+        if (r.window) {
             // a row's strengths count at evaluation j when lo <= t_eval[j][b] <= hi on the fp32 time staged above (both ends inclusive), else
-            // they are 0; an evaluation is wide when any row is left with a strength >= 1e-5 (the test of ctx_to_rows / ctx_to_dual)
-            const size_t rows = (size_t)(nfe > 0 ? nfe : 1) * c.B;
+            // they are 0; an evaluation is wide when any row is left guided (branch_count)
             wtab.assign(c.w.wtab_words, 0u);
             float* wt = reinterpret_cast<float*>(wtab.data());
-            float* wa = c.dual ? wt + rows : nullptr;
+            float* wa = r.dual ? wt + rows : nullptr;
             pattern.assign((size_t)nfe, 0);
             bool any_wide = false;
             for (int j = 0; j < nfe; ++j)
                 for (int b = 0; b < c.B; ++b) {
                     const float tj = rt[(size_t)j * c.B + b];
-                    const bool in = rc->lo_rows[b] <= tj && tj <= rc->hi_rows[b];
-                    const float ct = in ? rc->cfg_rows[b] : 0.0f, ca = (in && c.dual) ? rc->audio_rows[b] : 0.0f;
+                    const bool in = rc.lo_rows[b] <= tj && tj <= rc.hi_rows[b];
+                    const float ct = in ? rc.cfg_rows[b] : 0.0f, ca = (in && r.dual) ? rc.audio_rows[b] : 0.0f;
                     wt[(size_t)j * c.B + b] = ct;
                     if (wa) wa[(size_t)j * c.B + b] = ca;
-                    if (!(ct < 1e-5f) || (c.dual && !(ca < 1e-5f))) pattern[j] = 1;
+                    if (branch_count(r, &ct, &ca, 1) > 1) pattern[j] = 1;
                     any_wide = any_wide || pattern[j];
                 }
-            c.nb = any_wide ? (c.dual ? 3 : 2) : 1;
+            c.nb = any_wide ? r.nbr() : 1;
             c.pattern = pattern.data();
-            e->last_pattern = pattern;
+            c.e->last_pattern = pattern;
         }
         RC(stage_inputs(c, a, nullptr, tnfe, dts));
         RC(f5_launch_stage_words(words.data(), words.size(), c.p<uint32_t>(c.w.rscal), s));
-        if (rc->lo_rows) RC(f5_launch_stage_words(wtab.data(), wtab.size(), c.p<uint32_t>(c.w.wcfg), s));
-    } else {
-        eval_times(a->t, a->steps, a->method, tnfe, dts);
-        RC(stage_inputs(c, a, nullptr, tnfe, dts));
+        if (r.window) RC(f5_launch_stage_words(wtab.data(), wtab.size(), c.p<uint32_t>(c.w.wcfg), s));
     }
     // the mask travels like text / cond / y0: copied into the workspace outside the captured part, so one graph serves every mask of a shape
-    if (edit) RC(f5_launch_copy_bytes(cond_keep, c.ws + c.w.cond_keep, M1, s));
+    if (c.edit) RC(f5_launch_copy_bytes(rc.cond_keep, c.ws + c.w.cond_keep, (size_t)c.B * c.N, s));
+    return 0;
+}
 
-    // hipGraph cache.  The key is everything a captured node depends on BY VALUE: shapes, solver, branch count, masking and the
-    // workspace address.  Per-call scalars (cfg strength, time grid, dt) are read from workspace memory staged above.
+// hipGraph cache key: everything a captured node depends on BY VALUE: shapes, solver, branch count, masking, the route, the launch knobs and
+// options, and the workspace address.  Per-call scalars (cfg strength, time grid, dt) are read from workspace memory staged before.
+static std::string graph_key(const Ctx& c, const f5_sample_args* a, const std::vector<uint8_t>& pattern) {
     char shape_key[192];
     snprintf(shape_key, sizeof(shape_key), "B%d N%d nt%d st%d m%d nb%d mask%d edit%d rows%d dual%d ke%d ws%p opt", c.B, c.N, c.nt, a->steps,
-             a->method, c.nb, (int)c.use_mask, (int)c.edit, (int)c.rows, (int)c.dual, g_knob_epoch, a->workspace);
+             a->method, c.nb, (int)c.use_mask, (int)c.edit, (int)c.route.rows, (int)c.route.dual, g_knob_epoch, a->workspace);
     std::string key(shape_key);
-    for (const OptDesc& o : k_options) key += " " + std::to_string(e->opt.*o.member);
+    for (const OptDesc& o : k_options) key += " " + std::to_string(c.e->opt.*o.member);
     if (c.pattern) {
         // the wide / narrow pattern decides which evaluations run one branch: structural, so part of the key (nfe bits as hex); the
         // strengths and bounds behind it are staged values and are not
@@ -1416,6 +1392,13 @@ static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* con
             key += hex[v];
         }
     }
+    return key;
+}
+
+// the solve -- eager, or a cached / freshly captured hipGraph under `key` -- and the final splice into the caller's buffers
+static int launch_sample(const Ctx& c, const f5_sample_args* a, const std::string& key) {
+    f5_engine* e = c.e;
+    hipStream_t s = c.s;
     const bool graph_on = a->use_graph == F5_GRAPH_ON, graph_auto = a->use_graph == F5_GRAPH_AUTO;
     GraphCache::Entry* entry = (graph_on || graph_auto) ? e->graphs.find(key, a->workspace) : nullptr;
     bool graph = graph_on || entry != nullptr;
@@ -1439,42 +1422,57 @@ static int sample_impl(f5_engine* e, const f5_sample_args* a, const uint8_t* con
     } else {
         RC(run_sample_body(c, a));
     }
+    const int mel = e->cfg.mel_dim;
+    const size_t M1 = (size_t)c.B * c.N;
     const float* ylast = c.p<float>(c.w.traj) + (size_t)(a->steps - 1) * M1 * mel;
-    if (edit)
+    if (c.edit)
         RC(f5_launch_splice_keep(c.p<float>(c.w.cond), ylast, c.p<uint8_t>(c.w.cond_keep), a->out, c.B, c.N, mel, s));
     else
         RC(f5_launch_splice(c.p<float>(c.w.cond), ylast, c.p<int>(c.w.lens), a->out, c.B, c.N, mel, s));
     if (a->trajectory) RC(f5_launch_copy_words(c.ws + c.w.traj, a->trajectory, (size_t)a->steps * M1 * mel, s));
     return 0;
 }
-extern "C" int f5_sample(f5_engine* e, const f5_sample_args* a, void* stream) { return sample_impl(e, a, nullptr, false, stream); }
+
+static int sample_impl(f5_engine* e, const f5_sample_args* a, void* stream, const RowCtl& rc) {
+    RC(check_args(e, a));
+    F5_REQUIRE(a->y0 && (a->t || rc.route.rows) && a->out, "null pointer in f5_sample_args (y0/t/out)");
+    // (a window call's branch count is settled by stage_controls, once the evaluation times say which evaluations are wide)
+    const int nb = rc.route.rows ? branch_count(rc.route, rc.cfg_rows, rc.audio_rows, a->B) : branch_count(rc.route, &a->cfg_strength, nullptr, 1);
+    Ctx c = make_ctx(e, a, (hipStream_t)stream, rc.route, nb);
+    c.edit = rc.cond_keep != nullptr;
+    RC(validate_controls(c, a, rc));
+    SatScope sat(e->prec == F5_PREC_F16 && e->opt.sat_check, c.p<int>(c.w.status));
+    std::vector<uint8_t> pattern;       // f5_sample_window: wide / narrow per evaluation (c.pattern points into it)
+    RC(stage_controls(c, a, rc, pattern));
+    return launch_sample(c, a, graph_key(c, a, pattern));
+}
+extern "C" int f5_sample(f5_engine* e, const f5_sample_args* a, void* stream) { return sample_impl(e, a, stream, RowCtl{Route{}, "f5_sample"}); }
 extern "C" int f5_sample_edit(f5_engine* e, const f5_sample_args* a, const uint8_t* cond_keep_dev, void* stream) {
-    return sample_impl(e, a, cond_keep_dev, true, stream);
+    F5_REQUIRE(cond_keep_dev, "f5_sample_edit: cond_keep is null");
+    return sample_impl(e, a, stream, RowCtl{Route{}, "f5_sample_edit", cond_keep_dev});
 }
 extern "C" int f5_sample_rows(f5_engine* e, const f5_sample_args* a, const f5_row_controls* rc, void* stream) {
     F5_REQUIRE(rc != nullptr, "f5_sample_rows: controls is null");
     F5_REQUIRE(rc->t_rows != nullptr, "f5_sample_rows: controls.t_rows is null");
     F5_REQUIRE(rc->cfg_rows != nullptr, "f5_sample_rows: controls.cfg_rows is null");
-    const RowCtl ctl = {rc->t_rows, rc->cfg_rows, nullptr, "f5_sample_rows"};
-    return sample_impl(e, a, rc->cond_keep_dev, rc->cond_keep_dev != nullptr, stream, &ctl);
+    return sample_impl(e, a, stream, RowCtl{Route{true, false, false}, "f5_sample_rows", rc->cond_keep_dev, rc->t_rows, rc->cfg_rows});
 }
 extern "C" int f5_sample_dual(f5_engine* e, const f5_sample_args* a, const f5_dual_controls* dc, void* stream) {
     F5_REQUIRE(dc != nullptr, "f5_sample_dual: controls is null");
     F5_REQUIRE(dc->t_rows != nullptr, "f5_sample_dual: controls.t_rows is null");
     F5_REQUIRE(dc->text_cfg_rows != nullptr, "f5_sample_dual: controls.text_cfg_rows is null");
     F5_REQUIRE(dc->audio_cfg_rows != nullptr, "f5_sample_dual: controls.audio_cfg_rows is null");
-    const RowCtl ctl = {dc->t_rows, dc->text_cfg_rows, dc->audio_cfg_rows, "f5_sample_dual"};
-    return sample_impl(e, a, dc->cond_keep_dev, dc->cond_keep_dev != nullptr, stream, &ctl);
+    return sample_impl(e, a, stream,
+                       RowCtl{Route{true, true, false}, "f5_sample_dual", dc->cond_keep_dev, dc->t_rows, dc->text_cfg_rows, dc->audio_cfg_rows});
 }
-
 extern "C" int f5_sample_window(f5_engine* e, const f5_sample_args* a, const f5_window_controls* wc, void* stream) {
     F5_REQUIRE(wc != nullptr, "f5_sample_window: controls is null");
     F5_REQUIRE(wc->t_rows != nullptr, "f5_sample_window: controls.t_rows is null");
     F5_REQUIRE(wc->text_cfg_rows != nullptr, "f5_sample_window: controls.text_cfg_rows is null");
     F5_REQUIRE(wc->lo_rows != nullptr, "f5_sample_window: controls.lo_rows is null");
     F5_REQUIRE(wc->hi_rows != nullptr, "f5_sample_window: controls.hi_rows is null");
-    const RowCtl ctl = {wc->t_rows, wc->text_cfg_rows, wc->audio_cfg_rows, "f5_sample_window", wc->lo_rows, wc->hi_rows};
-    return sample_impl(e, a, wc->cond_keep_dev, wc->cond_keep_dev != nullptr, stream, &ctl);
+    return sample_impl(e, a, stream, RowCtl{Route{true, wc->audio_cfg_rows != nullptr, true}, "f5_sample_window", wc->cond_keep_dev, wc->t_rows,
+                                            wc->text_cfg_rows, wc->audio_cfg_rows, wc->lo_rows, wc->hi_rows});
 }
 extern "C" int f5_debug_last_sample_pattern(f5_engine* e, int* nfe, uint8_t* wide, int cap) {
     F5_REQUIRE(e && nfe, "null argument");
@@ -1499,7 +1497,7 @@ extern "C" int f5_sample_status_async(f5_engine* e, const f5_sample_args* a, int
 extern "C" int f5_engine_ln_fold_active(f5_engine* e, const f5_sample_args* a, int* active) {
     F5_REQUIRE(e && a && active, "null argument");
     F5_REQUIRE(a->B >= 1 && a->N >= 1 && a->nt >= 1 && a->steps >= 1 && a->method >= F5_EULER && a->method <= F5_RK4, "bad sizes");
-    const Ctx c = make_ctx(e, a, nullptr);
+    const Ctx c = make_ctx(e, a, nullptr, Route{}, branch_count(Route{}, &a->cfg_strength, nullptr, 1));
     const int st = ln_fold_state(c);
     if (st < 0) return 2;
     *active = st;
@@ -1511,101 +1509,61 @@ extern "C" int f5_sample_status(f5_engine* e, const f5_sample_args* a, int* flag
     return 0;
 }
 
-extern "C" int f5_dit_forward(f5_engine* e, const f5_sample_args* a, const float* x, float t, float* pred, float* null_pred,
-                              void* stream) {
+// One function evaluation.  t: the time (one float), or with a per-row route one time per batch row, [B] host floats.  outs: where the
+// branches go, in the engine's order F, N, T; a null entry, or one beyond the branches that ran, is not written.  Two branches when
+// args->cfg_strength is a guiding one, else one -- dual guidance always runs all three and does not read it.
+static int forward_impl(f5_engine* e, const f5_sample_args* a, const float* x, const float* t, Route route, float* const outs[3],
+                        const char* what, void* stream) {
     RC(check_args(e, a));
-    F5_REQUIRE(x && pred, "null pointer");
+    F5_REQUIRE(x && outs[0], "null pointer");
+    if (route.rows) {
+        F5_REQUIRE(t != nullptr, "%s: t_rows is null", what);
+        RC(check_route(e, route, what));
+        for (int b = 0; b < a->B; ++b) F5_REQUIRE(std::isfinite(t[b]), "%s: t_rows[%d] is not finite", what, b);
+    }
     hipStream_t s = (hipStream_t)stream;
     f5_sample_args a2 = *a;
     a2.steps = 2;
     a2.method = F5_EULER;
-    Ctx c = make_ctx(e, &a2, s);
-    F5_REQUIRE(a->workspace_bytes >= c.w.total, "workspace too small: %zu < %zu", a->workspace_bytes, c.w.total);
+    Ctx c = make_ctx(e, &a2, s, route, route.dual ? 3 : branch_count(route, &a2.cfg_strength, nullptr, 1));
+    RC(check_workspace(c, a, what));
+    if (route.rows && ln_fold_state(c) < 0) return 2;
     const int mel = e->cfg.mel_dim;
     const size_t M1 = (size_t)c.B * c.N;
     SatScope sat(e->prec == F5_PREC_F16 && e->opt.sat_check, c.p<int>(c.w.status));
-    std::vector<float> tnfe(1, t), dts(1, 0.0f);
+    std::vector<float> tnfe(1, t[0]), dts(1, 0.0f);
     RC(stage_inputs(c, &a2, x, tnfe, dts));
-    const Ops& K = c.ops;
+    if (route.rows) {
+        std::vector<uint32_t> words(c.w.rscal_words, 0u);       // [tgrid B | dt 2 B | cfg B (| audio B)]: only the times are read by a forward
+        memcpy(words.data(), t, (size_t)c.B * 4);
+        RC(f5_launch_stage_words(words.data(), words.size(), c.p<uint32_t>(c.w.rscal), s));
+    }
     RC(run_prep(c, 1));
-    RC(K.pack_x(c.p<float>(c.w.traj), c.pb(c.w.xin, 0), c.pb(c.w.xin, 1), (int)M1, mel, s));
+    RC(c.ops.pack_x(c.p<float>(c.w.traj), c.pb(c.w.xin, 0), c.pb(c.w.xin, 1), (int)M1, mel, s));
     RC(run_dit(c, 0));
-    RC(f5_launch_copy_words(c.ws + c.w.vel, pred, M1 * mel, s));
-    if (null_pred && c.nb == 2) RC(f5_launch_copy_words(c.ws + c.w.vel + M1 * mel * 4, null_pred, M1 * mel, s));
+    for (int br = 0; br < c.nb; ++br)
+        if (outs[br]) RC(f5_launch_copy_words(c.ws + c.w.vel + (size_t)br * M1 * mel * 4, outs[br], M1 * mel, s));
     return 0;
 }
 
+extern "C" int f5_dit_forward(f5_engine* e, const f5_sample_args* a, const float* x, float t, float* pred, float* null_pred,
+                              void* stream) {
+    float* const outs[3] = {pred, null_pred, nullptr};
+    return forward_impl(e, a, x, &t, Route{}, outs, "f5_dit_forward", stream);
+}
 // f5_dit_forward with one time per batch row (the reference's DiT takes `time` as (b,), dit.py:374-401): one batched forward where the
 // scalar entry point needs one call per distinct time.  Workspace: f5_workspace_bytes_rows with steps = 2, method = F5_EULER.
 extern "C" int f5_dit_forward_rows(f5_engine* e, const f5_sample_args* a, const float* x, const float* t_rows_host, float* pred,
                                    float* null_pred, void* stream) {
-    RC(check_args(e, a));
-    F5_REQUIRE(x && pred, "null pointer");
-    F5_REQUIRE(t_rows_host != nullptr, "f5_dit_forward_rows: t_rows is null");
-    RC(check_rows_route(e, "f5_dit_forward_rows"));
-    for (int b = 0; b < a->B; ++b) F5_REQUIRE(std::isfinite(t_rows_host[b]), "f5_dit_forward_rows: t_rows[%d] is not finite", b);
-    hipStream_t s = (hipStream_t)stream;
-    f5_sample_args a2 = *a;
-    a2.steps = 2;
-    a2.method = F5_EULER;
-    Ctx c = make_ctx(e, &a2, s);
-    ctx_to_rows(c, &a2, &a2.cfg_strength, 1);
-    F5_REQUIRE(a->workspace_bytes >= c.w.total_rows, "f5_dit_forward_rows: workspace too small: %zu < %zu (f5_workspace_bytes_rows)",
-               a->workspace_bytes, c.w.total_rows);
-    if (ln_fold_state(c) < 0) return 2;
-    const int mel = e->cfg.mel_dim;
-    const size_t M1 = (size_t)c.B * c.N;
-    SatScope sat(e->prec == F5_PREC_F16 && e->opt.sat_check, c.p<int>(c.w.status));
-    std::vector<float> tnfe(1, t_rows_host[0]), dts(1, 0.0f);
-    RC(stage_inputs(c, &a2, x, tnfe, dts));
-    std::vector<uint32_t> words(c.w.rscal_words, 0u);       // [tgrid B | dt 2 B | cfg B]: only the times are read by a forward
-    memcpy(words.data(), t_rows_host, (size_t)c.B * 4);
-    RC(f5_launch_stage_words(words.data(), words.size(), c.p<uint32_t>(c.w.rscal), s));
-    const Ops& K = c.ops;
-    RC(run_prep(c, 1));
-    RC(K.pack_x(c.p<float>(c.w.traj), c.pb(c.w.xin, 0), c.pb(c.w.xin, 1), (int)M1, mel, s));
-    RC(run_dit(c, 0));
-    RC(f5_launch_copy_words(c.ws + c.w.vel, pred, M1 * mel, s));
-    if (null_pred && c.nb == 2) RC(f5_launch_copy_words(c.ws + c.w.vel + M1 * mel * 4, null_pred, M1 * mel, s));
-    return 0;
+    float* const outs[3] = {pred, null_pred, nullptr};
+    return forward_impl(e, a, x, t_rows_host, Route{true, false, false}, outs, "f5_dit_forward_rows", stream);
 }
-
 // One evaluation of the three branches of dual guidance, one time per batch row: pred = F (audio and text kept), null_pred = N (both
-// dropped), text_pred = T (audio dropped, text kept).  All three always run (args->cfg_strength is not read).  Workspace:
-// f5_workspace_bytes_dual with steps = 2, method = F5_EULER.
+// dropped), text_pred = T (audio dropped, text kept).  Workspace: f5_workspace_bytes_dual with steps = 2, method = F5_EULER.
 extern "C" int f5_dit_forward_dual(f5_engine* e, const f5_sample_args* a, const float* x, const float* t_rows_host, float* pred,
                                    float* null_pred, float* text_pred, void* stream) {
-    RC(check_args(e, a));
-    F5_REQUIRE(x && pred, "null pointer");
-    F5_REQUIRE(t_rows_host != nullptr, "f5_dit_forward_dual: t_rows is null");
-    RC(check_dual_route(e, "f5_dit_forward_dual"));
-    for (int b = 0; b < a->B; ++b) F5_REQUIRE(std::isfinite(t_rows_host[b]), "f5_dit_forward_dual: t_rows[%d] is not finite", b);
-    hipStream_t s = (hipStream_t)stream;
-    f5_sample_args a2 = *a;
-    a2.steps = 2;
-    a2.method = F5_EULER;
-    Ctx c = make_ctx(e, &a2, s);
-    const float on = 1.0f;
-    ctx_to_dual(c, &a2, &on, &on, 1);
-    F5_REQUIRE(a->workspace_bytes >= c.w.total_rows, "f5_dit_forward_dual: workspace too small: %zu < %zu (f5_workspace_bytes_dual)",
-               a->workspace_bytes, c.w.total_rows);
-    if (ln_fold_state(c) < 0) return 2;
-    const int mel = e->cfg.mel_dim;
-    const size_t M1 = (size_t)c.B * c.N;
-    SatScope sat(e->prec == F5_PREC_F16 && e->opt.sat_check, c.p<int>(c.w.status));
-    std::vector<float> tnfe(1, t_rows_host[0]), dts(1, 0.0f);
-    RC(stage_inputs(c, &a2, x, tnfe, dts));
-    std::vector<uint32_t> words(c.w.rscal_words, 0u);       // [tgrid B | dt 2 B | cfg B | audio B]: only the times are read by a forward
-    memcpy(words.data(), t_rows_host, (size_t)c.B * 4);
-    RC(f5_launch_stage_words(words.data(), words.size(), c.p<uint32_t>(c.w.rscal), s));
-    const Ops& K = c.ops;
-    RC(run_prep(c, 1));
-    RC(K.pack_x(c.p<float>(c.w.traj), c.pb(c.w.xin, 0), c.pb(c.w.xin, 1), (int)M1, mel, s));
-    RC(run_dit(c, 0));
-    float* outs[3] = {pred, null_pred, text_pred};          // the branch order of the engine: F, N, T
-    for (int br = 0; br < 3; ++br)
-        if (outs[br]) RC(f5_launch_copy_words(c.ws + c.w.vel + (size_t)br * M1 * mel * 4, outs[br], M1 * mel, s));
-    return 0;
+    float* const outs[3] = {pred, null_pred, text_pred};
+    return forward_impl(e, a, x, t_rows_host, Route{true, true, false}, outs, "f5_dit_forward_dual", stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -9,7 +9,9 @@ from __future__ import annotations
 import ctypes as C
 import os
 import warnings
+from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass
 from pathlib import Path
 from typing import Dict, Optional, Sequence
 
@@ -86,89 +88,105 @@ class F5WindowControls(C.Structure):
                 ("hi_rows", C.c_void_p), ("cond_keep_dev", C.c_void_p)]
 
 
-class WindowRows(tuple):
-    """The per-row controls of a call with a guidance window: the (t_rows, cfg_rows[, audio_rows]) tuple of row_controls with the rows'
-    window bounds beside it, `window` = (lo_rows (B,) fp32, hi_rows (B,) fp32).  Its length still says single (2) or dual (3) guidance."""
-    window = None
+# Engine.workspace `rows` / Controls.plan -> (the sampling entry point, its controls struct, its workspace size query and that query's extra
+# arguments): the five routes of include/f5tts_hip.h.  The first is f5_sample_edit when the call carries a conditioning mask.
+ROUTES = {
+    False: ("f5_sample", None, "f5_workspace_bytes", ()),
+    True: ("f5_sample_rows", F5RowControls, "f5_workspace_bytes_rows", ()),
+    "dual": ("f5_sample_dual", F5DualControls, "f5_workspace_bytes_dual", ()),
+    "window": ("f5_sample_window", F5WindowControls, "f5_workspace_bytes_window", (0,)),
+    "window_dual": ("f5_sample_window", F5WindowControls, "f5_workspace_bytes_window", (1,)),
+}
 
 
-def window_rows(cfg_interval, B: int):
-    """`cfg_interval` of a sample() call -- one (lo, hi) pair or a (B, 2) array, one pair per row -- as (lo_rows, hi_rows), (B,) fp32 each.
-    Shape only: the values (finite, lo <= hi) are checked by the C call and, with a request's name, by generate.py."""
-    w = np.asarray(cfg_interval, dtype=np.float32)
-    if w.shape not in ((2,), (B, 2)):
-        raise ValueError(f"cfg_interval: expected (lo, hi) or {B} pairs of shape ({B}, 2), got shape {w.shape}")
-    w = np.broadcast_to(w, (B, 2))
-    return np.ascontiguousarray(w[:, 0]), np.ascontiguousarray(w[:, 1])
+@dataclass(frozen=True, eq=False)
+class Controls:
+    """The sampling controls of one sample() call, normalised (Controls.of): fp32 C-contiguous arrays.  An all-scalar call keeps `t`
+    (steps,) and `cfg` 0-d; as soon as anything is per row -- or audio / a window is given at all -- `t` is (B, steps) and `cfg`,
+    `audio` (dual guidance, docs/dual_guidance.md), `lo`, `hi` (guidance window, docs/guidance_window.md) are (B,) or None.  The C calls
+    read these arrays through the addresses in struct(): keep the object alive until the call has returned."""
+    t: np.ndarray
+    cfg: np.ndarray
+    audio: Optional[np.ndarray] = None
+    lo: Optional[np.ndarray] = None
+    hi: Optional[np.ndarray] = None
 
+    @classmethod
+    def of(cls, t, cfg_strength, B: int, audio_cfg_strength=None, cfg_interval=None) -> "Controls":
+        """`t` may be a (steps,) grid or one grid per row (B, steps), `cfg_strength` a float or a length-B sequence; either one being per
+        row selects the rows route (f5_sample_rows) and the other is broadcast.  audio_cfg_strength (a float or a length-B sequence):
+        dual guidance, f5_sample_dual -- always the per-row form, whatever the values are; `cfg_strength` is then the text strength.
+        cfg_interval ((lo, hi) or (B, 2)): guidance window, f5_sample_window -- always the per-row form too.  Shapes only: the values
+        (finite, lo <= hi) are checked by the C call and, with a request's name, by generate.py."""
+        t = np.asarray(t, dtype=np.float32)
+        audio = lo = hi = None
+        if cfg_interval is not None:
+            w = np.asarray(cfg_interval, dtype=np.float32)
+            if w.shape not in ((2,), (B, 2)):
+                raise ValueError(f"cfg_interval: expected (lo, hi) or {B} pairs of shape ({B}, 2), got shape {w.shape}")
+            w = np.broadcast_to(w, (B, 2))
+            lo, hi = np.ascontiguousarray(w[:, 0]), np.ascontiguousarray(w[:, 1])
+        if t.ndim not in (1, 2):
+            raise ValueError(f"t must be (steps,) or (B, steps), got shape {t.shape}")
+        if audio_cfg_strength is not None:
+            audio = np.asarray(audio_cfg_strength, dtype=np.float32)
+            if audio.ndim != 0 and audio.shape != (B,):
+                raise ValueError(f"per-row audio_cfg_strength: expected {B} values, got shape {audio.shape}")
+            audio = np.ascontiguousarray(np.broadcast_to(audio, (B,)), dtype=np.float32)
+        cfg = np.asarray(cfg_strength, dtype=np.float32)
+        if t.ndim == 1 and cfg.ndim == 0 and audio is None and lo is None:
+            return cls(np.ascontiguousarray(t), cfg)
+        if t.ndim == 2 and t.shape[0] != B:
+            raise ValueError(f"per-row time grid: expected {B} rows, got {t.shape[0]}")
+        if cfg.ndim != 0 and cfg.shape != (B,):
+            raise ValueError(f"per-row cfg_strength: expected {B} values, got shape {cfg.shape}")
+        return cls(np.ascontiguousarray(np.broadcast_to(t, (B, t.shape[-1])), dtype=np.float32),
+                   np.ascontiguousarray(np.broadcast_to(cfg, (B,)), dtype=np.float32), audio, lo, hi)
 
-def row_controls(t, cfg_strength, B: int, audio_cfg_strength=None, cfg_interval=None):
-    """Per-row sampling controls of a sample() call (f5_sample_rows): `t` may be a (steps,) grid or one grid per row (B, steps),
-    `cfg_strength` a float or a length-B sequence.  Either one being per-row selects the rows route and the other is broadcast.
-    -> (steps, None) for an all-scalar call, else (steps, (t_rows (B, steps) fp32, cfg_rows (B,) fp32)), both C-contiguous.
-    audio_cfg_strength (a float or a length-B sequence; docs/dual_guidance.md): dual guidance, f5_sample_dual -- always the per-row form,
-    whatever the values are, with a third entry audio_rows (B,) fp32; `cfg_strength` is then the text strength.
-    cfg_interval ((lo, hi) or (B, 2); docs/guidance_window.md): guidance window, f5_sample_window -- always the per-row form too, returned
-    as a WindowRows whose `window` holds (lo_rows, hi_rows)."""
-    t = np.asarray(t, dtype=np.float32)
-    if cfg_interval is not None:
-        window = window_rows(cfg_interval, B)
-        if t.ndim == 1:
-            t = np.broadcast_to(t, (B, t.shape[0]))
-        steps, rows = row_controls(t, cfg_strength, B, audio_cfg_strength)
-        rows = WindowRows(rows)
-        rows.window = window
-        return steps, rows
-    cfg_seq = np.ndim(cfg_strength) != 0
-    if t.ndim not in (1, 2):
-        raise ValueError(f"t must be (steps,) or (B, steps), got shape {t.shape}")
-    if audio_cfg_strength is not None:
-        audio = np.asarray(audio_cfg_strength, dtype=np.float32)
-        if audio.ndim != 0 and audio.shape != (B,):
-            raise ValueError(f"per-row audio_cfg_strength: expected {B} values, got shape {audio.shape}")
-        steps, rows = row_controls(t if t.ndim == 2 else np.broadcast_to(t, (B, t.shape[0])), cfg_strength, B)
-        return steps, rows + (np.ascontiguousarray(np.broadcast_to(audio, (B,)), dtype=np.float32),)
-    if t.ndim == 1 and not cfg_seq:
-        return int(t.shape[0]), None
-    if t.ndim == 2 and t.shape[0] != B:
-        raise ValueError(f"per-row time grid: expected {B} rows, got {t.shape[0]}")
-    cfg = np.asarray(cfg_strength, dtype=np.float32)
-    if cfg_seq and cfg.shape != (B,):
-        raise ValueError(f"per-row cfg_strength: expected {B} values, got shape {cfg.shape}")
-    steps = int(t.shape[-1])
-    t_rows = np.ascontiguousarray(np.broadcast_to(t, (B, steps)), dtype=np.float32)
-    cfg_rows = np.ascontiguousarray(np.broadcast_to(cfg, (B,)), dtype=np.float32)
-    return steps, (t_rows, cfg_rows)
+    @property
+    def steps(self) -> int:
+        return int(self.t.shape[-1])
 
+    @property
+    def plan(self):
+        """The route of the call, as Engine.workspace(rows=...) takes it: False, True (per-row), "dual", "window" or "window_dual"."""
+        if self.lo is not None:
+            return "window" if self.audio is None else "window_dual"
+        return self.t.ndim == 2 if self.audio is None else "dual"
 
-def _rows_slice(t, cfg_strength, b0: int, b1: int):
-    """The controls of batch rows [b0, b1) of a sample() call: per-row forms are sliced, shared ones pass through."""
-    t = np.asarray(t, dtype=np.float32)
-    return (t[b0:b1] if t.ndim == 2 else t), (cfg_strength if np.ndim(cfg_strength) == 0 else list(cfg_strength)[b0:b1])
+    # what goes into the scalar slots of the arguments, which a per-row route does not read: row 0's grid and the largest strength
+    @property
+    def scalar_t(self) -> np.ndarray:
+        return self.t[0] if self.t.ndim == 2 else self.t
 
+    @property
+    def scalar_cfg(self) -> float:
+        return float(self.cfg.max())
 
-def _audio_slice(audio_cfg_strength, b0: int, b1: int):
-    """The audio strengths of batch rows [b0, b1): None and a scalar pass through."""
-    if audio_cfg_strength is None or np.ndim(audio_cfg_strength) == 0:
-        return audio_cfg_strength
-    return list(np.asarray(audio_cfg_strength, dtype=np.float32)[b0:b1])
+    @property
+    def guided(self) -> bool:
+        """Whether any row has a strength the C call counts as guiding (>= 1e-5): the call then runs more than one branch."""
+        return bool(np.any(self.cfg >= 1e-5) or (self.audio is not None and np.any(self.audio >= 1e-5)))
 
+    def slice(self, b0: int, b1: int) -> "Controls":
+        """The controls of batch rows [b0, b1): per-row forms are sliced (views of this object's arrays), an all-scalar call is itself."""
+        if self.plan is False:
+            return self
+        return Controls(*(None if x is None else x[b0:b1] for x in (self.t, self.cfg, self.audio, self.lo, self.hi)))
 
-def _window_slice(cfg_interval, b0: int, b1: int):
-    """The guidance windows of batch rows [b0, b1): None and a single pair pass through."""
-    if cfg_interval is None or np.ndim(cfg_interval) == 1:
-        return cfg_interval
-    return np.asarray(cfg_interval, dtype=np.float32)[b0:b1]
+    def key_bytes(self) -> tuple:
+        """The values themselves, for a cache key: which evaluations of a window call run one branch follows from them."""
+        return tuple(x.tobytes() for x in (self.t, self.cfg, self.audio, self.lo, self.hi) if x is not None)
 
-
-def _plan_of(rows):
-    """The workspace plan a call's controls need (Engine.workspace `rows`): False, True (per-row), "dual", or with a guidance window
-    "window" / "window_dual"."""
-    if rows is None:
-        return False
-    if getattr(rows, "window", None) is not None:
-        return "window_dual" if len(rows) == 3 else "window"
-    return "dual" if len(rows) == 3 else True
+    def struct(self, cond_keep=None):
+        """-> (name of the C entry point, its filled controls struct); the struct is None for f5_sample / f5_sample_edit, which take the
+        mask as an argument.  cond_keep: the (B, N) uint8 tensor of an edit call, or None."""
+        name, ctype, _, _ = ROUTES[self.plan]
+        if ctype is None:
+            return ("f5_sample" if cond_keep is None else "f5_sample_edit"), None
+        rows = dict(t_rows=self.t, cfg_rows=self.cfg, text_cfg_rows=self.cfg, audio_cfg_rows=self.audio, lo_rows=self.lo, hi_rows=self.hi)
+        fields = {n: 0 if rows[n] is None else rows[n].ctypes.data for n, _ in ctype._fields_ if n != "cond_keep_dev"}
+        return name, ctype(cond_keep_dev=0 if cond_keep is None else cond_keep.data_ptr(), **fields)
 
 
 def library_path() -> Path:
@@ -303,6 +321,9 @@ OPTION_NAMES = ("q_premul", "qkv_transposed", "ln_fusion", "gemm_flags", "attn_p
 # the chip runs these launches under its power cap, and what fills idle CUs comes back as clock.  Hence opt-in: worth it for >= 48.
 SPLIT_MIN_BATCH = 0
 STATUS_FOLD_OVERFLOW, STATUS_FOLD_RAN, STATUS_SATURATED = 1, 2, 4      # include/f5tts_hip.h F5_STATUS_*
+# one half of a split sample(): the handle that runs it, its arguments (and what keeps their host arrays alive), its trajectory buffer, its
+# rows of the mask and of the controls
+_HalfCall = namedtuple("_HalfCall", "eng a keep traj cond_keep ctl")
 
 
 class Engine:
@@ -495,18 +516,12 @@ class Engine:
         of a guidance window behind it (f5_workspace_bytes_window)."""
         if method not in METHODS:
             raise ValueError(f"Unknown method: {method}")
+        plan = rows if isinstance(rows, str) else bool(rows)
+        if plan not in ROUTES:
+            raise ValueError(f"rows must be False, True, 'dual', 'window' or 'window_dual', got {rows!r}")
+        _, _, fn, extra = ROUTES[plan]
         nbytes = C.c_size_t()
-        if rows in ("window", "window_dual"):
-            check(self.lib.f5_workspace_bytes_window(self._h, B, N, nt, steps, METHODS[method], int(rows == "window_dual"), C.byref(nbytes)),
-                  "f5_workspace_bytes_window")
-        elif isinstance(rows, str):
-            if rows != "dual":
-                raise ValueError(f"rows must be False, True, 'dual', 'window' or 'window_dual', got {rows!r}")
-            check(self.lib.f5_workspace_bytes_dual(self._h, B, N, nt, steps, METHODS[method], C.byref(nbytes)), "f5_workspace_bytes_dual")
-        elif rows:
-            check(self.lib.f5_workspace_bytes_rows(self._h, B, N, nt, steps, METHODS[method], C.byref(nbytes)), "f5_workspace_bytes_rows")
-        else:
-            check(self.lib.f5_workspace_bytes(self._h, B, N, nt, steps, METHODS[method], C.byref(nbytes)), "f5_workspace_bytes")
+        check(getattr(self.lib, fn)(self._h, B, N, nt, steps, METHODS[method], *extra, C.byref(nbytes)), fn)
         if self._workspace is None or self._workspace.numel() < nbytes.value:
             self._workspace = None
             self._workspace = _aligned_bytes(nbytes.value, self.device)
@@ -553,25 +568,17 @@ class Engine:
         cond_keep = cond_keep.contiguous()
         return cond_keep.view(torch.uint8) if cond_keep.dtype == torch.bool else cond_keep
 
-    def _call_sample(self, a, cond_keep, st, rows=None) -> None:
-        """f5_sample, f5_sample_edit when the call carries a conditioning mask, f5_sample_rows when it carries per-row controls
-        (rows = (t_rows, cfg_rows) of row_controls; the mask rides in the controls), f5_sample_dual when they carry audio strengths too,
-        f5_sample_window when they carry a guidance window (WindowRows)."""
-        if getattr(rows, "window", None) is not None:
-            lo, hi = rows.window
-            wc = F5WindowControls(rows[0].ctypes.data, rows[1].ctypes.data, rows[2].ctypes.data if len(rows) == 3 else 0, lo.ctypes.data,
-                                  hi.ctypes.data, 0 if cond_keep is None else cond_keep.data_ptr())
-            check(self.lib.f5_sample_window(self._h, C.byref(a), C.byref(wc), st), "f5_sample_window")
-        elif rows is not None and len(rows) == 3:
-            dc = F5DualControls(rows[0].ctypes.data, rows[1].ctypes.data, rows[2].ctypes.data, 0 if cond_keep is None else cond_keep.data_ptr())
-            check(self.lib.f5_sample_dual(self._h, C.byref(a), C.byref(dc), st), "f5_sample_dual")
-        elif rows is not None:
-            rc = F5RowControls(rows[0].ctypes.data, rows[1].ctypes.data, 0 if cond_keep is None else cond_keep.data_ptr())
-            check(self.lib.f5_sample_rows(self._h, C.byref(a), C.byref(rc), st), "f5_sample_rows")
+    def _call_sample(self, a, cond_keep, st, ctl: Controls) -> None:
+        """The sampling entry point of the call's route (ROUTES): f5_sample, or f5_sample_edit when the call carries a conditioning mask,
+        else the per-row call that takes `ctl` -- and the mask -- as its controls struct."""
+        name, cs = ctl.struct(cond_keep)
+        fn = getattr(self.lib, name)
+        if cs is not None:
+            check(fn(self._h, C.byref(a), C.byref(cs), st), name)
         elif cond_keep is None:
-            check(self.lib.f5_sample(self._h, C.byref(a), st), "f5_sample")
+            check(fn(self._h, C.byref(a), st), name)
         else:
-            check(self.lib.f5_sample_edit(self._h, C.byref(a), ptr(cond_keep), st), "f5_sample_edit")
+            check(fn(self._h, C.byref(a), ptr(cond_keep), st), name)
 
     def sample(self, text: torch.Tensor, cond: torch.Tensor, lens: Sequence[int], durations: Sequence[int], y0: torch.Tensor,
                t: np.ndarray, method: str = "euler", cfg_strength: float = 2.0, use_mask: Optional[bool] = None,
@@ -596,42 +603,41 @@ class Engine:
         self._check_inputs(text, cond, lens, durations)
         cond_keep = self._check_keep(cond_keep, cond)
         self.check_status(block=False)                 # a pending check of the previous call: resolved here if it has arrived
+
+        def on_fallback(**over):                       # the same call on the bf16x3 engine
+            kw = dict(method=method, cfg_strength=cfg_strength, use_mask=use_mask, use_graph=use_graph, return_trajectory=return_trajectory,
+                      out=out, trajectory=trajectory, cond_keep=cond_keep, audio_cfg_strength=audio_cfg_strength, cfg_interval=cfg_interval)
+            return self._fallback.sample(text, cond, lens, durations, y0, t, **dict(kw, **over))
+
         if self._use_fallback:                         # an earlier call saturated fp16 / failed its cross-check: bf16x3 from now on
-            return self._fallback.sample(text, cond, lens, durations, y0, t, method=method, cfg_strength=cfg_strength, use_mask=use_mask,
-                                         use_graph=use_graph, return_trajectory=return_trajectory, out=out, trajectory=trajectory,
-                                         cond_keep=cond_keep, audio_cfg_strength=audio_cfg_strength, cfg_interval=cfg_interval)
+            return on_fallback()
         B, N, mel = cond.shape
-        steps, rows = row_controls(t, cfg_strength, B, audio_cfg_strength, cfg_interval)
+        ctl = Controls.of(t, cfg_strength, B, audio_cfg_strength, cfg_interval)
+        steps = ctl.steps
         assert y0.shape == cond.shape and y0.dtype == torch.float32 and y0.is_contiguous() and y0.is_cuda
         if use_mask is None:
             use_mask = B > 1                       # cfm.py:333-336
         if 0 < self.split_batch <= B and self.verify_calls == 0:
-            done = self._sample_split(text, cond, lens, durations, y0, t, steps, method, cfg_strength, use_mask, use_graph,
-                                      return_trajectory, out, trajectory, cond_keep, audio_cfg_strength, cfg_interval)
+            done = self._sample_split(text, cond, lens, durations, y0, ctl, method, use_mask, use_graph, return_trajectory, out, trajectory,
+                                      cond_keep)
             if done is not None:
                 return done                        # (None: a half reported its status word -- the whole call is repeated below, unsplit)
-        ws = self.workspace(B, N, text.shape[1], steps, method, rows=_plan_of(rows))
+        ws = self.workspace(B, N, text.shape[1], steps, method, rows=ctl.plan)
         if out is None:
             out = torch.empty_like(cond)
         if return_trajectory and trajectory is None:
             trajectory = torch.empty((steps, B, N, mel), dtype=torch.float32, device=self.device)
-        # (per-row route: the scalar slots of the arguments are not read; they carry row 0's grid and the largest strength)
-        a, keep = self._args(text, cond, lens, durations, y0, t if rows is None else rows[0][0], steps, method,
-                             cfg_strength if rows is None else float(rows[1].max()), use_mask, use_graph, out,
+        a, keep = self._args(text, cond, lens, durations, y0, ctl.scalar_t, steps, method, ctl.scalar_cfg, use_mask, use_graph, out,
                              trajectory if return_trajectory else None, ws)
-        launch = lambda: self._run_on_side_stream(lambda st: self._call_sample(a, cond_keep, st, rows))  # noqa: E731
+        launch = lambda: self._run_on_side_stream(lambda st: self._call_sample(a, cond_keep, st, ctl))  # noqa: E731
         launch()
         saturated = self._after_call(a, launch, f"sample(B={B}, N={N}, {method}, {steps} points)", (B, N, steps, method))
         del keep
         if saturated and self._use_fallback:           # ("sync": re-run THIS call in bf16x3, into the same output buffers)
-            return self._fallback.sample(text, cond, lens, durations, y0, t, method=method, cfg_strength=cfg_strength, use_mask=use_mask,
-                                         use_graph=use_graph, return_trajectory=return_trajectory, out=out, trajectory=trajectory,
-                                         cond_keep=cond_keep, audio_cfg_strength=audio_cfg_strength, cfg_interval=cfg_interval)
+            return on_fallback()
         if self.verify_calls > 0 and self.precision == "f16" and self._ensure_fallback() is not None:
             self.verify_calls -= 1
-            ref, ref_traj = self._fallback.sample(text, cond, lens, durations, y0, t, method=method, cfg_strength=cfg_strength,
-                                                  use_mask=use_mask, use_graph=False, return_trajectory=return_trajectory,
-                                                  cond_keep=cond_keep, audio_cfg_strength=audio_cfg_strength, cfg_interval=cfg_interval)
+            ref, ref_traj = on_fallback(use_graph=False, out=None, trajectory=None)
             self.last_verify_l1 = l1 = float((out - ref).abs().mean())
             if not (l1 <= self.verify_tol):
                 self.verify_events += 1
@@ -647,8 +653,8 @@ class Engine:
         return out, (trajectory if return_trajectory else None)
 
     # ---- two half batches on two streams ---------------------------------------------------------
-    def _sample_split(self, text, cond, lens, durations, y0, t, steps, method, cfg_strength, use_mask, use_graph, return_trajectory,
-                      out, trajectory, cond_keep=None, audio_cfg_strength=None, cfg_interval=None):
+    def _sample_split(self, text, cond, lens, durations, y0, ctl: Controls, method, use_mask, use_graph, return_trajectory, out, trajectory,
+                      cond_keep=None):
         """sample() of a large batch as two independent half batches: this engine runs utterances [0, h) on its stream, a sibling handle
         on the same weights arena runs [h, B) on its own, each enqueued by its own host thread (the HIP runtime lets a thread run only a
         few dozen launches ahead of the GPU, so one thread cannot keep two streams fed).  Utterances do not interact (both halves keep
@@ -663,68 +669,74 @@ class Engine:
         cur = torch.cuda.current_stream(self.device)
         if out is None:
             out = torch.empty_like(cond)
-        nt = text.shape[1]
+        nt, steps = text.shape[1], ctl.steps
         calls = []
         for eng, (b0, b1) in ((self, (0, h)), (sib, (h, B))):
             tr = torch.empty((steps, b1 - b0, N, mel), dtype=torch.float32, device=self.device) if return_trajectory else None
-            th, ch = _rows_slice(t, cfg_strength, b0, b1)                  # (each half gets its rows of the controls ...)
-            _, rows = row_controls(th, ch, b1 - b0, _audio_slice(audio_cfg_strength, b0, b1), _window_slice(cfg_interval, b0, b1))
-            ws = eng.workspace(b1 - b0, N, nt, steps, method, rows=_plan_of(rows))
-            a, keep = eng._args(text[b0:b1], cond[b0:b1], lens[b0:b1], durations[b0:b1], y0[b0:b1], th if rows is None else rows[0][0], steps,
-                                method, ch if rows is None else float(rows[1].max()), use_mask, use_graph, out[b0:b1], tr, ws)
-            calls.append((eng, a, keep, tr, None if cond_keep is None else cond_keep[b0:b1], rows))     # (... and of the mask)
+            half = ctl.slice(b0, b1)                   # (each half gets its rows of the controls ...)
+            ws = eng.workspace(b1 - b0, N, nt, steps, method, rows=half.plan)
+            a, keep = eng._args(text[b0:b1], cond[b0:b1], lens[b0:b1], durations[b0:b1], y0[b0:b1], half.scalar_t, steps, method,
+                                half.scalar_cfg, use_mask, use_graph, out[b0:b1], tr, ws)
+            calls.append(_HalfCall(eng, a, keep, tr, None if cond_keep is None else cond_keep[b0:b1], half))     # (... and of the mask)
 
-        def run(eng, a, ck, rows):
+        def run(c):
             torch.cuda.set_device(self.device)         # (the worker thread's current device)
-            eng._run_on_side_stream(lambda st: eng._call_sample(a, ck, st, rows), cur)
+            c.eng._run_on_side_stream(lambda st: c.eng._call_sample(c.a, c.cond_keep, st, c.ctl), cur)
 
-        guided = tuple(bool(np.any(np.asarray(c[5][1] if c[5] is not None else cfg_strength) >= 1e-5)
-                            or (c[5] is not None and len(c[5]) == 3 and np.any(c[5][2] >= 1e-5))) for c in calls)
-        key = (B, N, nt, steps, method, use_graph, bool(use_mask), return_trajectory, guided, cond_keep is not None, _plan_of(calls[0][5]))
-        if cfg_interval is not None:
+        key = (B, N, nt, steps, method, use_graph, bool(use_mask), return_trajectory, tuple(c.ctl.guided for c in calls), cond_keep is not None,
+               ctl.plan)
+        if ctl.lo is not None:
             # which evaluations run one branch follows from the times, strengths and bounds (the C call works it out): a new set of them
             # may mean a new graph, and a capture runs the halves one after the other
-            key += tuple(x.tobytes() for c in calls for x in tuple(c[5]) + tuple(c[5].window))
+            key += tuple(x for c in calls for x in c.ctl.key_bytes())
         if key in self._split_seen:
-            fut = self._pool.submit(run, calls[1][0], calls[1][1], calls[1][4], calls[1][5])
+            fut = self._pool.submit(run, calls[1])
             try:
-                run(calls[0][0], calls[0][1], calls[0][4], calls[0][5])
+                run(calls[0])
             finally:
                 fut.result()
         else:
-            for eng, a, _, _, ck, rows in calls:
-                run(eng, a, ck, rows)
+            for c in calls:
+                run(c)
             self._split_seen.add(key)
         flags = 0
         if self._status_host is not None and self.range_check != "off":
-            for eng, a, _, _, _, _ in calls:
-                flags |= eng._status_word_blocking(a, cur)
+            for c in calls:
+                flags |= c.eng._status_word_blocking(c.a, cur)
         if flags & (STATUS_FOLD_OVERFLOW | STATUS_SATURATED):
             return None
         self.split_events += 1
         if return_trajectory:
             if trajectory is None:
-                trajectory = torch.cat([calls[0][3], calls[1][3]], dim=1)
+                trajectory = torch.cat([calls[0].traj, calls[1].traj], dim=1)
             else:
-                trajectory[:, :h].copy_(calls[0][3])
-                trajectory[:, h:].copy_(calls[1][3])
+                trajectory[:, :h].copy_(calls[0].traj)
+                trajectory[:, h:].copy_(calls[1].traj)
         return out, (trajectory if return_trajectory else None)
 
-    def _status_word_blocking(self, a, cur=None) -> int:
-        """The status word of the call described by `a`, read behind it on this engine's stream; waits for it."""
-        if not self._status_free:
+    def _take_status_slot(self) -> int:
+        if not self._status_free:                      # 16 calls ahead of the GPU: wait for the oldest check
             self._status_pending[0][0].synchronize()
             self.check_status(block=False)
-        slot = self._status_free.pop(0)
-        holder = {}
+        return self._status_free.pop(0)
+
+    def _enqueue_status_read(self, a, slot: int, cur=None) -> torch.cuda.Event:
+        """The 4-byte copy of the status word of the call described by `a` into pinned slot `slot`, enqueued behind the call on this
+        engine's stream -> the event recorded behind the copy."""
+        done = []
 
         def enqueue_read(st):
             check(self.lib.f5_sample_status_async(self._h, C.byref(a), C.c_void_p(self._status_host[slot:].data_ptr()), st), "f5_sample_status_async")
-            holder["ev"] = torch.cuda.Event()
-            holder["ev"].record(torch.cuda.current_stream(self.device))
+            done.append(torch.cuda.Event())
+            done[0].record(torch.cuda.current_stream(self.device))
 
         self._run_on_side_stream(enqueue_read, cur)
-        holder["ev"].synchronize()
+        return done[0]
+
+    def _status_word_blocking(self, a, cur=None) -> int:
+        """The status word of the call described by `a`, read behind it on this engine's stream; waits for it."""
+        slot = self._take_status_slot()
+        self._enqueue_status_read(a, slot, cur).synchronize()
         flags = int(self._status_host[slot])
         self._status_free.append(slot)
         return flags
@@ -806,28 +818,17 @@ class Engine:
         mode = self.range_check
         if mode == "auto":
             mode = "async" if (shape == self._clean_shape and self._clean_calls >= self.range_probation) else "sync"
-        if not self._status_free:                      # 16 calls ahead of the GPU: wait for the oldest check
-            self._status_pending[0][0].synchronize()
-            self.check_status(block=False)
-        slot = self._status_free.pop(0)
-        holder = {}
-
-        def enqueue_read(st):
-            check(self.lib.f5_sample_status_async(self._h, C.byref(a), C.c_void_p(self._status_host[slot:].data_ptr()), st), "f5_sample_status_async")
-            holder["ev"] = torch.cuda.Event()
-            holder["ev"].record(torch.cuda.current_stream(self.device))
-
-        self._run_on_side_stream(enqueue_read)
+        slot = self._take_status_slot()
+        ev = self._enqueue_status_read(a, slot)
         if mode != "sync":
-            self._status_pending.append((holder["ev"], slot, what, shape))
+            self._status_pending.append((ev, slot, what, shape))
             return False
-        holder["ev"].synchronize()
+        ev.synchronize()
         flags = int(self._status_host[slot])
         if (flags & STATUS_FOLD_OVERFLOW) and not (flags & STATUS_SATURATED):
             self._resolve(flags, what, shape, rerun=True)
             launch()                                   # ln_fold is 0 now: this run cannot carry bit 0; bit 2 is looked at below
-            self._run_on_side_stream(enqueue_read)
-            holder["ev"].synchronize()
+            self._enqueue_status_read(a, slot).synchronize()
             flags = int(self._status_host[slot]) & ~STATUS_FOLD_OVERFLOW
         self._status_free.append(slot)
         return self._resolve(flags, what, shape, rerun=True)
@@ -860,16 +861,12 @@ class Engine:
         a, keep = self._args(text, cond, lens, durations, None, np.zeros(2, np.float32), 2, "euler", cfg_strength, use_mask,
                              False, None, None, ws)
         if dual:
-            launch = lambda: self._run_on_side_stream(lambda st: check(   # noqa: E731
-                self.lib.f5_dit_forward_dual(self._h, C.byref(a), ptr(x), C.c_void_p(t_rows.ctypes.data), ptr(pred), ptr(null), ptr(text_pred),
-                                             st), "f5_dit_forward_dual"))
+            name, targs = "f5_dit_forward_dual", (C.c_void_p(t_rows.ctypes.data), ptr(pred), ptr(null), ptr(text_pred))
         elif t_rows is None:
-            launch = lambda: self._run_on_side_stream(lambda st: check(   # noqa: E731
-                self.lib.f5_dit_forward(self._h, C.byref(a), ptr(x), C.c_float(t), ptr(pred), ptr(null), st), "f5_dit_forward"))
+            name, targs = "f5_dit_forward", (C.c_float(t), ptr(pred), ptr(null))
         else:
-            launch = lambda: self._run_on_side_stream(lambda st: check(   # noqa: E731
-                self.lib.f5_dit_forward_rows(self._h, C.byref(a), ptr(x), C.c_void_p(t_rows.ctypes.data), ptr(pred), ptr(null), st),
-                "f5_dit_forward_rows"))
+            name, targs = "f5_dit_forward_rows", (C.c_void_p(t_rows.ctypes.data), ptr(pred), ptr(null))
+        launch = lambda: self._run_on_side_stream(lambda st: check(getattr(self.lib, name)(self._h, C.byref(a), ptr(x), *targs, st), name))  # noqa: E731
         launch()
         saturated = self._after_call(a, launch, f"dit_forward(B={B}, N={N})", (B, N, 2, "forward"))
         del keep

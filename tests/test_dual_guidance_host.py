@@ -18,12 +18,13 @@ from f5_tts_mlx_amd import generate as G
 from f5_tts_mlx_amd.cfm import time_grid, time_grid_rows
 
 # (config, precision, B, N, nt, steps, method) -> f5_workspace_bytes, f5_workspace_bytes_rows of the commit before dual guidance,
-# taken from a build of that commit: the two-branch plans must not move
+# taken from a build of that commit: the two-branch plans must not move; and f5_workspace_bytes_dual of the commit before the planners
+# became one, taken from a build of that one: nor must the three-branch plan
 PARENT_BYTES = {
-    ("tiny", "bf16x3", 3, 37, 9, 5, "euler"): (5344000, 5553152),
-    ("tiny", "f16", 2, 80, 16, 3, "rk4"): (5211136, 5489920),
-    ("full", "f16", 2, 937, 120, 32, "euler"): (195817984, 230419456),
-    ("full", "mxfp8", 4, 500, 64, 4, "midpoint"): (187952128, 201346304),
+    ("tiny", "bf16x3", 3, 37, 9, 5, "euler"): (5344000, 5553152, 7101696),
+    ("tiny", "f16", 2, 80, 16, 3, "rk4"): (5211136, 5489920, 6790912),
+    ("full", "f16", 2, 937, 120, 32, "euler"): (195817984, 230419456, 283557376),
+    ("full", "mxfp8", 4, 500, 64, 4, "midpoint"): (187952128, 201346304, 258054656),
 }
 
 
@@ -49,7 +50,7 @@ def test_workspace_plans(key):
     try:
         plain, rows, dual = (_bytes(lib, fn, h, B, N, nt, steps, method)
                              for fn in ("f5_workspace_bytes", "f5_workspace_bytes_rows", "f5_workspace_bytes_dual"))
-        assert (plain, rows) == PARENT_BYTES[key]
+        assert (plain, rows, dual) == PARENT_BYTES[key]
         # the third branch: at least x (fp32) and the fp32 hoisted projection and velocity of B N more rows, on top of the rows plan
         assert dual >= rows + B * N * (2 * cfg.dim + cfg.mel_dim) * 4
         v = C.c_size_t()
@@ -97,20 +98,22 @@ def test_dual_controls_struct_matches_the_header(tmp_path):
 # ---- Engine's control normalisation ---------------------------------------------------------------------------------------------------
 def test_engine_row_controls_with_audio_strength():
     t = time_grid(5, -1.0)
-    assert E.row_controls(t, 2.0, 3, None) == (5, None)                        # None: today's call
-    steps, rows = E.row_controls(t, 2.0, 3, 1.5)                               # a scalar selects the route all the same
-    assert steps == 5 and len(rows) == 3 and E._plan_of(rows) == "dual"
-    tr, cr, ar = rows
+    c = E.Controls.of(t, 2.0, 3, None)                                         # None: today's call
+    assert c.steps == 5 and c.plan is False and c.struct()[1] is None
+    c = E.Controls.of(t, 2.0, 3, 1.5)                                          # a scalar selects the route all the same
+    assert c.steps == 5 and c.audio is not None and c.lo is None and c.plan == "dual"
+    tr, cr, ar = rows = (c.t, c.cfg, c.audio)
     assert tr.shape == (3, 5) and all(np.array_equal(r, t) for r in tr) and cr.tolist() == [2.0] * 3 and ar.tolist() == [1.5] * 3
     assert all(x.dtype == np.float32 and x.flags["C_CONTIGUOUS"] for x in rows)
     grids = time_grid_rows(5, [-1.0, None, -0.5])
-    steps, (tr, cr, ar) = E.row_controls(grids, [0.5, 0.0, 2.0], 3, [3.0, 0.0, 0.0])
-    assert np.array_equal(tr, grids) and cr.tolist() == [0.5, 0.0, 2.0] and ar.tolist() == [3.0, 0.0, 0.0]
+    c = E.Controls.of(grids, [0.5, 0.0, 2.0], 3, [3.0, 0.0, 0.0])
+    assert np.array_equal(c.t, grids) and c.cfg.tolist() == [0.5, 0.0, 2.0] and c.audio.tolist() == [3.0, 0.0, 0.0]
     with pytest.raises(ValueError, match="audio_cfg_strength: expected 3 values"):
-        E.row_controls(t, 2.0, 3, [1.0, 2.0])
-    assert E._plan_of(None) is False and E._plan_of(E.row_controls(t, [1.0, 2.0, 3.0], 3)[1]) is True
+        E.Controls.of(t, 2.0, 3, [1.0, 2.0])
+    assert E.Controls.of(t, 2.0, 3).plan is False and E.Controls.of(t, [1.0, 2.0, 3.0], 3).plan is True
     # the halves of a split call get their rows
-    assert E._audio_slice(None, 1, 3) is None and E._audio_slice(1.5, 1, 3) == 1.5 and E._audio_slice([3.0, 0.0, 0.5], 1, 3) == [0.0, 0.5]
+    assert E.Controls.of(t, 2.0, 3, None).slice(1, 3).audio is None and E.Controls.of(t, 2.0, 3, 1.5).slice(1, 3).audio.tolist() == [1.5, 1.5]
+    assert E.Controls.of(t, 2.0, 3, [3.0, 0.0, 0.5]).slice(1, 3).audio.tolist() == [0.0, 0.5]
 
 
 # ---- generate / generate_many / requests file / command line ---------------------------------------------------------------------------

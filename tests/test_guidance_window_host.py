@@ -93,32 +93,35 @@ def test_window_controls_struct_matches_the_header(tmp_path):
 # ---- Engine's control normalisation ---------------------------------------------------------------------------------------------------
 def test_engine_row_controls_with_cfg_interval():
     t = time_grid(5, -1.0)
-    assert E.row_controls(t, 2.0, 3, None, None) == (5, None)                  # None: today's call
-    steps, rows = E.row_controls(t, 2.0, 3, cfg_interval=(0.25, 0.5))          # one pair selects the route and is broadcast, with t and cfg
-    assert steps == 5 and isinstance(rows, E.WindowRows) and len(rows) == 2 and E._plan_of(rows) == "window"
-    tr, cr = rows
-    lo, hi = rows.window
+    c = E.Controls.of(t, 2.0, 3, None, None)                                   # None: today's call
+    assert c.steps == 5 and c.plan is False and c.struct()[1] is None
+    c = E.Controls.of(t, 2.0, 3, cfg_interval=(0.25, 0.5))                     # one pair selects the route and is broadcast, with t and cfg
+    assert c.steps == 5 and c.lo is not None and c.audio is None and c.plan == "window"
+    tr, cr, lo, hi = c.t, c.cfg, c.lo, c.hi
     assert tr.shape == (3, 5) and all(np.array_equal(r, t) for r in tr) and cr.tolist() == [2.0] * 3
     assert lo.tolist() == [0.25] * 3 and hi.tolist() == [0.5] * 3
     assert all(x.dtype == np.float32 and x.flags["C_CONTIGUOUS"] for x in (tr, cr, lo, hi))
     grids = time_grid_rows(5, [-1.0, None, -0.5])
     pairs = [[0.0, 0.5], [0.25, 0.75], [-1.0, 2.0]]
-    steps, rows = E.row_controls(grids, [0.5, 0.0, 2.0], 3, [3.0, 0.0, 0.0], pairs)          # per-row forms of everything, dual guidance
-    assert len(rows) == 3 and E._plan_of(rows) == "window_dual" and np.array_equal(rows[0], grids)
-    assert rows[1].tolist() == [0.5, 0.0, 2.0] and rows[2].tolist() == [3.0, 0.0, 0.0]
-    assert rows.window[0].tolist() == [0.0, 0.25, -1.0] and rows.window[1].tolist() == [0.5, 0.75, 2.0]
+    c = E.Controls.of(grids, [0.5, 0.0, 2.0], 3, [3.0, 0.0, 0.0], pairs)       # per-row forms of everything, dual guidance
+    assert c.audio is not None and c.plan == "window_dual" and np.array_equal(c.t, grids)
+    assert c.cfg.tolist() == [0.5, 0.0, 2.0] and c.audio.tolist() == [3.0, 0.0, 0.0]
+    assert c.lo.tolist() == [0.0, 0.25, -1.0] and c.hi.tolist() == [0.5, 0.75, 2.0]
     # rows without a window keep their plans
-    assert E._plan_of(E.row_controls(t, [1.0, 2.0, 3.0], 3)[1]) is True and E._plan_of(E.row_controls(t, 2.0, 3, 1.0)[1]) == "dual"
+    assert E.Controls.of(t, [1.0, 2.0, 3.0], 3).plan is True and E.Controls.of(t, 2.0, 3, 1.0).plan == "dual"
     for bad in ([0.1, 0.2, 0.3], [[0.1, 0.2]] * 2, 0.5, [[0.1, 0.2, 0.3]] * 3):
         with pytest.raises(ValueError, match=r"cfg_interval: expected \(lo, hi\) or 3 pairs of shape \(3, 2\)"):
-            E.row_controls(t, 2.0, 3, cfg_interval=bad)
+            E.Controls.of(t, 2.0, 3, cfg_interval=bad)
     with pytest.raises(ValueError, match="expected 3 values"):
-        E.row_controls(t, [1.0, 2.0], 3, cfg_interval=(0.0, 1.0))
+        E.Controls.of(t, [1.0, 2.0], 3, cfg_interval=(0.0, 1.0))
     with pytest.raises(ValueError, match="audio_cfg_strength: expected 3 values"):
-        E.row_controls(t, 2.0, 3, [1.0, 2.0], (0.0, 1.0))
+        E.Controls.of(t, 2.0, 3, [1.0, 2.0], (0.0, 1.0))
     # the halves of a split call get their rows
-    assert E._window_slice(None, 1, 3) is None and E._window_slice((0.1, 0.2), 1, 3) == (0.1, 0.2)
-    assert np.array_equal(E._window_slice(pairs, 1, 3), np.asarray(pairs[1:], np.float32))
+    assert E.Controls.of(t, 2.0, 3, None, None).slice(1, 3).lo is None
+    half = E.Controls.of(t, 2.0, 3, cfg_interval=(0.1, 0.2)).slice(1, 3)
+    assert half.lo.tolist() == [np.float32(0.1)] * 2 and half.hi.tolist() == [np.float32(0.2)] * 2
+    half = E.Controls.of(t, 2.0, 3, cfg_interval=pairs).slice(1, 3)
+    assert np.array_equal(np.stack([half.lo, half.hi], 1), np.asarray(pairs[1:], np.float32))
 
 
 # ---- generate / generate_many / requests file / command line ---------------------------------------------------------------------------

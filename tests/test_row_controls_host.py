@@ -121,24 +121,89 @@ def test_per_row():
 
 def test_engine_row_controls_normalisation():
     t = time_grid(5, -1.0)
-    assert E.row_controls(t, 2.0, 3) == (5, None)                     # all-scalar: the old route
-    steps, (tr, cr) = E.row_controls(t, [2.0, 0.0, 1.3], 3)           # per-row cfg broadcasts the grid
+    c = E.Controls.of(t, 2.0, 3)                                      # all-scalar: the old route
+    assert c.steps == 5 and c.plan is False and c.struct()[1] is None
+    c = E.Controls.of(t, [2.0, 0.0, 1.3], 3)                          # per-row cfg broadcasts the grid
+    steps, tr, cr = c.steps, c.t, c.cfg
     assert steps == 5 and tr.shape == (3, 5) and tr.dtype == np.float32 and tr.flags["C_CONTIGUOUS"] and all(np.array_equal(r, t) for r in tr)
     assert cr.dtype == np.float32 and cr.tolist() == [2.0, 0.0, np.float32(1.3)]
     grids = time_grid_rows(5, [-1.0, None, -0.5])
-    steps, (tr, cr) = E.row_controls(grids, 2.0, 3)                   # per-row grid broadcasts cfg
+    c = E.Controls.of(grids, 2.0, 3)                                  # per-row grid broadcasts cfg
+    steps, tr, cr = c.steps, c.t, c.cfg
     assert steps == 5 and np.array_equal(tr, grids) and cr.tolist() == [2.0, 2.0, 2.0] and cr.flags["C_CONTIGUOUS"]
     with pytest.raises(ValueError, match="expected 3 rows, got 2"):
-        E.row_controls(grids[:2], 2.0, 3)
+        E.Controls.of(grids[:2], 2.0, 3)
     with pytest.raises(ValueError, match="expected 3 values"):
-        E.row_controls(t, [1.0, 2.0], 3)
+        E.Controls.of(t, [1.0, 2.0], 3)
     with pytest.raises(ValueError, match=r"t must be \(steps,\) or \(B, steps\)"):
-        E.row_controls(np.zeros((2, 2, 2), np.float32), 2.0, 2)
+        E.Controls.of(np.zeros((2, 2, 2), np.float32), 2.0, 2)
     # the halves of a split call get their rows
-    th, ch = E._rows_slice(grids, [2.0, 0.0, 1.3], 1, 3)
-    assert np.array_equal(th, grids[1:3]) and ch == [0.0, 1.3]
-    th, ch = E._rows_slice(t, 2.0, 1, 3)
-    assert np.array_equal(th, t) and ch == 2.0
+    half = E.Controls.of(grids, [2.0, 0.0, 1.3], 3).slice(1, 3)
+    assert np.array_equal(half.t, grids[1:3]) and half.cfg.tolist() == [0.0, np.float32(1.3)]
+    half = E.Controls.of(t, 2.0, 3).slice(1, 3)
+    assert np.array_equal(half.t, t) and half.cfg == 2.0 and half.plan is False
+
+
+FIELDS = ("t", "cfg", "audio", "lo", "hi")
+
+
+def same_controls(a, b):
+    """Field by field: both None, or equal fp32 C-contiguous arrays of one shape."""
+    for f in FIELDS:
+        x, y = getattr(a, f), getattr(b, f)
+        assert (x is None) == (y is None), f
+        if x is not None:
+            assert x.dtype == y.dtype == np.float32 and x.shape == y.shape and np.array_equal(x, y), f
+            assert x.flags["C_CONTIGUOUS"] and y.flags["C_CONTIGUOUS"], f
+    assert a.plan == b.plan and a.steps == b.steps and a.guided == b.guided and a.key_bytes() == b.key_bytes()
+
+
+def sliced_input(v, b0, b1, per_row_ndim):
+    """Rows [b0, b1) of one sample() argument: a per-row form (ndim == per_row_ndim) is sliced, None and a shared one pass through."""
+    return v if v is None or np.ndim(v) != per_row_ndim else np.asarray(v)[b0:b1]
+
+
+@pytest.mark.parametrize("b0,b1", [(0, 2), (2, 3)])
+def test_controls_slice_is_controls_of_the_sliced_inputs(b0, b1):
+    B = 3
+    ts = (time_grid(5, -1.0), time_grid_rows(5, [-1.0, None, -0.5]))
+    cfgs = (2.0, [2.0, 0.0, 1.3])
+    audios = (None, 1.5, [3.0, 0.0, 0.5])
+    windows = (None, (0.25, 0.5), [[0.0, 0.5], [0.25, 0.75], [-1.0, 2.0]])
+    for t in ts:
+        for cfg in cfgs:
+            for audio in audios:
+                for win in windows:
+                    got = E.Controls.of(t, cfg, B, audio, win).slice(b0, b1)
+                    want = E.Controls.of(sliced_input(t, b0, b1, 2), sliced_input(cfg, b0, b1, 1), b1 - b0, sliced_input(audio, b0, b1, 1),
+                                         sliced_input(win, b0, b1, 2))
+                    same_controls(got, want)
+
+
+def test_controls_struct_names_the_entry_point_of_each_plan():
+    t, grids, B = time_grid(5, -1.0), time_grid_rows(5, [-1.0, None, -0.5]), 3
+    mask = torch.ones((B, 7), dtype=torch.uint8)
+    pairs = [[0.0, 0.5], [0.25, 0.75], [-1.0, 2.0]]
+    cases = [(E.Controls.of(t, 2.0, B), False, None, None),
+             (E.Controls.of(grids, 2.0, B), True, "f5_sample_rows", E.F5RowControls),
+             (E.Controls.of(t, 2.0, B, [3.0, 0.0, 0.5]), "dual", "f5_sample_dual", E.F5DualControls),
+             (E.Controls.of(t, [2.0, 0.0, 1.3], B, None, pairs), "window", "f5_sample_window", E.F5WindowControls),
+             (E.Controls.of(grids, 2.0, B, 1.5, (0.25, 0.5)), "window_dual", "f5_sample_window", E.F5WindowControls)]
+    for c, plan, name, ctype in cases:
+        assert c.plan == plan and (plan is not False or c.plan is False)
+        if ctype is None:                                             # the two calls without a controls struct: the mask is an argument
+            assert c.struct() == ("f5_sample", None) and c.struct(mask) == ("f5_sample_edit", None)
+            continue
+        for m in (None, mask):
+            got_name, cs = c.struct(m)
+            assert got_name == name and type(cs) is ctype
+            assert cs.cond_keep_dev == (None if m is None else m.data_ptr())       # (ctypes reads a void pointer of 0 back as None)
+            assert cs.t_rows == c.t.ctypes.data
+            assert (cs.cfg_rows if ctype is E.F5RowControls else cs.text_cfg_rows) == c.cfg.ctypes.data
+            if ctype is not E.F5RowControls:
+                assert cs.audio_cfg_rows == (None if c.audio is None else c.audio.ctypes.data)
+            if ctype is E.F5WindowControls:
+                assert cs.lo_rows == c.lo.ctypes.data and cs.hi_rows == c.hi.ctypes.data
 
 
 # ---- F5TTS.sample on a stand-in engine -----------------------------------------------------------------------------------------------
