@@ -19,7 +19,7 @@ import torch
 
 from .audio import MelSpec
 from .dit import DiT
-from .engine import noise_normal
+from .engine import check_isolate_rows, noise_normal
 from .utils import (default, exists, fetch_from_hub, lens_to_mask, list_str_to_idx, list_str_to_tensor,
                     mask_from_frac_lengths)
 from .weights import convert_upstream_weights, dequantize_mlx_checkpoint
@@ -234,9 +234,16 @@ class F5TTS:
                                                  # SPEAKER strength (full against text-only); None = the single-knob call, untouched
         cfg_interval=None,                       # extension (guidance window, docs/guidance_window.md): (lo, hi) or one pair per row; a
                                                  # row is guided only at evaluations whose time lies in [lo, hi]; None = guided throughout
+        isolate_rows: bool = False,              # extension (docs/isolate_rows.md): a row of a padded batch reads nothing from its own
+                                                 # frames n >= duration[b], so it no longer depends on its batch-mates; one value per
+                                                 # call (an engine option: one hipGraph serves each value), False = the call as it was
     ) -> tuple[torch.Tensor, torch.Tensor]:
         self.eval()
         device = self.transformer.device
+        iso_kw = {}
+        if isolate_rows is not False:            # (unset: nothing new is called, no option is written)
+            check_isolate_rows(isolate_rows, self.transformer.engine.precision)
+            iso_kw["isolate_rows"] = isolate_rows
         cond = torch.as_tensor(cond)
 
         # raw wave (cfm.py:283-286): batch 1 only, like the reference's `rearrange("1 n -> n")` -- or, with `wave_lens`, a padded batch
@@ -328,7 +335,7 @@ class F5TTS:
         out, trajectory = self.transformer.engine.sample(
             text.to(device).contiguous(), cond_p, lens.tolist(), duration.tolist(), y0, t, method=method,
             cfg_strength=[float(v) for v in cfg_rows] if cfg_seq else float(cfg_strength), use_mask=(batch > 1 or pad_to is not None), use_graph=use_graph, return_trajectory=True,
-            cond_keep=cond_keep, **dual_kw)
+            cond_keep=cond_keep, **dual_kw, **iso_kw)
 
         if exists(self._vocoder):
             out = self._vocoder(out)

@@ -3,7 +3,8 @@
 //   out[n][co] = sum_{tap, ci} x[n + tap - 15][ci] * w[co][tap][ci]      (M = tokens, N = 64, K = taps*64)
 // The A operand is a sliding window over ONE LDS-resident halo tile of x ((128 + taps - 1) rows x 64 ci),
 // so x is read from HBM once per block; the per-tap weight slab [64 co][64 ci] is double-buffered.
-// Sequence edges are zero padded per batch element (Conv1d padding); no mask (dit.py:251 passes none).
+// Sequence edges are zero padded per batch element (Conv1d padding); no mask (dit.py:251 passes none).  With F5ConvPosArgs::lens the
+// edge of element b is lens[b] instead of seq_len: the conv of that element alone, whatever the rows behind it hold.
 // Two kernels: f5_convpos_kernel (register-staged slabs, small LDS footprint: several workgroups per CU hide each other's round
 // trips) and, for single-segment grids of one round, f5_convpos_ring_kernel further down (same arithmetic, slabs by LDS-DMA into a ring).
 #include "convpos.hpp"
@@ -24,7 +25,9 @@ namespace F5_NS {
 // TPS = taps per pipeline step: the weight slabs of TPS taps are fetched, stored and synchronised together (fewer, fatter
 // steps).  Measured no better than TPS = 1 at batch 1 and worse at batch 32, where the 18 KB weight ring of TPS = 1 lets 3-4
 // workgroups share a CU (tools/convpos_bench.py); what did help at batch 1 is the block numbering below (25.5 -> 19.8 us).
-template <bool HP, int TPS>
+// LENS: the launch carries row lengths (F5ConvPosArgs::lens).  Without them the instantiation is the kernel as it was, instruction for
+// instruction: the batch-1 launches are one round of workgroups and pay for every scalar load in front of their first request.
+template <bool HP, int TPS, bool LENS>
 __global__ __launch_bounds__(256) void f5_convpos_kernel(F5ConvPosArgs p) {
     constexpr int NP = HP ? 2 : 1;
     constexpr int HALO = CP_ROWS + CP_MAXTAPS - 1;
@@ -61,12 +64,16 @@ __global__ __launch_bounds__(256) void f5_convpos_kernel(F5ConvPosArgs p) {
     const int halo = CP_ROWS + taps - 1;
     const size_t rowbase = (size_t)b * p.seq_len;
     const int kdim = taps * 64;
+    // row lengths: this element's rows n >= len_b are zeros in the halo tile, never loaded, and are not written.  A workgroup whose whole
+    // token tile lies there has nothing to write: it leaves (n0 and b are workgroup-uniform).
+    const int len_b = LENS ? min(max(p.lens[b], 0), p.seq_len) : p.seq_len;
+    if (LENS && n0 >= len_b) return;
 
-    // ---- stage the x halo tile (zero outside [0, seq_len)) --------------------------------------
+    // ---- stage the x halo tile (zero outside [0, len_b)) ----------------------------------------
     for (int qd = tid; qd < halo * 8; qd += 256) {
         const int r = qd >> 3, c = qd & 7;
         const int n = n0 - pad + r;
-        const bool ok = (n >= 0) && (n < p.seq_len);
+        const bool ok = (n >= 0) && (n < len_b);
 #pragma unroll
         for (int pp = 0; pp < NP; ++pp) {
             u32x4 v = {0u, 0u, 0u, 0u};
@@ -174,7 +181,7 @@ __global__ __launch_bounds__(256) void f5_convpos_kernel(F5ConvPosArgs p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int n = n0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            if (n < p.seq_len) {
+            if (n < len_b) {
                 const float v = f5_mish(acc[nb][r] + bias);
                 const size_t off = (rowbase + n) * p.ldo + co;
                 if ((CP_ABL & 8) && p.taps > 0) {
@@ -201,7 +208,7 @@ __global__ __launch_bounds__(256) void f5_convpos_kernel(F5ConvPosArgs p) {
 //   - the weight slabs go HBM -> LDS by global_load_lds (16 B per lane, no staging VGPRs) into a ring of NST slots of 8 KB; the first
 //     NST - 1 slabs are requested in the prologue, and behind every tap's barrier the next one goes into the slot of the tap before.
 //     One barrier per tap; the counted `s_waitcnt vmcnt` in front of it leaves NST - 3 slabs in flight;
-//   - the halo tile goes the same way, in front of slab 0 (rows outside [0, seq_len) are zeros written by ds_write), so the prologue
+//   - the halo tile goes the same way, in front of slab 0 (rows outside [0, len_b) are zeros written by ds_write), so the prologue
 //     is one burst of requests and not a chain of load -> store -> load;
 //   - the fragments of tap t + 1 are read from LDS into a second register set BEFORE the MFMAs of tap t (tools/convpos_bench.py's probe
 //     builds: with a read -> wait -> MFMA sequence per K step the tap loop without any slab traffic took 7.7 us against 3.4 us of
@@ -246,7 +253,7 @@ __device__ __forceinline__ void cp_vmcnt() {
 
 constexpr size_t cp_ring_lds_bytes(int nst) { return (size_t)(CPR_XROWS * 64 + nst * CPR_SLAB) * sizeof(op16_t); }
 
-template <int NST>
+template <int NST, bool LENS>
 __global__ __launch_bounds__(256) void f5_convpos_ring_kernel(F5ConvPosArgs p) {
     static_assert(NST >= 3 && 2 * (NST - 2) + 34 < 64, "ring depth: two slabs in use, vmcnt range");
     extern __shared__ __attribute__((aligned(16))) op16_t cp_smem[];
@@ -277,6 +284,9 @@ __global__ __launch_bounds__(256) void f5_convpos_ring_kernel(F5ConvPosArgs p) {
     const int halo = CP_ROWS + taps - 1;
     const size_t rowbase = (size_t)b * p.seq_len;
     const int kdim = taps * 64;
+    // row lengths as in f5_convpos_kernel; the workgroup-uniform exit lies in front of the first LDS-DMA issue and of every barrier
+    const int len_b = LENS ? min(max(p.lens[b], 0), p.seq_len) : p.seq_len;
+    if (LENS && n0 >= len_b) return;
 
     // ---- halo tile: in-range rows by LDS-DMA (the lanes of the other rows are masked off and write zeros themselves) ----------
 #pragma unroll
@@ -284,7 +294,7 @@ __global__ __launch_bounds__(256) void f5_convpos_ring_kernel(F5ConvPosArgs p) {
         const int qd = j * 256 + tid;
         const int r = qd >> 3, c = qd & 7;
         const int n = n0 - pad + r;
-        if (r < halo && n >= 0 && n < p.seq_len)
+        if (r < halo && n >= 0 && n < len_b)
             cp_glds16(p.in[0] + (rowbase + n) * p.ld + g * 64 + ((c ^ ((r >> 1) & 7)) << 3), sX + (j * 256 + wave * 64) * 8);
         else
             *reinterpret_cast<u32x4*>(&sX[qd * 8]) = u32x4{0u, 0u, 0u, 0u};
@@ -395,7 +405,7 @@ __global__ __launch_bounds__(256) void f5_convpos_ring_kernel(F5ConvPosArgs p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int n = n0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            if (n < p.seq_len) {
+            if (n < len_b) {
                 const float v = f5_mish(acc[nb][r] + bias);
                 const size_t off = (rowbase + n) * p.ldo + co;
                 if ((CP_ABL & 8) && p.taps > 0) {
@@ -414,19 +424,20 @@ __global__ __launch_bounds__(256) void f5_convpos_ring_kernel(F5ConvPosArgs p) {
     f5_sat_commit(trk, p.sat_flag);
 }
 
-// the ring kernel's LDS (84 KB at 8 slots) is beyond the 64 KB a kernel gets without asking: asked once per device
+// the ring kernel's LDS (84 KB at 8 slots) is beyond the 64 KB a kernel gets without asking: asked once per device and instantiation
+template <bool LENS>
 static int cp_launch_ring(const F5ConvPosArgs& ab, dim3 grid, hipStream_t stream) {
     constexpr size_t lds = cp_ring_lds_bytes(CP_RING_NST);
     static bool asked[64] = {};
     int dev = 0;
     F5_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "convpos: no current device");
     if (!asked[dev]) {
-        F5_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&f5_convpos_ring_kernel<CP_RING_NST>),
+        F5_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&f5_convpos_ring_kernel<CP_RING_NST, LENS>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
                    "convpos: %zu bytes of LDS refused", lds);
         asked[dev] = true;
     }
-    hipLaunchKernelGGL((f5_convpos_ring_kernel<CP_RING_NST>), grid, dim3(256), lds, stream, ab);
+    hipLaunchKernelGGL((f5_convpos_ring_kernel<CP_RING_NST, LENS>), grid, dim3(256), lds, stream, ab);
     return 0;
 }
 
@@ -468,21 +479,28 @@ int f5_launch_convpos(const F5ConvPosArgs& a, hipStream_t stream) {
     if (reached & F5CP_XCD) grid = dim3((unsigned)nwg, 1, 1);   // group-per-XCD numbering (see the kernel)
     F5ConvPosArgs ab = a;
     if (ab.sat_flag == nullptr) ab.sat_flag = f5_sat_flag_host;
+    // every kernel in two instantiations: with row lengths (a.lens) and as it was
+#define CP_LAUNCH(HP_, TPS_)                                                                                              \
+    {                                                                                                                     \
+        if (ab.lens) hipLaunchKernelGGL((f5_convpos_kernel<HP_, TPS_, true>), grid, dim3(256), 0, stream, ab);            \
+        else hipLaunchKernelGGL((f5_convpos_kernel<HP_, TPS_, false>), grid, dim3(256), 0, stream, ab);                   \
+    }
     switch (reached & (F5CP_XCD - 1)) {
     case F5CP_HP1:
     case F5CP_HP2:
         F5_REQUIRE(a.in[1] && a.W[1], "convpos: bf16x3 needs lo operands");
         // the three-pass kernel is built for 1 and 2 taps per step only: a selector of 4 or 8 runs <true, 2>
-        if ((reached & (F5CP_XCD - 1)) == F5CP_HP2) hipLaunchKernelGGL((f5_convpos_kernel<true, 2>), grid, dim3(256), 0, stream, ab);
-        else hipLaunchKernelGGL((f5_convpos_kernel<true, 1>), grid, dim3(256), 0, stream, ab);
+        if ((reached & (F5CP_XCD - 1)) == F5CP_HP2) CP_LAUNCH(true, 2)
+        else CP_LAUNCH(true, 1)
         break;
     case F5CP_RING:
-        if (const int rc = cp_launch_ring(ab, grid, stream)) return rc;
+        if (const int rc = ab.lens ? cp_launch_ring<true>(ab, grid, stream) : cp_launch_ring<false>(ab, grid, stream)) return rc;
         break;
-    case F5CP_4: hipLaunchKernelGGL((f5_convpos_kernel<false, 4>), grid, dim3(256), 0, stream, ab); break;
-    case F5CP_2: hipLaunchKernelGGL((f5_convpos_kernel<false, 2>), grid, dim3(256), 0, stream, ab); break;
-    default: hipLaunchKernelGGL((f5_convpos_kernel<false, 1>), grid, dim3(256), 0, stream, ab); break;
+    case F5CP_4: CP_LAUNCH(false, 4) break;
+    case F5CP_2: CP_LAUNCH(false, 2) break;
+    default: CP_LAUNCH(false, 1) break;
     }
+#undef CP_LAUNCH
     F5_LAUNCH_CHECK();
     f5dbg::last_convpos_kernel = reached;
     return 0;

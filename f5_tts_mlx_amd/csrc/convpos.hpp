@@ -27,6 +27,9 @@ struct F5ConvPosArgs {
     float* out_f32;
     int ldo;
     int* sat_flag;        // where mode 0's 16-bit pack reports saturation (fp16 build, op16.hpp); null = rowops.hpp f5_sat_flag_host
+    const int* lens;      // device [B], or null: element b is lens[b] <= seq_len tokens long (elements stay seq_len rows apart).  Rows
+                          // n >= lens[b] are read as zero without being loaded, are not written, and report no saturation
+                          // (docs/isolate_rows.md); null launches the instantiations without row lengths: the kernels as they were
 };
 
 int f5_launch_convpos(const F5ConvPosArgs& a, hipStream_t stream);

@@ -106,6 +106,8 @@ struct F5Options {
                           // back to back -- the same kernels with the same arguments, 31 replays of ~165 nodes (round-6 probe: does a long exec cost more per node?)
     int sat_check = 1;    // precision f16: every 16-bit operand producer reports values beyond +-65 504 in the status word (bit 2); 0 = A/B
     int null_keeps_cond = 0;   // the second (null) branch keeps the audio conditioning: DiT.__call__(drop_audio_cond=False, drop_text=True), dit.py:374-401
+    int isolate_rows = 0;      // calls with use_mask: row b reads nothing from its own positions n >= durations[b] -- conv-pos and the text blocks'
+                               // depthwise conv see zeros there, the text GRN norms over the row's own frames (docs/isolate_rows.md)
 };
 static F5Options g_default_options;
 static int g_live_engines = 0;   // f5_debug_set_{ln_fusion,qkv_transposed,q_premul} only change the DEFAULTS: with engines alive they say so
@@ -293,27 +295,34 @@ extern "C" int f5_engine_set_graph_cache(f5_engine* e, int max_graphs) {
 }
 
 // The engine options by name.  Switches are 0 / 1, tri-states -1 (automatic) / 0 / 1, gemm_flags is a raw word.  One table serves
-// set, get, the message that lists the names and the option part of the graph key.
+// set, get, the message that lists the names and the option part of the graph key.  `group`: null = a launch option, named inside the
+// parentheses of that message (the list callers parse); an option of another kind is named behind the list under its group.
 enum OptKind { OPT_SWITCH, OPT_TRI, OPT_INT };
 static const struct OptDesc {
     const char* name;
     int F5Options::*member;
     OptKind kind;
+    const char* group = nullptr;
 } k_options[] = {
     {"q_premul", &F5Options::q_premul, OPT_SWITCH},     {"qkv_transposed", &F5Options::qkv_tr, OPT_SWITCH},
     {"ln_fusion", &F5Options::fuse_ln, OPT_SWITCH},     {"gemm_flags", &F5Options::gemm_flags, OPT_INT},
     {"attn_pipe", &F5Options::attn_pipe, OPT_TRI},      {"null_keeps_cond", &F5Options::null_keeps_cond, OPT_SWITCH},
     {"ln_fold", &F5Options::ln_fold, OPT_TRI},          {"sat_check", &F5Options::sat_check, OPT_SWITCH},
     {"graph_split", &F5Options::graph_split, OPT_SWITCH}, {"fold_stats", &F5Options::fold_stats, OPT_TRI},
+    {"isolate_rows", &F5Options::isolate_rows, OPT_SWITCH, "row isolation"},
 };
 static const OptDesc* find_option(const char* name) {
-    std::string names;
+    std::string names, grouped;
     for (const OptDesc& o : k_options) {
         if (strcmp(o.name, name) == 0) return &o;
+        if (o.group) {
+            grouped += std::string("; ") + o.group + ": " + o.name;
+            continue;
+        }
         names += names.empty() ? "" : ", ";
         names += o.name;
     }
-    f5_set_error("unknown engine option %s (%s)", name, names.c_str());
+    f5_set_error("unknown engine option %s (%s)%s", name, names.c_str(), grouped.c_str());
     return nullptr;
 }
 extern "C" int f5_engine_set_option(f5_engine* e, const char* name, int value) {
@@ -588,6 +597,7 @@ struct Ctx : LaunchView {
     bool edit = false;  // f5_sample_edit: conditioning frames are chosen by the mask at w.cond_keep instead of n < lens[b]
     Route route;        // rows: time and guidance strength per batch row (w.r*); dual: three branches F, N, T (w.nbr == 3)
     bool use_mask;
+    bool isolate = false;   // engine option isolate_rows in a call with use_mask: conv-pos, the text blocks' conv and GRN stop at each row's duration
     // f5_sample_window: wide (1) / narrow (0) per evaluation, null = every evaluation runs `nb` branches.  A narrow one runs the
     // conditional branch alone and its stage takes k = F for every row (the effective strengths at w.wcfg / w.wacfg are 0 there).
     const uint8_t* pattern = nullptr;
@@ -724,13 +734,22 @@ static int run_prep(const Ctx& c, int nfe) {
     int cur = 0;
     for (int i = 0; i < cf.conv_layers; ++i) {
         const TextBlockW& t = e->tblocks[i];
-        RC(K.dwconv_ln(c.p<float>(w.te[cur]), c.a<float>(t.dw_w), c.a<float>(t.dw_b), c.a<float>(t.ln_w),
+        // isolate_rows: both branches' rows end at their durations (the first 2 B entries of dur2), conv and GRN stop there
+        if (c.isolate)
+            RC(K.dwconv_ln_ragged(c.p<float>(w.te[cur]), c.a<float>(t.dw_w), c.a<float>(t.dw_b), c.a<float>(t.ln_w), c.a<float>(t.ln_b),
+                                  c.pb(w.tln, 0), c.pb(w.tln, 1), 2 * c.B, c.N, Dt, 1e-6f, c.p<int>(w.dur2), s));
+        else
+            RC(K.dwconv_ln(c.p<float>(w.te[cur]), c.a<float>(t.dw_w), c.a<float>(t.dw_b), c.a<float>(t.ln_w),
                                c.a<float>(t.ln_b), c.pb(w.tln, 0), c.pb(w.tln, 1), 2 * c.B, c.N, Dt, 1e-6f, s));
         F5GemmArgs g1 = gemm_base(c, c.pb(w.tln, 0), c.pb(w.tln, 1), Dt, t.pw1, M2, TF, Dt, c.a<float>(t.b1));
         g1.out_f32 = c.p<float>(w.tg);
         g1.ldo = TF;
         RC(K.gemm(g1, EPI_GELU_ERF, s));
-        RC(K.grn(c.p<float>(w.tg), c.a<float>(t.gamma), c.a<float>(t.beta), c.p<float>(w.grn_partial),
+        if (c.isolate)
+            RC(K.grn_ragged(c.p<float>(w.tg), c.a<float>(t.gamma), c.a<float>(t.beta), c.p<float>(w.grn_partial), c.p<float>(w.grn_nx),
+                            c.pb(w.tg2, 0), c.pb(w.tg2, 1), 2 * c.B, c.N, TF, c.p<int>(w.dur2), s));
+        else
+            RC(K.grn(c.p<float>(w.tg), c.a<float>(t.gamma), c.a<float>(t.beta), c.p<float>(w.grn_partial),
                          c.p<float>(w.grn_nx), c.pb(w.tg2, 0), c.pb(w.tg2, 1), 2 * c.B, c.N, TF, s));
         F5GemmArgs g2 = gemm_base(c, c.pb(w.tg2, 0), c.pb(w.tg2, 1), TF, t.pw2, M2, Dt, TF, c.a<float>(t.b2));
         g2.out_f32 = c.p<float>(w.te[cur ^ 1]);
@@ -805,6 +824,7 @@ static int run_dit(const Ctx& c, int j) {
     cp.ld = D;
     cp.ldo = D;
     cp.nseg = c.nseg();
+    cp.lens = c.isolate ? c.p<int>(w.dur2) : nullptr;       // isolate_rows: one duration per element of the launch, nb B of dur2's nbr B
     cp.in[0] = c.pb(w.xb, 0);
     cp.in[1] = c.pb(w.xb, 1);
     cp.W[0] = c.wm(e->conv_w[0], 0);
@@ -1226,6 +1246,7 @@ static Ctx make_ctx(f5_engine* e, const f5_sample_args* a, hipStream_t s, Route 
     c.nb = nb;
     c.npad = (a->N + 63) / 64 * 64;
     c.use_mask = a->use_mask != 0;
+    c.isolate = c.use_mask && e->opt.isolate_rows != 0;     // without a mask the call has no padding: today's launches
     return c;
 }
 
@@ -1433,7 +1454,16 @@ static int launch_sample(const Ctx& c, const f5_sample_args* a, const std::strin
     return 0;
 }
 
+// engine option isolate_rows on a precision the row-isolated mode is not claimed for; `what` names the call
+static int check_isolate(const f5_engine* e, const char* what) {
+    F5_REQUIRE(!(e && e->opt.isolate_rows && e->prec == F5_PREC_MXFP8),
+               "%s: engine option isolate_rows = 1 is not supported in precision mxfp8 (row isolation is claimed for f16, bf16 and bf16x3); set "
+               "isolate_rows = 0", what);
+    return 0;
+}
+
 static int sample_impl(f5_engine* e, const f5_sample_args* a, void* stream, const RowCtl& rc) {
+    RC(check_isolate(e, rc.what));
     RC(check_args(e, a));
     F5_REQUIRE(a->y0 && (a->t || rc.route.rows) && a->out, "null pointer in f5_sample_args (y0/t/out)");
     // (a window call's branch count is settled by stage_controls, once the evaluation times say which evaluations are wide)
@@ -1514,6 +1544,7 @@ extern "C" int f5_sample_status(f5_engine* e, const f5_sample_args* a, int* flag
 // args->cfg_strength is a guiding one, else one -- dual guidance always runs all three and does not read it.
 static int forward_impl(f5_engine* e, const f5_sample_args* a, const float* x, const float* t, Route route, float* const outs[3],
                         const char* what, void* stream) {
+    RC(check_isolate(e, what));
     RC(check_args(e, a));
     F5_REQUIRE(x && outs[0], "null pointer");
     if (route.rows) {
@@ -1977,26 +2008,7 @@ extern "C" int f5_op_rope_table(float* cos_t, float* sin_t, int seq_len, int dim
 extern "C" int f5_op_convpos(const void* in_hi, const void* in_lo, const void* w_hi, const void* w_lo, const float* bias,
                              void* out_hi, void* out_lo, float* out_f32, int B, int seq_len, int C, int groups, int taps,
                              int nseg, int mode, void* stream) {
-    F5ConvPosArgs cp;
-    memset(&cp, 0, sizeof(cp));
-    cp.in[0] = (const op16_t*)in_hi;
-    cp.in[1] = (const op16_t*)in_lo;
-    cp.W[0] = (const op16_t*)w_hi;
-    cp.W[1] = (const op16_t*)w_lo;
-    cp.bias = bias;
-    cp.B = B;
-    cp.seq_len = seq_len;
-    cp.C = C;
-    cp.groups = groups;
-    cp.taps = taps;
-    cp.ld = C;
-    cp.ldo = C;
-    cp.nseg = nseg;
-    cp.mode = mode;
-    cp.out_bf[0] = (op16_t*)out_hi;
-    cp.out_bf[1] = (op16_t*)out_lo;
-    cp.out_f32 = out_f32;
-    return g_ops.convpos(cp, (hipStream_t)stream);
+    return f5_op_convpos_ragged(in_hi, in_lo, w_hi, w_lo, bias, out_hi, out_lo, out_f32, B, seq_len, C, groups, taps, nseg, mode, nullptr, stream);
 }
 
 // MFMA rate yardstick of the current operand type (f5_op_set_operand_type): see rowops.hip mfma_peak_kernel
@@ -2022,6 +2034,33 @@ extern "C" int f5_op_dwconv_ln_ragged(const float* x, const float* dw_w, const f
                                   (hipStream_t)stream);
 }
 
+// f5_op_convpos with row lengths (F5ConvPosArgs::lens, dev [B]; NULL = f5_op_convpos)
+extern "C" int f5_op_convpos_ragged(const void* in_hi, const void* in_lo, const void* w_hi, const void* w_lo, const float* bias,
+                                    void* out_hi, void* out_lo, float* out_f32, int B, int seq_len, int C, int groups, int taps,
+                                    int nseg, int mode, const int32_t* lens_dev, void* stream) {
+    F5ConvPosArgs cp;
+    memset(&cp, 0, sizeof(cp));
+    cp.in[0] = (const op16_t*)in_hi;
+    cp.in[1] = (const op16_t*)in_lo;
+    cp.W[0] = (const op16_t*)w_hi;
+    cp.W[1] = (const op16_t*)w_lo;
+    cp.bias = bias;
+    cp.B = B;
+    cp.seq_len = seq_len;
+    cp.C = C;
+    cp.groups = groups;
+    cp.taps = taps;
+    cp.ld = C;
+    cp.ldo = C;
+    cp.nseg = nseg;
+    cp.mode = mode;
+    cp.out_bf[0] = (op16_t*)out_hi;
+    cp.out_bf[1] = (op16_t*)out_lo;
+    cp.out_f32 = out_f32;
+    cp.lens = lens_dev;
+    return g_ops.convpos(cp, (hipStream_t)stream);
+}
+
 extern "C" size_t f5_op_grn_scratch_floats(int nbatch, int seq_len, int dim) {
     return f5_grn_partial_floats(nbatch, seq_len, dim) + (size_t)nbatch * dim;
 }
@@ -2029,6 +2068,14 @@ extern "C" int f5_op_grn(const float* g, const float* gamma, const float* beta, 
                          int nbatch, int seq_len, int dim, void* stream) {
     float* nx = scratch + f5_grn_partial_floats(nbatch, seq_len, dim);
     return g_ops.grn(g, gamma, beta, scratch, nx, (op16_t*)out_hi, (op16_t*)out_lo, nbatch, seq_len, dim, (hipStream_t)stream);
+}
+extern "C" int f5_op_grn_ragged(const float* g, const float* gamma, const float* beta, float* scratch, void* out_hi, void* out_lo,
+                                int nbatch, int seq_len, int dim, const int32_t* lens_dev, void* stream) {
+    F5_REQUIRE(scratch, "f5_op_grn_ragged: scratch is null");
+    F5_REQUIRE(nbatch >= 1 && seq_len >= 1 && dim >= 1, "f5_op_grn_ragged: bad sizes nbatch=%d seq_len=%d dim=%d", nbatch, seq_len, dim);
+    float* nx = scratch + f5_grn_partial_floats(nbatch, seq_len, dim);
+    return g_ops.grn_ragged(g, gamma, beta, scratch, nx, (op16_t*)out_hi, (op16_t*)out_lo, nbatch, seq_len, dim, lens_dev,
+                            (hipStream_t)stream);
 }
 
 extern "C" int f5_op_text_embed(const int32_t* text, int nt, const float* table, const float* pos_table, int max_pos, float* out,

@@ -139,6 +139,11 @@ struct Ops {
         return h ? f5hf::f5_launch_grn(g, gamma, beta, partial, nx, H(hi), H(lo), nbatch, seq_len, dim, s)
                  : f5bf::f5_launch_grn(g, gamma, beta, partial, nx, hi, lo, nbatch, seq_len, dim, s);
     }
+    int grn_ragged(const float* g, const float* gamma, const float* beta, float* partial, float* nx, op16_t* hi, op16_t* lo, int nbatch,
+                   int seq_len, int dim, const int* lens, hipStream_t s) const {
+        return h ? f5hf::f5_launch_grn_ragged(g, gamma, beta, partial, nx, H(hi), H(lo), nbatch, seq_len, dim, lens, s)
+                 : f5bf::f5_launch_grn_ragged(g, gamma, beta, partial, nx, hi, lo, nbatch, seq_len, dim, lens, s);
+    }
     int pack_cond_text(const float* cond, const int* lens, const float* text_emb, op16_t* hi, op16_t* lo, int B, int seq_len,
                        int mel_dim, int dt, int null_keeps_cond, hipStream_t s) const {
         return h ? f5hf::f5_launch_pack_cond_text(cond, lens, text_emb, H(hi), H(lo), B, seq_len, mel_dim, dt, null_keeps_cond, s)

@@ -481,6 +481,78 @@ int f5_launch_grn(const float* g, const float* gamma, const float* beta, float* 
     return 0;
 }
 
+// GRN of a padded batch whose element b is lens[b] <= seq_len tokens long (elements stay seq_len rows apart): the norm runs over the
+// element's own tokens.  The chunks stay GRN_CHUNK tokens, aligned at token 0, and are summed in grn_finish_kernel's order, so a valid
+// token gets the bits f5_launch_grn gives on the element alone at seq_len = lens[b]: the chunk the length cuts stops there, as the last
+// chunk of the short call does, and a chunk wholly behind it adds +0.0f to a sum that is never negative.  The padding is not loaded.
+__global__ __launch_bounds__(256) void grn_partial_ragged_kernel(const float* __restrict__ g, float* __restrict__ partial, int seq_len,
+                                                                 int dim, int nchunk, const int* __restrict__ lens) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const int ch = blockIdx.y, b = blockIdx.z;
+    if (c >= dim) return;
+    const int len = min(max(lens[b], 0), seq_len);              // a length that lies cannot take the loads out of the element
+    const int n0 = ch * GRN_CHUNK;
+    const int n1 = min(n0 + GRN_CHUNK, len);
+    float acc = 0.0f;
+    for (int n = n0; n < n1; ++n) {
+        const float v = g[((size_t)b * seq_len + n) * dim + c];
+        acc += v * v;
+    }
+    partial[((size_t)b * nchunk + ch) * dim + c] = acc;
+}
+
+// grn_apply_kernel for that batch: a token n >= lens[b] writes zeros by selection -- its g is not loaded -- and reports no saturation
+__global__ __launch_bounds__(256) void grn_apply_ragged_kernel(const float* __restrict__ g, const float* __restrict__ nx,
+                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                               op16_t* __restrict__ out_hi, op16_t* __restrict__ out_lo, int seq_len,
+                                                               int dim, size_t total4, const int* __restrict__ lens, int* sat_flag) {
+    const size_t i4 = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i4 >= total4) return;
+    const size_t idx = i4 * 4;
+    const int c = (int)(idx % dim);
+    const size_t row = idx / dim;
+    const int b = (int)(row / seq_len);
+    const int n = (int)(row - (size_t)b * seq_len);
+    if (n >= min(max(lens[b], 0), seq_len)) {
+        *reinterpret_cast<u32x2*>(out_hi + idx) = u32x2{0u, 0u};
+        if (out_lo) *reinterpret_cast<u32x2*>(out_lo + idx) = u32x2{0u, 0u};
+        return;
+    }
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + idx);
+    const f32x4 nv = *reinterpret_cast<const f32x4*>(nx + (size_t)b * dim + c);
+    const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c);
+    const f32x4 be = *reinterpret_cast<const f32x4*>(beta + c);
+    float y[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) y[e] = ga[e] * (gv[e] * nv[e]) + be[e] + gv[e];
+    f5_sat_t trk;
+    *reinterpret_cast<u32x2*>(out_hi + idx) = u32x2{f5_pack2(y[0], y[1], trk), f5_pack2(y[2], y[3], trk)};
+    if (out_lo) *reinterpret_cast<u32x2*>(out_lo + idx) = u32x2{f5_pack2_lo(y[0], y[1]), f5_pack2_lo(y[2], y[3])};
+    f5_sat_commit(trk, sat_flag);
+}
+
+int f5_launch_grn_ragged(const float* g, const float* gamma, const float* beta, float* partial, float* nx, op16_t* out_hi,
+                         op16_t* out_lo, int nbatch, int seq_len, int dim, const int* lens, hipStream_t s) {
+    F5_REQUIRE(g && gamma && beta, "grn_ragged: g / gamma / beta is null");
+    F5_REQUIRE(partial && nx, "grn_ragged: scratch is null");
+    F5_REQUIRE(out_hi, "grn_ragged: out_hi is null");
+    F5_REQUIRE(lens, "grn_ragged: lens is null");
+    F5_REQUIRE(nbatch >= 1 && nbatch <= 65535, "grn_ragged: nbatch must be in [1, 65535] (got %d)", nbatch);
+    F5_REQUIRE(seq_len >= 1, "grn_ragged: seq_len must be >= 1 (got %d)", seq_len);
+    F5_REQUIRE(dim >= 4 && dim % 4 == 0, "grn_ragged: dim must be a multiple of 4 (got %d)", dim);
+    const int nchunk = f5_cdiv(seq_len, GRN_CHUNK);
+    F5_REQUIRE(nchunk <= 65535, "grn_ragged: seq_len = %d is beyond %d chunks of %d tokens", seq_len, 65535, GRN_CHUNK);
+    hipLaunchKernelGGL(grn_partial_ragged_kernel, dim3(f5_cdiv(dim, 256), nchunk, nbatch), dim3(256), 0, s, g, partial, seq_len, dim,
+                       nchunk, lens);
+    hipLaunchKernelGGL(grn_finish_kernel, dim3(nbatch), dim3(256), 0, s, partial, nx, dim, nchunk);
+    const size_t total4 = (size_t)nbatch * seq_len * dim / 4;
+    F5_REQUIRE(f5_cdiv((long)total4, 256) <= 0x7fffffffL, "grn_ragged: nbatch * seq_len * dim = %zu values exceed one grid", total4 * 4);
+    hipLaunchKernelGGL(grn_apply_ragged_kernel, dim3(f5_cdiv((long)total4, 256)), dim3(256), 0, s, g, nx, gamma, beta, out_hi, out_lo,
+                       seq_len, dim, total4, lens, f5_sat_flag_host);
+    F5_LAUNCH_CHECK();
+    return 0;
+}
+
 // =================================================================================================
 // TextEmbedding index path + gather.  out layout [2 branches][B][seq][dim]; ids_out [2][B][seq];
 // keep_out [2][B][seq] (1 where the ORIGINAL id != 0, i.e. not filler; same for both branches) -- bit exact.

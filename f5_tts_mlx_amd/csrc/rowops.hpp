@@ -44,6 +44,10 @@ int f5_launch_dwconv_ln_ragged(const float* x, const float* dw_w, const float* d
 int f5_launch_grn(const float* g, const float* gamma, const float* beta, float* partial, float* nx, op16_t* out_hi,
                   op16_t* out_lo, int nbatch, int seq_len, int dim, hipStream_t s);
 size_t f5_grn_partial_floats(int nbatch, int seq_len, int dim);
+// the same on a padded batch: element b's norm runs over its own lens[b] (dev [nbatch], 0 .. seq_len) tokens, which get the bits of
+// f5_launch_grn on the element alone; tokens past the length write zeros, their g is not loaded.  Scratch as f5_launch_grn.
+int f5_launch_grn_ragged(const float* g, const float* gamma, const float* beta, float* partial, float* nx, op16_t* out_hi,
+                         op16_t* out_lo, int nbatch, int seq_len, int dim, const int* lens, hipStream_t s);
 
 // TextEmbedding index path + gather (dit.py:196-222): ids (+1, pad 0, mask, drop) -> emb + pos.
 int f5_launch_text_embed(const int* text, int nt, const float* table, const float* pos_table, int max_pos, float* out,

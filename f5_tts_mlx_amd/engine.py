@@ -236,6 +236,9 @@ def load_library() -> C.CDLL:
                         ("f5_op_resid_gate_ln_rows", [C.c_void_p] * 8 + [C.c_int] * 4 + [C.c_size_t, C.c_void_p]),
                         ("f5_op_ode_stage_rows", [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 7
                          + [C.c_int, C.c_int, C.c_void_p]),
+                        # row isolation (docs/isolate_rows.md): conv-pos and GRN with row lengths
+                        ("f5_op_convpos_ragged", [C.c_void_p] * 8 + [C.c_int] * 7 + [C.c_void_p] * 2),
+                        ("f5_op_grn_ragged", [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p] * 2),
                         # MX-fp8 producers and the QKV projection of the mode (float arguments: eps, q_premul)
                         ("f5_op_ln_modulate_f8", [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
                         ("f5_op_quantize_mx_bf16", [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -311,7 +314,21 @@ class OperandRangeWarning(RuntimeWarning):
 
 RANGE_CHECKS = ("sync", "auto", "async", "off")
 OPTION_NAMES = ("q_premul", "qkv_transposed", "ln_fusion", "gemm_flags", "attn_pipe", "null_keeps_cond", "ln_fold", "sat_check",
-                "graph_split", "fold_stats")
+                "graph_split", "fold_stats", "isolate_rows")
+# the options a bf16x3 fall-back engine carries over from the engine it serves: they change WHAT is computed, not how fast
+FALLBACK_OPTIONS = ("null_keeps_cond", "isolate_rows")
+
+
+def check_isolate_rows(value, precision: str) -> bool:
+    """Validates the `isolate_rows` argument of a sampling call (docs/isolate_rows.md) before anything is launched: a bool, and not True on
+    an mxfp8 model (row isolation is claimed for f16, bf16 and bf16x3).  It is one value per call and not a per-request key: it is an engine
+    option, part of the hipGraph key, and one graph serves each value."""
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"isolate_rows must be a bool, got {value!r}")
+    if value and precision == "mxfp8":
+        raise ValueError("isolate_rows=True is not supported on an mxfp8 model: row isolation is claimed for precision 'f16', 'bf16' and "
+                         "'bf16x3'")
+    return bool(value)
 # Engine.split_batch: sample() of at least this many utterances runs as TWO half batches on two HIP streams (Engine._sample_split);
 # 0 = never, the default.  The launches of a DiT block are a strict chain and each is 3.7 ... 11 rounds of one-workgroup-per-CU tiles, so
 # its last, partly filled round idles CUs (profiles/r06/m_sweep_tile_rounds.jsonl: +22 ... 29 us at every round boundary); a second,
@@ -413,6 +430,7 @@ class Engine:
         self.verify_tol = 1e-3
         self.verify_events = 0                         # cross-checks that failed (the engine switched to bf16x3)
         self.last_verify_l1: Optional[float] = None
+        self._isolate_arg = False                      # the value the last call's `isolate_rows` argument left in the engine option
 
     def _run_on_side_stream(self, fn, cur=None):
         cur = torch.cuda.current_stream(self.device) if cur is None else cur      # (torch's current stream is per host thread)
@@ -462,9 +480,9 @@ class Engine:
 
     def set_option(self, name: str, value: int) -> None:
         """Per-engine launch option ("q_premul", "qkv_transposed", "ln_fusion", "gemm_flags", "attn_pipe", "null_keeps_cond", "ln_fold",
-        "sat_check"; include/f5tts_hip.h): other engines of the process keep their own values, cached hipGraphs are keyed on them."""
+        "sat_check", "graph_split", "fold_stats", "isolate_rows"; include/f5tts_hip.h): other engines of the process keep their own values, cached hipGraphs are keyed on them."""
         check(self.lib.f5_engine_set_option(self._h, name.encode(), int(value)), f"f5_engine_set_option({name})")
-        if self._fallback is not None and name == "null_keeps_cond":
+        if self._fallback is not None and name in FALLBACK_OPTIONS:
             self._fallback.set_option(name, value)
         if self._sibling is not None:
             self._sibling.set_option(name, value)
@@ -495,9 +513,20 @@ class Engine:
         if self._fallback is None and self._host_weights is not None:
             fb = Engine(self.cfg, precision="bf16x3", device=self.device, range_check="off")
             fb.load_weights(self._host_weights)
-            fb.set_option("null_keeps_cond", self.get_option("null_keeps_cond"))
+            for name in FALLBACK_OPTIONS:
+                fb.set_option(name, self.get_option(name))
             self._fallback = fb
         return self._fallback
+
+    def _apply_isolate_rows(self, isolate_rows) -> None:
+        """The call-level `isolate_rows` argument -> engine option "isolate_rows" (and that of the sibling and fall-back engines, through
+        set_option).  Written only when the argument differs from what the last call left: a caller that never passes it writes nothing."""
+        if isolate_rows is False and not self._isolate_arg:
+            return
+        want = check_isolate_rows(isolate_rows, self.precision)
+        if want != self._isolate_arg:
+            self.set_option("isolate_rows", int(want))
+            self._isolate_arg = want
 
     def get_option(self, name: str) -> int:
         v = C.c_int()
@@ -584,7 +613,7 @@ class Engine:
                t: np.ndarray, method: str = "euler", cfg_strength: float = 2.0, use_mask: Optional[bool] = None,
                use_graph=True, return_trajectory: bool = True, out: Optional[torch.Tensor] = None,
                trajectory: Optional[torch.Tensor] = None, cond_keep: Optional[torch.Tensor] = None, audio_cfg_strength=None,
-               cfg_interval=None):
+               cfg_interval=None, isolate_rows: bool = False):
         """ODE solve on the GPU. cond (B,N,mel) fp32 zero-padded to N=max(durations); text (B,nt) int32
         (-1 padded); y0 (B,N,mel).  use_graph: True / False / "auto" (eager on the first sighting of a shape
         signature, captured hipGraph from the second on).  Per-request controls: `t` may also be (B, steps), one grid per row, and
@@ -597,16 +626,21 @@ class Engine:
         whatever the values are.  cfg_interval ((lo, hi) or a (B, 2) array; None = today's call): guidance window, f5_sample_window -- a
         row is guided only at evaluations whose time lies in its [lo, hi] (both ends inclusive), and an evaluation in which no row is
         guided runs the conditional branch alone (docs/guidance_window.md); it follows the call like the dual strengths do.
+        isolate_rows (docs/isolate_rows.md): True = with a mask, row b reads nothing from its own frames n >= durations[b] (conv-pos, the
+        text blocks' conv and GRN stop there), so its result no longer depends on its batch-mates; it sets the engine option of that name
+        for this call and the calls after it until another value is passed -- one value per call, part of the hipGraph key.
         Returns (out (B,N,mel), trajectory (steps,B,N,mel) or None)."""
         if method not in METHODS:
             raise ValueError(f"Unknown method: {method}")
         self._check_inputs(text, cond, lens, durations)
         cond_keep = self._check_keep(cond_keep, cond)
+        self._apply_isolate_rows(isolate_rows)
         self.check_status(block=False)                 # a pending check of the previous call: resolved here if it has arrived
 
         def on_fallback(**over):                       # the same call on the bf16x3 engine
             kw = dict(method=method, cfg_strength=cfg_strength, use_mask=use_mask, use_graph=use_graph, return_trajectory=return_trajectory,
-                      out=out, trajectory=trajectory, cond_keep=cond_keep, audio_cfg_strength=audio_cfg_strength, cfg_interval=cfg_interval)
+                      out=out, trajectory=trajectory, cond_keep=cond_keep, audio_cfg_strength=audio_cfg_strength, cfg_interval=cfg_interval,
+                      isolate_rows=isolate_rows)
             return self._fallback.sample(text, cond, lens, durations, y0, t, **dict(kw, **over))
 
         if self._use_fallback:                         # an earlier call saturated fp16 / failed its cross-check: bf16x3 from now on
@@ -834,15 +868,16 @@ class Engine:
         return self._resolve(flags, what, shape, rerun=True)
 
     def dit_forward(self, x: torch.Tensor, text: torch.Tensor, cond: torch.Tensor, lens, durations, t: float,
-                    cfg_strength: float = 2.0, use_mask: Optional[bool] = None, audio_cfg_strength=None):
+                    cfg_strength: float = 2.0, use_mask: Optional[bool] = None, audio_cfg_strength=None, isolate_rows: bool = False):
         """One DiT evaluation (cond branch and, when cfg_strength >= 1e-5, null branch).  t: a float, or one time per batch row (length-B
         sequence: one batched f5_dit_forward_rows call).  audio_cfg_strength not None (its values are not read): the three branches of
-        dual guidance in one f5_dit_forward_dual call -> (pred, null_pred, text_pred)."""
+        dual guidance in one f5_dit_forward_dual call -> (pred, null_pred, text_pred).  isolate_rows: as in sample()."""
         self._check_inputs(text, cond, lens, durations)
+        self._apply_isolate_rows(isolate_rows)
         self.check_status(block=False)
         if self._use_fallback:
             return self._fallback.dit_forward(x, text, cond, lens, durations, t, cfg_strength=cfg_strength, use_mask=use_mask,
-                                              audio_cfg_strength=audio_cfg_strength)
+                                              audio_cfg_strength=audio_cfg_strength, isolate_rows=isolate_rows)
         B, N, mel = cond.shape
         if use_mask is None:
             use_mask = B > 1
@@ -872,5 +907,5 @@ class Engine:
         del keep
         if saturated and self._use_fallback:
             return self._fallback.dit_forward(x, text, cond, lens, durations, t, cfg_strength=cfg_strength, use_mask=use_mask,
-                                              audio_cfg_strength=audio_cfg_strength)
+                                              audio_cfg_strength=audio_cfg_strength, isolate_rows=isolate_rows)
         return (pred, null, text_pred) if dual else (pred, null)

@@ -23,6 +23,7 @@ import torch
 
 from . import audio as _audio
 from .cfm import F5TTS
+from .engine import check_isolate_rows
 from .utils import convert_char_to_pinyin
 
 SAMPLE_RATE = 24_000
@@ -156,12 +157,17 @@ def generate(
     cross_fade_ms: Optional[float] = None,  # extension (sentence joins, docs/sentence_joins.md): linear cross-fade between sentences
     sentence_pause_ms: Optional[float] = None,   # extension: silence between sentences; the sentences then fade to and from it
     trim_sentence_db: Optional[float] = None,    # extension: cut leading / trailing near-silence below this level off every sentence
+    isolate_rows: bool = False,             # extension (docs/isolate_rows.md): with batch_sentences, a sentence's frames no longer depend
+                                            # on the other sentences of the batch.  False = the call as it was: no new keyword to sample()
 ):
     """generate.py:113-245.  `batch_sentences=True` (opt-in, no reference counterpart; SURVEY.md section 8(f)2 names it as the point of
     owning the app loop): the sentences of a multi-sentence text are sampled as one ragged batch -- one `sample()` call, one set of
     launches at M = 2 x (sum of frames) instead of one set per sentence.  It is NOT bit-compatible with the loop: in a batch the
-    key-padding mask exists (cfm.py:333-336), and GRN (convnext_v2.py:16) and the conv position embedding (dit.py:251) see the padding
-    up to the longest sentence, exactly as the reference's own `sample()` behaves for a batch; what it equals is `sample()` of that
+    key-padding mask exists (cfm.py:333-336), and by default GRN (convnext_v2.py:16) and the conv position embedding (dit.py:251) see
+    the padding up to the longest sentence, exactly as the reference's own `sample()` behaves for a batch.  `isolate_rows=True`
+    (docs/isolate_rows.md) takes the padding out of both: every sentence then runs the arithmetic of its own solo `sample()` and
+    lands within the parity gate of it, whatever shares the batch -- still not the loop's bits, since a sentence alone runs at another
+    length on other kernels.  What the call equals is `sample()` of that
     batch (tests/test_model_gpu.py::test_generate_batch_sentences), each element vocoded on its own frames (the padded tail of a
     shorter sentence never reaches the vocoder).  `vocode_batched=True` (opt-in, only together with `batch_sentences`) makes that one
     `decode(mel, lens=frames)` call on the padded batch instead of one call per sentence: the vocoder's three launches that mix time
@@ -186,10 +192,15 @@ def generate(
     if cross_fade_ms is not None or sentence_pause_ms is not None or trim_sentence_db is not None:
         join = join_options(cross_fade_ms, sentence_pause_ms, trim_sentence_db)
     window_kw = {} if cfg_interval is None else dict(cfg_interval=_interval(cfg_interval, "request 0: cfg_interval"))
+    if isolate_rows is not False:
+        check_isolate_rows(isolate_rows, "")                          # (a bool; the model's precision is looked at once there is a model)
     if output_sample_rate is not None:
         output_sample_rate = _audio._rate(output_sample_rate, "output_sample_rate")
     if f5tts is None:
         f5tts = F5TTS.from_pretrained(model_name, quantization_bits=quantization_bits)
+    iso_kw = {}
+    if isolate_rows is not False:
+        iso_kw["isolate_rows"] = check_isolate_rows(isolate_rows, f5tts.transformer.engine.precision)
     if getattr(f5tts, "_vocoder", None) is None:
         # sample() would hand back mel frames; trimming them by audio samples and writing a WAV would produce garbage
         raise RuntimeError("generate() needs a model with a vocoder (F5TTS(..., vocoder=...) / from_pretrained with Vocos)")
@@ -260,7 +271,7 @@ def generate(
         try:
             f5tts._vocoder = None
             mel, _ = f5tts.sample(cond, text=texts, duration=durs, steps=steps, method=method, speed=speed, cfg_strength=cfg_strength,
-                                  sway_sampling_coef=sway_sampling_coef, seed=seed, **dual_kw)
+                                  sway_sampling_coef=sway_sampling_coef, seed=seed, **dual_kw, **iso_kw)
         finally:
             f5tts._vocoder = voc
         frames = f5tts.last_durations                                 # per-element frame counts after the clamps of cfm.py:317-318
@@ -422,6 +433,7 @@ def generate_many(
     cross_fade_ms=None,
     sentence_pause_ms=None,
     trim_sentence_db=None,
+    isolate_rows: bool = False,
 ):
     """Many voices in one call (no reference counterpart; docs/multi_voice.md).  requests: a list of (generation_text, ref_audio_path or
     None, ref_audio_text); None = the bundled sample and its text.  -> a list of waves, one per request, in order.
@@ -453,15 +465,25 @@ def generate_many(
     result, each request sliced to its own length: the bits of resampling each request by itself, since the filter treats everything
     outside a wave as zero and the padding is exactly zero.
 
+    isolate_rows (docs/isolate_rows.md; False: the call as it was, sample() gets no new keyword): True = a row of the batch reads nothing
+    from its own padding, so a request's audio no longer depends on which requests share the call: every row lands within the parity
+    gate of its solo sample() for the durations it was given.  One value for the call and NOT a key of a controls entry: it is an engine
+    option, part of the hipGraph key, and one graph serves each value.  (Durations from the duration predictor are predicted on the padded
+    batch and are not covered, see the doc.)
+
     It equals prepare_references -> sample(mel, text, durations, lens=frames) -> the decode -> the same slices, bit for bit; it does
-    NOT equal a loop of generate() calls bit for bit (the batch has a key-padding mask, GRN and the conv position embedding see the
-    padding, and the gain is fp64 arithmetic on fp32 block sums instead of torch's fp32 mean).
+    NOT equal a loop of generate() calls bit for bit (the batch has a key-padding mask, the gain is fp64 arithmetic on fp32 block sums
+    instead of torch's fp32 mean, and by default GRN and the conv position embedding see the padding; with isolate_rows they do not, and
+    what remains is the rounding order of other kernel routes, not the batch-mates).
     ValueError before any launch, naming the request: an empty list, a request without text, a reference recording without a
     transcript, a reference at a rate the resampler refuses, a `controls` list of the wrong length or with an unknown key, a join
-    setting that is negative or not finite, a trim level not below 0, a cfg_interval that is not two finite numbers with lo <= hi."""
+    setting that is negative or not finite, a trim level not below 0, a cfg_interval that is not two finite numbers with lo <= hi, an
+    isolate_rows that is not a bool or is True on an mxfp8 model."""
     requests = list(requests)
     if not requests:
         raise ValueError("generate_many needs at least one request")
+    if isolate_rows is not False:
+        check_isolate_rows(isolate_rows, "" if f5tts is None else f5tts.transformer.engine.precision)
     join = None                                                       # all three unset: nothing of the join is called
     if cross_fade_ms is not None or sentence_pause_ms is not None or trim_sentence_db is not None:
         join = join_options(cross_fade_ms, sentence_pause_ms, trim_sentence_db, len(requests))
@@ -493,6 +515,9 @@ def generate_many(
 
     if f5tts is None:
         f5tts = F5TTS.from_pretrained(model_name, quantization_bits=quantization_bits)
+    iso_kw = {}
+    if isolate_rows is not False:
+        iso_kw["isolate_rows"] = check_isolate_rows(isolate_rows, f5tts.transformer.engine.precision)
     voc = getattr(f5tts, "_vocoder", None)
     if voc is None:
         raise RuntimeError("generate_many() needs a model with a vocoder (F5TTS(..., vocoder=...) / from_pretrained with Vocos)")
@@ -521,7 +546,7 @@ def generate_many(
         f5tts._vocoder = None
         mel, _ = f5tts.sample(cond, text=texts, duration=durs, lens=lens, steps=steps, method=method, speed=ctl["speed"],
                               cfg_strength=ctl["cfg_strength"], sway_sampling_coef=ctl["sway_sampling_coef"], seed=ctl["seed"],
-                              **{k: ctl[k] for k in (AUDIO_CFG_KEY, CFG_INTERVAL_KEY) if k in ctl})
+                              **{k: ctl[k] for k in (AUDIO_CFG_KEY, CFG_INTERVAL_KEY) if k in ctl}, **iso_kw)
     finally:
         f5tts._vocoder = voc
     frames = f5tts.last_durations                                     # per-row frame counts after the clamps of cfm.py:317-318
@@ -682,6 +707,9 @@ def parse_args(argv=None):
                     help="with --requests: cut leading and trailing silence below DB dB off every reference (-42 is customary; default: cut nothing)")
     ap.add_argument("--cfg-interval", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="guidance window: guide only at function evaluations whose time lies in [LO, HI] (default: throughout)")
+    ap.add_argument("--isolate-rows", action="store_true",
+                    help="with --requests or --batch-sentences: a row of the batch reads nothing from its own padding, so its audio does not depend on "
+                         "what shares the batch (docs/isolate_rows.md)")
     ap.add_argument("--cross-fade-ms", type=float, default=None, metavar="MS",
                     help="linear cross-fade of MS milliseconds between the sentences of a text (default: plain concatenation)")
     ap.add_argument("--sentence-pause-ms", type=float, default=None, metavar="MS",
@@ -714,7 +742,8 @@ def main(argv=None):
                               trim_silence_db=ns.trim_silence, output_sample_rate=ns.output_rate,
                               controls=controls if any(c is not None for c in controls) else None,
                               **({} if ns.audio_cfg is None else dict(audio_cfg_strength=ns.audio_cfg)),
-                              **({} if ns.cfg_interval is None else dict(cfg_interval=tuple(ns.cfg_interval))), **joins)
+                              **({} if ns.cfg_interval is None else dict(cfg_interval=tuple(ns.cfg_interval))),
+                              **(dict(isolate_rows=True) if ns.isolate_rows else {}), **joins)
         for r, wave in zip(reqs, waves):
             if r["output"] is not None:
                 write_wav(r["output"], wave.detach().cpu().numpy(), ns.output_rate or SAMPLE_RATE)
@@ -734,6 +763,7 @@ def main(argv=None):
              output_sample_rate=ns.output_rate, batch_sentences=ns.batch_sentences, vocode_batched=ns.vocode_batched,
              **({} if ns.audio_cfg is None else dict(audio_cfg_strength=ns.audio_cfg)),
              **({} if ns.cfg_interval is None else dict(cfg_interval=tuple(ns.cfg_interval))),
+             **(dict(isolate_rows=True) if ns.isolate_rows else {}),
              **{k: v for k, v in (("cross_fade_ms", ns.cross_fade_ms), ("sentence_pause_ms", ns.sentence_pause_ms),
                                   ("trim_sentence_db", ns.trim_sentence_db)) if v is not None})
 

@@ -68,7 +68,12 @@ int f5_engine_graph_count(f5_engine* e);
  * DiT.__call__(drop_audio_cond=False, drop_text=True), dit.py:374-401), "ln_fold" (LN-modulate folded into the epilogues of the block
  * GEMMs around it, see f5_debug_set_op_fold_producer: -1 (default) = where it is measured faster: >= 22 000 rows (batch >= 12 at the
  * 335M shape and 937 frames) with the four block GEMMs on the 256x256 / role-split 128x256 kernels, f16 / bf16 modes; 0 = never;
- * 1 = wherever it can run (batch >= 4 at that shape), f5_sample fails where it cannot).
+ * 1 = wherever it can run (batch >= 4 at that shape), f5_sample fails where it cannot), "isolate_rows" (0; 1 = in a call with
+ * args->use_mask, row b reads nothing from its own positions n >= durations[b]: both conv-pos launches and the depthwise conv of the
+ * text blocks read zeros there and the text GRN norms over the row's own durations[b] frames, so a row of a padded batch runs the
+ * arithmetic of the reference's sample() on that row alone, docs/isolate_rows.md.  It serves f5_sample, _edit, _rows, _dual, _window
+ * and f5_dit_forward*; a call without use_mask launches what it launches with 0; the workspace sizes do not change; precision mxfp8
+ * refuses it in every one of those calls, before any launch).
  * Part of the hipGraph cache key.  New engines start from the process defaults (f5_debug_set_ln_fusion / _qkv_transposed /
  * _q_premul). */
 int f5_engine_set_option(f5_engine* e, const char* name, int value);
@@ -281,6 +286,14 @@ int f5_op_rope_table_g4(float* tq, float* tk, int seq_len, int dim_head, float q
 int f5_op_convpos(const void* in_hi, const void* in_lo, const void* w_hi, const void* w_lo, const float* bias, void* out_hi,
                   void* out_lo, float* out_f32, int B, int seq_len, int C, int groups, int taps, int nseg, int mode,
                   void* stream);
+/* f5_op_convpos on a padded batch: lens_dev, device [B], element b is lens[b] <= seq_len tokens long (elements stay seq_len rows apart).
+ * Rows n >= lens[b] are read as zero without being loaded (NaN there stays out), are not written in either mode and report no
+ * saturation; a workgroup whose whole 128-token tile lies at or beyond lens[b] returns at once.  Same kernels and routes as
+ * f5_op_convpos; rows n < lens[b] get the bits f5_op_convpos gives at the same shape on an input with zeros past the lengths.
+ * lens_dev == NULL: f5_op_convpos. */
+int f5_op_convpos_ragged(const void* in_hi, const void* in_lo, const void* w_hi, const void* w_lo, const float* bias, void* out_hi,
+                         void* out_lo, float* out_f32, int B, int seq_len, int C, int groups, int taps, int nseg, int mode,
+                         const int32_t* lens_dev, void* stream);
 /* dit.py:270 */
 int f5_op_ln_modulate(const float* x, const float* scale, const float* shift, void* out_hi, void* out_lo, int rows, int dim,
                       void* stream);
@@ -295,6 +308,11 @@ int f5_op_dwconv_ln(const float* x, const float* dw_w, const float* dw_b, const 
 size_t f5_op_grn_scratch_floats(int nbatch, int seq_len, int dim);
 int f5_op_grn(const float* g, const float* gamma, const float* beta, float* scratch, void* out_hi, void* out_lo, int nbatch,
               int seq_len, int dim, void* stream);
+/* f5_op_grn on a padded batch: lens_dev, device [nbatch], element b's norm runs over its own lens[b] <= seq_len tokens.  Tokens
+ * n < lens[b] get the bits of f5_op_grn on that element alone at seq_len = lens[b]; tokens past the length are exact zeros, their g is
+ * not loaded and they report no saturation.  scratch: f5_op_grn_scratch_floats(nbatch, seq_len, dim) floats. */
+int f5_op_grn_ragged(const float* g, const float* gamma, const float* beta, float* scratch, void* out_hi, void* out_lo, int nbatch,
+                     int seq_len, int dim, const int32_t* lens_dev, void* stream);
 /* dit.py:196-222 (index path is bit exact) */
 int f5_op_text_embed(const int32_t* text, int nt, const float* table, const float* pos_table, int max_pos, float* out,
                      int32_t* ids_out, uint8_t* keep_out, int B, int seq_len, int dim, void* stream);
