@@ -128,6 +128,10 @@ struct f5_engine : WeightStore {
     MatBF conv_w[2];
     size_t conv_b[2];
     std::vector<BlockW> blocks;
+    // LN fold constants (run_prep): the blocks' QKV / FF1 weights (bytes) and biases (bytes) sit `fold_stride` apart in the arena; uniform =
+    // at one stride for every block, so the blocks of a projection go in ONE fold_consts launch (build_arena_plan)
+    long fold_stride[4] = {0, 0, 0, 0};       // qkv weight, ff1 weight, qkv bias, ff1 bias
+    bool fold_uniform = false;
     MatBF wout;
     size_t bout;
     Ops ops;                          // kernels of this engine's operand type
@@ -245,6 +249,17 @@ static int build_arena_plan(f5_engine* e) {
         e->add_mat(q + "ff.ff.layers.2.weight", w.ff2, 0, D, FF, 0, FF, 0, {D, FF});
         e->add_f32(q + "ff.ff.layers.2.bias", w.bff2, {D});
     }
+    // every block allocates the same tensors in the same order, so the strides are uniform; checked, because run_prep batches on it
+    const BlockW& b0 = e->blocks[0];
+    const auto offs = [&](const BlockW& w, int k) { return (long)(k == 0 ? w.qkv.hi : k == 1 ? w.ff1.hi : k == 2 ? w.bqkv : w.bff1); };
+    e->fold_uniform = L >= 2;
+    for (int k = 0; k < 4; ++k) {
+        long& st = e->fold_stride[k];
+        st = L >= 2 ? offs(e->blocks[1], k) - offs(b0, k) : 0;
+        for (int i = 1; i < L; ++i) e->fold_uniform = e->fold_uniform && offs(e->blocks[i], k) - offs(b0, k) == i * st;
+        e->fold_uniform = e->fold_uniform && st > 0 && st % (k < 2 ? 8 : 4) == 0;
+    }
+    for (int i = 1; i < L; ++i) e->fold_uniform = e->fold_uniform && e->blocks[i].qkv.ld == b0.qkv.ld && e->blocks[i].ff1.ld == b0.ff1.ld;
     e->add_f32(p + "norm_out.linear.weight", e->ada_w + (size_t)L * 6 * D * D * 4, {2 * D, D});
     e->add_f32(p + "norm_out.linear.bias", e->ada_b + (size_t)L * 6 * D * 4, {2 * D});
     e->wout = alloc_mat(b, M, D, np);
@@ -518,7 +533,7 @@ static Workspace plan_workspace(const f5_engine* e, int B, int N, int nt, int st
         w.ao[p] = p < np ? b.take(MB * D * 2) : 0;
         w.ffh[p] = p < np ? b.take(MB * FF * 2) : 0;
     }
-    // LN fold buffers only where the fold can run (a superset of ln_fold_state(): that one also knows the branch count of the call):
+    // LN fold buffers only where the fold can run (a superset of the LN plan's fold: that one also knows the branch count of the call):
     // one-pass 16-bit operand modes, the option not 0, and -- in the automatic mode -- enough rows for it to be chosen with both branches
     // (... or few enough for the single-round kernels of the batch-1-sized route, gemm_route.hpp f5_gemm_fold_small: <= 2 048 rows at width 1024)
     w.fold_planned = np == 1 && e->prec != F5_PREC_MXFP8 && e->opt.ln_fold != 0 &&
@@ -588,9 +603,25 @@ extern "C" int f5_workspace_bytes_window(f5_engine* e, int B, int N, int nt, int
 // ------------------------------------------------------------------------------------------------
 // launch context
 // ------------------------------------------------------------------------------------------------
+// Who writes the 16-bit operand `h` that a block's QKV / FF1 GEMM reads -- one answer per context, not per block:
+enum LnMode {
+    LN_KERNEL,       // the LN-modulate kernel, a launch of its own (the MX-fp8 blocks: its fp8 twin)
+    LN_TAIL,         // the tail fused behind a small-tile residual GEMM (option ln_fusion, gemm.hpp ln_counter)
+    LN_FOLD_ROWF,    // LN fold: the residual GEMM leaves x (1 + scale) and slice statistics, a fold_rows launch the row factors
+    LN_FOLD_STATS,   // LN fold, statistics form: the consumer GEMM merges the slice statistics itself
+    LN_ROWS,         // per-row controls: resid_gate_ln_rows gates the residual and modulates in one row kernel
+};
+struct LnPlan {
+    LnMode mode = LN_KERNEL;
+    int fold_state = 0;               // 0 = no fold, 1 = on the staged kernels, 2 = on the batch-1-sized route: f5_engine_ln_fold_active, status bit 1
+    const char* refused = nullptr;    // ln_fold = 1 cannot run here: the message (a format that takes the entry point's name), raised by ln_refusal
+    bool fold() const { return fold_state != 0; }
+};
+
 struct Ctx : LaunchView {
     f5_engine* e;
     Workspace w;
+    LnPlan ln;          // decided by make_ctx, once per context
     hipStream_t s;
     int B, N, nt, nb;   // nb = branches evaluated per function evaluation (1 or 2; 1 or 3 with dual guidance)
     int npad;
@@ -615,34 +646,38 @@ static F5GemmArgs gemm_base(const Ctx& c, const op16_t* a_hi, const op16_t* a_lo
     return g;
 }
 
+// The LN plan of a context: a function of the engine options, precision, route and nb B N, the rows of one evaluation.
 // LN fold (gemm.hpp fold_*): 44 of the 46 LN-modulate launches of a forward disappear into the epilogues of the GEMMs around them
 // (the first LN of block 0 follows conv-pos and the final one feeds a small-tile GEMM: both keep the LN kernel).  Only where all
 // four block GEMMs of this shape run on the staged kernels, in the one-pass operand modes, with the transposed q / k tiles.
-// -> 0 = off, 1 = on, -1 = required by the option but impossible here (error set; `what` names the entry point of a window call)
-static int ln_fold_state(const Ctx& c, const char* what = "") {
+static LnPlan ln_fold_state(const Ctx& c) {
     const f5_engine* e = c.e;
     const f5_config& cf = e->cfg;
-    if (e->opt.ln_fold == 0) return 0;
-    if (c.route.rows) {        // the fold's constants c1, c2 are built per evaluation, not per row
-        if (e->opt.ln_fold != 1) return 0;
-        if (c.route.window)
-            f5_set_error("%s: ln_fold = 1: the folded LN cannot run with per-row sampling controls (its constants are per evaluation); use "
-                         "ln_fold = -1 or 0", what);
-        else
-            f5_set_error("ln_fold = 1: the folded LN cannot run with per-row sampling controls (its constants are per evaluation); use ln_fold = "
-                         "-1 or 0 for f5_sample_rows / f5_dit_forward_rows");
-        return -1;
-    }
     const int D = cf.dim, FF = cf.ff_dim, M = c.nb * c.B * c.N;
+    LnPlan p;
+    if (c.route.rows) {        // the fold's constants c1, c2 are built per evaluation, not per row; the tail has no per-row form either
+        p.mode = LN_ROWS;
+        if (e->opt.ln_fold == 1)
+            p.refused = c.route.window ? "%s: ln_fold = 1: the folded LN cannot run with per-row sampling controls (its constants are per "
+                                         "evaluation); use ln_fold = -1 or 0"
+                                       : "ln_fold = 1: the folded LN cannot run with per-row sampling controls (its constants are per evaluation); "
+                                         "use ln_fold = -1 or 0 for f5_sample_rows / f5_dit_forward_rows";
+        return p;
+    }
+    F5GemmQuery q = {};
+    q.M = M;
+    q.seq_len = c.N;
+    q.nseg = c.nseg();
+    // the fused tail: the out-projection and FF2 are the same launch to the routing (EPI_RESID_GATE, N = ldo = D), so one question serves both
+    q.N = D;
+    q.epi = EPI_RESID_GATE;
+    if (e->prec != F5_PREC_MXFP8 && e->opt.fuse_ln && c.w.lncnt_words != 0 && f5_gemm_resid_ln_fusable(q, D)) p.mode = LN_TAIL;
+    if (e->opt.ln_fold == 0) return p;
     bool ok = e->np == 1 && e->prec != F5_PREC_MXFP8 && e->opt.qkv_tr && !e->opt.fuse_ln && D % 256 == 0 && D <= 2048 && FF % 256 == 0 &&
               (e->opt.gemm_flags & 16384) == 0 && cf.depth >= 1;
     bool small = ok && D == 1024 && e->opt.fold_stats != 0 && (e->opt.gemm_flags & (8 | 256)) == 0;   // the single-round kernels: statistics form only
     if (ok) {
-        F5GemmQuery q = {};
-        q.M = M;
-        q.seq_len = c.N;
-        q.nseg = 1;
-        q.g4 = true;             // (e->opt.qkv_tr is part of `ok`)
+        q.g4 = true;             // (e->opt.qkv_tr and nseg == 1 are part of `ok`)
         const int shapes[4][2] = {{3 * D, EPI_QKV_ROPE}, {D, EPI_RESID_GATE}, {FF, EPI_GELU_TANH}, {D, EPI_RESID_GATE}};
         for (const auto& sh : shapes) {
             q.N = sh[0];
@@ -651,15 +686,24 @@ static int ln_fold_state(const Ctx& c, const char* what = "") {
             small = small && f5_gemm_fold_small(q);
         }
     }
-    if (e->opt.ln_fold < 0 && !(M >= LN_FOLD_AUTO_ROWS && ok) && !(small && LN_FOLD_SMALL_AUTO)) return 0;
-    if (!c.w.fold_planned) ok = small = false;      // (cannot happen: the plan's predicate is a superset of this one)
-    if (!ok && !small && e->opt.ln_fold == 1) {
-        f5_set_error("ln_fold = 1: this shape / precision cannot run the folded LN (needs f16 or bf16, qkv_transposed, no ln_fusion, dim %% 256 "
-                     "== 0, and all four block GEMMs on the 256x256 / role-split 128x256 kernels -- batch >= 4 at the 335M shape -- or on the "
-                     "single-round kernels of the batch-1-sized route: width 1024, fold_stats != 0)");
-        return -1;
-    }
-    return ok ? 1 : (small ? 2 : 0);
+    if (e->opt.ln_fold < 0 && !(M >= LN_FOLD_AUTO_ROWS && ok) && !(small && LN_FOLD_SMALL_AUTO)) return p;
+    if (!ok && !small)
+        p.refused = "ln_fold = 1: this shape / precision cannot run the folded LN (needs f16 or bf16, qkv_transposed, no ln_fusion, dim %% 256 "
+                    "== 0, and all four block GEMMs on the 256x256 / role-split 128x256 kernels -- batch >= 4 at the 335M shape -- or on the "
+                    "single-round kernels of the batch-1-sized route: width 1024, fold_stats != 0)";
+    p.fold_state = ok ? 1 : (small ? 2 : 0);
+    // statistics form: always on the batch-1-sized route (state 2: its kernels have no other), by option on the staged kernels (measured
+    // slower there: every tile of a multi-round launch repeats the merge -- +1.9 % at batch 32, +1.6 % at 8, profiles/r06)
+    if (p.fold()) p.mode = (p.fold_state == 2 || (e->opt.fold_stats == 1 && D == 1024)) ? LN_FOLD_STATS : LN_FOLD_ROWF;
+    return p;
+}
+// The refusal of a forced fold (return code 2), raised where the entry point's order of refusals puts it; `what` names the entry point.
+static int ln_refusal(const Ctx& c, const char* what) {
+    // (plan_workspace's predicate contains the LN plan's only while LN_FOLD_SMALL_AUTO is off and nb <= 2: checked, not assumed)
+    F5_REQUIRE(!c.ln.fold() || c.w.fold_planned, "internal: the LN fold is on but the workspace plan has no room for it");
+    if (!c.ln.refused) return 0;
+    f5_set_error(c.ln.refused, what);
+    return 2;
 }
 
 // loop-invariant preparation: time/adaLN tables, text path, hoisted input projection, masks, rope
@@ -684,27 +728,15 @@ static int run_prep(const Ctx& c, int nfe) {
         RC(f5_launch_skinny_gemm(th, c.a<float>(e->time_w2), c.a<float>(e->time_b2), temb, nt_rows, D, D, 0, 0, s));
         RC(f5_launch_skinny_gemm(temb, c.a<float>(e->ada_w), c.a<float>(e->ada_b), modt, nt_rows, (6 * L + 2) * D, D, 1, 0, s));
     }
-    const int fold = ln_fold_state(c);
-    if (fold < 0) return 2;
-    if (fold && nfe > 0) {
+    if (c.ln.fold_state && nfe > 0) {
         // c1 = W (1 + scale), c2 = W shift + bias for every evaluation and block: QKV against (scale_msa, shift_msa), FF1 against
         // (scale_mlp, shift_mlp); mod rows are [shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp] (dit.py:53-58)
         const int FF = cf.ff_dim;
         const size_t vstride = (size_t)(6 * L + 2) * D, ostride = (size_t)L * (3 * D + FF);
-        // the 22 blocks of a projection in ONE launch when their weights sit at a uniform stride in the arena (they do: every block
-        // allocates the same tensors in the same order), else block by block
-        const BlockW& b0 = e->blocks[0];
-        bool uniform = L >= 2;
-        const long sq = L >= 2 ? (long)e->blocks[1].qkv.hi - (long)b0.qkv.hi : 0, sf = L >= 2 ? (long)e->blocks[1].ff1.hi - (long)b0.ff1.hi : 0;
-        const long sbq = L >= 2 ? (long)e->blocks[1].bqkv - (long)b0.bqkv : 0, sbf = L >= 2 ? (long)e->blocks[1].bff1 - (long)b0.bff1 : 0;
-        for (int i = 1; i < L && uniform; ++i) {
-            const BlockW& bw = e->blocks[i];
-            uniform = (long)bw.qkv.hi - (long)b0.qkv.hi == i * sq && (long)bw.ff1.hi - (long)b0.ff1.hi == i * sf &&
-                      (long)bw.bqkv - (long)b0.bqkv == i * sbq && (long)bw.bff1 - (long)b0.bff1 == i * sbf && bw.qkv.ld == b0.qkv.ld &&
-                      bw.ff1.ld == b0.ff1.ld;
-        }
-        uniform = uniform && sq > 0 && sf > 0 && sbq > 0 && sbf > 0 && sq % 8 == 0 && sf % 8 == 0 && sbq % 4 == 0 && sbf % 4 == 0;
-        const int nlaunch = uniform ? 1 : L, count = uniform ? L : 1;
+        // the 22 blocks of a projection in ONE launch when their weights sit at a uniform stride in the arena (f5_engine::fold_uniform),
+        // else block by block
+        const long sq = e->fold_stride[0], sf = e->fold_stride[1], sbq = e->fold_stride[2], sbf = e->fold_stride[3];
+        const int nlaunch = e->fold_uniform ? 1 : L, count = e->fold_uniform ? L : 1;
         for (int i = 0; i < nlaunch; ++i) {
             const BlockW& bw = e->blocks[i];
             const float* m6 = c.p<float>(w.mod) + (size_t)i * 6 * D;
@@ -777,32 +809,24 @@ static int run_prep(const Ctx& c, int nfe) {
     return 0;
 }
 
-// one batched (cond + null) DiT forward; input = xin (bf16 padded state), modulation row `j`
-// f5_debug_set_ln_fusion: LN-modulate fused behind the residual GEMMs of small-tile launches (gemm.hpp ln_counter).  OFF by
-// default: bit-identical, but measured SLOWER at batch 1 (88.5 / 90.3 ms per sample against 75.1 / 78.6 on the same boxes,
-// profiles/r02/ln_fusion_ab.txt): a cross-XCD hand-over inside a kernel is three dependent trips to the memory side (write-through
-// ack, counter atomic, agent-scope re-read: ~10 us per GEMM) where the separate LN launch costs 5.2 us.
-static int run_dit(const Ctx& c, int j) {
+// ---- one batched DiT forward (the context's nb branches); input = xin (16-bit padded state), modulation row `j`: run_dit below runs the
+// input stage, the blocks and the output projection.  What the parts of one evaluation share:
+struct DitEval {
+    int j;                // the evaluation: row of the fold-constant tables
+    const float* mod;     // its modulation vector; per-row controls: vector 0 of the [nfe][B][(6L+2) D] table, the row kernels step through the B vectors
+    // LN fold, the one piece of state that travels from GEMM to GEMM: the rows' shift m lives in lnmean[cur_mean]; in the statistics form a
+    // consumer reads it, writes the rows' new means into the other half and the halves swap; a fold_rows launch updates lnmean[0] in place
+    int cur_mean = 0;
+};
+static float* ln_mean(const Ctx& c, int which) { return c.p<float>(c.w.lnmean) + (size_t)which * c.nb * c.B * c.N; }
+
+// x = Wx * x_t + Hc  (dit.py:250), all branches share x_t; then x += conv_pos_embed(x)  (dit.py:251)
+static int dit_input(const Ctx& c) {
     const f5_engine* e = c.e;
     const f5_config& cf = e->cfg;
     const Workspace& w = c.w;
-    const int D = cf.dim, FF = cf.ff_dim, L = cf.depth, H = cf.heads;
-    const int M1 = c.B * c.N, M = c.nb * M1;
-    hipStream_t s = c.s;
-    const Ops& K = c.ops;
-    // per-row controls: `mod` is vector 0 of evaluation j in the [nfe][B][(6L+2) D] table; the row kernels step through the B vectors
-    const size_t vstride = (size_t)(6 * L + 2) * D;
-    const float* mod = c.route.rows ? c.p<float>(w.rmod) + (size_t)j * c.B * vstride : c.p<float>(w.mod) + (size_t)j * vstride;
-    // the gated projections of that route leave their fp32 result (bias included) here: q | k are dead once the attention has run
-    float* yscratch = reinterpret_cast<float*>(c.pb(w.qk, 0));
-    auto ln_rows = [&](const float* y, const float* gate, const uint8_t* keep, const float* scale, const float* shift) {
-        return K.resid_gate_ln_rows(y, c.p<float>(w.x), gate, keep, scale, shift, c.pb(w.h, 0), c.pb(w.h, 1), M, D, c.N, c.B, vstride, 1e-6f, s);
-    };
-    const uint8_t* rowkeep = c.use_mask ? c.p<uint8_t>(w.rowkeep) : nullptr;
-    const int* kvlen = c.use_mask ? c.p<int>(w.dur2) : nullptr;
-
-    // x = Wx * x_t + Hc  (dit.py:250), both branches share x_t
-    F5GemmArgs g0 = gemm_base(c, c.pb(w.xin, 0), c.pb(w.xin, 1), 128, e->wx, M, D, 128, nullptr);
+    const int D = cf.dim, M1 = c.B * c.N;
+    F5GemmArgs g0 = gemm_base(c, c.pb(w.xin, 0), c.pb(w.xin, 1), 128, e->wx, c.nb * M1, D, 128, nullptr);
     g0.a_row_mod = M1;
     g0.addrows = c.p<float>(w.hc);
     g0.ldadd = D;
@@ -811,9 +835,8 @@ static int run_dit(const Ctx& c, int j) {
     g0.out_bf[0] = c.pb(w.xb, 0);
     g0.out_bf[1] = c.pb(w.xb, 1);
     g0.ldob = D;
-    RC(K.gemm(g0, EPI_ADDROWS, s));
+    RC(c.ops.gemm(g0, EPI_ADDROWS, c.s));
 
-    // x += conv_pos_embed(x)  (dit.py:251)
     F5ConvPosArgs cp;
     memset(&cp, 0, sizeof(cp));
     cp.B = c.nb * c.B;
@@ -833,7 +856,7 @@ static int run_dit(const Ctx& c, int j) {
     cp.mode = 0;
     cp.out_bf[0] = c.pb(w.c1, 0);
     cp.out_bf[1] = c.pb(w.c1, 1);
-    RC(K.convpos(cp, s));
+    RC(c.ops.convpos(cp, c.s));
     cp.in[0] = c.pb(w.c1, 0);
     cp.in[1] = c.pb(w.c1, 1);
     cp.W[0] = c.wm(e->conv_w[1], 0);
@@ -842,239 +865,203 @@ static int run_dit(const Ctx& c, int j) {
     cp.mode = 1;
     cp.out_bf[0] = cp.out_bf[1] = nullptr;
     cp.out_f32 = c.p<float>(w.x);
-    RC(K.convpos(cp, s));
+    return c.ops.convpos(cp, c.s);
+}
 
-    // q leaves the QKV epilogue multiplied by softmax_scale * log2(e) (one rounding, like the unscaled q): the attention kernels
-    // then get their scores in exp2 units straight from the matrix cores (attention.hip v2f).  Single-segment operand modes only;
-    // bf16x3 keeps the unscaled q (hi / lo split of the reference-exact value).  f5_debug_set_q_premul(0) = A/B.
-    const float qpre = q_premul_factor(e);
-    for (int i = 0; i < L && e->prec == F5_PREC_MXFP8; ++i) {
-        // MX-fp8 block: the four GEMMs run on e4m3 operands with E8M0 block scales (v_mfma_scale_f32_32x32x64_f8f6f4); their A
-        // operands are produced directly in that format by the LN kernel, the attention epilogue and the GELU epilogue.
-        // q / k / V^T and the attention itself stay bf16, the residual stream fp32.
-        const BlockW& bw = e->blocks[i];
-        const float* m6 = mod + (size_t)i * 6 * D;
-        auto f8args = [&](const uint8_t* a8, const uint8_t* as, int lda, const MatF8& wm, int N_, int K_, const float* bias) {
-            F5GemmArgs g;
-            memset(&g, 0, sizeof(g));
-            g.A8 = a8;
-            g.As = as;
-            g.lda8 = lda;
-            g.W8 = (const uint8_t*)(e->arena + wm.q);
-            g.Ws = (const uint8_t*)(e->arena + wm.s);
-            g.ldw8 = wm.ld;
-            g.M = M;
-            g.N = N_;
-            g.K = K_;
-            g.nseg = 1;
-            g.bias = bias;
-            g.debug_flags = e->opt.gemm_flags;
-            return g;
-        };
-        RC(f5_launch_ln_modulate_f8(c.p<float>(w.x), m6 + D, m6, c.p<uint8_t>(w.h8), c.p<uint8_t>(w.h8s), M, D, 1e-6f, s));
-        F5GemmArgs gq = f8args(c.p<uint8_t>(w.h8), c.p<uint8_t>(w.h8s), D, bw.qkv8, 3 * D, D, c.a<float>(bw.bqkv));
-        gq.out_bf[0] = c.pb(w.qk, 0);
-        gq.ldob = 2 * D;
-        gq.rope_cos = c.p<float>(w.rope_cos);
-        gq.rope_sin = c.p<float>(w.rope_sin);
-        gq.seq_len = c.N;
-        gq.npad = c.npad;
-        gq.heads = H;
-        gq.dmodel = D;
-        gq.vt[0] = c.pb(w.vt, 0);
-        gq.q_premul = qpre;
-        RC(f5_launch_gemm_f8(gq, EPI_QKV_ROPE, s));
+// What the QKV projection and the attention of a block are given in either precision.
+// q leaves the QKV epilogue multiplied by softmax_scale * log2(e) (one rounding, like the unscaled q): the attention kernels
+// then get their scores in exp2 units straight from the matrix cores (attention.hip v2f).  Single-segment operand modes only;
+// bf16x3 keeps the unscaled q (hi / lo split of the reference-exact value).  f5_debug_set_q_premul(0) = A/B.
+static void dit_qkv_fields(const Ctx& c, F5GemmArgs& g) {
+    const Workspace& w = c.w;
+    f5_qkv_rope_fields(g, c.pb(w.qk, 0), c.pb(w.qk, 1), c.pb(w.vt, 0), c.pb(w.vt, 1), c.p<float>(w.rope_cos), c.p<float>(w.rope_sin), c.N, c.npad,
+                       c.e->cfg.heads, c.e->cfg.dim, q_premul_factor(c.e));
+}
+static F5AttnArgs dit_attn_args(const Ctx& c, op16_t* out_hi, op16_t* out_lo) {
+    const f5_config& cf = c.e->cfg;
+    const Workspace& w = c.w;
+    return f5_attn_args(c.pb(w.qk, 0), c.pb(w.qk, 1), c.pb(w.vt, 0), c.pb(w.vt, 1), out_hi, out_lo, c.use_mask ? c.p<int>(w.dur2) : nullptr,
+                        c.nb * c.B, cf.heads, c.N, c.npad, cf.dim, 1.0f / sqrtf((float)cf.dim_head), c.e->np == 2, 2 * cf.dim, cf.dim,
+                        q_premul_factor(c.e) != 0.0f, c.e->opt.attn_pipe);
+}
 
-        F5AttnArgs at;
-        memset(&at, 0, sizeof(at));
-        at.qk[0] = c.pb(w.qk, 0);
-        at.vt[0] = c.pb(w.vt, 0);
-        at.out8 = c.p<uint8_t>(w.ao8);
-        at.out8s = c.p<uint8_t>(w.ao8s);
-        at.ldo8 = D;
-        at.kv_len = kvlen;
-        at.B = c.nb * c.B;
-        at.H = H;
-        at.seq_len = c.N;
-        at.npad = c.npad;
-        at.ldqk = 2 * D;
-        at.ldo = D;
-        at.dmodel = D;
-        at.hp = 0;
-        at.scale = 1.0f / sqrtf((float)cf.dim_head);
-        at.q_prescaled = qpre != 0.0f;
-        at.pipe = e->opt.attn_pipe;
-        RC(K.attention(at, s));
+// MX-fp8 block: the four GEMMs run on e4m3 operands with E8M0 block scales (v_mfma_scale_f32_32x32x64_f8f6f4); their A
+// operands are produced directly in that format by the LN kernel, the attention epilogue and the GELU epilogue.
+// q / k / V^T and the attention itself stay bf16, the residual stream fp32.
+static int dit_block_f8(const Ctx& c, const DitEval& ev, int i) {
+    const f5_engine* e = c.e;
+    const Workspace& w = c.w;
+    const int D = e->cfg.dim, FF = e->cfg.ff_dim, M = c.nb * c.B * c.N;
+    hipStream_t s = c.s;
+    const BlockW& bw = e->blocks[i];
+    const float* m6 = ev.mod + (size_t)i * 6 * D;
+    uint8_t *h8 = c.p<uint8_t>(w.h8), *h8s = c.p<uint8_t>(w.h8s), *ao8 = c.p<uint8_t>(w.ao8), *ao8s = c.p<uint8_t>(w.ao8s);
+    auto f8args = [&](const uint8_t* a8, const uint8_t* as, int lda, const MatF8& wm, int N_, int K_, size_t bias) {
+        F5GemmArgs g = f5_gemm_f8_args(a8, as, e->arena + wm.q, e->arena + wm.s, lda, wm.ld, M, N_, K_, c.a<float>(bias));
+        g.debug_flags = e->opt.gemm_flags;
+        return g;
+    };
+    RC(f5_launch_ln_modulate_f8(c.p<float>(w.x), m6 + D, m6, h8, h8s, M, D, 1e-6f, s));
+    F5GemmArgs gq = f8args(h8, h8s, D, bw.qkv8, 3 * D, D, bw.bqkv);
+    dit_qkv_fields(c, gq);
+    RC(f5_launch_gemm_f8(gq, EPI_QKV_ROPE, s));
 
-        F5GemmArgs go = f8args(c.p<uint8_t>(w.ao8), c.p<uint8_t>(w.ao8s), D, bw.o8, D, D, c.a<float>(bw.bo));
-        go.out_f32 = c.p<float>(w.x);
-        go.ldo = D;
-        go.gate = m6 + 2 * D;
-        go.rowkeep = rowkeep;
-        RC(f5_launch_gemm_f8(go, EPI_RESID_GATE, s));
+    F5AttnArgs at = dit_attn_args(c, nullptr, nullptr);
+    at.out8 = ao8;
+    at.out8s = ao8s;
+    at.ldo8 = D;
+    RC(c.ops.attention(at, s));
 
-        RC(f5_launch_ln_modulate_f8(c.p<float>(w.x), m6 + 4 * D, m6 + 3 * D, c.p<uint8_t>(w.h8), c.p<uint8_t>(w.h8s), M, D, 1e-6f, s));
-        F5GemmArgs g1 = f8args(c.p<uint8_t>(w.h8), c.p<uint8_t>(w.h8s), D, bw.ff1_8, FF, D, c.a<float>(bw.bff1));
-        g1.out8 = c.p<uint8_t>(w.ffh8);
-        g1.out8s = c.p<uint8_t>(w.ffh8s);
-        g1.ldo8 = FF;
-        RC(f5_launch_gemm_f8(g1, EPI_GELU_TANH, s));
-        F5GemmArgs g2 = f8args(c.p<uint8_t>(w.ffh8), c.p<uint8_t>(w.ffh8s), FF, bw.ff2_8, D, FF, c.a<float>(bw.bff2));
-        g2.out_f32 = c.p<float>(w.x);
-        g2.ldo = D;
-        g2.gate = m6 + 5 * D;
-        RC(f5_launch_gemm_f8(g2, EPI_RESID_GATE, s));
+    F5GemmArgs go = f8args(ao8, ao8s, D, bw.o8, D, D, bw.bo);
+    go.out_f32 = c.p<float>(w.x);
+    go.ldo = D;
+    go.gate = m6 + 2 * D;
+    go.rowkeep = c.use_mask ? c.p<uint8_t>(w.rowkeep) : nullptr;
+    RC(f5_launch_gemm_f8(go, EPI_RESID_GATE, s));
+
+    RC(f5_launch_ln_modulate_f8(c.p<float>(w.x), m6 + 4 * D, m6 + 3 * D, h8, h8s, M, D, 1e-6f, s));
+    F5GemmArgs g1 = f8args(h8, h8s, D, bw.ff1_8, FF, D, bw.bff1);
+    g1.out8 = c.p<uint8_t>(w.ffh8);
+    g1.out8s = c.p<uint8_t>(w.ffh8s);
+    g1.ldo8 = FF;
+    RC(f5_launch_gemm_f8(g1, EPI_GELU_TANH, s));
+    F5GemmArgs g2 = f8args(g1.out8, g1.out8s, FF, bw.ff2_8, D, FF, bw.bff2);
+    g2.out_f32 = c.p<float>(w.x);
+    g2.ldo = D;
+    g2.gate = m6 + 5 * D;
+    return f5_launch_gemm_f8(g2, EPI_RESID_GATE, s);
+}
+
+// LN fold, consumer side (QKV: col0 = 0, FF1: col0 = 3 D): the GEMM finishes the LN in its epilogue with the constants of this evaluation
+// and block (run_prep), from the row factors or -- statistics form -- from the producer's slice statistics
+static void fold_consumer(const Ctx& c, DitEval& ev, F5GemmArgs& g, int i, int col0) {
+    const f5_config& cf = c.e->cfg;
+    const size_t off = ((size_t)ev.j * cf.depth + i) * (3 * cf.dim + cf.ff_dim) + col0;
+    if (c.ln.mode == LN_FOLD_STATS) {
+        g.fold_stats = c.p<float>(c.w.lnstats);
+        g.fold_stats_ld = c.nb * c.B * c.N;
+        g.fold_shift = ln_mean(c, ev.cur_mean);
+        g.fold_mean_out = ln_mean(c, ev.cur_mean ^ 1);
+        g.fold_eps = 1e-6f;
+        ev.cur_mean ^= 1;
+    } else {
+        g.fold_rowf = c.p<float>(c.w.lnrowf);
     }
-    // LN-modulate fused behind the residual GEMMs where the launch is small-tile (gemm.hpp ln_counter): at batch 1 that removes
-    // 2 of the 7 launches of a block; h_ready = the h operand of the next QKV / final projection already exists
-    const float* mf = mod + (size_t)L * 6 * D;  // final adaLN: (scale, shift) order, dit.py:287
-    bool h_ready = false;
-    auto fuse_ln = [&](F5GemmArgs& g, const float* scale, const float* shift) -> bool {
-        if (c.route.rows || !e->opt.fuse_ln || w.lncnt_words == 0 || !f5_gemm_resid_ln_fusable(f5bf::f5_gemm_query(g, EPI_RESID_GATE), g.ldo)) return false;
+    g.fold_c1 = c.p<float>(c.w.foldc[0]) + off;
+    g.fold_c2 = c.p<float>(c.w.foldc[1]) + off;
+}
+
+// A residual GEMM of a 16-bit block (out-projection, FF2): x += gate * (y * keep), and the LN-modulate (scale, shift) behind it that leaves
+// `h`, the operand of the next GEMM -- the one place that acts on the LN plan.  `final`: the LN is the one in front of the output
+// projection, which feeds a small mel GEMM: kernel and fold leave it to dit_output, tail and rows produce it here.
+static int resid_ln(const Ctx& c, DitEval& ev, F5GemmArgs& g, const float* gate, const uint8_t* keep, const float* scale, const float* shift,
+                    bool final) {
+    const Workspace& w = c.w;
+    const int D = c.e->cfg.dim, M = c.nb * c.B * c.N;
+    const LnMode mode = c.ln.mode;
+    g.ldo = D;
+    if (mode == LN_ROWS) {
+        // the GEMM leaves its fp32 result (bias included) in q | k, dead once the attention has run; then x += gate[row] * (keep ? y : 0)
+        // and the LN-modulate in one row kernel
+        g.out_f32 = reinterpret_cast<float*>(c.pb(w.qk, 0));
+        RC(c.ops.gemm(g, EPI_F32, c.s));
+        return c.ops.resid_gate_ln_rows(g.out_f32, c.p<float>(w.x), gate, keep, scale, shift, c.pb(w.h, 0), c.pb(w.h, 1), M, D, c.N, c.B,
+                                        (size_t)(6 * c.e->cfg.depth + 2) * D, 1e-6f, c.s);
+    }
+    g.out_f32 = c.p<float>(w.x);
+    g.gate = gate;
+    g.rowkeep = keep;
+    if (mode == LN_TAIL) {        // h = LN(x) (1 + scale) + shift in the same launch
         g.ln_counter = c.p<int>(w.lncnt);
         g.ln_scale = scale;
         g.ln_shift = shift;
         g.ln_out[0] = c.pb(w.h, 0);
         g.ln_out[1] = c.pb(w.h, 1);
         g.ln_eps = 1e-6f;
-        return true;
-    };
-    // LN fold: the residual GEMMs leave x (1 + scale) in the operand type in `h` and the row sums in `lnstats`; QKV / FF1 finish the
-    // LN in their epilogues with the constants of this evaluation (run_prep)
-    const int fold_state = ln_fold_state(c);
-    if (fold_state < 0) return 2;
-    const bool fold = fold_state >= 1;
-    const float* fc1 = c.p<float>(w.foldc[0]) + (size_t)j * L * (3 * D + FF);
-    const float* fc2 = c.p<float>(w.foldc[1]) + (size_t)j * L * (3 * D + FF);
-    // the rows' shift m lives in lnmean[cur_mean]; with fold_stats a consumer reads it, writes the rows' new means into the other half and
-    // the halves swap; with a f5_fold_rows launch the kernel updates lnmean[0] in place
-    // statistics form: always on the batch-1-sized route (state 2: its kernels have no other), by option on the staged kernels (measured
-    // slower there: every tile of a multi-round launch repeats the merge -- +1.9 % at batch 32, +1.6 % at 8, profiles/r06)
-    const bool stats_form = fold_state == 2 || (fold && e->opt.fold_stats == 1 && D == 1024);
-    int cur_mean = 0;
-    auto lnmean = [&](int which) { return c.p<float>(w.lnmean) + (size_t)which * M; };
-    auto fold_consumer = [&](F5GemmArgs& g, int block, int col0) {
-        if (stats_form) {
-            g.fold_stats = c.p<float>(w.lnstats);
-            g.fold_stats_ld = M;
-            g.fold_shift = lnmean(cur_mean);
-            g.fold_mean_out = lnmean(cur_mean ^ 1);
-            g.fold_eps = 1e-6f;
-            cur_mean ^= 1;
-        } else {
-            g.fold_rowf = c.p<float>(w.lnrowf);
-        }
-        g.fold_c1 = fc1 + (size_t)block * (3 * D + FF) + col0;
-        g.fold_c2 = fc2 + (size_t)block * (3 * D + FF) + col0;
-    };
-    auto fold_producer = [&](F5GemmArgs& g, const float* next_scale) {
+    }
+    const bool fold = c.ln.fold() && !final;
+    if (fold) {                   // producer: x (1 + scale) in the operand type in `h`, the row sums in `lnstats`
         g.x16_out = c.pb(w.h, 0);
         g.ldx16 = D;
-        g.x16_scale = next_scale;
-        g.x16_shift = lnmean(cur_mean);            // the row's mean at the previous LayerNorm (LN kernel of block 0 / the last consumer / fold_rows)
+        g.x16_scale = scale;
+        g.x16_shift = ln_mean(c, ev.cur_mean);     // the row's mean at the previous LayerNorm (LN kernel of block 0 / the last consumer / fold_rows)
         g.stats_out = c.p<float>(w.lnstats);
         g.stats_ld = M;
         g.x16_overflow = c.p<int>(w.status);
-    };
-    auto fold_rows = [&]() {
-        if (stats_form) return 0;
-        return K.fold_rows(c.p<float>(w.lnstats), M, D / 64, M, 1e-6f, c.p<float>(w.lnrowf), c.p<float>(w.lnmean), s);
-    };
-    bool h_folded = false;                       // `h` holds x (1 + scale) + row sums (fold) instead of the finished LN-modulate
-    for (int i = 0; i < L && e->prec != F5_PREC_MXFP8; ++i) {
-        const BlockW& bw = e->blocks[i];
-        const float* m6 = mod + (size_t)i * 6 * D;  // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-        if (!h_ready && c.route.rows) RC(ln_rows(nullptr, nullptr, nullptr, m6 + D, m6));
-        else if (!h_ready) RC(K.ln_modulate(c.p<float>(w.x), m6 + D, m6, c.pb(w.h, 0), c.pb(w.h, 1), M, D, 1e-6f, s, fold ? c.p<float>(w.lnmean) : nullptr));
-        F5GemmArgs gq = gemm_base(c, c.pb(w.h, 0), c.pb(w.h, 1), D, bw.qkv, M, 3 * D, D, c.a<float>(bw.bqkv));
-        if (h_folded) fold_consumer(gq, i, 0);
-        gq.out_bf[0] = c.pb(w.qk, 0);
-        gq.out_bf[1] = c.pb(w.qk, 1);
-        gq.ldob = 2 * D;
-        gq.rope_cos = c.p<float>(w.rope_cos);
-        gq.rope_sin = c.p<float>(w.rope_sin);
-        gq.seq_len = c.N;
-        gq.npad = c.npad;
-        gq.heads = H;
-        gq.dmodel = D;
-        gq.vt[0] = c.pb(w.vt, 0);
-        gq.vt[1] = c.pb(w.vt, 1);
-        gq.q_premul = qpre;
-        if (e->opt.qkv_tr) {                             // pair-major tables (the q pair carries qpre, or 1): used by the 256x256 kernel
-            const float* t = c.p<float>(w.rope_t);
-            const size_t tn = (size_t)32 * c.N;
-            gq.rope_g4q = t;
-            gq.rope_g4k = t + 2 * tn;
-        }
-        RC(K.gemm(gq, EPI_QKV_ROPE, s));
-
-        F5AttnArgs at;
-        memset(&at, 0, sizeof(at));
-        for (int p = 0; p < 2; ++p) {
-            at.qk[p] = c.pb(w.qk, p);
-            at.vt[p] = c.pb(w.vt, p);
-            at.out[p] = c.pb(w.ao, p);
-        }
-        at.kv_len = kvlen;
-        at.B = c.nb * c.B;
-        at.H = H;
-        at.seq_len = c.N;
-        at.npad = c.npad;
-        at.ldqk = 2 * D;
-        at.ldo = D;
-        at.dmodel = D;
-        at.hp = e->np == 2;
-        at.scale = 1.0f / sqrtf((float)cf.dim_head);
-        at.q_prescaled = qpre != 0.0f;
-        at.pipe = e->opt.attn_pipe;
-        RC(K.attention(at, s));
-
-        F5GemmArgs go = gemm_base(c, c.pb(w.ao, 0), c.pb(w.ao, 1), D, bw.o, M, D, D, c.a<float>(bw.bo));
-        go.out_f32 = c.route.rows ? yscratch : c.p<float>(w.x);
-        go.ldo = D;
-        if (!c.route.rows) {
-            go.gate = m6 + 2 * D;
-            go.rowkeep = rowkeep;
-        }
-        const bool fused_mlp_ln = fuse_ln(go, m6 + 4 * D, m6 + 3 * D);     // h = LN(x) (1 + scale_mlp) + shift_mlp in the same launch
-        if (fold) fold_producer(go, m6 + 4 * D);
-        RC(K.gemm(go, c.route.rows ? EPI_F32 : EPI_RESID_GATE, s));
-        if (fold) RC(fold_rows());
-
-        // per-row controls: x += gate_msa[row] * (keep ? y : 0), then the mlp LN-modulate, in one row kernel
-        if (c.route.rows) RC(ln_rows(yscratch, m6 + 2 * D, rowkeep, m6 + 4 * D, m6 + 3 * D));
-        else if (!fused_mlp_ln && !fold) RC(K.ln_modulate(c.p<float>(w.x), m6 + 4 * D, m6 + 3 * D, c.pb(w.h, 0), c.pb(w.h, 1), M, D, 1e-6f, s));
-        F5GemmArgs g1 = gemm_base(c, c.pb(w.h, 0), c.pb(w.h, 1), D, bw.ff1, M, FF, D, c.a<float>(bw.bff1));
-        if (fold) fold_consumer(g1, i, 3 * D);
-        g1.out_bf[0] = c.pb(w.ffh, 0);
-        g1.out_bf[1] = c.pb(w.ffh, 1);
-        g1.ldob = FF;
-        RC(K.gemm(g1, EPI_GELU_TANH, s));
-        F5GemmArgs g2 = gemm_base(c, c.pb(w.ffh, 0), c.pb(w.ffh, 1), FF, bw.ff2, M, D, FF, c.a<float>(bw.bff2));
-        g2.out_f32 = c.route.rows ? yscratch : c.p<float>(w.x);
-        g2.ldo = D;
-        if (!c.route.rows) g2.gate = m6 + 5 * D;
-        // the LN that follows FF2: the next block's attention LN (scale_msa, shift_msa), or the final one (dit.py:287: scale, shift)
-        const float* m6n = m6 + 6 * D;
-        h_ready = (i + 1 < L) ? fuse_ln(g2, m6n + D, m6n) : fuse_ln(g2, mf, mf + D);
-        h_folded = fold && i + 1 < L;            // (the final LN feeds the small mel projection: it keeps the LN kernel)
-        if (h_folded) {
-            fold_producer(g2, m6n + D);
-            h_ready = true;
-        }
-        RC(K.gemm(g2, c.route.rows ? EPI_F32 : EPI_RESID_GATE, s));
-        if (h_folded) RC(fold_rows());
-        if (c.route.rows) {        // x += gate_mlp[row] * y, then the LN that follows (no row mask on FF2, as in the gated epilogue above)
-            RC(i + 1 < L ? ln_rows(yscratch, m6 + 5 * D, nullptr, m6n + D, m6n) : ln_rows(yscratch, m6 + 5 * D, nullptr, mf, mf + D));
-            h_ready = true;
-        }
     }
-    if (!h_ready) RC(K.ln_modulate(c.p<float>(w.x), mf, mf + D, c.pb(w.h, 0), c.pb(w.h, 1), M, D, 1e-6f, s));
-    F5GemmArgs gf = gemm_base(c, c.pb(w.h, 0), c.pb(w.h, 1), D, e->wout, M, cf.mel_dim, D, c.a<float>(e->bout));
+    RC(c.ops.gemm(g, EPI_RESID_GATE, c.s));
+    if (fold && mode == LN_FOLD_ROWF) return c.ops.fold_rows(c.p<float>(w.lnstats), M, D / 64, M, 1e-6f, c.p<float>(w.lnrowf), c.p<float>(w.lnmean), c.s);
+    if (mode == LN_KERNEL && !final) return c.ops.ln_modulate(c.p<float>(w.x), scale, shift, c.pb(w.h, 0), c.pb(w.h, 1), M, D, 1e-6f, c.s);
+    return 0;
+}
+
+// 16-bit block (bf16, f16, bf16x3)
+static int dit_block(const Ctx& c, DitEval& ev, int i) {
+    const f5_engine* e = c.e;
+    const Workspace& w = c.w;
+    const int D = e->cfg.dim, FF = e->cfg.ff_dim, L = e->cfg.depth, M = c.nb * c.B * c.N;
+    hipStream_t s = c.s;
+    const Ops& K = c.ops;
+    const BlockW& bw = e->blocks[i];
+    const float* m6 = ev.mod + (size_t)i * 6 * D;  // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
+    if (i == 0) {     // no residual GEMM in front of block 0: its attention LN is a launch of its own, which also seeds the fold's row means
+        if (c.ln.mode == LN_ROWS)
+            RC(K.resid_gate_ln_rows(nullptr, c.p<float>(w.x), nullptr, nullptr, m6 + D, m6, c.pb(w.h, 0), c.pb(w.h, 1), M, D, c.N, c.B,
+                                    (size_t)(6 * L + 2) * D, 1e-6f, s));
+        else
+            RC(K.ln_modulate(c.p<float>(w.x), m6 + D, m6, c.pb(w.h, 0), c.pb(w.h, 1), M, D, 1e-6f, s, c.ln.fold() ? c.p<float>(w.lnmean) : nullptr));
+    }
+    F5GemmArgs gq = gemm_base(c, c.pb(w.h, 0), c.pb(w.h, 1), D, bw.qkv, M, 3 * D, D, c.a<float>(bw.bqkv));
+    if (c.ln.fold() && i > 0) fold_consumer(c, ev, gq, i, 0);
+    dit_qkv_fields(c, gq);
+    if (e->opt.qkv_tr) {                             // pair-major tables (the q pair carries qpre, or 1): used by the 256x256 kernel
+        gq.rope_g4q = c.p<float>(w.rope_t);
+        gq.rope_g4k = gq.rope_g4q + (size_t)64 * c.N;
+    }
+    RC(K.gemm(gq, EPI_QKV_ROPE, s));
+    RC(K.attention(dit_attn_args(c, c.pb(w.ao, 0), c.pb(w.ao, 1)), s));
+
+    F5GemmArgs go = gemm_base(c, c.pb(w.ao, 0), c.pb(w.ao, 1), D, bw.o, M, D, D, c.a<float>(bw.bo));
+    RC(resid_ln(c, ev, go, m6 + 2 * D, c.use_mask ? c.p<uint8_t>(w.rowkeep) : nullptr, m6 + 4 * D, m6 + 3 * D, false));
+    F5GemmArgs g1 = gemm_base(c, c.pb(w.h, 0), c.pb(w.h, 1), D, bw.ff1, M, FF, D, c.a<float>(bw.bff1));
+    if (c.ln.fold()) fold_consumer(c, ev, g1, i, 3 * D);
+    g1.out_bf[0] = c.pb(w.ffh, 0);
+    g1.out_bf[1] = c.pb(w.ffh, 1);
+    g1.ldob = FF;
+    RC(K.gemm(g1, EPI_GELU_TANH, s));
+    F5GemmArgs g2 = gemm_base(c, c.pb(w.ffh, 0), c.pb(w.ffh, 1), FF, bw.ff2, M, D, FF, c.a<float>(bw.bff2));
+    // the LN that follows FF2: the next block's attention LN (shift_msa, scale_msa), or the final one (dit.py:287: scale, shift); no row
+    // mask on FF2
+    const float* m6n = m6 + 6 * D;
+    const bool final = i + 1 == L;
+    return resid_ln(c, ev, g2, m6 + 5 * D, nullptr, final ? m6n : m6n + D, final ? m6n + D : m6n, final);
+}
+
+// the final LN (unless the last block's FF2 left it: tail, rows) and the mel projection
+static int dit_output(const Ctx& c, const DitEval& ev) {
+    const f5_config& cf = c.e->cfg;
+    const Workspace& w = c.w;
+    const int D = cf.dim, M = c.nb * c.B * c.N;
+    const float* mf = ev.mod + (size_t)cf.depth * 6 * D;  // final adaLN: (scale, shift) order, dit.py:287
+    if (c.ln.mode != LN_TAIL && c.ln.mode != LN_ROWS)
+        RC(c.ops.ln_modulate(c.p<float>(w.x), mf, mf + D, c.pb(w.h, 0), c.pb(w.h, 1), M, D, 1e-6f, c.s));
+    F5GemmArgs gf = gemm_base(c, c.pb(w.h, 0), c.pb(w.h, 1), D, c.e->wout, M, cf.mel_dim, D, c.a<float>(c.e->bout));
     gf.out_f32 = c.p<float>(w.vel);
     gf.ldo = cf.mel_dim;
-    RC(K.gemm(gf, EPI_F32, s));
-    return 0;
+    return c.ops.gemm(gf, EPI_F32, c.s);
+}
+
+// f5_debug_set_ln_fusion: LN-modulate fused behind the residual GEMMs of small-tile launches (gemm.hpp ln_counter): at batch 1 that
+// removes 2 of the 7 launches of a block.  OFF by default: bit-identical, but measured SLOWER at batch 1 (88.5 / 90.3 ms per sample
+// against 75.1 / 78.6 on the same boxes, profiles/r02/ln_fusion_ab.txt): a cross-XCD hand-over inside a kernel is three dependent trips
+// to the memory side (write-through ack, counter atomic, agent-scope re-read: ~10 us per GEMM) where the separate LN launch costs 5.2 us.
+static int run_dit(const Ctx& c, int j) {
+    const f5_config& cf = c.e->cfg;
+    const size_t vstride = (size_t)(6 * cf.depth + 2) * cf.dim;
+    DitEval ev = {j, c.route.rows ? c.p<float>(c.w.rmod) + (size_t)j * c.B * vstride : c.p<float>(c.w.mod) + (size_t)j * vstride};
+    RC(dit_input(c));
+    for (int i = 0; i < cf.depth; ++i) RC(c.e->prec == F5_PREC_MXFP8 ? dit_block_f8(c, ev, i) : dit_block(c, ev, i));
+    return dit_output(c, ev);
 }
 
 // steps [i0, i1) of the solve; i0 == 0 also runs the per-call preparation (hoisted tables, text path, first operand pack)
@@ -1103,6 +1090,8 @@ static int run_sample_body(const Ctx& c, const f5_sample_args* a, int i0 = 0, in
     const bool win = c.pattern != nullptr;
     Ctx narrow = c;
     narrow.nb = 1;
+    // another row count, so its own LN plan; a window call is a per-row route, which shuts out tail and fold: always the rows mode
+    if (win) narrow.ln = ln_fold_state(narrow);
     int jcur = 0;
     auto dit = [&](int j) {
         jcur = j;
@@ -1202,9 +1191,7 @@ static int stage_inputs(Ctx& c, const f5_sample_args* a, const float* x_override
     const size_t nd = (size_t)(1 + w.nbr) * c.B;     // lens and the durations of every branch
     F5_REQUIRE(w.scal_words == (size_t)1 + nd + nfe1 + a->steps + 1 + w.lncnt_words && dts.size() <= (size_t)a->steps,
                "internal: scalar staging layout");
-    const int fold_state = ln_fold_state(c);
-    if (fold_state < 0) return 2;
-    words[0] = fold_state >= 1 ? 2u : 0u;            // status word: bit 1 = the LN fold runs in this call, bit 0 is the kernels'
+    words[0] = c.ln.fold() ? 2u : 0u;                // status word: bit 1 = the LN fold runs in this call, bit 0 is the kernels'
     uint32_t* wd = words.data() + 1;
     memcpy(wd, a->lens, (size_t)c.B * 4);
     for (int br = 1; br <= w.nbr; ++br)
@@ -1247,6 +1234,8 @@ static Ctx make_ctx(f5_engine* e, const f5_sample_args* a, hipStream_t s, Route 
     c.npad = (a->N + 63) / 64 * 64;
     c.use_mask = a->use_mask != 0;
     c.isolate = c.use_mask && e->opt.isolate_rows != 0;     // without a mask the call has no padding: today's launches
+    // nb is final here, except for a window call (stage_controls): a per-row route, whose plan does not read it
+    c.ln = ln_fold_state(c);
     return c;
 }
 
@@ -1325,13 +1314,11 @@ static int validate_controls(const Ctx& c, const f5_sample_args* a, const RowCtl
             F5_REQUIRE(rc.lo_rows[b] <= rc.hi_rows[b], "%s: lo_rows[%d] = %g is above hi_rows[%d] = %g", rc.what, b, rc.lo_rows[b], b,
                        rc.hi_rows[b]);
         }
-        // (the window call tries the forced-fold refusal before the size, the other per-row calls after it; a call without per-row
-        // controls meets it in stage_inputs)
-        if (r.window && ln_fold_state(c, rc.what) < 0) return 2;
+        // (the window call tries the forced-fold refusal before the size, every other call after it)
+        if (r.window) RC(ln_refusal(c, rc.what));
     }
     RC(check_workspace(c, a, rc.what));
-    if (r.rows && ln_fold_state(c, rc.what) < 0) return 2;
-    return 0;
+    return ln_refusal(c, rc.what);
 }
 
 // Stages the call's inputs and controls into the workspace.  Per-row routes: the rows words ([tgrid nfe x B | dt steps x B | cfg B
@@ -1528,9 +1515,8 @@ extern "C" int f5_engine_ln_fold_active(f5_engine* e, const f5_sample_args* a, i
     F5_REQUIRE(e && a && active, "null argument");
     F5_REQUIRE(a->B >= 1 && a->N >= 1 && a->nt >= 1 && a->steps >= 1 && a->method >= F5_EULER && a->method <= F5_RK4, "bad sizes");
     const Ctx c = make_ctx(e, a, nullptr, Route{}, branch_count(Route{}, &a->cfg_strength, nullptr, 1));
-    const int st = ln_fold_state(c);
-    if (st < 0) return 2;
-    *active = st;
+    RC(ln_refusal(c, ""));
+    *active = c.ln.fold_state;
     return 0;
 }
 extern "C" int f5_sample_status(f5_engine* e, const f5_sample_args* a, int* flags, void* stream) {
@@ -1558,7 +1544,7 @@ static int forward_impl(f5_engine* e, const f5_sample_args* a, const float* x, c
     a2.method = F5_EULER;
     Ctx c = make_ctx(e, &a2, s, route, route.dual ? 3 : branch_count(route, &a2.cfg_strength, nullptr, 1));
     RC(check_workspace(c, a, what));
-    if (route.rows && ln_fold_state(c) < 0) return 2;
+    RC(ln_refusal(c, what));
     const int mel = e->cfg.mel_dim;
     const size_t M1 = (size_t)c.B * c.N;
     SatScope sat(e->prec == F5_PREC_F16 && e->opt.sat_check, c.p<int>(c.w.status));
@@ -1853,19 +1839,7 @@ extern "C" int f5_op_gemm_f8(const void* a8, const void* a_scales, const void* w
                              int M, int N, int K, int lda8, int ldw8, int ldo, int epi, void* stream) {
     F5_REQUIRE(epi == EPI_F32 || epi == EPI_BF16 || epi == EPI_GELU_TANH || epi == EPI_RESID_GATE,
                "f5_op_gemm_f8 supports epilogues 0, 1, 2 and 4");
-    F5GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A8 = (const uint8_t*)a8;
-    g.As = (const uint8_t*)a_scales;
-    g.W8 = (const uint8_t*)w8;
-    g.Ws = (const uint8_t*)w_scales;
-    g.lda8 = lda8;
-    g.ldw8 = ldw8;
-    g.M = M;
-    g.N = N;
-    g.K = K;
-    g.nseg = 1;
-    g.bias = bias;
+    F5GemmArgs g = f5_gemm_f8_args(a8, a_scales, w8, w_scales, lda8, ldw8, M, N, K, bias);
     g.gate = gate;
     g.rowkeep = rowkeep;
     g.out_f32 = out_f32;
@@ -1892,33 +1866,12 @@ extern "C" int f5_op_ln_modulate_f8(const float* x, const float* scale, const fl
                                     float eps, void* stream) {
     return f5_launch_ln_modulate_f8(x, scale, shift, (uint8_t*)q, (uint8_t*)q_scales, rows, dim, eps, (hipStream_t)stream);
 }
-// the QKV projection of an mxfp8 block: F5GemmArgs filled as run_dit fills them
+// the QKV projection of an mxfp8 block: the argument builders of run_dit's own launch
 extern "C" int f5_op_qkv_rope_f8(const void* a8, const void* a_scales, const void* w8, const void* w_scales, const float* bias,
                                  const float* rope_cos, const float* rope_sin, void* qk, void* vt, int B, int seq_len, int npad, int heads,
                                  int dmodel, int lda8, int ldw8, float q_premul, void* stream) {
-    F5GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A8 = (const uint8_t*)a8;
-    g.As = (const uint8_t*)a_scales;
-    g.W8 = (const uint8_t*)w8;
-    g.Ws = (const uint8_t*)w_scales;
-    g.lda8 = lda8;
-    g.ldw8 = ldw8;
-    g.M = B * seq_len;
-    g.N = 3 * dmodel;
-    g.K = dmodel;
-    g.nseg = 1;
-    g.bias = bias;
-    g.out_bf[0] = (op16_t*)qk;
-    g.ldob = 2 * dmodel;
-    g.rope_cos = rope_cos;
-    g.rope_sin = rope_sin;
-    g.seq_len = seq_len;
-    g.npad = npad;
-    g.heads = heads;
-    g.dmodel = dmodel;
-    g.vt[0] = (op16_t*)vt;
-    g.q_premul = q_premul;
+    F5GemmArgs g = f5_gemm_f8_args(a8, a_scales, w8, w_scales, lda8, ldw8, B * seq_len, 3 * dmodel, dmodel, bias);
+    f5_qkv_rope_fields(g, qk, nullptr, vt, nullptr, rope_cos, rope_sin, seq_len, npad, heads, dmodel, q_premul);
     return f5_launch_gemm_f8(g, EPI_QKV_ROPE, (hipStream_t)stream);
 }
 
@@ -1943,26 +1896,8 @@ extern "C" int f5_debug_set_op_q_premul(float v) {
 extern "C" int f5_op_attention_ex(const void* qk_hi, const void* qk_lo, const void* vt_hi, const void* vt_lo, void* out_hi, void* out_lo,
                                   const int32_t* kv_len, int B, int H, int seq_len, int npad, int dmodel, float scale, int hp, int ldqk,
                                   int ldo, int q_prescaled, int pipe, void* out8, void* out8s, int ldo8, void* stream) {
-    F5AttnArgs at;
-    memset(&at, 0, sizeof(at));
-    at.qk[0] = (const op16_t*)qk_hi;
-    at.qk[1] = (const op16_t*)qk_lo;
-    at.vt[0] = (const op16_t*)vt_hi;
-    at.vt[1] = (const op16_t*)vt_lo;
-    at.out[0] = (op16_t*)out_hi;
-    at.out[1] = (op16_t*)out_lo;
-    at.kv_len = kv_len;
-    at.B = B;
-    at.H = H;
-    at.seq_len = seq_len;
-    at.npad = npad;
-    at.ldqk = ldqk;
-    at.ldo = ldo;
-    at.dmodel = dmodel;
-    at.hp = hp;
-    at.scale = scale;
-    at.q_prescaled = q_prescaled;
-    at.pipe = pipe;
+    F5AttnArgs at = f5_attn_args(qk_hi, qk_lo, vt_hi, vt_lo, out_hi, out_lo, kv_len, B, H, seq_len, npad, dmodel, scale, hp, ldqk, ldo, q_prescaled,
+                                 pipe);
     at.out8 = (uint8_t*)out8;
     at.out8s = (uint8_t*)out8s;
     at.ldo8 = ldo8;
@@ -1980,20 +1915,8 @@ extern "C" int f5_op_qkv_rope(const void* a_hi, const void* a_lo, const void* w_
                               const float* rope_cos, const float* rope_sin, void* qk_hi, void* qk_lo, void* vt_hi, void* vt_lo,
                               int B, int seq_len, int npad, int heads, int dmodel, int nseg, void* stream) {
     F5GemmArgs g = f5_gemm_args(a_hi, a_lo, w_hi, w_lo, dmodel, dmodel, B * seq_len, 3 * dmodel, dmodel, nseg, bias);
-    g.out_bf[0] = (op16_t*)qk_hi;
-    g.out_bf[1] = (op16_t*)qk_lo;
-    g.ldob = 2 * dmodel;
-    g.rope_cos = rope_cos;
-    g.rope_sin = rope_sin;
-    g.seq_len = seq_len;
-    g.npad = npad;
-    g.heads = heads;
-    g.dmodel = dmodel;
-    g.q_premul = nseg == 1 ? g_op_q_premul : 0.0f;
-    g.rope_g4q = g_op_rope_t[0];
-    g.rope_g4k = g_op_rope_t[1];
-    g.vt[0] = (op16_t*)vt_hi;
-    g.vt[1] = (op16_t*)vt_lo;
+    f5_qkv_rope_fields(g, qk_hi, qk_lo, vt_hi, vt_lo, rope_cos, rope_sin, seq_len, npad, heads, dmodel, nseg == 1 ? g_op_q_premul : 0.0f,
+                       g_op_rope_t[0], g_op_rope_t[1]);
     if (g_op_fold.rowf != nullptr || g_op_fold_stats.stats != nullptr) op_fold_consumer(g);
     return g_ops.gemm(g, EPI_QKV_ROPE, (hipStream_t)stream);
 }

@@ -68,6 +68,64 @@ static inline F5GemmArgs f5_gemm_args(const void* a_hi, const void* a_lo, const 
     g.bias = bias;
     return g;
 }
+// the same for an MX-fp8 launch: e4m3 operands with their E8M0 block scales, one operand segment
+static inline F5GemmArgs f5_gemm_f8_args(const void* a8, const void* a_scales, const void* w8, const void* w_scales, int lda8, int ldw8, int M,
+                                         int N, int K, const float* bias) {
+    F5GemmArgs g = f5_gemm_args(nullptr, nullptr, nullptr, nullptr, 0, 0, M, N, K, 1, bias);
+    g.A8 = (const uint8_t*)a8;
+    g.As = (const uint8_t*)a_scales;
+    g.W8 = (const uint8_t*)w8;
+    g.Ws = (const uint8_t*)w_scales;
+    g.lda8 = lda8;
+    g.ldw8 = ldw8;
+    return g;
+}
+// what EPI_QKV_ROPE reads beyond operands and shape: q | k out, token-major rotation tables, head geometry, V^T out, the factor folded
+// into q (0 = none) and, optionally, the group-major tables of the transposed q / k tiles
+static inline void f5_qkv_rope_fields(F5GemmArgs& g, void* qk_hi, void* qk_lo, void* vt_hi, void* vt_lo, const float* rope_cos,
+                                      const float* rope_sin, int seq_len, int npad, int heads, int dmodel, float q_premul,
+                                      const float* rope_g4q = nullptr, const float* rope_g4k = nullptr) {
+    g.out_bf[0] = (op16_t*)qk_hi;
+    g.out_bf[1] = (op16_t*)qk_lo;
+    g.ldob = 2 * dmodel;
+    g.rope_cos = rope_cos;
+    g.rope_sin = rope_sin;
+    g.seq_len = seq_len;
+    g.npad = npad;
+    g.heads = heads;
+    g.dmodel = dmodel;
+    g.vt[0] = (op16_t*)vt_hi;
+    g.vt[1] = (op16_t*)vt_lo;
+    g.q_premul = q_premul;
+    g.rope_g4q = rope_g4q;
+    g.rope_g4k = rope_g4k;
+}
+// attention over q | k rows and V^T as the QKV epilogue leaves them; the MX-fp8 output (out8, out8s, ldo8) stays with the caller
+static inline F5AttnArgs f5_attn_args(const void* qk_hi, const void* qk_lo, const void* vt_hi, const void* vt_lo, void* out_hi, void* out_lo,
+                                      const int* kv_len, int B, int H, int seq_len, int npad, int dmodel, float scale, int hp, int ldqk,
+                                      int ldo, int q_prescaled, int pipe) {
+    F5AttnArgs at;
+    memset(&at, 0, sizeof(at));
+    at.qk[0] = (const op16_t*)qk_hi;
+    at.qk[1] = (const op16_t*)qk_lo;
+    at.vt[0] = (const op16_t*)vt_hi;
+    at.vt[1] = (const op16_t*)vt_lo;
+    at.out[0] = (op16_t*)out_hi;
+    at.out[1] = (op16_t*)out_lo;
+    at.kv_len = kv_len;
+    at.B = B;
+    at.H = H;
+    at.seq_len = seq_len;
+    at.npad = npad;
+    at.ldqk = ldqk;
+    at.ldo = ldo;
+    at.dmodel = dmodel;
+    at.hp = hp;
+    at.scale = scale;
+    at.q_prescaled = q_prescaled;
+    at.pipe = pipe;
+    return at;
+}
 
 // Kernels of one operand type.  `h` selects the fp16 build.
 struct Ops {
@@ -189,17 +247,7 @@ struct Ops {
                  const float* rope_sin, op16_t* qk_hi, op16_t* qk_lo, op16_t* vt_hi, op16_t* vt_lo, int B, int seq_len, int npad, int heads,
                  int dmodel, int nseg, hipStream_t s) const {
         F5GemmArgs g = f5_gemm_args(a_hi, a_lo, w_hi, w_lo, dmodel, dmodel, B * seq_len, 3 * dmodel, dmodel, nseg, bias);
-        g.out_bf[0] = qk_hi;
-        g.out_bf[1] = qk_lo;
-        g.ldob = 2 * dmodel;
-        g.rope_cos = rope_cos;
-        g.rope_sin = rope_sin;
-        g.seq_len = seq_len;
-        g.npad = npad;
-        g.heads = heads;
-        g.dmodel = dmodel;
-        g.vt[0] = vt_hi;
-        g.vt[1] = vt_lo;
+        f5_qkv_rope_fields(g, qk_hi, qk_lo, vt_hi, vt_lo, rope_cos, rope_sin, seq_len, npad, heads, dmodel, 0.0f);
         return gemm(g, EPI_QKV_ROPE, s);
     }
     // launches without 16-bit operands: one build serves both operand types
