@@ -197,10 +197,15 @@ class F5TTS:
         loss = masked.sum() / torch.clamp(m.sum().to(torch.float32), min=1e-6)                      # :249
         return loss.mean()
 
-    def predict_duration(self, cond, text, speed=1.0, lens=None):
+    def predict_duration(self, cond, text, speed=1.0, lens=None, isolate_rows: bool = False):
         """cfm.py:253-262.  Extension: `lens` (frames of conditioning per row of a padded batch) goes to the predictor when given, so
-        that it masks each row's padding; without it the call is the reference's.  `speed` may be one value per row."""
-        duration_in_sec = self._duration_predictor(cond, text) if lens is None else self._duration_predictor(cond, text, lens=lens)
+        that it masks each row's padding; without it the call is the reference's.  `speed` may be one value per row.  isolate_rows
+        (docs/duration_rows.md; False: the call as it was): True = the predictor runs every row at its own length, so a row's frame
+        count does not depend on its batch-mates."""
+        kw = {} if lens is None else dict(lens=lens)
+        if isolate_rows is not False:
+            kw["isolate_rows"] = check_isolate_rows(isolate_rows, "")
+        duration_in_sec = self._duration_predictor(cond, text, **kw)
         frame_rate = self._mel_spec.sample_rate // self._mel_spec.hop_length
         if np.ndim(speed) != 0:
             speed = torch.as_tensor(speed, dtype=torch.float32, device=duration_in_sec.device)
@@ -236,7 +241,8 @@ class F5TTS:
                                                  # row is guided only at evaluations whose time lies in [lo, hi]; None = guided throughout
         isolate_rows: bool = False,              # extension (docs/isolate_rows.md): a row of a padded batch reads nothing from its own
                                                  # frames n >= duration[b], so it no longer depends on its batch-mates; one value per
-                                                 # call (an engine option: one hipGraph serves each value), False = the call as it was
+                                                 # call (an engine option: one hipGraph serves each value), False = the call as it was;
+                                                 # with duration=None the prediction is row-isolated too (docs/duration_rows.md)
     ) -> tuple[torch.Tensor, torch.Tensor]:
         self.eval()
         device = self.transformer.device
@@ -283,7 +289,8 @@ class F5TTS:
                 text = list_str_to_tensor(text)
             assert text.shape[0] == batch
         if duration is None and self._duration_predictor is not None:
-            duration = self.predict_duration(cond, text, speed) if lens is None else self.predict_duration(cond, text, speed, lens=lens)
+            # (under isolate_rows the prediction is row-isolated as well: docs/duration_rows.md)
+            duration = self.predict_duration(cond, text, speed, **({} if lens is None else dict(lens=lens)), **iso_kw)
         max_duration_cap = int(max_duration)
         text, lens, duration, max_duration = prepare_lengths(text, cond_seq_len, batch, duration, lens, max_duration, method)
         self.last_durations = [int(d) for d in duration.tolist()]     # extension: frames per element after the clamps (cfm.py:317-318)

@@ -30,6 +30,7 @@ struct DWorkspace {
     size_t lens, text, mel;  // staged caller inputs (outside the captured part)
     size_t mask, te, ids, keep, t_nxt, tg, scratch, x, cos_t, sin_t, pred;
     size_t tln[2], tg2[2], a0[2], xb[2], c1[2], h[2], qk[2], vt[2], ao[2], ffh[2];
+    size_t rowlen = 0;       // row lengths L[b] = max(lens[b], text_lens[b]) of f5_predict_duration_rows, staged like lens; behind the plain plan
 };
 
 struct f5_duration : WeightStore {
@@ -40,7 +41,7 @@ struct f5_duration : WeightStore {
     MatBF proj, conv_w[2];
     size_t conv_b[2];
     std::vector<DBlock> blocks;
-    GraphCache graphs;       // at most 8; keyed by (B, n_in, nt).  The caller keeps one workspace per shape: nothing is purged
+    GraphCache graphs;       // at most 8; keyed by (B, n_in, nt, row-isolated).  The caller keeps one workspace per shape: nothing is purged
 };
 
 extern "C" int f5_duration_create(const f5_duration_config* cfg, int precision, f5_duration** out) {
@@ -227,7 +228,7 @@ static int dshape_ok(const f5_duration* d, int B, int n_in, int nt) {
     return 0;
 }
 
-static DWorkspace dplan(const f5_duration* d, int B, int n_in, int nt) {
+static DWorkspace dplan(const f5_duration* d, int B, int n_in, int nt, bool isolated = false) {
     const f5_duration_config& c = d->cfg;
     const int N = n_in > nt ? n_in : nt, npad = (N + 63) / 64 * 64;
     const size_t rows = (size_t)B * N, D = c.dim, Dt = c.text_dim, TF = 2 * Dt, K0 = 128 + Dt;
@@ -261,6 +262,7 @@ static DWorkspace dplan(const f5_duration* d, int B, int n_in, int nt) {
         w.ao[p] = on ? b.take(rows * D * 2) : 0;
         w.ffh[p] = on ? b.take(rows * c.ff_dim * 2) : 0;
     }
+    if (isolated) w.rowlen = b.take((size_t)B * 4);      // the one buffer the row-isolated call adds: everything above is the plain plan
     w.total = b.off;
     return w;
 }
@@ -272,8 +274,19 @@ extern "C" int f5_duration_workspace_bytes(f5_duration* d, int B, int n_in, int 
     return 0;
 }
 
-// the launch sequence of DurationPredictor._run_ops (f5_tts_mlx_amd/duration.py), everything on the workspace and the arena
-static int duration_body(const f5_duration* d, const DWorkspace& w, char* ws, int B, int N, int nt, hipStream_t s) {
+// the plan of f5_duration_workspace_bytes plus the staged row lengths of f5_predict_duration_rows ([B] int32 behind it)
+extern "C" int f5_duration_workspace_bytes_rows(f5_duration* d, int B, int n_in, int nt, size_t* bytes) {
+    F5_REQUIRE(d && bytes, "null argument");
+    RC(dshape_ok(d, B, n_in, nt));
+    *bytes = dplan(d, B, n_in, nt, true).total;
+    return 0;
+}
+
+// the launch sequence of DurationPredictor._run_ops (f5_tts_mlx_amd/duration.py), everything on the workspace and the arena.
+// rowlen (dev [B], or null = the plain call): the row-isolated mode (docs/duration_rows.md).  Row b reads nothing from its own positions
+// n >= rowlen[b]: the text blocks' depthwise conv and GRN, both conv-pos launches and every attention launch take the lengths; the
+// launches in between work row by row, and the head's mean stays over n < lens[b].  What positions n >= rowlen[b] hold is never read.
+static int duration_body(const f5_duration* d, const DWorkspace& w, char* ws, int B, int N, int nt, const int* rowlen, hipStream_t s) {
     const f5_duration_config& c = d->cfg;
     const Ops& K = d->ops;
     const int D = c.dim, Dt = c.text_dim, TF = 2 * c.text_dim, FF = c.ff_dim, H = c.heads, K0 = 128 + c.text_dim;
@@ -294,13 +307,20 @@ static int duration_body(const f5_duration* d, const DWorkspace& w, char* ws, in
     float* t_nxt = L.p<float>(w.t_nxt);
     float* scratch = L.p<float>(w.scratch);
     for (const DTextBlock& k : d->tblocks) {
-        RC(K.dwconv_ln(t_cur, L.a<float>(k.dw_w), L.a<float>(k.dw_b), L.a<float>(k.ln_w), L.a<float>(k.ln_b), L.pb(w.tln, 0), L.pb(w.tln, 1), B, N, Dt, 1e-6f, s));
+        if (rowlen)
+            RC(K.dwconv_ln_ragged(t_cur, L.a<float>(k.dw_w), L.a<float>(k.dw_b), L.a<float>(k.ln_w), L.a<float>(k.ln_b), L.pb(w.tln, 0), L.pb(w.tln, 1), B, N, Dt, 1e-6f, rowlen, s));
+        else
+            RC(K.dwconv_ln(t_cur, L.a<float>(k.dw_w), L.a<float>(k.dw_b), L.a<float>(k.ln_w), L.a<float>(k.ln_b), L.pb(w.tln, 0), L.pb(w.tln, 1), B, N, Dt, 1e-6f, s));
         F5GemmArgs g1 = L.gemm(L.pb(w.tln, 0), L.pb(w.tln, 1), Dt, k.pw1, rows, TF, Dt, L.a<float>(k.b1));
         g1.out_f32 = L.p<float>(w.tg);
         g1.ldo = TF;
         g1.ldob = TF;
         RC(K.gemm(g1, EPI_GELU_ERF, s));
-        RC(K.grn(L.p<float>(w.tg), L.a<float>(k.gamma), L.a<float>(k.beta), scratch, scratch + f5_grn_partial_floats(B, N, TF), L.pb(w.tg2, 0), L.pb(w.tg2, 1), B, N, TF, s));
+        float* nx = scratch + f5_grn_partial_floats(B, N, TF);
+        if (rowlen)
+            RC(K.grn_ragged(L.p<float>(w.tg), L.a<float>(k.gamma), L.a<float>(k.beta), scratch, nx, L.pb(w.tg2, 0), L.pb(w.tg2, 1), B, N, TF, rowlen, s));
+        else
+            RC(K.grn(L.p<float>(w.tg), L.a<float>(k.gamma), L.a<float>(k.beta), scratch, nx, L.pb(w.tg2, 0), L.pb(w.tg2, 1), B, N, TF, s));
         F5GemmArgs g2 = L.gemm(L.pb(w.tg2, 0), L.pb(w.tg2, 1), TF, k.pw2, rows, Dt, TF, L.a<float>(k.b2));
         g2.resid = t_cur;
         g2.ldres = Dt;
@@ -342,6 +362,7 @@ static int duration_body(const f5_duration* d, const DWorkspace& w, char* ws, in
         cp.out_bf[0] = j == 0 ? L.pb(w.c1, 0) : nullptr;
         cp.out_bf[1] = j == 0 ? L.pb(w.c1, 1) : nullptr;
         cp.out_f32 = j == 0 ? nullptr : L.p<float>(w.x);
+        cp.lens = rowlen;                             // null = the instantiations without row lengths
         RC(K.convpos(cp, s));
     }
 
@@ -370,6 +391,7 @@ static int duration_body(const f5_duration* d, const DWorkspace& w, char* ws, in
         at.hp = d->np == 2;
         at.scale = 0.125f;
         at.pipe = -1;
+        at.kv_len = rowlen;                           // null = every key
         RC(K.attention(at, s));
         F5GemmArgs go = L.gemm(L.pb(w.ao, 0), L.pb(w.ao, 1), D, k.o, rows, D, D, L.a<float>(k.bo));
         go.gate = L.a<float>(d->ones);
@@ -395,10 +417,9 @@ static int duration_body(const f5_duration* d, const DWorkspace& w, char* ws, in
     return 0;
 }
 
-// Replaces `self._duration_predictor(cond, text)` and the frame arithmetic of F5TTS.predict_duration (cfm.py:253-262).
-extern "C" int f5_predict_duration(f5_duration* d, const f5_duration_args* a, void* stream) {
-    F5_REQUIRE(d && a, "f5_predict_duration: null argument");
-    F5_REQUIRE(a->mel && a->text && a->seconds && a->workspace, "f5_predict_duration: null mel / text / seconds / workspace");
+// One prediction.  rowlen == null: f5_predict_duration; else host [B] row lengths of f5_predict_duration_rows (already checked).
+static int predict(f5_duration* d, const f5_duration_args* a, const uint32_t* rowlen, const char* fn, void* stream) {
+    F5_REQUIRE(a->mel && a->text && a->seconds && a->workspace, "%s: null mel / text / seconds / workspace", fn);
     F5_REQUIRE(d->finalized, "duration predictor weights are not finalized");
     const int B = a->B, n_in = a->n_in, nt = a->nt;
     RC(dshape_ok(d, B, n_in, nt));
@@ -406,17 +427,18 @@ extern "C" int f5_predict_duration(f5_duration* d, const f5_duration_args* a, vo
     F5_REQUIRE(((uintptr_t)a->workspace & 255) == 0, "duration predictor workspace must be 256-byte aligned");
     F5_REQUIRE((((uintptr_t)a->mel | (uintptr_t)a->text | (uintptr_t)a->seconds | (uintptr_t)a->frames) & 3) == 0,
                "duration predictor: mel / text / seconds / frames must be 4-byte aligned");
-    const DWorkspace w = dplan(d, B, n_in, nt);
+    const DWorkspace w = dplan(d, B, n_in, nt, rowlen != nullptr);
     F5_REQUIRE(a->workspace_bytes >= w.total, "duration predictor workspace too small: %zu < %zu", a->workspace_bytes, w.total);
     const int N = n_in > nt ? n_in : nt, mel = d->cfg.mel_dim;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)a->workspace;
     void* workspace = a->workspace;
     // caller buffers are staged outside the graph: the captured nodes only reference the workspace and the arena, so a replay serves
-    // new mel / text / lens of the same shape
+    // new mel / text / lens (and row lengths) of the same shape
     std::vector<uint32_t> lens((size_t)B);
-    for (int b = 0; b < B; ++b) lens[b] = (uint32_t)(a->lens ? a->lens[b] : N);
+    for (int b = 0; b < B; ++b) lens[b] = (uint32_t)(a->lens ? a->lens[b] : (rowlen ? n_in : N));
     RC(f5_launch_stage_words(lens.data(), lens.size(), reinterpret_cast<uint32_t*>(ws + w.lens), s));
+    if (rowlen) RC(f5_launch_stage_words(rowlen, (size_t)B, reinterpret_cast<uint32_t*>(ws + w.rowlen), s));
     RC(f5_launch_copy_words(a->text, ws + w.text, (size_t)B * nt, s));
     if (n_in == N) {
         RC(f5_launch_copy_words(a->mel, ws + w.mel, (size_t)B * N * mel, s));
@@ -427,19 +449,45 @@ extern "C" int f5_predict_duration(f5_duration* d, const f5_duration_args* a, vo
         for (int b = 0; b < B; ++b)
             RC(f5_launch_copy_words(a->mel + (size_t)b * n_in * mel, ws + w.mel + (size_t)b * N * mel * 4, (size_t)n_in * mel, s));
     }
+    const int* rowlen_dev = rowlen ? reinterpret_cast<const int*>(ws + w.rowlen) : nullptr;
     if (a->use_graph) {
         char key[64];
-        snprintf(key, sizeof(key), "B%d n%d nt%d", B, n_in, nt);
+        snprintf(key, sizeof(key), "B%d n%d nt%d%s", B, n_in, nt, rowlen ? " rows" : "");
         GraphCache::Entry* g = d->graphs.find(key, workspace);
-        if (!g) RC(d->graphs.capture(key, workspace, s, 1, [&](int) { return duration_body(d, w, ws, B, N, nt, s); }, &g));
+        if (!g) RC(d->graphs.capture(key, workspace, s, 1, [&](int) { return duration_body(d, w, ws, B, N, nt, rowlen_dev, s); }, &g));
         RC(GraphCache::launch(g, s));
     } else {
-        RC(duration_body(d, w, ws, B, N, nt, s));
+        RC(duration_body(d, w, ws, B, N, nt, rowlen_dev, s));
     }
     // frame_rate / speed are by-value scalars: they stay outside the graph, like the copies to the caller
     if (a->frames) RC(d->ops.seconds_to_frames(reinterpret_cast<const float*>(ws + w.pred), a->frames, B, a->frame_rate, a->speed, s));
     RC(f5_launch_copy_words(ws + w.pred, a->seconds, (size_t)B, s));
     return 0;
+}
+
+// Replaces `self._duration_predictor(cond, text)` and the frame arithmetic of F5TTS.predict_duration (cfm.py:253-262).
+extern "C" int f5_predict_duration(f5_duration* d, const f5_duration_args* a, void* stream) {
+    F5_REQUIRE(d && a, "f5_predict_duration: null argument");
+    return predict(d, a, nullptr, "f5_predict_duration", stream);
+}
+
+// The row-isolated prediction of a padded batch (docs/duration_rows.md): row b runs at its own length L[b] = max(lens[b], text_lens[b]),
+// the N a call of that row alone would run at (duration.py:218-220), and reads nothing from its positions n >= L[b].  text_lens: host
+// [B], one past the row's last text id >= 0.  lens == NULL: every lens[b] = n_in.  Everything is checked before the first launch.
+extern "C" int f5_predict_duration_rows(f5_duration* d, const f5_duration_args* a, const int32_t* text_lens, void* stream) {
+    F5_REQUIRE(d && a && text_lens, "f5_predict_duration_rows: null argument");
+    const int B = a->B, n_in = a->n_in, nt = a->nt;
+    RC(dshape_ok(d, B, n_in, nt));
+    std::vector<uint32_t> rowlen((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        const int tl = text_lens[b], ln = a->lens ? a->lens[b] : n_in;
+        F5_REQUIRE(tl >= 0 && tl <= nt, "duration predictor: row %d: text_lens = %d is outside [0, nt = %d]", b, tl, nt);
+        F5_REQUIRE(ln >= 1 && ln <= n_in, "duration predictor: row %d: lens = %d is outside [1, n_in = %d]", b, ln, n_in);
+        const int len = ln > tl ? ln : tl;
+        F5_REQUIRE(len >= 4, "duration predictor: row %d: its length max(lens, text_lens) = %d is below 4 (a call of the row alone needs N >= 4)", b, len);
+        rowlen[b] = (uint32_t)len;
+    }
+    return predict(d, a, rowlen.data(), "f5_predict_duration_rows", stream);
 }
 
 // Status word of the last f5_predict_duration on the workspace of `a` (its first 32-bit word): F5_STATUS_SATURATED = a producer of a

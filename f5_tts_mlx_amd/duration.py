@@ -89,6 +89,29 @@ NATIVE_DEFAULT = False      # DurationPredictor.native: the measurement behind i
 MAX_WORKSPACES = 8          # workspaces kept per predictor, one per (B, n_in, nt): what the handle keeps graphs for
 
 
+def row_lengths(text, n_in: int, lens=None):
+    """The lengths of the rows of a padded call in the row-isolated mode (docs/duration_rows.md), from HOST data: text (b, nt) int, -1
+    padded; lens (b,) mel frames per row, None = every row has n_in -> three lists (lens, tokens, L).  tokens[b] is one past the row's
+    last text id >= 0 and L[b] = max(lens[b], tokens[b]) the N a call of that row alone would run at (duration.py:218-220).  ValueError
+    for what `f5_predict_duration_rows` refuses: lens[b] outside [1, n_in], L[b] < 4."""
+    ids = np.asarray(torch.as_tensor(text).cpu())
+    if ids.ndim != 2:
+        raise ValueError(f"text must be (b, nt), got shape {ids.shape}")
+    B, nt = ids.shape
+    lens = [int(n_in)] * B if lens is None else [int(v) for v in torch.as_tensor(lens).reshape(-1).tolist()]
+    if len(lens) != B:
+        raise ValueError(f"lens: expected {B} values, got {len(lens)}")
+    tokens = [int(nt - np.argmax(row[::-1] >= 0)) if (row >= 0).any() else 0 for row in ids]
+    rows = [max(a, b) for a, b in zip(lens, tokens)]
+    for b in range(B):
+        if not 1 <= lens[b] <= n_in:
+            raise ValueError(f"duration predictor: row {b}: lens = {lens[b]} is outside [1, n_in = {n_in}]")
+        if rows[b] < 4:
+            raise ValueError(f"duration predictor: row {b}: its length max(lens, text_lens) = {rows[b]} is below 4 (a call of the row "
+                             "alone needs N >= 4)")
+    return lens, tokens, rows
+
+
 def _split(x: torch.Tensor, two: bool, dtype: torch.dtype = torch.bfloat16):
     """fp32 -> 16-bit MFMA operand (bf16, or fp16 saturated at +-65504 like the device producers) + optional residual."""
     hi = (x.clamp(-65504.0, 65504.0) if dtype == torch.float16 else x).to(dtype)
@@ -232,10 +255,16 @@ class DurationPredictor:
         self.transformer.load_weights(dict(weights))
 
     def __call__(self, inp: torch.Tensor, text, *, lens: Optional[torch.Tensor] = None, return_loss=False, native: Optional[bool] = None,
-                 use_graph: bool = True) -> torch.Tensor:
+                 use_graph: bool = True, isolate_rows: bool = False) -> torch.Tensor:
         """seconds (b,) fp32.  native=True: one `f5_predict_duration` call (hipGraph replay when use_graph); native=False: the
-        Python-sequenced launches of `_run_ops`; None: this instance's `native` attribute (NATIVE_DEFAULT unless set)."""
+        Python-sequenced launches of `_run_ops`; None: this instance's `native` attribute (NATIVE_DEFAULT unless set).
+        isolate_rows (docs/duration_rows.md; False: the call as it was): True = row b of a padded batch runs at its own length
+        L[b] = max(lens[b], its token count) and reads nothing from its positions n >= L[b], so its seconds do not depend on its
+        batch-mates; lens=None is then every row's n_in frames.  ValueError before any launch for a value that is not a bool, a lens[b]
+        outside [1, n_in] and a row shorter than 4."""
         native = self.native if native is None else native
+        if isolate_rows is not False:
+            E.check_isolate_rows(isolate_rows, self.transformer.precision)
         if return_loss:
             raise NotImplementedError("training loss (duration.py:229-260) is out of scope")
         T = self.transformer
@@ -253,7 +282,12 @@ class DurationPredictor:
             assert text.shape[0] == batch
         text = torch.as_tensor(text).to(torch.int32)
         if native:
-            return self.predict_native(inp, text, lens=lens, frame_rate=None, use_graph=use_graph)[0]
+            iso = dict(isolate_rows=True) if isolate_rows else {}
+            return self.predict_native(inp, text, lens=lens, frame_rate=None, use_graph=use_graph, **iso)[0]
+        rowlen_d = None
+        if isolate_rows:                                    # from the host copy of text, before anything is launched or uploaded
+            lens, _, rows = row_lengths(text, seq_len, lens)
+            rowlen_d = torch.tensor(rows, dtype=torch.int32).to(dev)
         if seq_len < text.shape[1]:                         # duration.py:218-220
             pad = torch.zeros((batch, text.shape[1] - seq_len, inp.shape[2]), device=dev)
             inp = torch.cat([inp, pad], dim=1)              # plumbing: zero padding of the input buffer
@@ -266,15 +300,16 @@ class DurationPredictor:
         text_d = text.contiguous().to(dev)
 
         with E.operand_type(T.precision):                  # the f5_op_* entry points take this model's operand type
-            return self._run_ops(lib, dev, ns, W, T, inp, text, text_d, mask_d, batch, seq_len)
+            return self._run_ops(lib, dev, ns, W, T, inp, text, text_d, mask_d, batch, seq_len, rowlen_d)
 
-    def _workspace(self, B: int, n_in: int, nt: int) -> torch.Tensor:
-        key = (B, n_in, nt)
+    def _workspace(self, B: int, n_in: int, nt: int, rows: bool = False) -> torch.Tensor:
+        key = (B, n_in, nt, True) if rows else (B, n_in, nt)
         ws = self._workspaces.pop(key, None)
         if ws is None:
             T = self.transformer
             nbytes = C.c_size_t()
-            E.check(T.lib.f5_duration_workspace_bytes(T._h, B, n_in, nt, C.byref(nbytes)), "f5_duration_workspace_bytes")
+            fn = "f5_duration_workspace_bytes_rows" if rows else "f5_duration_workspace_bytes"
+            E.check(getattr(T.lib, fn)(T._h, B, n_in, nt, C.byref(nbytes)), fn)
             while len(self._workspaces) >= MAX_WORKSPACES:                  # least recently used first (dict order)
                 self._workspaces.pop(next(iter(self._workspaces)))
             ws = E._aligned_bytes(nbytes.value, T.device)
@@ -283,19 +318,24 @@ class DurationPredictor:
 
     def predict_native(self, mel: torch.Tensor, text: torch.Tensor, *, lens: Optional[torch.Tensor] = None,
                        frame_rate: Optional[float] = 93.0, speed: float = 1.0, use_graph: bool = True,
-                       workspace: Optional[torch.Tensor] = None):
+                       workspace: Optional[torch.Tensor] = None, isolate_rows: bool = False):
         """One `f5_predict_duration` call: mel (b, n_in, mel_dim) fp32, text (b, nt) int32 (-1 padded), lens host (b,) or None
         -> (seconds (b,) fp32, frames (b,) int32 = (int32)(seconds * frame_rate / speed), or None when frame_rate is None).
-        Sets `last_status`."""
+        Sets `last_status`.  isolate_rows=True: one `f5_predict_duration_rows` call (docs/duration_rows.md) on a workspace of
+        `f5_duration_workspace_bytes_rows`; the token counts are taken from the host copy of `text`."""
         T = self.transformer
         if not T._h.value:
             raise RuntimeError("duration predictor weights not loaded")
         lib, dev = T.lib, T.device
+        c_tokens = None
+        if isolate_rows is not False and E.check_isolate_rows(isolate_rows, T.precision):
+            lens, tokens, _ = row_lengths(text, mel.shape[1], lens)
+            c_tokens = (C.c_int32 * len(tokens))(*tokens)
         mel = mel.to(dev, torch.float32).contiguous()
         text = text.to(dev, torch.int32).contiguous()
         B, n_in, nt = mel.shape[0], mel.shape[1], text.shape[1]
         assert mel.shape[2] == T.mel_dim and text.shape[0] == B
-        ws = self._workspace(B, n_in, nt) if workspace is None else workspace
+        ws = self._workspace(B, n_in, nt, c_tokens is not None) if workspace is None else workspace
         c_lens = None
         if exists(lens):
             host = torch.as_tensor(lens).to("cpu", torch.int64).tolist()
@@ -316,7 +356,10 @@ class DurationPredictor:
         flags = C.c_int(0)
         with torch.cuda.device(dev), torch.cuda.stream(run):
             sp = C.c_void_p(run.cuda_stream)
-            E.check(lib.f5_predict_duration(T._h, C.byref(args), sp), "f5_predict_duration")
+            if c_tokens is None:
+                E.check(lib.f5_predict_duration(T._h, C.byref(args), sp), "f5_predict_duration")
+            else:
+                E.check(lib.f5_predict_duration_rows(T._h, C.byref(args), c_tokens, sp), "f5_predict_duration_rows")
             if T.precision == "f16":                        # the other operand types have fp32's range: nothing can set the word
                 E.check(lib.f5_duration_status(T._h, C.byref(args), C.byref(flags), sp), "f5_duration_status")
         if run is not cur:
@@ -332,7 +375,8 @@ class DurationPredictor:
                           stacklevel=2)
         return seconds, frames
 
-    def _run_ops(self, lib, dev, ns, W, T, inp, text, text_d, mask_d, batch, seq_len):
+    def _run_ops(self, lib, dev, ns, W, T, inp, text, text_d, mask_d, batch, seq_len, rowlen_d=None):
+        """rowlen_d (dev int32 (b,), None = the plain call): the row-isolated mode, the `f5_op_*_ragged` twins and attention's kv_len."""
         B, N, D, Dt, H = batch, seq_len, T.dim, T.text_dim, T.heads
         rows, npad = B * N, (N + 63) // 64 * 64
         P, st = E.ptr, E.stream_ptr(dev)
@@ -353,10 +397,17 @@ class DurationPredictor:
         tg2, tg2l = bf(rows, 2 * Dt), lo(bf(rows, 2 * Dt))
         scratch = torch.empty(lib.f5_op_grn_scratch_floats(B, N, 2 * Dt), device=dev)
         for blk in W["tblocks"]:
-            ck(lib.f5_op_dwconv_ln(P(t_cur), P(blk["dw_w"]), P(blk["dw_b"]), P(blk["ln_w"]), P(blk["ln_b"]), P(tln), P(tlnl), B, N, Dt, st))
+            if rowlen_d is None:
+                ck(lib.f5_op_dwconv_ln(P(t_cur), P(blk["dw_w"]), P(blk["dw_b"]), P(blk["ln_w"]), P(blk["ln_b"]), P(tln), P(tlnl), B, N, Dt, st))
+            else:
+                ck(lib.f5_op_dwconv_ln_ragged(P(t_cur), P(blk["dw_w"]), P(blk["dw_b"]), P(blk["ln_w"]), P(blk["ln_b"]), P(tln), P(tlnl), B, N, Dt,
+                                              P(rowlen_d), st))
             ck(lib.f5_op_gemm(P(tln), P(tlnl), P(blk["pw1"][0]), P(blk["pw1"][1]), P(blk["b1"]), P(tg), P(None), P(None), rows,
                               2 * Dt, Dt, Dt, Dt, 2 * Dt, ns, 3, st))
-            ck(lib.f5_op_grn(P(tg), P(blk["gamma"]), P(blk["beta"]), P(scratch), P(tg2), P(tg2l), B, N, 2 * Dt, st))
+            if rowlen_d is None:
+                ck(lib.f5_op_grn(P(tg), P(blk["gamma"]), P(blk["beta"]), P(scratch), P(tg2), P(tg2l), B, N, 2 * Dt, st))
+            else:
+                ck(lib.f5_op_grn_ragged(P(tg), P(blk["gamma"]), P(blk["beta"]), P(scratch), P(tg2), P(tg2l), B, N, 2 * Dt, P(rowlen_d), st))
             ck(lib.f5_op_gemm_resid_keep(P(tg2), P(tg2l), P(blk["pw2"][0]), P(blk["pw2"][1]), P(blk["b2"]), P(t_cur), P(None),
                                          P(t_nxt), rows, Dt, 2 * Dt, 2 * Dt, 2 * Dt, Dt, ns, st))
             t_cur, t_nxt = t_nxt, t_cur
@@ -372,8 +423,14 @@ class DurationPredictor:
         xb, xbl, c1, c1l = bf(rows, D), lo(bf(rows, D)), bf(rows, D), lo(bf(rows, D))
         ck(lib.f5_op_pack_bf16(P(x), P(None), P(xb), P(xbl), rows, D, D, 0, st))
         (cw0, cb0), (cw1, cb1) = W["conv"]
-        ck(lib.f5_op_convpos(P(xb), P(xbl), P(cw0[0]), P(cw0[1]), P(cb0), P(c1), P(c1l), P(None), B, N, D, D // 64, 31, ns, 0, st))
-        ck(lib.f5_op_convpos(P(c1), P(c1l), P(cw1[0]), P(cw1[1]), P(cb1), P(None), P(None), P(x), B, N, D, D // 64, 31, ns, 1, st))
+        if rowlen_d is None:
+            ck(lib.f5_op_convpos(P(xb), P(xbl), P(cw0[0]), P(cw0[1]), P(cb0), P(c1), P(c1l), P(None), B, N, D, D // 64, 31, ns, 0, st))
+            ck(lib.f5_op_convpos(P(c1), P(c1l), P(cw1[0]), P(cw1[1]), P(cb1), P(None), P(None), P(x), B, N, D, D // 64, 31, ns, 1, st))
+        else:
+            ck(lib.f5_op_convpos_ragged(P(xb), P(xbl), P(cw0[0]), P(cw0[1]), P(cb0), P(c1), P(c1l), P(None), B, N, D, D // 64, 31, ns, 0,
+                                        P(rowlen_d), st))
+            ck(lib.f5_op_convpos_ragged(P(c1), P(c1l), P(cw1[0]), P(cw1[1]), P(cb1), P(None), P(None), P(x), B, N, D, D // 64, 31, ns, 1,
+                                        P(rowlen_d), st))
 
         # ---- pre-LN transformer blocks without modulation / gates / masks (duration.py:64-94)
         cos_t, sin_t = torch.empty((N, 32), device=dev), torch.empty((N, 32), device=dev)
@@ -387,7 +444,7 @@ class DurationPredictor:
             ck(lib.f5_op_ln_modulate(P(x), P(W["zeros"]), P(W["zeros"]), P(h), P(hl), rows, D, st))
             ck(lib.f5_op_qkv_rope(P(h), P(hl), P(blk["qkv"][0]), P(blk["qkv"][1]), P(blk["bqkv"]), P(cos_t), P(sin_t), P(qk), P(qkl),
                                   P(vt), P(vtl), B, N, npad, H, D, ns, st))
-            ck(lib.f5_op_attention(P(qk), P(qkl), P(vt), P(vtl), P(ao), P(aol), P(None), B, H, N, npad, D, C.c_float(0.125), int(two), st))
+            ck(lib.f5_op_attention(P(qk), P(qkl), P(vt), P(vtl), P(ao), P(aol), P(rowlen_d), B, H, N, npad, D, C.c_float(0.125), int(two), st))
             ck(lib.f5_op_gemm_resid_gate(P(ao), P(aol), P(blk["o"][0]), P(blk["o"][1]), P(blk["bo"]), P(W["ones"]), P(None), P(x), rows,
                                          D, D, D, D, D, ns, st))
             ck(lib.f5_op_ln_modulate(P(x), P(W["zeros"]), P(W["zeros"]), P(h), P(hl), rows, D, st))

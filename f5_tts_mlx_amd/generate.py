@@ -468,8 +468,9 @@ def generate_many(
     isolate_rows (docs/isolate_rows.md; False: the call as it was, sample() gets no new keyword): True = a row of the batch reads nothing
     from its own padding, so a request's audio no longer depends on which requests share the call: every row lands within the parity
     gate of its solo sample() for the durations it was given.  One value for the call and NOT a key of a controls entry: it is an engine
-    option, part of the hipGraph key, and one graph serves each value.  (Durations from the duration predictor are predicted on the padded
-    batch and are not covered, see the doc.)
+    option, part of the hipGraph key, and one graph serves each value.  Durations from the duration predictor are covered: sample()
+    then asks for the row-isolated prediction, in which a request's frame count does not depend on its batch-mates either
+    (docs/duration_rows.md).
 
     It equals prepare_references -> sample(mel, text, durations, lens=frames) -> the decode -> the same slices, bit for bit; it does
     NOT equal a loop of generate() calls bit for bit (the batch has a key-padding mask, the gain is fp64 arithmetic on fp32 block sums

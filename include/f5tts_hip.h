@@ -795,7 +795,7 @@ typedef struct f5_duration_args {
     int32_t* frames;           /* dev  [B] or NULL: (int32)(seconds * frame_rate / speed), an fp32 product, an fp32 division, truncation */
     void* workspace;           /* dev, f5_duration_workspace_bytes, 256-byte aligned                         */
     size_t workspace_bytes;
-    int32_t use_graph;         /* != 0: the launch sequence is captured per (B, n_in, nt, workspace) and replayed, <= 8 graphs kept (LRU) */
+    int32_t use_graph;         /* != 0: the launch sequence is captured per (B, n_in, nt, workspace) -- and per entry point, f5_predict_duration / _rows -- and replayed, <= 8 graphs kept (LRU) */
 } f5_duration_args;
 /* mel / text / lens are staged into the workspace and seconds / frames copied out by kernels OUTSIDE the captured part: a replay
  * serves new inputs of the same shape.  The handle carries its own operand type: the process-wide one (f5_op_set_operand_type) is
@@ -807,6 +807,21 @@ int f5_predict_duration(f5_duration* d, const f5_duration_args* args, void* stre
  * Synchronises `stream`.  No reference counterpart. */
 int f5_duration_status(f5_duration* d, const f5_duration_args* args, int* flags, void* stream);
 int f5_duration_graph_count(f5_duration* d);
+/* Row-isolated prediction of a padded batch (docs/duration_rows.md; no reference counterpart).  f5_predict_duration runs every row at
+ * N = max(n_in, nt): the text blocks' depthwise conv and GRN, both conv-pos layers and the attention (which has no key mask) read a
+ * row's padding, so a row's seconds depend on its batch-mates.  Here row b has the length L[b] = max(lens[b], text_lens[b]) -- the N a
+ * call of that row alone would run at (duration.py:218-220) -- and reads nothing from its own positions n >= L[b]: the depthwise conv
+ * leaves those taps out, the GRN norms over L[b] positions, both conv-pos launches read them as zero, every attention launch gets
+ * kv_len = L, and the head's mean stays over n < lens[b].  Values are selected by the index test, never multiplied by a mask: mel
+ * frames n >= lens[b] may be NaN.  Filler text positions text_lens[b] <= n < L[b] belong to the row, as in a call of the row alone.
+ * text_lens: host [B], one past the row's last text id >= 0.  args->lens == NULL: every lens[b] = n_in.  The lengths are staged next
+ * to lens outside the captured part (a replay serves new lengths of the same shape); the graph is keyed apart from
+ * f5_predict_duration's, which keeps its key, its launches and its bits; the status word is the same word.  Workspace:
+ * f5_duration_workspace_bytes_rows (the plan of f5_duration_workspace_bytes plus [B] int32 behind it).  Refused before any launch,
+ * naming the row: text_lens[b] outside [0, nt], lens[b] outside [1, n_in], L[b] < 4 (a call of that row alone is refused for N < 4),
+ * a workspace below f5_duration_workspace_bytes_rows, and everything f5_predict_duration refuses. */
+int f5_duration_workspace_bytes_rows(f5_duration* d, int B, int n_in, int nt, size_t* bytes);
+int f5_predict_duration_rows(f5_duration* d, const f5_duration_args* args, const int32_t* text_lens /* host [B] */, void* stream);
 
 #ifdef __cplusplus
 }
