@@ -67,7 +67,8 @@ enum F5ConvPosKernel {
     F5CP_HP1,        // f5_convpos_kernel<true,1>
     F5CP_HP2,        // f5_convpos_kernel<true,2>
     F5CP_RING,       // f5_convpos_ring_kernel
-    F5CP_XCD = 16
+    F5CP_XCD = 16,
+    F5CP_N48 = 32    // the 48-channels-per-group instantiation of f5_convpos_kernel<., .>: ",48" inside the name's brackets
 };
 namespace f5dbg {
 extern int last_convpos_kernel;

@@ -27,8 +27,14 @@ namespace F5_NS {
 // workgroups share a CU (tools/convpos_bench.py); what did help at batch 1 is the block numbering below (25.5 -> 19.8 us).
 // LENS: the launch carries row lengths (F5ConvPosArgs::lens).  Without them the instantiation is the kernel as it was, instruction for
 // instruction: the batch-1 launches are one round of workgroups and pay for every scalar load in front of their first request.
-template <bool HP, int TPS, bool LENS>
+// CPG: channels per group, 64 or 48.  A 48-channel group sits in a 64-wide tile of its own: the halo tile holds columns g*48 .. g*48+47
+// and zeros in the other 16 (never loaded), the weight slabs come zero padded to [64 co][tap][64 ci] from the weight store
+// (host_common.hpp f5_pack_conv_groups), the K steps stop at 48 input channels and the epilogue writes 48 columns.  Of the 6 MFMAs per
+// tap and wave a quarter multiply the zero rows co = 48..63: the price of a 32-wide MFMA on a 48-wide group.  Every CPG test below is a
+// constant: 64 instantiates the kernel as it was.
+template <bool HP, int TPS, bool LENS, int CPG>
 __global__ __launch_bounds__(256) void f5_convpos_kernel(F5ConvPosArgs p) {
+    static_assert(CPG == 64 || CPG == 48, "channels per group: 64, or 48 in a zero-padded 64-wide tile");
     constexpr int NP = HP ? 2 : 1;
     constexpr int HALO = CP_ROWS + CP_MAXTAPS - 1;
     __shared__ __attribute__((aligned(16))) op16_t sX[NP][HALO * XLD];
@@ -73,11 +79,11 @@ __global__ __launch_bounds__(256) void f5_convpos_kernel(F5ConvPosArgs p) {
     for (int qd = tid; qd < halo * 8; qd += 256) {
         const int r = qd >> 3, c = qd & 7;
         const int n = n0 - pad + r;
-        const bool ok = (n >= 0) && (n < len_b);
+        const bool ok = (n >= 0) && (n < len_b) && (CPG == 64 || c < CPG / 8);
 #pragma unroll
         for (int pp = 0; pp < NP; ++pp) {
             u32x4 v = {0u, 0u, 0u, 0u};
-            if (ok) v = *reinterpret_cast<const u32x4*>(p.in[pp] + (rowbase + n) * p.ld + g * 64 + c * 8);
+            if (ok) v = *reinterpret_cast<const u32x4*>(p.in[pp] + (rowbase + n) * p.ld + g * CPG + c * 8);
             *reinterpret_cast<u32x4*>(&sX[pp][r * XLD + c * 8]) = v;
         }
     }
@@ -132,7 +138,9 @@ __global__ __launch_bounds__(256) void f5_convpos_kernel(F5ConvPosArgs p) {
             for (int r = 0; r < 16; ++r) {
                 int n = n0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
                 if (n > p.seq_len - 1) n = p.seq_len - 1;
-                old[nb][r] = p.out_f32[(rowbase + n) * p.ldo + g * 64 + nb * 32 + lr];
+                // (a 48-channel group: the lanes of columns 48..63 load column 47, and never use it)
+                if (CPG == 64) old[nb][r] = p.out_f32[(rowbase + n) * p.ldo + g * 64 + nb * 32 + lr];
+                else old[nb][r] = p.out_f32[(rowbase + n) * p.ldo + g * CPG + min(nb * 32 + lr, CPG - 1)];
             }
     }
 
@@ -144,7 +152,7 @@ __global__ __launch_bounds__(256) void f5_convpos_kernel(F5ConvPosArgs p) {
             const int t = t0 + tt;
             if (!(CP_ABL & 2) && t < taps) {
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
+                for (int ks = 0; ks < CPG / 16; ++ks) {
                     const int aoff = (wave * 32 + lr + t) * XLD + ks * 16 + hi * 8;
                     const op16x8 a = *reinterpret_cast<const op16x8*>(&sX[0][aoff]);
                     op16x8 al = a;
@@ -171,17 +179,17 @@ __global__ __launch_bounds__(256) void f5_convpos_kernel(F5ConvPosArgs p) {
     // the two bias values are requested together and waited for ONCE, outside the per-row conditionals: with the load inside the
     // nb loop the compiler put its `s_waitcnt vmcnt(0)` for it into every conditional row block, where it also waits for all the
     // stores issued so far -- the stores of a lane went out one memory round trip apart
-    float bias2[2] = {p.bias[g * 64 + lr], p.bias[g * 64 + 32 + lr]};
+    float bias2[2] = {p.bias[g * CPG + lr], p.bias[CPG == 64 ? g * 64 + 32 + lr : g * CPG + min(32 + lr, CPG - 1)]};
     asm volatile("" : "+v"(bias2[0]), "+v"(bias2[1]));
     f5_sat_t trk;
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
-        const int co = g * 64 + nb * 32 + lr;
+        const int co = g * CPG + nb * 32 + lr;
         const float bias = bias2[nb];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int n = n0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            if (n < len_b) {
+            if (n < len_b && (CPG == 64 || nb * 32 + lr < CPG)) {     // a 48-channel group: columns 48..63 of the tile belong to no channel
                 const float v = f5_mish(acc[nb][r] + bias);
                 const size_t off = (rowbase + n) * p.ldo + co;
                 if ((CP_ABL & 8) && p.taps > 0) {
@@ -454,36 +462,52 @@ int f5_convpos_xcd_map = 1;   // 0: plain 3-D block numbering (A/B)
 //   of one round.  Below 512 tokens or beyond one round several workgroups share a CU, and f5_convpos_kernel<false,1>'s 36 KB of LDS
 //   lets 3-4 of them hide each other's round trips (batch 32: 304 us), which the ring kernel's 84 KB does not.
 //   selector 8 forces it for every single-segment launch; with three segments 8 acts like 2 and 4: f5_convpos_kernel<true,2>.
-int f5_convpos_route(int B, int seq_len, int groups, int nseg) {
+// Narrow groups (cpg = 32 or 48 channels per group) never take the ring kernel, which is built for 64-channel groups only: selector 8
+// acts like 1 there.  `groups` is the launch's own count: at 32 channels the grid runs groups / 2 super groups (f5_launch_convpos).
+int f5_convpos_route(int B, int seq_len, int groups, int nseg, int cpg) {
+    if (cpg == 32) groups /= 2;
+    const bool narrow = cpg != 64;
     const long nwg = (long)f5_cdiv(seq_len, CP_ROWS) * groups * B;
     const bool xcd = groups % 8 == 0 && f5_convpos_xcd_map;
     const int tps = f5_convpos_tps;
     int k;
     if (nseg == 3) k = tps > 1 ? F5CP_HP2 : F5CP_HP1;
-    else if (tps == 8 || (tps == 0 && xcd && seq_len >= 512 && nwg <= CP_RING_MAX_WG)) k = F5CP_RING;
-    else if (tps >= 4) k = F5CP_4;
+    else if (!narrow && (tps == 8 || (tps == 0 && xcd && seq_len >= 512 && nwg <= CP_RING_MAX_WG))) k = F5CP_RING;
+    else if (tps >= 4 && tps != 8) k = F5CP_4;
+    else if (tps == 8) k = F5CP_1;
     else if (tps >= 2) k = F5CP_2;
     else k = F5CP_1;       // measured (tools/convpos_bench.py): 1 tap per step beats 2 and 4 at every size (batch 32: 304 / 355 / 629 us)
-    return k | (xcd ? F5CP_XCD : 0);
+    return k | (xcd ? F5CP_XCD : 0) | (cpg == 48 ? F5CP_N48 : 0);
 }
 
 int f5_launch_convpos(const F5ConvPosArgs& a, hipStream_t stream) {
     f5dbg::last_convpos_kernel = F5CP_NONE;                // a launch that is refused, or fails, reports no kernel
     F5_REQUIRE(a.B > 0 && a.seq_len > 0 && a.groups > 0, "convpos: bad shape");
-    F5_REQUIRE(a.C == a.groups * 64, "convpos: channels per group must be 64 (C=%d groups=%d)", a.C, a.groups);
+    // channels per group: 64; 48 (own instantiation); 32 as block-diagonal 64-wide super groups of two (the weights come packed that way
+    // from the weight store, so the launch is the 64-channel one on half the groups)
+    const int cpg = a.C % a.groups == 0 ? a.C / a.groups : 0;
+    F5_REQUIRE(cpg == 64 || cpg == 48 || (cpg == 32 && a.groups % 2 == 0),
+               "convpos: channels per group must be 32 (an even number of groups), 48 or 64 (C=%d groups=%d)", a.C, a.groups);
+    const int groups = cpg == 32 ? a.groups / 2 : a.groups;
     F5_REQUIRE(a.taps >= 1 && a.taps <= CP_MAXTAPS && (a.taps & 1), "convpos: taps must be odd and <= %d", CP_MAXTAPS);
     F5_REQUIRE(a.ld % 8 == 0, "convpos: ld must be a multiple of 8");
-    dim3 grid(f5_cdiv(a.seq_len, CP_ROWS), a.groups, a.B);
+    dim3 grid(f5_cdiv(a.seq_len, CP_ROWS), groups, a.B);
     const long nwg = (long)grid.x * grid.y * grid.z;
-    const int reached = f5_convpos_route(a.B, a.seq_len, a.groups, a.nseg);
+    const int reached = f5_convpos_route(a.B, a.seq_len, a.groups, a.nseg, cpg);
     if (reached & F5CP_XCD) grid = dim3((unsigned)nwg, 1, 1);   // group-per-XCD numbering (see the kernel)
     F5ConvPosArgs ab = a;
+    ab.groups = groups;
     if (ab.sat_flag == nullptr) ab.sat_flag = f5_sat_flag_host;
     // every kernel in two instantiations: with row lengths (a.lens) and as it was
+#define CP_LAUNCH_W(HP_, TPS_, CPG_)                                                                                      \
+    {                                                                                                                     \
+        if (ab.lens) hipLaunchKernelGGL((f5_convpos_kernel<HP_, TPS_, true, CPG_>), grid, dim3(256), 0, stream, ab);      \
+        else hipLaunchKernelGGL((f5_convpos_kernel<HP_, TPS_, false, CPG_>), grid, dim3(256), 0, stream, ab);             \
+    }
 #define CP_LAUNCH(HP_, TPS_)                                                                                              \
     {                                                                                                                     \
-        if (ab.lens) hipLaunchKernelGGL((f5_convpos_kernel<HP_, TPS_, true>), grid, dim3(256), 0, stream, ab);            \
-        else hipLaunchKernelGGL((f5_convpos_kernel<HP_, TPS_, false>), grid, dim3(256), 0, stream, ab);                   \
+        if (cpg == 48) CP_LAUNCH_W(HP_, TPS_, 48)                                                                         \
+        else CP_LAUNCH_W(HP_, TPS_, 64)                                                                                   \
     }
     switch (reached & (F5CP_XCD - 1)) {
     case F5CP_HP1:
@@ -501,6 +525,7 @@ int f5_launch_convpos(const F5ConvPosArgs& a, hipStream_t stream) {
     default: CP_LAUNCH(false, 1) break;
     }
 #undef CP_LAUNCH
+#undef CP_LAUNCH_W
     F5_LAUNCH_CHECK();
     f5dbg::last_convpos_kernel = reached;
     return 0;

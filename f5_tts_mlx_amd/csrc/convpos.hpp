@@ -18,7 +18,8 @@ namespace F5_NS {
 
 struct F5ConvPosArgs {
     const op16_t* in[2];  // hi, lo: [B*seq_len][ld] channels-last
-    const op16_t* W[2];   // hi, lo: [C][taps*64]  (reference layout (out, k, in/groups) flattened)
+    const op16_t* W[2];   // hi, lo: [C][taps*64]  (reference layout (out, k, in/groups) flattened).  Narrow groups come packed by
+                          // f5_pack_conv_groups (host_common.hpp): 32 channels per group [C][taps*64] block diagonal, 48 [groups*64][taps*64]
     const float* bias;    // [C]
     int B, seq_len, C, groups, taps, ld;
     int nseg;             // 1 bf16, 3 bf16x3
@@ -34,6 +35,7 @@ struct F5ConvPosArgs {
 
 int f5_launch_convpos(const F5ConvPosArgs& a, hipStream_t stream);
 // the kernel f5_launch_convpos runs for this shape under the current selectors: an F5ConvPosKernel, plus F5CP_XCD (host only)
-int f5_convpos_route(int B, int seq_len, int groups, int nseg);
+// (cpg = channels per group of the launch: 32, 48 or 64)
+int f5_convpos_route(int B, int seq_len, int groups, int nseg, int cpg = 64);
 }  // namespace F5_NS
 #endif

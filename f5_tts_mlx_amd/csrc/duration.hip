@@ -109,13 +109,12 @@ extern "C" int f5_duration_create(const f5_duration_config* cfg, int precision, 
     d->add_mat(p + "input_embed.proj.weight", d->proj, 0, D, M + Dt, M, M + Dt, 128, {D, M + Dt});
     d->add_f32(p + "input_embed.proj.bias", d->bproj, {D});
     // conv position embedding: the kernel works on 64-channel groups; 32-channel groups are loaded as block-diagonal 64-wide super
-    // groups (f5_duration_load_tensor)
+    // groups (host_common.hpp f5_pack_conv_groups, on the way into the weight store)
     const int kc = c.conv_pos_kernel, gin = D / c.conv_pos_groups;
     for (int j = 0; j < 2; ++j) {
-        d->conv_w[j] = alloc_mat(b, D, kc * 64, np);
-        d->conv_b[j] = b.take((size_t)D * 4);
         const std::string q = p + "input_embed.conv_pos_embed.conv1d.layers." + std::to_string(j * 2) + ".";
-        d->add_mat(q + "weight", d->conv_w[j], 0, D, kc * 64, 0, kc * 64, 0, {D, kc, gin});
+        d->conv_w[j] = d->add_conv_groups(b, q + "weight", D, kc, gin);
+        d->conv_b[j] = b.take((size_t)D * 4);
         d->add_f32(q + "bias", d->conv_b[j], {D});
     }
     d->blocks.resize(c.depth);
@@ -181,22 +180,7 @@ extern "C" int f5_duration_load_tensor(f5_duration* d, const char* name, const f
     RC(d->lookup(key, name, &dsts));
     RC(d->match(name, *dsts, ndim, shape, &count));
     F5_REQUIRE(d->arena, "f5_duration_set_weights_arena must be called first");
-    const int D = d->cfg.dim, kc = d->cfg.conv_pos_kernel;
-    for (TensorDst& t : *dsts) {
-        if (t.kind == 1 && t.shape.size() == 3 && t.shape[2] == 32) {
-            // conv-pos weight (dim, k, 32): output channel o reads the 32 input channels of ITS group; two groups share one 64-channel
-            // super group of the kernel, so o's taps go to the half of the 64 columns that holds its group, the other half stays zero
-            std::vector<float> m((size_t)D * kc * 64, 0.0f);
-            for (int o = 0; o < D; ++o) {
-                const int off = ((o / 32) % 2) * 32;
-                for (int k = 0; k < kc; ++k)
-                    memcpy(&m[((size_t)o * kc + k) * 64 + off], host + ((size_t)o * kc + k) * 32, 32 * sizeof(float));
-            }
-            RC(d->upload(t, m.data(), m.size()));
-        } else {
-            RC(d->upload(t, host, count));
-        }
-    }
+    for (TensorDst& t : *dsts) RC(d->upload(t, host, count));      // (conv-pos weights of 32-channel groups are packed on the way in)
     return 0;
 }
 

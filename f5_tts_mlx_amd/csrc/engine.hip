@@ -210,28 +210,29 @@ static int build_arena_plan(f5_engine* e) {
     e->add_mat(p + "input_embed.proj.weight", e->wct, 0, D, IN, 2 * M, IN, 128, {D, IN});
     e->add_f32(p + "input_embed.proj.bias", e->bproj, {D});
     const int kc = c.conv_pos_kernel, gin = D / c.conv_pos_groups;
-    for (int j = 0; j < 2; ++j) {
-        e->conv_w[j] = alloc_mat(b, D, kc * gin, np);
-        e->conv_b[j] = b.take((size_t)D * 4);
+    for (int j = 0; j < 2; ++j) {      // 64 channels per group: the tensor as it is; 32 and 48 in the packed form of f5_pack_conv_groups
         const std::string q = p + "input_embed.conv_pos_embed.conv1d.layers." + std::to_string(j * 2) + ".";
-        e->add_mat(q + "weight", e->conv_w[j], 0, D, kc * gin, 0, kc * gin, 0, {D, kc, gin});
+        e->conv_w[j] = e->add_conv_groups(b, q + "weight", D, kc, gin);
+        e->conv_b[j] = b.take((size_t)D * 4);
         e->add_f32(q + "bias", e->conv_b[j], {D});
     }
+    // attention inner width I = heads * dim_head (dit.py:117-125: dim -> I -> dim); q | k | v rows of the fused projection are I apart
+    const int I = c.heads * c.dim_head;
     e->blocks.resize(L);
     for (int i = 0; i < L; ++i) {
         BlockW& w = e->blocks[i];
         const std::string q = p + "transformer_blocks." + std::to_string(i) + ".";
-        w.qkv = alloc_mat(b, 3 * D, D, np);
-        w.o = alloc_mat(b, D, D, np);
+        w.qkv = alloc_mat(b, 3 * I, D, np);
+        w.o = alloc_mat(b, D, I, np);
         w.ff1 = alloc_mat(b, FF, D, np);
         w.ff2 = alloc_mat(b, D, FF, np);
         if (e->prec == F5_PREC_MXFP8) {
-            w.qkv8 = alloc_f8(b, 3 * D, D);
-            w.o8 = alloc_f8(b, D, D);
+            w.qkv8 = alloc_f8(b, 3 * I, D);
+            w.o8 = alloc_f8(b, D, I);
             w.ff1_8 = alloc_f8(b, FF, D);
             w.ff2_8 = alloc_f8(b, D, FF);
         }
-        w.bqkv = b.take((size_t)3 * D * 4);
+        w.bqkv = b.take((size_t)3 * I * 4);
         w.bo = b.take((size_t)D * 4);
         w.bff1 = b.take((size_t)FF * 4);
         w.bff2 = b.take((size_t)D * 4);
@@ -239,10 +240,10 @@ static int build_arena_plan(f5_engine* e) {
         e->add_f32(q + "attn_norm.linear.bias", e->ada_b + (size_t)i * 6 * D * 4, {6 * D});
         const char* nm[3] = {"to_q", "to_k", "to_v"};
         for (int k = 0; k < 3; ++k) {
-            e->add_mat(q + "attn." + nm[k] + ".weight", w.qkv, k * D, D, D, 0, D, 0, {D, D});
-            e->add_f32(q + "attn." + nm[k] + ".bias", w.bqkv + (size_t)k * D * 4, {D});
+            e->add_mat(q + "attn." + nm[k] + ".weight", w.qkv, k * I, I, D, 0, D, 0, {I, D});
+            e->add_f32(q + "attn." + nm[k] + ".bias", w.bqkv + (size_t)k * I * 4, {I});
         }
-        e->add_mat(q + "attn.to_out.layers.0.weight", w.o, 0, D, D, 0, D, 0, {D, D});
+        e->add_mat(q + "attn.to_out.layers.0.weight", w.o, 0, D, I, 0, I, 0, {D, I});
         e->add_f32(q + "attn.to_out.layers.0.bias", w.bo, {D});
         e->add_mat(q + "ff.ff.layers.0.layers.0.weight", w.ff1, 0, FF, D, 0, D, 0, {FF, D});
         e->add_f32(q + "ff.ff.layers.0.layers.0.bias", w.bff1, {FF});
@@ -277,11 +278,22 @@ extern "C" int f5_engine_create(const f5_config* cfg, int precision, f5_engine**
                "unknown precision %d", precision);
     F5_REQUIRE(precision != F5_PREC_MXFP8 || (cfg->ff_dim % 256 == 0 && cfg->dim % 256 == 0), "mxfp8 needs dim and ff_dim to be multiples of 256");
     F5_REQUIRE(c.dim_head == 64, "dim_head must be 64 (got %d)", c.dim_head);
-    F5_REQUIRE(c.heads * c.dim_head == c.dim, "heads * dim_head must equal dim (%d * %d != %d)", c.heads, c.dim_head, c.dim);
+    // the accepted family (docs/geometries.md): the attention inner width need not be the model width, conv-pos groups may be 32, 48 or
+    // 64 channels wide, the text width is a multiple of 128
+    const int inner = c.heads * c.dim_head;
+    F5_REQUIRE(c.heads >= 1 && inner % 256 == 0, "heads * dim_head must be a multiple of 256 (got %d * %d = %d)", c.heads, c.dim_head, inner);
+    F5_REQUIRE(inner <= 1024, "heads * dim_head must be <= 1024 (got %d * %d = %d)", c.heads, c.dim_head, inner);
+    const int cpg = c.conv_pos_groups >= 1 && c.dim % c.conv_pos_groups == 0 ? c.dim / c.conv_pos_groups : 0;
+    F5_REQUIRE(cpg == 64 || cpg == 48 || (cpg == 32 && c.conv_pos_groups % 2 == 0),
+               "dim / conv_pos_groups must be 32, 48 or 64 channels per group (got %d / %d)", c.dim, c.conv_pos_groups);
     F5_REQUIRE(c.dim % 256 == 0 && c.dim <= 1024, "dim must be a multiple of 256 and <= 1024 (got %d)", c.dim);
-    F5_REQUIRE(c.dim / c.conv_pos_groups == 64, "dim / conv_pos_groups must be 64");
     F5_REQUIRE(c.conv_pos_kernel % 2 == 1 && c.conv_pos_kernel <= 31, "conv_pos_kernel must be odd and <= 31");
-    F5_REQUIRE(c.text_dim % 256 == 0 && c.text_dim <= 1024, "text_dim must be a multiple of 256 and <= 1024 (got %d)", c.text_dim);
+    F5_REQUIRE(c.text_dim >= 128 && c.text_dim % 128 == 0 && c.text_dim <= 1024, "text_dim must be a multiple of 128 and <= 1024 (got %d)", c.text_dim);
+    // the MX-fp8 blocks are built and measured for the original family only
+    F5_REQUIRE(precision != F5_PREC_MXFP8 || (inner == c.dim && cpg == 64 && c.text_dim % 256 == 0),
+               "mxfp8 needs heads * dim_head == dim, 64-channel conv-pos groups and text_dim %% 256 == 0 (got inner %d, dim %d, %d channels per "
+               "group, text_dim %d): run this geometry in f16, bf16 or bf16x3",
+               inner, c.dim, cpg, c.text_dim);
     F5_REQUIRE(c.ff_dim % 128 == 0 && c.text_ff_dim % 128 == 0, "ff dims must be multiples of 128");
     F5_REQUIRE(c.mel_dim >= 1 && c.mel_dim <= 128, "mel_dim must be in [1,128]");
     F5_REQUIRE(c.freq_embed_dim % 256 == 0 && c.freq_embed_dim <= 1024, "freq_embed_dim must be a multiple of 256");
@@ -476,6 +488,7 @@ struct Route {
 static Workspace plan_workspace(const f5_engine* e, int B, int N, int nt, int steps, int method, Route route) {
     const f5_config& c = e->cfg;
     const int D = c.dim, Dt = c.text_dim, FF = c.ff_dim, TF = c.text_ff_dim, L = c.depth, np = e->np, mel = c.mel_dim, nbr = route.nbr();
+    const int I = c.heads * c.dim_head;      // attention inner width: q, k, V^T and the attention output are I wide
     const size_t M1 = (size_t)B * N, M2 = 2 * M1, MB = (size_t)nbr * M1;
     const int nfe = (steps - 1) * nfe_per_step(method);
     const int npad = (N + 63) / 64 * 64;
@@ -528,9 +541,11 @@ static Workspace plan_workspace(const f5_engine* e, int B, int N, int nt, int st
         w.xb[p] = p < np ? b.take(MB * D * 2) : 0;
         w.c1[p] = p < np ? b.take(MB * D * 2) : 0;
         w.h[p] = p < np ? b.take(MB * D * 2) : 0;
-        w.qk[p] = p < np ? b.take(MB * 2 * D * 2) : 0;
+        // q | k also parks the fp32 result of the two gated projections on the per-row route (resid_ln, LN_ROWS): M D floats, more than
+        // the 2 I 16-bit values per row when I < D
+        w.qk[p] = p < np ? b.take(MB * (size_t)2 * (p == 0 && I < D ? D : I) * 2) : 0;
         w.vt[p] = p < np ? b.take(w.vt_bytes) : 0;
-        w.ao[p] = p < np ? b.take(MB * D * 2) : 0;
+        w.ao[p] = p < np ? b.take(MB * I * 2) : 0;
         w.ffh[p] = p < np ? b.take(MB * FF * 2) : 0;
     }
     // LN fold buffers only where the fold can run (a superset of the LN plan's fold: that one also knows the branch count of the call):
@@ -673,8 +688,11 @@ static LnPlan ln_fold_state(const Ctx& c) {
     q.epi = EPI_RESID_GATE;
     if (e->prec != F5_PREC_MXFP8 && e->opt.fuse_ln && c.w.lncnt_words != 0 && f5_gemm_resid_ln_fusable(q, D)) p.mode = LN_TAIL;
     if (e->opt.ln_fold == 0) return p;
+    // (the fold's constants and statistics are laid out for heads * dim_head == dim, and it was measured on the original family only:
+    // 64-channel conv-pos groups, text_dim % 256 == 0 -- docs/geometries.md)
+    const bool base_family = cf.heads * cf.dim_head == D && D / cf.conv_pos_groups == 64 && cf.text_dim % 256 == 0;
     bool ok = e->np == 1 && e->prec != F5_PREC_MXFP8 && e->opt.qkv_tr && !e->opt.fuse_ln && D % 256 == 0 && D <= 2048 && FF % 256 == 0 &&
-              (e->opt.gemm_flags & 16384) == 0 && cf.depth >= 1;
+              (e->opt.gemm_flags & 16384) == 0 && cf.depth >= 1 && base_family;
     bool small = ok && D == 1024 && e->opt.fold_stats != 0 && (e->opt.gemm_flags & (8 | 256)) == 0;   // the single-round kernels: statistics form only
     if (ok) {
         q.g4 = true;             // (e->opt.qkv_tr and nseg == 1 are part of `ok`)
@@ -689,7 +707,7 @@ static LnPlan ln_fold_state(const Ctx& c) {
     if (e->opt.ln_fold < 0 && !(M >= LN_FOLD_AUTO_ROWS && ok) && !(small && LN_FOLD_SMALL_AUTO)) return p;
     if (!ok && !small)
         p.refused = "ln_fold = 1: this shape / precision cannot run the folded LN (needs f16 or bf16, qkv_transposed, no ln_fusion, dim %% 256 "
-                    "== 0, and all four block GEMMs on the 256x256 / role-split 128x256 kernels -- batch >= 4 at the 335M shape -- or on the "
+                    "== 0, heads * dim_head == dim, 64-channel conv-pos groups, text_dim %% 256 == 0, and all four block GEMMs on the 256x256 / role-split 128x256 kernels -- batch >= 4 at the 335M shape -- or on the "
                     "single-round kernels of the batch-1-sized route: width 1024, fold_stats != 0)";
     p.fold_state = ok ? 1 : (small ? 2 : 0);
     // statistics form: always on the batch-1-sized route (state 2: its kernels have no other), by option on the staged kernels (measured
@@ -875,14 +893,14 @@ static int dit_input(const Ctx& c) {
 static void dit_qkv_fields(const Ctx& c, F5GemmArgs& g) {
     const Workspace& w = c.w;
     f5_qkv_rope_fields(g, c.pb(w.qk, 0), c.pb(w.qk, 1), c.pb(w.vt, 0), c.pb(w.vt, 1), c.p<float>(w.rope_cos), c.p<float>(w.rope_sin), c.N, c.npad,
-                       c.e->cfg.heads, c.e->cfg.dim, q_premul_factor(c.e));
+                       c.e->cfg.heads, c.e->cfg.heads * c.e->cfg.dim_head, q_premul_factor(c.e));      // "dmodel" = width of the q and k sections
 }
 static F5AttnArgs dit_attn_args(const Ctx& c, op16_t* out_hi, op16_t* out_lo) {
     const f5_config& cf = c.e->cfg;
     const Workspace& w = c.w;
     return f5_attn_args(c.pb(w.qk, 0), c.pb(w.qk, 1), c.pb(w.vt, 0), c.pb(w.vt, 1), out_hi, out_lo, c.use_mask ? c.p<int>(w.dur2) : nullptr,
-                        c.nb * c.B, cf.heads, c.N, c.npad, cf.dim, 1.0f / sqrtf((float)cf.dim_head), c.e->np == 2, 2 * cf.dim, cf.dim,
-                        q_premul_factor(c.e) != 0.0f, c.e->opt.attn_pipe);
+                        c.nb * c.B, cf.heads, c.N, c.npad, cf.heads * cf.dim_head, 1.0f / sqrtf((float)cf.dim_head), c.e->np == 2,
+                        2 * cf.heads * cf.dim_head, cf.heads * cf.dim_head, q_premul_factor(c.e) != 0.0f, c.e->opt.attn_pipe);
 }
 
 // MX-fp8 block: the four GEMMs run on e4m3 operands with E8M0 block scales (v_mfma_scale_f32_32x32x64_f8f6f4); their A
@@ -1000,6 +1018,7 @@ static int dit_block(const Ctx& c, DitEval& ev, int i) {
     const f5_engine* e = c.e;
     const Workspace& w = c.w;
     const int D = e->cfg.dim, FF = e->cfg.ff_dim, L = e->cfg.depth, M = c.nb * c.B * c.N;
+    const int I = e->cfg.heads * e->cfg.dim_head;      // attention inner width (dit.py:117-125)
     hipStream_t s = c.s;
     const Ops& K = c.ops;
     const BlockW& bw = e->blocks[i];
@@ -1011,7 +1030,7 @@ static int dit_block(const Ctx& c, DitEval& ev, int i) {
         else
             RC(K.ln_modulate(c.p<float>(w.x), m6 + D, m6, c.pb(w.h, 0), c.pb(w.h, 1), M, D, 1e-6f, s, c.ln.fold() ? c.p<float>(w.lnmean) : nullptr));
     }
-    F5GemmArgs gq = gemm_base(c, c.pb(w.h, 0), c.pb(w.h, 1), D, bw.qkv, M, 3 * D, D, c.a<float>(bw.bqkv));
+    F5GemmArgs gq = gemm_base(c, c.pb(w.h, 0), c.pb(w.h, 1), D, bw.qkv, M, 3 * I, D, c.a<float>(bw.bqkv));
     if (c.ln.fold() && i > 0) fold_consumer(c, ev, gq, i, 0);
     dit_qkv_fields(c, gq);
     if (e->opt.qkv_tr) {                             // pair-major tables (the q pair carries qpre, or 1): used by the 256x256 kernel
@@ -1021,7 +1040,7 @@ static int dit_block(const Ctx& c, DitEval& ev, int i) {
     RC(K.gemm(gq, EPI_QKV_ROPE, s));
     RC(K.attention(dit_attn_args(c, c.pb(w.ao, 0), c.pb(w.ao, 1)), s));
 
-    F5GemmArgs go = gemm_base(c, c.pb(w.ao, 0), c.pb(w.ao, 1), D, bw.o, M, D, D, c.a<float>(bw.bo));
+    F5GemmArgs go = gemm_base(c, c.pb(w.ao, 0), c.pb(w.ao, 1), I, bw.o, M, D, I, c.a<float>(bw.bo));
     RC(resid_ln(c, ev, go, m6 + 2 * D, c.use_mask ? c.p<uint8_t>(w.rowkeep) : nullptr, m6 + 4 * D, m6 + 3 * D, false));
     F5GemmArgs g1 = gemm_base(c, c.pb(w.h, 0), c.pb(w.h, 1), D, bw.ff1, M, FF, D, c.a<float>(bw.bff1));
     if (c.ln.fold()) fold_consumer(c, ev, g1, i, 3 * D);
@@ -1714,6 +1733,7 @@ static std::string convpos_kernel_name(int word) {
                                         "f5_convpos_kernel<true,1>", "f5_convpos_kernel<true,2>", "f5_convpos_ring_kernel"};
     const int k = word & (F5CP_XCD - 1);
     std::string s = k <= F5CP_RING ? names[k] : "";
+    if (k != F5CP_NONE && k != F5CP_RING && (word & F5CP_N48)) s.insert(s.size() - 1, ",48");     // f5_convpos_kernel<false,1,48>
     if (k != F5CP_NONE && (word & F5CP_XCD)) s += "+xcd";
     return s;
 }
@@ -1723,8 +1743,13 @@ extern "C" int f5_debug_last_convpos_kernel(char* buf, int n) { return copy_name
 // The name a conv-pos launch of this shape would report under the current selectors, without launching anything or touching a device
 // (f5_convpos_route is the launcher's own decision; the selectors are the same in both operand builds)
 extern "C" int f5_debug_convpos_route(int B, int seq_len, int groups, int nseg, char* buf, int n) {
+    return f5_debug_convpos_route_groups(B, seq_len, groups, 64, nseg, buf, n);
+}
+// the same for `groups` groups of cpg = 32, 48 or 64 channels (narrow groups never reach the ring kernel)
+extern "C" int f5_debug_convpos_route_groups(int B, int seq_len, int groups, int cpg, int nseg, char* buf, int n) {
     F5_REQUIRE(B > 0 && seq_len > 0 && groups > 0 && (nseg == 1 || nseg == 3), "convpos route: bad shape");
-    copy_name(convpos_kernel_name(f5bf::f5_convpos_route(B, seq_len, groups, nseg)), buf, n);
+    F5_REQUIRE(cpg == 64 || cpg == 48 || (cpg == 32 && groups % 2 == 0), "convpos route: channels per group must be 32, 48 or 64");
+    copy_name(convpos_kernel_name(f5bf::f5_convpos_route(B, seq_len, groups, nseg, cpg)), buf, n);
     return 0;
 }
 // The route (gemm_route.hpp) a GEMM launch of this shape would take under the current knobs and process-wide flags, without launching
@@ -1921,6 +1946,17 @@ extern "C" int f5_op_qkv_rope(const void* a_hi, const void* a_lo, const void* w_
     return g_ops.gemm(g, EPI_QKV_ROPE, (hipStream_t)stream);
 }
 
+// f5_op_qkv_rope for an attention inner width that is not the model width: a [B seq_len][K], w [3 inner][K], q | k [.][2 inner]
+// (inner = heads * 64; docs/geometries.md).  The hooks f5_op_qkv_rope reads apply but for the LN fold, which is laid out for K == inner.
+extern "C" int f5_op_qkv_rope_k(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias,
+                                const float* rope_cos, const float* rope_sin, void* qk_hi, void* qk_lo, void* vt_hi, void* vt_lo,
+                                int B, int seq_len, int npad, int heads, int inner, int K, int nseg, void* stream) {
+    F5GemmArgs g = f5_gemm_args(a_hi, a_lo, w_hi, w_lo, K, K, B * seq_len, 3 * inner, K, nseg, bias);
+    f5_qkv_rope_fields(g, qk_hi, qk_lo, vt_hi, vt_lo, rope_cos, rope_sin, seq_len, npad, heads, inner, nseg == 1 ? g_op_q_premul : 0.0f,
+                       g_op_rope_t[0], g_op_rope_t[1]);
+    return g_ops.gemm(g, EPI_QKV_ROPE, (hipStream_t)stream);
+}
+
 extern "C" int f5_op_rope_table_g4(float* tq, float* tk, int seq_len, int dim_head, float qscale, void* stream) {
     return f5_launch_rope_table_g4(tq, tk, seq_len, dim_head, qscale, (hipStream_t)stream);
 }
@@ -1982,6 +2018,20 @@ extern "C" int f5_op_convpos_ragged(const void* in_hi, const void* in_lo, const 
     cp.out_f32 = out_f32;
     cp.lens = lens_dev;
     return g_ops.convpos(cp, (hipStream_t)stream);
+}
+
+// The weight store's packing of a conv-pos weight (C, taps, cpg), cpg = 32, 48 or 64, on the host (host_common.hpp f5_pack_conv_groups):
+// out = [f5_op_conv_packed_rows(C, cpg)][taps * 64] floats, the matrix f5_op_convpos reads once rounded to the operand type.  No device.
+extern "C" int f5_op_conv_packed_rows(int C, int cpg) {
+    return (C > 0 && (cpg == 64 || cpg == 48 || cpg == 32) && C % cpg == 0) ? f5_conv_packed_rows(C, cpg) : -1;
+}
+extern "C" int f5_op_pack_conv_groups(const float* w, int C, int taps, int cpg, float* out) {
+    F5_REQUIRE(w && out && taps >= 1, "pack_conv_groups: null argument / no taps");
+    F5_REQUIRE(f5_op_conv_packed_rows(C, cpg) > 0, "pack_conv_groups: channels per group must be 32, 48 or 64 and divide C (C=%d cpg=%d)", C, cpg);
+    std::vector<float> m;
+    f5_pack_conv_groups(w, C, taps, cpg, m);
+    memcpy(out, m.data(), m.size() * sizeof(float));
+    return 0;
 }
 
 extern "C" size_t f5_op_grn_scratch_floats(int nbatch, int seq_len, int dim) {

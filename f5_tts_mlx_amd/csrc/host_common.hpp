@@ -303,7 +303,25 @@ struct TensorDst {      // where (part of) a reference tensor goes
     int c0 = 0, c1 = 0, dst_c0 = 0;  // source column range -> destination column offset
     std::vector<int64_t> shape;
     bool loaded = false;
+    int conv_cpg = 0;   // != 0: a conv-pos weight (C, taps, conv_cpg), placed as f5_pack_conv_groups leaves it
 };
+
+// Conv-pos weights (C, taps, cpg) in the reference's layout -> the matrix f5_launch_convpos reads, 64 input columns per tap:
+//   cpg 64: [C][taps * 64], the tensor as it is;
+//   cpg 32: [C][taps * 64], two groups share one block-diagonal 64-wide super group: output channel o keeps its 32 input channels in the
+//           half of the 64 columns that holds its group, the other half is zero;
+//   cpg 48: [C / 48 * 64][taps * 64], a group in a 64-row tile of its own: rows g * 64 + 0..47 hold the group's output channels with
+//           their 48 input channels in columns 0..47, everything else is zero.
+static inline int f5_conv_packed_rows(int C, int cpg) { return cpg == 48 ? C / 48 * 64 : C; }
+static inline void f5_pack_conv_groups(const float* w, int C, int taps, int cpg, std::vector<float>& m) {
+    m.assign((size_t)f5_conv_packed_rows(C, cpg) * taps * 64, 0.0f);
+    for (int o = 0; o < C; ++o) {
+        const int row = cpg == 48 ? o / 48 * 64 + o % 48 : o;
+        const int off = cpg == 32 ? ((o / 32) % 2) * 32 : 0;
+        for (int k = 0; k < taps; ++k)
+            memcpy(&m[((size_t)row * taps + k) * 64 + off], w + ((size_t)o * taps + k) * cpg, (size_t)cpg * sizeof(float));
+    }
+}
 
 static inline MatBF alloc_mat(Bump& b, int rows, int ld, int np) {
     MatBF m;
@@ -377,6 +395,14 @@ struct WeightStore {
         tmap[name].push_back(d);
     }
     void add_mat(const std::string& name, const MatBF& m, int rows, int cols) { add_mat(name, m, 0, rows, cols, 0, cols, 0, {rows, cols}); }
+    // a conv-pos weight (C, taps, cpg), cpg = 32, 48 or 64: the matrix is allocated here, in the packed form of f5_pack_conv_groups
+    MatBF add_conv_groups(Bump& b, const std::string& name, int C, int taps, int cpg) {
+        const int rows = f5_conv_packed_rows(C, cpg);
+        const MatBF m = alloc_mat(b, rows, taps * 64, np);
+        add_mat(name, m, 0, rows, taps * 64, 0, taps * 64, 0, {C, taps, cpg});
+        tmap[name].back().conv_cpg = cpg;
+        return m;
+    }
 
     int set_arena(void* dev_arena, size_t bytes, hipStream_t s) {
         F5_REQUIRE(bytes >= arena_need, "%sweights arena too small: %zu < %zu", label, bytes, arena_need);
@@ -407,6 +433,13 @@ struct WeightStore {
         return 0;
     }
     int upload(TensorDst& d, const float* host, size_t count) {
+        if (d.conv_cpg != 0 && d.conv_cpg != 64) {        // narrow conv-pos groups: packed on the way in
+            std::vector<float> m;
+            f5_pack_conv_groups(host, (int)d.shape[0], (int)d.shape[1], d.conv_cpg, m);
+            RC(f5_upload_tensor(arena, d, m.data(), m.size(), np, f16));
+            d.loaded = true;
+            return 0;
+        }
         RC(f5_upload_tensor(arena, d, host, count, np, f16));
         d.loaded = true;
         return 0;

@@ -289,11 +289,100 @@ __global__ __launch_bounds__(256) void dwconv_ln_kernel(const float* __restrict_
     f5_sat_commit(trk, sat_flag);
 }
 
+// The widths that are no multiple of 256 (128, 384, 640, 896: text_dim = 128 k): the same row on a 128-column granule, one wave per
+// token, lane owns NG float2 chunks (dim = NG * 128).  RAGGED: with row lengths, as dwconv_ln_ragged_kernel below (taps beyond
+// lens[b] are skipped, a token n >= lens[b] writes zeros).  The multiples of 256 keep the float4 kernels.
+template <int NG, bool RAGGED>
+__global__ __launch_bounds__(256) void dwconv_ln_g128_kernel(const float* __restrict__ x, const float* __restrict__ dw_w,
+                                                             const float* __restrict__ dw_b, const float* __restrict__ ln_w,
+                                                             const float* __restrict__ ln_b, op16_t* __restrict__ out_hi,
+                                                             op16_t* __restrict__ out_lo, int rows, int seq_len, float eps,
+                                                             const int* __restrict__ lens, int* sat_flag) {
+    constexpr int DIM = NG * 128;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int b = row / seq_len, n = row - b * seq_len;
+    const int len = RAGGED ? min(max(lens[b], 0), seq_len) : seq_len;
+    if (RAGGED && n >= len) {
+#pragma unroll
+        for (int i = 0; i < NG; ++i) {
+            const int c = i * 128 + lane * 2;
+            *reinterpret_cast<uint32_t*>(out_hi + (size_t)row * DIM + c) = 0u;
+            if (out_lo) *reinterpret_cast<uint32_t*>(out_lo + (size_t)row * DIM + c) = 0u;
+        }
+        return;
+    }
+    f5_sat_t trk;
+    float y[NG][2];
+    float sum = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+        const int c = i * 128 + lane * 2;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) y[i][e] = dw_b[c + e];
+#pragma unroll
+        for (int t = 0; t < 7; ++t) {
+            const int nn = n + t - 3;
+            if (nn >= 0 && nn < len) {
+                const f5_f32x2 xv = *reinterpret_cast<const f5_f32x2*>(x + ((size_t)b * seq_len + nn) * DIM + c);
+#pragma unroll
+                for (int e = 0; e < 2; ++e) y[i][e] += xv[e] * dw_w[(c + e) * 7 + t];
+            }
+        }
+        sum += y[i][0] + y[i][1];
+    }
+    const float mean = f5_wave_sum(sum) * (1.0f / DIM);
+    float sq = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NG; ++i)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const float d = y[i][e] - mean;
+            sq += d * d;
+        }
+    const float rstd = rsqrtf(f5_wave_sum(sq) * (1.0f / DIM) + eps);
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+        const int c = i * 128 + lane * 2;
+        float z[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) z[e] = (y[i][e] - mean) * rstd * ln_w[c + e] + ln_b[c + e];
+        *reinterpret_cast<uint32_t*>(out_hi + (size_t)row * DIM + c) = f5_pack2(z[0], z[1], trk);
+        if (out_lo) *reinterpret_cast<uint32_t*>(out_lo + (size_t)row * DIM + c) = f5_pack2_lo(z[0], z[1]);
+    }
+    f5_sat_commit(trk, sat_flag);
+}
+// dim = 128, 384, 640 or 896; lens == nullptr launches the instantiation without row lengths
+static int dwconv_ln_g128_launch(const float* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b, op16_t* out_hi,
+                                  op16_t* out_lo, int rows, int seq_len, int dim, float eps, const int* lens, hipStream_t s) {
+    const dim3 grid(f5_cdiv(rows, 4)), block(256);
+#define DW_G128(NG_)                                                                                                              \
+    if (lens) hipLaunchKernelGGL((dwconv_ln_g128_kernel<NG_, true>), grid, block, 0, s, x, dw_w, dw_b, ln_w, ln_b, out_hi, out_lo, rows, \
+                                 seq_len, eps, lens, f5_sat_flag_host);                                                           \
+    else hipLaunchKernelGGL((dwconv_ln_g128_kernel<NG_, false>), grid, block, 0, s, x, dw_w, dw_b, ln_w, ln_b, out_hi, out_lo, rows,   \
+                            seq_len, eps, lens, f5_sat_flag_host);
+    switch (dim / 128) {
+        case 1: DW_G128(1) break;
+        case 3: DW_G128(3) break;
+        case 5: DW_G128(5) break;
+        case 7: DW_G128(7) break;
+        default: F5_REQUIRE(false, "dwconv_ln: no 128-column instantiation for dim %d", dim);
+    }
+#undef DW_G128
+    return 0;
+}
+
 int f5_launch_dwconv_ln(const float* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* ln_b,
                         op16_t* out_hi, op16_t* out_lo, int nbatch, int seq_len, int dim, float eps, hipStream_t s) {
-    F5_REQUIRE(dim % 256 == 0 && dim >= 256 && dim <= 1024, "dwconv_ln: dim must be 256/512/768/1024 (got %d)", dim);
+    F5_REQUIRE(dim % 128 == 0 && dim >= 128 && dim <= 1024, "dwconv_ln: dim must be 256/512/768/1024 or 128/384/640/896 (got %d)", dim);
     const int rows = nbatch * seq_len;
     const dim3 grid(f5_cdiv(rows, 4)), block(256);
+    if (dim % 256 != 0) {
+        if (const int rc = dwconv_ln_g128_launch(x, dw_w, dw_b, ln_w, ln_b, out_hi, out_lo, rows, seq_len, dim, eps, nullptr, s)) return rc;
+        F5_LAUNCH_CHECK();
+        return 0;
+    }
 #define DW_ARGS x, dw_w, dw_b, ln_w, ln_b, out_hi, out_lo, rows, seq_len, eps, f5_sat_flag_host
     switch (dim / 256) {
         case 1: hipLaunchKernelGGL((dwconv_ln_kernel<1>), grid, block, 0, s, DW_ARGS); break;
@@ -384,9 +473,14 @@ int f5_launch_dwconv_ln_ragged(const float* x, const float* dw_w, const float* d
     F5_REQUIRE(nbatch >= 1, "dwconv_ln_ragged: nbatch must be >= 1 (got %d)", nbatch);
     F5_REQUIRE(seq_len >= 2, "dwconv_ln_ragged: seq_len must be >= 2 (got %d)", seq_len);
     F5_REQUIRE((long)nbatch * seq_len <= 0x7fffffffL, "dwconv_ln_ragged: nbatch * seq_len = %ld rows exceed 2^31 - 1", (long)nbatch * seq_len);
-    F5_REQUIRE(dim % 256 == 0 && dim >= 256 && dim <= 1024, "dwconv_ln_ragged: dim must be 256/512/768/1024 (got %d)", dim);
+    F5_REQUIRE(dim % 128 == 0 && dim >= 128 && dim <= 1024, "dwconv_ln_ragged: dim must be 256/512/768/1024 or 128/384/640/896 (got %d)", dim);
     const int rows = nbatch * seq_len;
     const dim3 grid(f5_cdiv(rows, 4)), block(256);
+    if (dim % 256 != 0) {
+        if (const int rc = dwconv_ln_g128_launch(x, dw_w, dw_b, ln_w, ln_b, out_hi, out_lo, rows, seq_len, dim, eps, lens, s)) return rc;
+        F5_LAUNCH_CHECK();
+        return 0;
+    }
 #define DW_ARGS x, dw_w, dw_b, ln_w, ln_b, out_hi, out_lo, rows, seq_len, eps, lens, f5_sat_flag_host
     switch (dim / 256) {
         case 1: hipLaunchKernelGGL((dwconv_ln_ragged_kernel<1>), grid, block, 0, s, DW_ARGS); break;

@@ -239,6 +239,11 @@ def load_library() -> C.CDLL:
                         # row isolation (docs/isolate_rows.md): conv-pos and GRN with row lengths
                         ("f5_op_convpos_ragged", [C.c_void_p] * 8 + [C.c_int] * 7 + [C.c_void_p] * 2),
                         ("f5_op_grn_ragged", [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p] * 2),
+                        # narrow conv-pos groups (docs/geometries.md): the weight store's packing on the host, the route by group width
+                        ("f5_op_conv_packed_rows", [C.c_int, C.c_int]),
+                        ("f5_op_pack_conv_groups", [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+                        ("f5_debug_convpos_route_groups", [C.c_int] * 5 + [C.c_char_p, C.c_int]),
+                        ("f5_op_qkv_rope_k", [C.c_void_p] * 11 + [C.c_int] * 7 + [C.c_void_p]),
                         # MX-fp8 producers and the QKV projection of the mode (float arguments: eps, q_premul)
                         ("f5_op_ln_modulate_f8", [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
                         ("f5_op_quantize_mx_bf16", [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

@@ -48,6 +48,11 @@ class DiTConfig:
     def text_ff_dim(self) -> int:
         return self.text_dim * self.conv_mult
 
+    @property
+    def inner_dim(self) -> int:
+        """Attention inner width (dit.py:117-125): to_q / to_k / to_v project dim -> heads * dim_head, to_out back to dim."""
+        return self.heads * self.dim_head
+
     def as_dict(self):
         return asdict(self)
 
@@ -58,10 +63,16 @@ F5TTS_335M = DiTConfig()  # cfm.py:459-469
 TINY = DiTConfig(dim=256, depth=2, heads=4, dim_head=64, ff_mult=2, mel_dim=100,
                  text_num_embeds=64, text_dim=256, conv_layers=2, conv_pos_groups=4)
 
+# the model the reference's training script builds (train_libritts_small.py): attention inner width 8 * 64 = 512 under a 768-wide model,
+# 16 conv-pos groups of 48 channels (dit.py:30 hard-wires 16 groups), 384-wide text; a byte-level vocabulary of 256 (docs/geometries.md)
+REF_SMALL = DiTConfig(dim=768, depth=16, heads=8, dim_head=64, ff_mult=2, mel_dim=100,
+                      text_num_embeds=256, text_dim=384, conv_layers=4, conv_pos_groups=16)
+
 
 def param_specs(cfg: DiTConfig) -> List[Tuple[str, Tuple[int, ...], str]]:
     """(name, shape, kind) in the canonical order used for seeded generation."""
     D, Dt, FF, TF = cfg.dim, cfg.text_dim, cfg.ff_dim, cfg.text_ff_dim
+    I = cfg.inner_dim            # == D in the 335M model; the draws of every such configuration are what they were
     gin = cfg.dim // cfg.conv_pos_groups
     specs: List[Tuple[str, Tuple[int, ...], str]] = []
     add = specs.append
@@ -93,9 +104,9 @@ def param_specs(cfg: DiTConfig) -> List[Tuple[str, Tuple[int, ...], str]]:
         add((q + "attn_norm.linear.weight", (6 * D, D), "adaln"))
         add((q + "attn_norm.linear.bias", (6 * D,), "bias"))
         for nm in ("to_q", "to_k", "to_v"):
-            add((q + f"attn.{nm}.weight", (D, D), "linear"))
-            add((q + f"attn.{nm}.bias", (D,), "bias"))
-        add((q + "attn.to_out.layers.0.weight", (D, D), "linear"))
+            add((q + f"attn.{nm}.weight", (I, D), "linear"))
+            add((q + f"attn.{nm}.bias", (I,), "bias"))
+        add((q + "attn.to_out.layers.0.weight", (D, I), "linear"))
         add((q + "attn.to_out.layers.0.bias", (D,), "bias"))
         add((q + "ff.ff.layers.0.layers.0.weight", (FF, D), "linear"))
         add((q + "ff.ff.layers.0.layers.0.bias", (FF,), "bias"))

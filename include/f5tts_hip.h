@@ -24,20 +24,23 @@ extern "C" {
 
 typedef struct f5_engine f5_engine;
 
-/* Constructor arguments of the reference DiT (dit.py:332-346) + derived sizes. */
+/* Constructor arguments of the reference DiT (dit.py:332-346) + derived sizes.  The accepted family (docs/geometries.md): dim a
+ * multiple of 256 up to 1024; dim_head 64; the attention inner width heads * dim_head a multiple of 256 up to 1024, equal to dim or
+ * not (dit.py:117-125 projects dim -> inner -> dim); dim / conv_pos_groups 32, 48 or 64 channels per group; text_dim a multiple of 128
+ * up to 1024.  F5_PREC_MXFP8 accepts only inner == dim, 64-channel groups and text_dim % 256 == 0. */
 typedef struct f5_config {
     int32_t dim;             /* 1024 */
     int32_t depth;           /* 22 */
-    int32_t heads;           /* 16 */
+    int32_t heads;           /* 16 (heads * dim_head: a multiple of 256, <= 1024; need not equal dim) */
     int32_t dim_head;        /* 64 (only 64 is supported by the attention kernel) */
     int32_t ff_dim;          /* dim * ff_mult = 2048 */
     int32_t mel_dim;         /* 100 */
     int32_t text_num_embeds; /* 2545 (embedding table has +1 rows, dit.py:184) */
-    int32_t text_dim;        /* 512 */
+    int32_t text_dim;        /* 512 (a multiple of 128, <= 1024) */
     int32_t text_ff_dim;     /* text_dim * conv_mult = 1024 */
     int32_t conv_layers;     /* 4; 0 = plain embedding: no positional table, no ConvNeXt blocks, no masking (dit.py:188-194) */
     int32_t conv_pos_kernel; /* 31 */
-    int32_t conv_pos_groups; /* 16 (dim / groups must be 64) */
+    int32_t conv_pos_groups; /* 16 (dim / groups must be 32, 48 or 64; 32 needs an even group count) */
     int32_t freq_embed_dim;  /* 256 */
     int32_t text_max_pos;    /* 4096 */
     int32_t text_mask_padding; /* 1 (dit.py:186): zero the text embedding at filler / padded positions around every text block */
@@ -276,13 +279,20 @@ int f5_op_attention_ex(const void* qk_hi, const void* qk_lo, const void* vt_hi, 
 int f5_op_qkv_rope(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias,
                    const float* rope_cos, const float* rope_sin, void* qk_hi, void* qk_lo, void* vt_hi, void* vt_lo, int B,
                    int seq_len, int npad, int heads, int dmodel, int nseg, void* stream);
+/* the same for an attention inner width (inner = heads * 64) that is not the input width K (dit.py:117-125): a [B seq_len][K],
+ * w [3 inner][K], q | k [B seq_len][2 inner], V^T [B heads 64][npad].  The LN-fold hooks do not apply. */
+int f5_op_qkv_rope_k(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias,
+                     const float* rope_cos, const float* rope_sin, void* qk_hi, void* qk_lo, void* vt_hi, void* vt_lo, int B,
+                     int seq_len, int npad, int heads, int inner, int K, int nseg, void* stream);
 int f5_op_rope_table(float* cos_t, float* sin_t, int seq_len, int dim_head, void* stream);
 /* GROUP-major twins of the rotation tables: tq / tk are [dim_head/4][seq_len][4] floats (16 seq_len dim_head/4 bytes each, 16-byte
  * aligned), element (g, n) = (cos, cos, sin, sin) of rotation pairs 2g, 2g + 1 at position n, the q table multiplied by qscale (1 = plain
  * q): with them the staged QKV kernels accumulate the q / k column tiles transposed (rotation pairs in-lane, one 16-byte load per lane
  * and 4 features); sample() builds its own */
 int f5_op_rope_table_g4(float* tq, float* tk, int seq_len, int dim_head, float qscale, void* stream);
-/* dit.py:29-50 one grouped conv + Mish; mode 0 -> bf16 out, mode 1 -> out_f32 += */
+/* dit.py:29-50 one grouped conv + Mish; mode 0 -> bf16 out, mode 1 -> out_f32 +=.  C / groups = 64, 48 or 32 channels per group; w is
+ * the matrix f5_op_pack_conv_groups leaves ([f5_op_conv_packed_rows(C, C / groups)][taps * 64], rounded to the operand type): at 64
+ * channels per group the reference tensor (C, taps, 64) as it is. */
 int f5_op_convpos(const void* in_hi, const void* in_lo, const void* w_hi, const void* w_lo, const float* bias, void* out_hi,
                   void* out_lo, float* out_f32, int B, int seq_len, int C, int groups, int taps, int nseg, int mode,
                   void* stream);
@@ -294,6 +304,13 @@ int f5_op_convpos(const void* in_hi, const void* in_lo, const void* w_hi, const 
 int f5_op_convpos_ragged(const void* in_hi, const void* in_lo, const void* w_hi, const void* w_lo, const float* bias, void* out_hi,
                          void* out_lo, float* out_f32, int B, int seq_len, int C, int groups, int taps, int nseg, int mode,
                          const int32_t* lens_dev, void* stream);
+/* The weight store's packing of a conv-pos weight w = (C, taps, cpg) fp32, cpg = C / groups = 32, 48 or 64, done on the host (no
+ * device): out = [f5_op_conv_packed_rows(C, cpg)][taps * 64] floats.  cpg 64: w itself.  cpg 32: C rows, two groups share a block-
+ * diagonal 64-wide super group (output channel o keeps its 32 input channels in columns ((o / 32) % 2) * 32 ... + 31 of every tap, the
+ * rest is zero).  cpg 48: C / 48 * 64 rows, group g in rows g * 64 ... g * 64 + 47 with its 48 input channels in columns 0 ... 47 of
+ * every tap, zeros elsewhere.  f5_op_conv_packed_rows: -1 for a width other than 32 / 48 / 64 or one that does not divide C. */
+int f5_op_conv_packed_rows(int C, int cpg);
+int f5_op_pack_conv_groups(const float* w, int C, int taps, int cpg, float* out);
 /* dit.py:270 */
 int f5_op_ln_modulate(const float* x, const float* scale, const float* shift, void* out_hi, void* out_lo, int rows, int dim,
                       void* stream);
@@ -470,13 +487,16 @@ int f5_debug_last_gemm_kernel(char* buf, int n);
  * with "+f8" appended when the launch carried the MX-fp8 output; "" after a launch that was refused.  Host side only. */
 int f5_debug_last_attn_kernel(char* buf, int n);
 /* the same for the conv-pos kernel: the instantiation the most recent conv-pos launch of the process resolved to --
- * f5_convpos_kernel<false,1> / <false,2> / <false,4> / <true,1> / <true,2> -- with "+xcd" appended when the 1-D "groups dealt to XCDs"
+ * f5_convpos_kernel<false,1> / <false,2> / <false,4> / <true,1> / <true,2> (",48" inside the brackets for the 48-channels-per-group
+ * instantiation: f5_convpos_kernel<false,1,48>) -- with "+xcd" appended when the 1-D "groups dealt to XCDs"
  * block numbering ran; "" after a launch that was refused.  Host side only: nothing reaches a kernel.  The operand type is
  * f5_op_get_operand_type's. */
 int f5_debug_last_convpos_kernel(char* buf, int n);
 /* which conv-pos kernel WOULD a launch of this shape run under the current selectors?  The launcher's own decision, in the names of
  * f5_debug_last_convpos_kernel (f5_convpos_ring_kernel among them); nothing is launched and no device is touched. */
 int f5_debug_convpos_route(int B, int seq_len, int groups, int nseg, char* buf, int n);
+/* the same for `groups` groups of cpg = 32, 48 or 64 channels each: narrow groups never run f5_convpos_ring_kernel */
+int f5_debug_convpos_route_groups(int B, int seq_len, int groups, int cpg, int nseg, char* buf, int n);
 /* which kernel WOULD it run?  The same routing function the launcher switches over (csrc/gemm_route.hpp), asked for a launch of this
  * epilogue and shape under the current selectors (f5_debug_set_gemm_tile / _ring / _qkv_tile) and process-wide flags; nothing is
  * launched and no device is touched.  variant_bits: 1 = group-major rotation tables set (transposed q / k tiles), 2 = fused LN tail,
