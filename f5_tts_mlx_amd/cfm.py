@@ -28,7 +28,8 @@ from .weights import convert_upstream_weights, dequantize_mlx_checkpoint
 # sequenced by csrc/engine.hip: run_sample_body); `sample()` has no host-side ODE loop.  The module-level names the reference
 # exports stay importable for user code that integrates its own vector field: one explicit Runge-Kutta driver parameterised by a
 # tableau (stage offsets c, stage weights a of the previous stage only -- all three schemes are "chain" schemes -- and output
-# weights b), over torch tensors instead of mx.arrays.
+# weights b), over torch tensors instead of mx.arrays.  The multistep solvers ab2 / ab3 (docs/multistep.md; not in the reference) live in
+# the same places -- mode 2 of the stage kernels, the same sequencer -- and have their restatement next to it (_adams_bashforth).
 
 
 def _explicit_rk(func: Callable, y0: torch.Tensor, t, c, a, b) -> torch.Tensor:
@@ -63,6 +64,60 @@ def odeint_midpoint(func, y0, t):
 def odeint_rk4(func, y0, t):
     """cfm.py:94-122: classic fourth-order Runge-Kutta."""
     return _explicit_rk(func, y0, t, c=(0.0, 0.5, 0.5, 1.0), a=(0.0, 0.5, 0.5, 1.0), b=(1 / 6, 2 / 6, 2 / 6, 1 / 6))
+
+
+def ab_weights(t, i: int, order: int) -> np.ndarray:
+    """Weights (w0, w1, w2) of Adams-Bashforth step i on the grid t, float32: y_{i+1} = y_i + h (w0 k_i + w1 k_{i-1} + w2 k_{i-2}).
+
+    They integrate the Lagrange interpolant through the nodes in use over [t_i, t_{i+1}], divided by h = t_{i+1} - t_i; with
+    a = t_i - t_{i-1} and b = t_i - t_{i-2}: order 2 gives 1 + h/(2a), -h/(2a); order 3 gives (h^2/3 + (a+b)h/2 + ab)/(ab),
+    -(h^2/3 + bh/2)/(a(b-a)), (h^2/3 + ah/2)/(b(b-a)).  The order of step i is min(i + 1, order); a spacing that is not positive
+    (a <= 0; order 3: b - a <= 0) drops the step to the highest order whose spacings are.  Computed in float64 from the float32 grid
+    values and rounded once; an absent weight is exactly 0.  The engine stages the same numbers (csrc/engine.hip ab_weights)."""
+    t = np.asarray(t, dtype=np.float32).astype(np.float64)
+    h = t[i + 1] - t[i]
+    a = t[i] - t[i - 1] if i >= 1 else 0.0
+    b = t[i] - t[i - 2] if i >= 2 else 0.0
+    ord_ = min(int(order), i + 1)
+    if ord_ >= 3 and not b - a > 0.0:
+        ord_ = 2
+    if ord_ >= 2 and not a > 0.0:
+        ord_ = 1
+    w = np.array([1.0, 0.0, 0.0], dtype=np.float64)
+    if ord_ == 2:
+        w[0] = 1.0 + h / (2.0 * a)
+        w[1] = 0.0 - h / (2.0 * a)                  # (0 - x: a step of length 0 gives +0, not -0)
+    elif ord_ == 3:
+        w[0] = (h * h / 3.0 + (a + b) * h / 2.0 + a * b) / (a * b)
+        w[1] = 0.0 - (h * h / 3.0 + b * h / 2.0) / (a * (b - a))
+        w[2] = (h * h / 3.0 + a * h / 2.0) / (b * (b - a))
+    return w.astype(np.float32)
+
+
+def _adams_bashforth(func: Callable, y0: torch.Tensor, t, order: int) -> torch.Tensor:
+    """Fixed-grid Adams-Bashforth with variable-step weights (ab_weights): one evaluation per step, at the grid point."""
+    tg = np.asarray([float(x) for x in t], dtype=np.float32)
+    states, ks, y = [y0], [], y0
+    for i in range(len(t) - 1):
+        ks = [func(t[i], y)] + ks[:2]
+        w = ab_weights(tg, i, order)
+        incr = float(w[0]) * ks[0]
+        for wj, kj in zip(w[1:], ks[1:]):
+            if wj != 0.0:
+                incr = incr + float(wj) * kj
+        y = y + (t[i + 1] - t[i]) * incr
+        states.append(y)
+    return torch.stack(states)
+
+
+def odeint_ab2(func, y0, t):
+    """Adams-Bashforth of order 2 on the grid t (not in the reference; docs/multistep.md): step 0 is the Euler step."""
+    return _adams_bashforth(func, y0, t, 2)
+
+
+def odeint_ab3(func, y0, t):
+    """Adams-Bashforth of order 3 on the grid t: step 0 is the Euler step, step 1 is second order."""
+    return _adams_bashforth(func, y0, t, 3)
 
 
 def time_grid(steps: int, sway_sampling_coef: Optional[float]) -> np.ndarray:
@@ -107,7 +162,7 @@ def prepare_lengths(text: torch.Tensor, cond_seq_len: int, batch: int, duration,
     duration = torch.maximum(lens + 1, duration)                            # cfm.py:317
     duration = torch.clip(duration, 0, max_duration)                        # cfm.py:318
     max_duration = int(duration.max().item())                               # cfm.py:319
-    if method not in ("midpoint", "euler", "rk4"):
+    if method not in ("midpoint", "euler", "rk4", "ab2", "ab3"):           # ab2 / ab3: docs/multistep.md
         raise ValueError(f"Unknown method: {method}")                       # cfm.py:390
     return text, lens, duration, max_duration
 
@@ -219,7 +274,7 @@ class F5TTS:
         *,
         lens: Optional[torch.Tensor] = None,
         steps=8,
-        method: Literal["euler", "midpoint", "rk4"] = "rk4",
+        method: Literal["euler", "midpoint", "rk4", "ab2", "ab3"] = "rk4",
         cfg_strength=2.0,
         speed=1.0,
         sway_sampling_coef=-1.0,

@@ -85,6 +85,8 @@ struct Workspace {
     // f5_sample_window only (Route::window; behind the rows part): the rows' EFFECTIVE strengths of every evaluation, [nfe][B] floats
     // each, staged per call; stage j reads row j where the rows / dual calls read the one [B] vector at rcfg / racfg
     size_t wcfg = 0, wacfg = 0, wtab_words = 0;
+    // F5_AB2 / F5_AB3 only (behind everything else): the weight triples, [steps - 1][3] floats, on a per-row route [steps - 1][B][3]
+    size_t abw = 0, abw_words = 0;
 };
 
 // Per-engine launch options: everything that reaches a kernel as a by-value argument or changes the launch sequence of sample()
@@ -141,7 +143,31 @@ struct f5_engine : WeightStore {
     std::vector<uint8_t> last_pattern; // f5_sample_window: wide (1) / narrow (0) per evaluation of the most recent call (f5_debug_last_sample_pattern)
 };
 
-static int nfe_per_step(int method) { return method == F5_EULER ? 1 : (method == F5_MIDPOINT ? 2 : 4); }
+static bool method_known(int method) { return method >= F5_EULER && method <= F5_AB3; }
+// Adams-Bashforth: the highest order the method reaches (0 = a one-step method)
+static int ab_order(int method) { return method == F5_AB2 ? 2 : (method == F5_AB3 ? 3 : 0); }
+static int nfe_per_step(int method) { return (method == F5_EULER || ab_order(method)) ? 1 : (method == F5_MIDPOINT ? 2 : 4); }
+// The weights of Adams-Bashforth step i on the grid t (fp32 values, arithmetic in fp64, rounded once): the integral over [t_i, t_i+1] of
+// the Lagrange interpolant through (t_i, k_i), (t_i-1, k_i-1) (, (t_i-2, k_i-2)), divided by h.  a = t_i - t_i-1, b = t_i - t_i-2.  Order
+// min(i + 1, order); a spacing that is not positive (a <= 0; third order: b - a <= 0) drops to the highest order whose spacings are.  An
+// absent weight is exactly 0.  (cfm.ab_weights is the same rule in Python.)
+static void ab_weights(const float* t, int i, int order, float w[3]) {
+    const double h = (double)t[i + 1] - (double)t[i];
+    const double a = i >= 1 ? (double)t[i] - (double)t[i - 1] : 0.0, b = i >= 2 ? (double)t[i] - (double)t[i - 2] : 0.0;
+    int ord = order < i + 1 ? order : i + 1;
+    if (ord >= 3 && !(b - a > 0.0)) ord = 2;
+    if (ord >= 2 && !(a > 0.0)) ord = 1;
+    w[0] = 1.0f;
+    w[1] = w[2] = 0.0f;
+    if (ord == 2) {
+        w[0] = (float)(1.0 + h / (2.0 * a));
+        w[1] = (float)(0.0 - h / (2.0 * a));          // (0 - x: a step of length 0 gives +0, not -0)
+    } else if (ord == 3) {
+        w[0] = (float)((h * h / 3.0 + (a + b) * h / 2.0 + a * b) / (a * b));
+        w[1] = (float)(0.0 - (h * h / 3.0 + b * h / 2.0) / (a * (b - a)));
+        w[2] = (float)((h * h / 3.0 + a * h / 2.0) / (b * (b - a)));
+    }
+}
 
 static MatF8 alloc_f8(Bump& b, int rows, int ld) {
     MatF8 m;
@@ -589,6 +615,10 @@ static Workspace plan_workspace(const f5_engine* e, int B, int N, int nt, int st
             w.wacfg = route.dual ? w.wcfg + rows * 4 : 0;
         }
     }
+    if (ab_order(method)) {
+        w.abw_words = (size_t)3 * (steps > 1 ? steps - 1 : 1) * (route.rows ? B : 1);
+        w.abw = b.take(w.abw_words * 4);
+    }
     w.total = b.off;
     return w;
 }
@@ -598,7 +628,7 @@ static Workspace plan_workspace(const f5_engine* e, int B, int N, int nt, int st
 static int workspace_bytes(f5_engine* e, int B, int N, int nt, int steps, int method, Route route, size_t* bytes) {
     F5_REQUIRE(e && bytes, "null argument");
     F5_REQUIRE(B >= 1 && N >= 1 && steps >= 1, "bad sizes B=%d N=%d steps=%d", B, N, steps);
-    F5_REQUIRE(method >= F5_EULER && method <= F5_RK4, "Unknown method: %d", method);
+    F5_REQUIRE(method_known(method), "Unknown method: %d", method);
     *bytes = plan_workspace(e, B, N, nt, steps, method, route).total;
     return 0;
 }
@@ -1143,6 +1173,20 @@ static int run_sample_body(const Ctx& c, const f5_sample_args* a, int i0 = 0, in
             o.coef = 1.0f;
             o.out = ynext;
             RC(stage(o));
+        } else if (ab_order(a->method)) {
+            // the velocities of the last three steps as a ring in w.kst: step i writes slot i % 3 and reads the other two, so no launch
+            // reads the buffer it writes; they live in the workspace, so they outlast a graph segment (graph_split)
+            RC(dit(i));
+            o.coef = 1.0f;
+            o.out = ynext;
+            o.kstore = kst + (size_t)(i % 3) * M1 * mel;
+            if (i > 0) {
+                o.mode = 2;
+                o.k1 = kst + (size_t)((i + 2) % 3) * M1 * mel;
+                o.k2 = (i > 1 && ab_order(a->method) == 3) ? kst + (size_t)((i + 1) % 3) * M1 * mel : nullptr;
+                o.abw = c.p<float>(w.abw) + (size_t)3 * i * (c.route.rows ? c.B : 1);
+            }
+            RC(stage(o));
         } else if (a->method == F5_MIDPOINT) {
             RC(dit(2 * i));
             o.coef = 0.5f;
@@ -1186,7 +1230,7 @@ static int check_args(const f5_engine* e, const f5_sample_args* a) {
                a->steps);
     // the RoPE / head-split epilogues step through a 4-row group with a single wrap at the sequence boundary
     F5_REQUIRE(a->N >= 4, "sequences shorter than 4 mel frames are not supported (N=%d)", a->N);
-    F5_REQUIRE(a->method >= F5_EULER && a->method <= F5_RK4, "Unknown method: %d", a->method);
+    F5_REQUIRE(method_known(a->method), "Unknown method: %d", a->method);
     F5_REQUIRE(a->text && a->cond && a->lens && a->durations && a->workspace, "null pointer in f5_sample_args");
     F5_REQUIRE(((uintptr_t)a->workspace & 255) == 0, "workspace must be 256-byte aligned");
     for (int b = 0; b < a->B; ++b) {
@@ -1264,7 +1308,7 @@ static void eval_times(const float* t, int steps, int method, std::vector<float>
         const float t0 = t[i];
         const float dt = t[i + 1] - t0;
         dts.push_back(dt);
-        if (method == F5_EULER) {
+        if (method == F5_EULER || ab_order(method)) {
             tnfe.push_back(t0);
         } else if (method == F5_MIDPOINT) {
             tnfe.push_back(t0);
@@ -1394,6 +1438,16 @@ static int stage_controls(Ctx& c, const f5_sample_args* a, const RowCtl& rc, std
         RC(stage_inputs(c, a, nullptr, tnfe, dts));
         RC(f5_launch_stage_words(words.data(), words.size(), c.p<uint32_t>(c.w.rscal), s));
         if (r.window) RC(f5_launch_stage_words(wtab.data(), wtab.size(), c.p<uint32_t>(c.w.wcfg), s));
+    }
+    if (ab_order(a->method) && a->steps > 1) {
+        // Adams-Bashforth weights of every step, per row on a per-row route ([steps - 1][B][3]); step 0's triple is (1, 0, 0) and is not read
+        const int nrow = r.rows ? c.B : 1;
+        std::vector<uint32_t> abw(c.w.abw_words, 0u);
+        float* wv = reinterpret_cast<float*>(abw.data());
+        for (int i = 0; i + 1 < a->steps; ++i)
+            for (int b = 0; b < nrow; ++b)
+                ab_weights(r.rows ? rc.t_rows + (size_t)b * a->steps : a->t, i, ab_order(a->method), wv + ((size_t)i * nrow + b) * 3);
+        RC(f5_launch_stage_words(abw.data(), abw.size(), c.p<uint32_t>(c.w.abw), s));
     }
     // the mask travels like text / cond / y0: copied into the workspace outside the captured part, so one graph serves every mask of a shape
     if (c.edit) RC(f5_launch_copy_bytes(rc.cond_keep, c.ws + c.w.cond_keep, (size_t)c.B * c.N, s));
@@ -1532,7 +1586,7 @@ extern "C" int f5_sample_status_async(f5_engine* e, const f5_sample_args* a, int
 // the only configuration that can set bit 0 of the status word; host-side, no GPU work.  f5_dit_forward: pass steps = 2, method = F5_EULER.
 extern "C" int f5_engine_ln_fold_active(f5_engine* e, const f5_sample_args* a, int* active) {
     F5_REQUIRE(e && a && active, "null argument");
-    F5_REQUIRE(a->B >= 1 && a->N >= 1 && a->nt >= 1 && a->steps >= 1 && a->method >= F5_EULER && a->method <= F5_RK4, "bad sizes");
+    F5_REQUIRE(a->B >= 1 && a->N >= 1 && a->nt >= 1 && a->steps >= 1 && method_known(a->method), "bad sizes");
     const Ctx c = make_ctx(e, a, nullptr, Route{}, branch_count(Route{}, &a->cfg_strength, nullptr, 1));
     RC(ln_refusal(c, ""));
     *active = c.ln.fold_state;
@@ -2187,6 +2241,39 @@ extern "C" int f5_op_ode_stage_dual(const float* pred, const float* text_pred, c
     o.rows = rows;
     o.mel_dim = mel_dim;
     return g_ops.ode_stage_dual(o, text_pred, audio_cfg_rows, text_cfg_rows, dt_rows, rows_per_vec, nvec, (hipStream_t)stream);
+}
+// Mode 2 of the three stage kernels, the Adams-Bashforth step (rowops.hpp F5OdeArgs): route 0 = the scalar kernel (cfg_ptr, dt and
+// abw [3] for the call; text_pred, audio_cfg_rows, rows_per_vec and nvec not read), 1 = per row (cfg_rows, dt_rows, abw [nvec][3]),
+// 2 = dual guidance (text_pred and audio_cfg_rows as well).  k1 / k2: the velocities of the step before and the one before that, or null.
+extern "C" int f5_op_ode_stage_ab(int route, const float* pred, const float* text_pred, const float* null_pred, const float* audio_cfg_rows,
+                                  const float* cfg, const float* base, const float* dt, const float* abw, int rows_per_vec, int nvec,
+                                  float* kstore, const float* k1, const float* k2, float* out, void* xin_hi, void* xin_lo, int rows,
+                                  int mel_dim, void* stream) {
+    F5_REQUIRE(route >= 0 && route <= 2, "ode_stage_ab: route must be 0, 1 or 2 (got %d)", route);
+    F5_REQUIRE(pred != nullptr && base != nullptr && dt != nullptr && out != nullptr, "ode_stage_ab: null pred / base / dt / out");
+    F5_REQUIRE(rows >= 1 && mel_dim >= 1, "ode_stage_ab: no rows / columns (got %d, %d)", rows, mel_dim);
+    F5_REQUIRE(route == 0 || cfg != nullptr, "ode_stage_ab: null cfg_rows");
+    F5OdeArgs o;
+    memset(&o, 0, sizeof(o));
+    o.pred = pred;
+    o.null_pred = null_pred;
+    o.cfg_ptr = cfg;
+    o.base = base;
+    o.dt_ptr = dt;
+    o.coef = 1.0f;
+    o.divisor = 1.0f;
+    o.mode = 2;
+    o.kstore = kstore;
+    o.k1 = k1;
+    o.k2 = k2;
+    o.abw = abw;
+    o.out = out;
+    o.xin_hi = (op16_t*)xin_hi;
+    o.xin_lo = (op16_t*)xin_lo;
+    o.rows = rows;
+    o.mel_dim = mel_dim;
+    if (route == 2) return g_ops.ode_stage_dual(o, text_pred, audio_cfg_rows, cfg, dt, rows_per_vec, nvec, (hipStream_t)stream);
+    return route == 1 ? g_ops.ode_stage_rows(o, cfg, dt, rows_per_vec, nvec, (hipStream_t)stream) : g_ops.ode_stage(o, (hipStream_t)stream);
 }
 extern "C" int f5_op_pack_cond_text_dual(const float* cond, const int32_t* lens, const float* text_emb, void* out_hi, void* out_lo, int B,
                                          int seq_len, int mel_dim, int dt, void* stream) {

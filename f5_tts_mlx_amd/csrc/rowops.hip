@@ -943,10 +943,13 @@ int f5_launch_pack_x(const float* y, op16_t* out_hi, op16_t* out_lo, int rows, i
 //     k = (F + (F - T) a) + (T - N) c
 // T is loaded when either strength is >= 1e-5, N only when c >= 1e-5; a row with both below takes k = F.  All by selection.
 enum { ODE_SCALAR = 0, ODE_ROWS = 1, ODE_DUAL = 2 };
-template <int ROUTE>
-__device__ __forceinline__ void f5_ode_stage_elem(const F5OdeArgs& p, const float* __restrict__ cfg_rows, const float* __restrict__ dt_rows,
+// AB (mode 2, the Adams-Bashforth step) is an instantiation of its own, so the kernels of modes 0 and 1 do not change with it: the
+// increment is w0 k + w1 k1 + w2 k2 with the step's weights from abw ([3], per row [nvec][3]); a history term whose pointer is null or
+// whose weight is exactly 0 is left out by selection (not loaded, so what lies in a buffer that no weight names reaches nothing).
+template <int ROUTE, bool AB = false>
+__device__ __forceinline__ void f5_ode_stage_elem(const F5OdeCore& p, const float* __restrict__ cfg_rows, const float* __restrict__ dt_rows,
                                                   int rows_per_vec, int nvec, const float* __restrict__ text_pred = nullptr,
-                                                  const float* __restrict__ audio_rows = nullptr) {
+                                                  const float* __restrict__ audio_rows = nullptr, const float* __restrict__ abw = nullptr) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;   // over rows * 128 (padded columns)
     if (i >= (size_t)p.rows * 128) return;
     const size_t row = i >> 7;
@@ -957,10 +960,12 @@ __device__ __forceinline__ void f5_ode_stage_elem(const F5OdeArgs& p, const floa
         const float pr = p.pred[idx];
         float k = pr;
         float dt;
+        const float* wv = abw;
         if (ROUTE == ODE_DUAL) {
             const int v = (int)((row / (size_t)rows_per_vec) % (size_t)nvec);
             const float ca = audio_rows[v], ct = cfg_rows[v];
             dt = dt_rows[v];
+            if (AB) wv = abw + 3 * v;
             const bool text_on = !(ct < 1e-5f);
             if (text_pred && (text_on || !(ca < 1e-5f))) {
                 const float tp = text_pred[idx];
@@ -971,16 +976,25 @@ __device__ __forceinline__ void f5_ode_stage_elem(const F5OdeArgs& p, const floa
             const int v = (int)((row / (size_t)rows_per_vec) % (size_t)nvec);
             const float cfg = cfg_rows[v];
             dt = dt_rows[v];
+            if (AB) wv = abw + 3 * v;
             if (p.null_pred && !(cfg < 1e-5f)) k = pr + (pr - p.null_pred[idx]) * cfg;
         } else {
             if (p.null_pred) k = pr + (pr - p.null_pred[idx]) * (p.cfg_ptr ? p.cfg_ptr[0] : p.cfg);     // cfm.py:364
             dt = p.dt_ptr[0];
         }
         if (p.kstore) p.kstore[idx] = k;
-        const float a = (p.coef * dt) / p.divisor;
-        float upd = k;
-        if (p.mode == 1) upd = ((p.k1[idx] + 2.0f * p.k2[idx]) + 2.0f * p.k3[idx]) + k;  // cfm.py:117
-        o = p.base[idx] + a * upd;
+        if (AB) {
+            const float w1 = wv[1], w2 = wv[2];
+            float inc = wv[0] * k;
+            if (p.k1 && w1 != 0.0f) inc = fmaf(w1, p.k1[idx], inc);
+            if (p.k2 && w2 != 0.0f) inc = fmaf(w2, p.k2[idx], inc);
+            o = fmaf(dt, inc, p.base[idx]);
+        } else {
+            const float a = (p.coef * dt) / p.divisor;
+            float upd = k;
+            if (p.mode == 1) upd = ((p.k1[idx] + 2.0f * p.k2[idx]) + 2.0f * p.k3[idx]) + k;  // cfm.py:117
+            o = p.base[idx] + a * upd;
+        }
         p.out[idx] = o;
     }
     if (p.xin_hi) {
@@ -992,21 +1006,48 @@ __device__ __forceinline__ void f5_ode_stage_elem(const F5OdeArgs& p, const floa
         f5_sat_commit(trk, p.sat_flag);
     }
 }
-__global__ __launch_bounds__(256) void ode_stage_kernel(F5OdeArgs p) { f5_ode_stage_elem<ODE_SCALAR>(p, nullptr, nullptr, 1, 1); }
-__global__ __launch_bounds__(256) void ode_stage_rows_kernel(F5OdeArgs p, const float* __restrict__ cfg_rows,
+__global__ __launch_bounds__(256) void ode_stage_kernel(F5OdeCore p) { f5_ode_stage_elem<ODE_SCALAR>(p, nullptr, nullptr, 1, 1); }
+__global__ __launch_bounds__(256) void ode_stage_rows_kernel(F5OdeCore p, const float* __restrict__ cfg_rows,
                                                              const float* __restrict__ dt_rows, int rows_per_vec, int nvec) {
     f5_ode_stage_elem<ODE_ROWS>(p, cfg_rows, dt_rows, rows_per_vec, nvec);
 }
-__global__ __launch_bounds__(256) void ode_stage_dual_kernel(F5OdeArgs p, const float* __restrict__ text_pred,
+__global__ __launch_bounds__(256) void ode_stage_dual_kernel(F5OdeCore p, const float* __restrict__ text_pred,
                                                              const float* __restrict__ audio_rows, const float* __restrict__ text_rows,
                                                              const float* __restrict__ dt_rows, int rows_per_vec, int nvec) {
     f5_ode_stage_elem<ODE_DUAL>(p, text_rows, dt_rows, rows_per_vec, nvec, text_pred, audio_rows);
 }
+__global__ __launch_bounds__(256) void ode_stage_ab_kernel(F5OdeCore p, const float* __restrict__ abw) {
+    f5_ode_stage_elem<ODE_SCALAR, true>(p, nullptr, nullptr, 1, 1, nullptr, nullptr, abw);
+}
+__global__ __launch_bounds__(256) void ode_stage_ab_rows_kernel(F5OdeCore p, const float* __restrict__ cfg_rows,
+                                                                const float* __restrict__ dt_rows, int rows_per_vec, int nvec,
+                                                                const float* __restrict__ abw) {
+    f5_ode_stage_elem<ODE_ROWS, true>(p, cfg_rows, dt_rows, rows_per_vec, nvec, nullptr, nullptr, abw);
+}
+__global__ __launch_bounds__(256) void ode_stage_ab_dual_kernel(F5OdeCore p, const float* __restrict__ text_pred,
+                                                                const float* __restrict__ audio_rows, const float* __restrict__ text_rows,
+                                                                const float* __restrict__ dt_rows, int rows_per_vec, int nvec,
+                                                                const float* __restrict__ abw) {
+    f5_ode_stage_elem<ODE_DUAL, true>(p, text_rows, dt_rows, rows_per_vec, nvec, text_pred, audio_rows, abw);
+}
+// what mode 2 asks of every launcher; `what` names the launcher
+static int f5_ode_check_ab(const F5OdeArgs& a, const char* what) {
+    F5_REQUIRE(a.mode != 2 || (a.abw != nullptr && a.kstore != nullptr), "%s: mode 2 needs abw and kstore", what);
+    F5_REQUIRE(a.mode != 2 || (a.kstore != a.k1 && a.kstore != a.k2), "%s: mode 2: kstore is one of the history buffers", what);
+    return 0;
+}
 int f5_launch_ode_stage(const F5OdeArgs& a, hipStream_t s) {
     F5_REQUIRE(a.mel_dim <= 128, "ode_stage: mel_dim must be <= 128");
-    F5OdeArgs ab = a;
+    if (int rc = f5_ode_check_ab(a, "ode_stage")) return rc;
+    F5OdeCore ab = a;
     if (ab.sat_flag == nullptr) ab.sat_flag = f5_sat_flag_host;
-    hipLaunchKernelGGL(ode_stage_kernel, dim3(f5_cdiv((long)a.rows * 128, 256)), dim3(256), 0, s, ab);
+    const dim3 grid(f5_cdiv((long)a.rows * 128, 256));
+    if (a.mode == 2) {
+        F5_REQUIRE(a.dt_ptr != nullptr, "ode_stage: mode 2: dt_ptr is null");
+        hipLaunchKernelGGL(ode_stage_ab_kernel, grid, dim3(256), 0, s, ab, a.abw);
+    } else {
+        hipLaunchKernelGGL(ode_stage_kernel, grid, dim3(256), 0, s, ab);
+    }
     F5_LAUNCH_CHECK();
     return 0;
 }
@@ -1021,11 +1062,18 @@ int f5_launch_ode_stage_dual(const F5OdeArgs& a, const float* text_pred, const f
     F5_REQUIRE(nvec >= 1, "ode_stage_dual: nvec must be >= 1 (got %d)", nvec);
     F5_REQUIRE(a.mel_dim <= 128, "ode_stage_dual: mel_dim must be <= 128");
     F5_REQUIRE(a.rows >= 1 && a.mel_dim >= 1, "ode_stage_dual: no rows / columns (got %d, %d)", a.rows, a.mel_dim);
-    F5_REQUIRE(a.mode == 0 || (a.mode == 1 && a.k1 != nullptr && a.k2 != nullptr && a.k3 != nullptr), "ode_stage_dual: mode 1 needs k1, k2 and k3");
-    F5OdeArgs ab = a;
+    F5_REQUIRE(a.mode == 0 || a.mode == 2 || (a.mode == 1 && a.k1 != nullptr && a.k2 != nullptr && a.k3 != nullptr),
+               "ode_stage_dual: mode 1 needs k1, k2 and k3");
+    if (int rc = f5_ode_check_ab(a, "ode_stage_dual")) return rc;
+    F5OdeCore ab = a;
     if (ab.sat_flag == nullptr) ab.sat_flag = f5_sat_flag_host;
-    hipLaunchKernelGGL(ode_stage_dual_kernel, dim3(f5_cdiv((long)a.rows * 128, 256)), dim3(256), 0, s, ab, text_pred, audio_cfg_rows,
-                       text_cfg_rows, dt_rows, rows_per_vec, nvec);
+    const dim3 grid(f5_cdiv((long)a.rows * 128, 256));
+    if (a.mode == 2)
+        hipLaunchKernelGGL(ode_stage_ab_dual_kernel, grid, dim3(256), 0, s, ab, text_pred, audio_cfg_rows, text_cfg_rows, dt_rows,
+                           rows_per_vec, nvec, a.abw);
+    else
+        hipLaunchKernelGGL(ode_stage_dual_kernel, grid, dim3(256), 0, s, ab, text_pred, audio_cfg_rows, text_cfg_rows, dt_rows,
+                           rows_per_vec, nvec);
     F5_LAUNCH_CHECK();
     return 0;
 }
@@ -1034,10 +1082,14 @@ int f5_launch_ode_stage_rows(const F5OdeArgs& a, const float* cfg_rows, const fl
     F5_REQUIRE(cfg_rows != nullptr && dt_rows != nullptr, "ode_stage_rows: null cfg_rows / dt_rows");
     F5_REQUIRE(rows_per_vec >= 1 && nvec >= 1, "ode_stage_rows: rows_per_vec and nvec must be >= 1 (got %d, %d)", rows_per_vec, nvec);
     F5_REQUIRE(a.rows >= 1, "ode_stage_rows: no rows (got %d)", a.rows);
-    F5OdeArgs ab = a;
+    if (int rc = f5_ode_check_ab(a, "ode_stage_rows")) return rc;
+    F5OdeCore ab = a;
     if (ab.sat_flag == nullptr) ab.sat_flag = f5_sat_flag_host;
-    hipLaunchKernelGGL(ode_stage_rows_kernel, dim3(f5_cdiv((long)a.rows * 128, 256)), dim3(256), 0, s, ab, cfg_rows, dt_rows, rows_per_vec,
-                       nvec);
+    const dim3 grid(f5_cdiv((long)a.rows * 128, 256));
+    if (a.mode == 2)
+        hipLaunchKernelGGL(ode_stage_ab_rows_kernel, grid, dim3(256), 0, s, ab, cfg_rows, dt_rows, rows_per_vec, nvec, a.abw);
+    else
+        hipLaunchKernelGGL(ode_stage_rows_kernel, grid, dim3(256), 0, s, ab, cfg_rows, dt_rows, rows_per_vec, nvec);
     F5_LAUNCH_CHECK();
     return 0;
 }

@@ -82,8 +82,12 @@ int f5_launch_pack_x(const float* y, op16_t* out_hi, op16_t* out_lo, int rows, i
 // CFG combine + ODE stage (cfm.py:38-122, :364).  k = pred + (pred - null) * cfg  (pred only when !has_null)
 //   mode 0: out = base + a * k                         (optionally k -> kstore)
 //   mode 1: out = base + a * (k1 + 2*k2 + 2*k3 + k)    (RK4 final)
+//   mode 2: out = fma(dt, fma(w2, k2, fma(w1, k1, w0 * k)), base), k -> kstore   (Adams-Bashforth step; coef / divisor / k3 not read)
+//           k1 = the velocity of the step before, k2 = of the one before that, w = abw[0..2] (device, per row: abw[3 v + j]).  A term
+//           whose pointer is null or whose weight is exactly 0 is left out by selection: its buffer is not loaded.  kernels of its own
+//           (F5OdeArgs::abw is no argument of the mode 0 / 1 kernels, which take the F5OdeCore part)
 // also writes the bf16 padded copy of `out` (next DiT input) when xin_hi != null.
-struct F5OdeArgs {
+struct F5OdeCore {
     const float* pred;
     const float* null_pred;  // may be null
     float cfg;               // guidance scale when cfg_ptr is null
@@ -102,6 +106,9 @@ struct F5OdeArgs {
     op16_t* xin_lo;
     int rows, mel_dim;
     int* sat_flag;           // null = f5_sat_flag_host (op16.hpp f5_sat_commit)
+};
+struct F5OdeArgs : F5OdeCore {
+    const float* abw;        // mode 2: device weights of this step, [3] (f5_launch_ode_stage) or [nvec][3] (the per-row launchers)
 };
 int f5_launch_ode_stage(const F5OdeArgs& a, hipStream_t s);
 // the same with guidance scale and step size PER ROW: row r uses cfg_rows[v] and dt_rows[v] (dev fp32 [nvec] each), v = (r / rows_per_vec)

@@ -269,7 +269,7 @@ def main(argv=None):
                     help="seconds of the source to regenerate, optionally with the new duration of that stretch; repeatable, in order")
     ap.add_argument("--output", required=True, help="WAV file to write")
     ap.add_argument("--steps", type=int, default=8, help="ODE grid points")
-    ap.add_argument("--method", default="rk4", choices=("euler", "midpoint", "rk4"), help="ODE solver")
+    ap.add_argument("--method", default="rk4", choices=("euler", "midpoint", "rk4", "ab2", "ab3"), help="ODE solver")
     ap.add_argument("--cfg", type=float, default=2.0, help="classifier-free guidance strength")
     ap.add_argument("--sway-coef", type=float, default=-1.0, help="sway-sampling coefficient of the time grid")
     ap.add_argument("--seed", type=int, default=None, help="noise seed")

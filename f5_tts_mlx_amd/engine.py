@@ -25,7 +25,7 @@ from .weights import DiTConfig, check_weights
 _LIB_PATH = Path(os.environ["F5TTS_HIP_LIB"]).resolve() if os.environ.get("F5TTS_HIP_LIB") else Path(__file__).resolve().parent / "csrc" / "libf5tts_hip.so"
 _lib = None
 
-METHODS = {"euler": 0, "midpoint": 1, "rk4": 2}
+METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "ab2": 3, "ab3": 4}     # ab2 / ab3: docs/multistep.md
 # MFMA operand encodings (include/f5tts_hip.h).  "f16": IEEE half operands, the one-pass mode that meets the 1e-3 mel-L1 gate;
 # "bf16": bfloat16 operands (outside the gate by 2-4x); "bf16x3": hi/lo split, 3 passes, fp32-class; "mxfp8": MX-fp8 block GEMMs
 # (gfx950 scaled MFMA), everything else bf16
@@ -232,6 +232,8 @@ def load_library() -> C.CDLL:
                         ("f5_op_ode_stage_dual", [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 7
                          + [C.c_int, C.c_int, C.c_void_p]),
                         ("f5_op_pack_cond_text_dual", [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
+                        # mode 2 of the three stage kernels, the Adams-Bashforth step (docs/multistep.md)
+                        ("f5_op_ode_stage_ab", [C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
                         ("f5_op_pack_cond_text_dual_keep", [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
                         ("f5_op_resid_gate_ln_rows", [C.c_void_p] * 8 + [C.c_int] * 4 + [C.c_size_t, C.c_void_p]),
                         ("f5_op_ode_stage_rows", [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 7

@@ -138,7 +138,7 @@ def generate(
     ref_audio_path: Optional[str] = None,
     ref_audio_text: Optional[str] = None,
     steps: int = 8,
-    method: Literal["euler", "midpoint"] = "rk4",
+    method: Literal["euler", "midpoint", "rk4", "ab2", "ab3"] = "rk4",
     cfg_strength: float = 2.0,
     sway_sampling_coef: float = -1.0,
     speed: float = 1.0,  # used when duration is None as part of the duration heuristic
@@ -416,7 +416,7 @@ def generate_many(
     requests,
     *,
     steps: int = 8,
-    method: Literal["euler", "midpoint", "rk4"] = "rk4",
+    method: Literal["euler", "midpoint", "rk4", "ab2", "ab3"] = "rk4",
     cfg_strength: float = 2.0,
     sway_sampling_coef: float = -1.0,
     speed: float = 1.0,
@@ -694,7 +694,8 @@ def parse_args(argv=None):
                "with an error rather than guessing.")
     for flag, kind, dflt, doc in _CLI:
         ap.add_argument(flag, type=kind, default=dflt, help=doc)
-    ap.add_argument("--method", default="rk4", choices=("euler", "midpoint", "rk4"), help="ODE solver")
+    ap.add_argument("--method", default="rk4", choices=("euler", "midpoint", "rk4", "ab2", "ab3"),
+                    help="ODE solver (ab2 / ab3: Adams-Bashforth, one evaluation per step, docs/multistep.md)")
     ap.add_argument("--q", type=int, default=None, choices=(4, 8), help="load the MLX 4/8-bit checkpoint (model_v1_{4,8}b.safetensors).  The group-quantised weights are EXPANDED to fp32 on load and run "
                          "through the same 16-bit MFMA kernels as the full checkpoint: unlike in the reference this saves neither memory nor time here")
     ap.add_argument("--resample-ref", action="store_true", help="accept a --ref-audio of any sample rate: it is converted to 24 kHz on the GPU")

@@ -52,7 +52,14 @@ typedef struct f5_config {
  * MX-fp8 (e4m3 + E8M0 per 32), rest bf16 -- a reduced-precision mode. */
 enum { F5_PREC_BF16 = 0, F5_PREC_BF16X3 = 1, F5_PREC_MXFP8 = 2, F5_PREC_F16 = 3 };
 enum { F5_GRAPH_OFF = 0, F5_GRAPH_ON = 1, F5_GRAPH_AUTO = 2 };  /* f5_sample_args.use_graph */
-enum { F5_EULER = 0, F5_MIDPOINT = 1, F5_RK4 = 2 };       /* cfm.py:38-122 */
+enum { F5_EULER = 0, F5_MIDPOINT = 1, F5_RK4 = 2,         /* cfm.py:38-122 */
+       /* Adams-Bashforth of order 2 / 3 on the call's (possibly non-uniform, possibly per-row) grid: ONE evaluation per step, at the grid
+        * point t_i, like Euler; step i adds h (w0 k_i + w1 k_{i-1} + w2 k_{i-2}), k = the guided velocities of this and the two steps
+        * before, kept in the workspace.  The weights integrate the Lagrange interpolant through the nodes in use over [t_i, t_{i+1}],
+        * computed on the host in fp64 from the fp32 grid and rounded once; step 0 is the Euler step, step 1 is second order; a step
+        * whose back-spacing is not positive drops to the highest order whose spacings are (docs/multistep.md).  Every entry point and
+        * every size query takes them; the workspace grows by the weight words only. */
+       F5_AB2 = 3, F5_AB3 = 4 };
 
 const char* f5_last_error(void);
 int f5_version(void);
@@ -120,7 +127,7 @@ typedef struct f5_sample_args {
     const float* y0;           /* dev  [B][N][mel] initial noise, zero beyond durations[b]       */
     const float* t;            /* host [steps] time grid (cfm.py:379-381)                        */
     int32_t steps;             /* number of grid POINTS                                          */
-    int32_t method;            /* F5_EULER / F5_MIDPOINT / F5_RK4                                */
+    int32_t method;            /* F5_EULER / F5_MIDPOINT / F5_RK4 / F5_AB2 / F5_AB3               */
     float cfg_strength;        /* < 1e-5 disables the null branch (cfm.py:352)                   */
     int32_t use_mask;          /* key-padding mask + output row mask; reference: batch > 1       */
     int32_t use_graph;         /* F5_GRAPH_ON: capture/replay the whole call as one hipGraph (cached per shape signature,
@@ -377,6 +384,17 @@ int f5_op_ode_stage_dual(const float* pred, const float* text_pred, const float*
                          const float* text_cfg_rows, const float* base, const float* dt_rows, int rows_per_vec, int nvec, float coef,
                          float divisor, int mode, float* kstore, const float* k1, const float* k2, const float* k3, float* out,
                          void* xin_hi, void* xin_lo, int rows, int mel_dim, void* stream);
+/* Mode 2 of the three stage kernels, the Adams-Bashforth step of F5_AB2 / F5_AB3 (kernels of their own: modes 0 and 1 are untouched).
+ * route 0 = f5_op_ode_stage's rule for k (cfg: device scalar or NULL, dt and abw [3] for the call; text_pred, audio_cfg_rows,
+ * rows_per_vec and nvec are not read), 1 = f5_op_ode_stage_rows' (cfg and dt [nvec], abw [nvec][3]), 2 = f5_op_ode_stage_dual's.  Then
+ *     out = fma(dt, fma(w2, k2, fma(w1, k1, w0 k)), base),   k -> kstore,   (w0, w1, w2) = abw[3 v ...]
+ * k1 / k2: the velocities of the step before and of the one before that.  A term whose pointer is NULL or whose weight is exactly 0 is
+ * left out by selection: its buffer is not loaded.  The padded 16-bit copy of out goes to xin_hi / xin_lo as in mode 0.  Refused before
+ * a launch: a route outside 0..2; null pred, base, dt, out, abw or kstore; kstore equal to k1 or k2; what the route's launcher refuses. */
+int f5_op_ode_stage_ab(int route, const float* pred, const float* text_pred, const float* null_pred, const float* audio_cfg_rows,
+                       const float* cfg, const float* base, const float* dt, const float* abw, int rows_per_vec, int nvec,
+                       float* kstore, const float* k1, const float* k2, float* out, void* xin_hi, void* xin_lo, int rows, int mel_dim,
+                       void* stream);
 /* Residual update and the LayerNorm-modulate behind it with per-row vectors: row r of the [rows][dim] buffers reads vector
  * v = (r / rows_per_vec) % nvec of gate / ln_scale / ln_shift (vec_stride >= dim floats apart, a multiple of 4).
  * With y (fp32 [rows][dim], the GEMM result including bias; may be NULL): x = fmaf(gate[v][c], rowkeep[r] ? y : 0, x) in place (rowkeep
